@@ -139,7 +139,12 @@ def parse():
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="N > 1: strong (default, the metric) = ONE chromosome's blocks in contiguous ranges over the ranks; weak "
                          "= one whole chromosome per rank.  The other mode is timed after the headline (`other_scaling`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller (found records, tested-pixel "
+                         "counts, level statistics of every block) as DIR/<name>.npy, float64, at most 64 MB; see dump_outputs")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     a.no_cpu, a.no_file = a.no_cpu or a.core, a.no_file or a.core
     return a
 
@@ -151,9 +156,16 @@ def make_band(n, dpx, depth, nloops, seed, res, device, reps=8):
     from mustache_amd.normalize import normalize_band
     cols = 16384
     raw = torch.empty((dpx + 2, n), dtype=torch.float64, device=device)
-    for i0 in range(0, n, cols):                      # generated in column slabs to bound temporaries
-        i1 = min(n, i0 + cols)
-        raw[:, i0:i1] = band_counts(n, dpx, depth, nloops, seed, i0=i0, i1=i1, device=device)
+    # the planted loops' stamps overlap in places and index_add_ sums them with atomics on the GPU: its deterministic variant
+    # makes the input bit-identical from run to run (--dump-outputs compares runs output for output)
+    det, det_warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        for i0 in range(0, n, cols):                      # generated in column slabs to bound temporaries
+            i1 = min(n, i0 + cols)
+            raw[:, i0:i1] = band_counts(n, dpx, depth, nloops, seed, i0=i0, i1=i1, device=device)
+    finally:
+        torch.use_deterministic_algorithms(det, warn_only=det_warn)
     band, _, _ = normalize_band(raw, n, dpx, res)      # untimed: code objects, and the allocator's first 4 GB block
     ms = []
     # steady state: HIP events around mst_normalize_band (both kernels); the clocks and the TLB settle over ~4 calls, so 3
@@ -194,7 +206,7 @@ class Workload:
             self.mine = shard_blocks(nb, self.rank, self.world)
             self.total_mpix = nb * self.CH * self.CH / 1e6
 
-    def step(self, skip_empty=False, download=True, fma=False):
+    def step(self, skip_empty=False, download=True, fma=False, keep=False):
         """rows 2-7 for this rank's blocks; returns the found records per group of blocks.  The blocks go through the fused
         kernel as ONE launch in two or three STAGES (mst_scale_space_band_stage: one work list, so tiles shared by consecutive
         blocks are computed once across the stages too): the p-values and the pinned download of one stage's blocks run on a
@@ -211,9 +223,68 @@ class Workload:
             self._groups_for = key
             self._group_starts = [[self.start[i] for i in g] for g in groups]
         # blocks are windows of the band: cut, filled (mustache.py:703-706) and masked (:699) inside the fused kernel
-        return list(self.pipe.engine.sigma_loop_band_overlapped(
+        results = self.pipe.engine.sigma_loop_band_overlapped(
             self.band, self.n, self.dpx, self._group_starts, self.CH, skip_empty=skip_empty,
-            download=download, timing=self.kernel_ms, sort=False, with_value=False, with_q=False, fma=fma))
+            download=download, timing=self.kernel_ms, sort=False, with_value=False, with_q=False, fma=fma)
+        if not keep:
+            return list(results)
+        # keep=True: a group's record arrays are views of staging buffers that the group after next reuses, so the groups that
+        # have one are copied as they are yielded (under the next stage's kernel); the last two stay valid until the next step
+        import numpy as np
+        kept = []
+        for gi, (recs, fits, nzc) in enumerate(results):
+            if gi + 2 < len(self._group_starts):
+                recs = [{k: np.array(v) for k, v in d.items()} for d in recs]
+            kept.append((recs, fits, nzc))
+        return kept
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(w, last, out_dir, rank, world):
+    """--dump-outputs DIR: what the last timed step handed its caller, for this rank's blocks in block order, as float64 .npy
+    files (`<name>_rank<r>.npy` with several ranks), so that two builds can be compared output for output:
+      block_index, block_start   the block (position in the chromosome's tiling) and its first bin
+      tested_pixels, found_count per block: pixels tested, found records
+      level_mu, level_sigma      per block and tested level: the statistics the p-values were computed with
+      record_*                   the found records of all blocks (block index, pixel = row * chunk + column inside the block,
+                                 sigma level, p-value), ordered by block, pixel, level (the kernel appends them in no fixed order)
+      record_index               which records of that order are written: all of them, or above 64 MB in all (across ranks) a
+                                 fixed sample (seed 0) of them"""
+    import numpy as np
+    blocks, starts, tested, found, mu, sd, rec = [], [], [], [], [], [], []
+    for group, (recs, fits, nzc) in zip(w.groups, last):
+        nzc = nzc.numpy()
+        assert len(recs) == len(fits) == len(nzc) == len(group), (len(recs), len(fits), len(nzc), len(group))
+        for j, b in enumerate(group):
+            d = recs[j]
+            order = np.lexsort((d["level"], d["pixel"]))
+            blocks.append(b)
+            starts.append(w.start[b])
+            tested.append(nzc[j])
+            found.append(len(order))
+            mu.append(fits[j][0])
+            sd.append(fits[j][1])
+            rec.append(np.stack([np.full(len(order), b, np.float64), d["pixel"][order].astype(np.float64),
+                                 d["level"][order].astype(np.float64), d["pval"][order].astype(np.float64)], axis=1))
+    by_block = np.argsort(blocks, kind="stable")
+    rec = np.concatenate([rec[i] for i in by_block]) if rec else np.zeros((0, 4))
+    out = {"block_index": np.asarray(blocks, np.float64)[by_block], "block_start": np.asarray(starts, np.float64)[by_block],
+           "tested_pixels": np.asarray(tested, np.float64)[by_block], "found_count": np.asarray(found, np.float64)[by_block],
+           "level_mu": np.asarray(mu, np.float64)[by_block], "level_sigma": np.asarray(sd, np.float64)[by_block]}
+    budget = DUMP_BYTES // world - sum(a.nbytes for a in out.values())
+    keep = min(len(rec), max(0, budget // (5 * 8)))       # five float64 per written record, its index included
+    index = np.arange(len(rec)) if keep == len(rec) else np.sort(np.random.default_rng(0).choice(len(rec), keep, replace=False))
+    out["record_index"] = index.astype(np.float64)
+    for k, name in enumerate(("block", "pixel", "level", "pval")):
+        out["record_" + name] = np.ascontiguousarray(rec[index, k])
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    print("bench.py: --dump-outputs: %d blocks, %d of %d found records -> %s" % (len(blocks), keep, len(rec), out_dir),
+          file=sys.stderr, flush=True)
 
 
 class Ctx:
@@ -230,9 +301,10 @@ class Ctx:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(self, skip_empty, steps, warmup, fma=False):
+    def timed(self, skip_empty, steps, warmup, fma=False, keep_last=False):
         """-> (job seconds = max over ranks, this rank's kernel launch times [ms], last step's records, every rank's own
-        seconds up to its stream-synchronised end, before the closing barrier)"""
+        seconds up to its stream-synchronised end, before the closing barrier).  The last step's records are only whole with
+        keep_last (Workload.step keep), and only until the workload's next step."""
         import torch
         w = self.w
         for _ in range(warmup):
@@ -240,8 +312,8 @@ class Ctx:
         w.kernel_ms.clear()
         self.barrier()
         t0 = time.time()
-        for _ in range(steps):
-            last = w.step(skip_empty, fma=fma)
+        for i in range(steps):
+            last = w.step(skip_empty, fma=fma, keep=keep_last and i == steps - 1)
         torch.cuda.synchronize()
         own = time.time() - t0
         self.barrier()
@@ -558,9 +630,11 @@ def main():
     cx = Ctx(w, args, device, rank, world, grouped, backend)
     w.step(False)          # set-up, untimed: first-touch of the pinned staging buffers and the allocator's block cache
 
-    dt, kms, last, owns = cx.timed(False, args.steps, args.warmup)
+    dt, kms, last, owns = cx.timed(False, args.steps, args.warmup, keep_last=bool(args.dump_outputs))
     ms_per_step = dt / args.steps * 1e3
     value = w.total_mpix / (dt / args.steps)
+    if args.dump_outputs:
+        dump_outputs(w, last, args.dump_outputs, rank, world)
 
     # roofline of the dominant kernel (this rank's launches): algorithmic flops per launch / event-timed duration
     launches_per_step = max(1, len(kms) // args.steps)

@@ -84,6 +84,35 @@ def test_bench_one_rank_small():
     assert j["diff_genome_5kb"]["block_pairs"] == g["blocks"] and j["diff_genome_5kb"]["value"] > 0
 
 
+def test_bench_dump_outputs_are_identical_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the last timed step's records, counts and level statistics as float64 .npy files, 64 MB at most;
+    two runs with the same inputs (and a different number of timed steps, which the line reports) write identical files"""
+    import numpy as np
+    dumps = []
+    for steps in (2, 3):
+        d = tmp_path / ("steps%d" % steps)
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--small", "--no-cpu",
+                            "--no-file", "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _last_json(r.stdout)
+        _check_line(j, 1, steps, 1)
+        assert set(j) == KEPT, sorted(set(j) ^ KEPT)
+        dumps.append({f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))})
+    a, b = dumps
+    assert set(a) == {"block_index", "block_start", "tested_pixels", "found_count", "level_mu", "level_sigma", "record_index",
+                      "record_block", "record_pixel", "record_level", "record_pval"}
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype == np.float64 and a[k].shape == b[k].shape and np.array_equal(a[k], b[k], equal_nan=True), k
+    assert np.array_equal(a["block_index"], np.arange(12)) and (a["tested_pixels"] > 0).all()
+    # the records written are all of them or, above the size cap, a sample: indices into the records of all blocks in order
+    idx, total = a["record_index"].astype(np.int64), int(a["found_count"].sum())
+    assert 0 < len(idx) <= total and len(idx) == len(a["record_pval"]) and (np.diff(idx) > 0).all() and idx[-1] < total
+    assert len(idx) == total or sum(x.nbytes for x in a.values()) > (64 << 20) - 40
+    assert np.array_equal(a["record_block"], np.searchsorted(np.cumsum(a["found_count"]), idx, side="right"))
+    assert ((a["record_pval"] >= 0) & (a["record_pval"] <= 1)).all()
+
+
 def test_bench_two_ranks_gloo_one_device():
     env = dict(os.environ, MST_BENCH_BACKEND="gloo", MST_BENCH_ONE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",

@@ -461,3 +461,43 @@ def test_bench_stage_cuts():
     for nb in range(1, 130):
         c = bench.stage_cuts(nb, 4000)
         assert c[0] == 0 and c[-1] == nb and all(b > a for a, b in zip(c[:-1], c[1:]))
+
+
+def test_bench_dump_outputs_orders_records_and_samples_above_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on host data shaped like Workload.step's: blocks in block order whatever the stage split, records
+    by pixel and level inside each block, and above the size cap a seeded sample that is the same on every call"""
+    import types
+    import torch
+    import bench
+    rng = np.random.default_rng(5)
+    recs, fits = {}, {}
+    for b in range(5):
+        m = int(rng.integers(0, 40))
+        recs[b] = dict(pixel=rng.permutation(1000)[:m].astype(np.uint32), level=rng.integers(0, 8, m).astype(np.uint8),
+                       pval=rng.random(m))
+        fits[b] = (rng.random(3), rng.random(3))
+    groups = [[3, 4], [0, 1, 2]]
+    w = types.SimpleNamespace(groups=groups, start=[1000 * b for b in range(5)])
+    last = [([recs[b] for b in g], [fits[b] for b in g], torch.tensor([10 * b + 1 for b in g], dtype=torch.int32)) for g in groups]
+    bench.dump_outputs(w, last, str(tmp_path / "all"), 0, 1)
+    d = {f[:-4]: np.load(str(tmp_path / "all" / f)) for f in os.listdir(str(tmp_path / "all"))}
+    assert all(a.dtype == np.float64 for a in d.values())
+    assert np.array_equal(d["block_index"], np.arange(5)) and np.array_equal(d["block_start"], np.arange(5) * 1000.0)
+    assert np.array_equal(d["tested_pixels"], np.arange(5) * 10.0 + 1)
+    assert np.array_equal(d["found_count"], [len(recs[b]["pval"]) for b in range(5)])
+    assert np.array_equal(d["level_mu"], np.stack([fits[b][0] for b in range(5)]))
+    assert np.array_equal(d["record_index"], np.arange(sum(len(recs[b]["pval"]) for b in range(5))))
+    for b in range(5):
+        sel = d["record_block"] == b
+        o = np.argsort(recs[b]["pixel"])
+        assert np.array_equal(d["record_pixel"][sel], recs[b]["pixel"][o]) and np.array_equal(d["record_pval"][sel], recs[b]["pval"][o])
+        assert np.array_equal(d["record_level"][sel], recs[b]["level"][o])
+    small = sum(a.nbytes for k, a in d.items() if not k.startswith("record_")) + 40 * 25
+    monkeypatch.setattr(bench, "DUMP_BYTES", small)
+    for k in ("s1", "s2"):
+        bench.dump_outputs(w, last, str(tmp_path / k), 0, 1)
+    s1, s2 = ({f[:-4]: np.load(str(tmp_path / k / f)) for f in os.listdir(str(tmp_path / k))} for k in ("s1", "s2"))
+    assert len(s1["record_index"]) == 25 and sum(a.nbytes for a in s1.values()) <= small
+    assert all(np.array_equal(s1[k], s2[k]) for k in s1)
+    idx = s1["record_index"].astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(s1["record_pval"], d["record_pval"][idx])
