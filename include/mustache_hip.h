@@ -278,9 +278,12 @@ MST_STABLE int mst_band_to_coo(const double *band, const int64_t *x, const int64
  *   local != 0 : branch A (:628-669), taken by the caller when (n - dpx) * res > 2e6; `window` = int(2e6 / res).
  *                (local == 1: the library picks the kernel -- the walking kernel (blocks of `window` samples along each
  *                diagonal, one scan per sample) for windows up to 4096, blocked sums (16-sample blocks) up to ~8400 and
- *                (32-sample blocks, samples only in LDS) up to 16384, an error beyond.  PROFILE builds additionally accept
- *                local == 2 (blocked sums whatever the window) and local == 3 (round 1's segment kernel) as cross-checks;
- *                the product library refuses them.)
+ *                (32-sample blocks, samples only in LDS) up to 16384, and the strip form beyond (two strips of in-block
+ *                partial sums + tile-local prefix sums of per-diagonal 32-sample block sums; windows up to 192 992 bins,
+ *                resolutions down to ~11 bp), an error beyond that, with the limit in the message.
+ *                local == 4: the strip form at any window >= 2 -- the cross-check of the forms above, in every build.
+ *                PROFILE builds additionally accept local == 2 (blocked sums whatever the window) and local == 3 (round 1's
+ *                segment kernel) as cross-checks; the product library refuses them.)
  *                Per diagonal d <= dpx+1: vals = v + 0.001; counts / sum / sum of squares over the zero-padded
  *                window [i - window/2, i - window/2 + window - 1] (np.convolve 'same'); local variance and mean
  *                with the global fallback below 30 samples or when non-finite; z = (vals - mean)/sqrt(var),

@@ -775,6 +775,234 @@ normalize_walk_kernel(const double *__restrict__ band_in, double *__restrict__ b
     }
 }
 
+// ---- Branch A, strip form (windows the LDS-resident forms cannot hold; local == 4 at any window) ---------------------------
+// A workgroup owns kSSeg consecutive outputs [seg0, seg0 + kSSeg) of one diagonal.  The window of output i is [ta, tb),
+// ta = i - left, tb = ta + W; with A = ta rounded UP and B = tb rounded DOWN to a multiple of 32 (absolute positions),
+//     window sum = head [ta, A)  +  whole 32-sample blocks [A, B)  +  tail [B, tb)
+// exactly as in normalize_local_kernel<32, false, true>, but without the SEG + W samples in LDS:
+//   * every head lies in a strip of kSSeg + 32 samples from base = floor32(seg0 - left), every tail in a strip of as many from
+//     floor32(seg0 - left + W).  Both strips are staged as in-block partial sums, formed by a 32-lane DPP scan: the head
+//     strip holds, per sample, the sum from it to the end of its block (the lanes take the block's samples in reverse order),
+//     the tail strip the sum from the start of its block to it -- a head or a tail is ONE LDS read instead of up to 31
+//     additions.
+//   * the whole blocks come from the sums of all 32-sample blocks of the diagonal, formed once by band_block_sums_kernel
+//     (0.6 B per sample in HBM), read for the tile's (kSSeg + W) / 32 blocks and turned into exclusive prefix sums over the
+//     TILE (not the diagonal: the prefixes cover at most kSSeg + W + 32 samples, so the difference of two costs at most a few
+//     ulp of the window sum), by a chunked scan in a fixed order.
+// 20 B of LDS per 32 bins of window plus 41 KB of strips: windows up to kStripMaxW bins.  Every order of summation depends only
+// on absolute positions and W (segments start at multiples of kSSeg; a block's lanes, a strip's blocks and the tile's scan
+// chunks are fixed by them), so the same band gives the same bytes whatever n and the grid are.  Counts are exact integers.
+constexpr int kSSeg = 1024;
+constexpr int kSBlk = 32;
+constexpr int kSStrip = kSSeg + kSBlk;                  // samples per strip
+constexpr int kSStripPad = (kSStrip + kThreads - 1) / kThreads * kThreads;
+constexpr size_t kStripLds = (sizeof(double) * 2 + sizeof(int)) * 2 * kSStrip;      // the two strips
+constexpr size_t strip_lds(int W) {                     // dynamic LDS of one workgroup at window W
+    return kStripLds + (sizeof(double) * 2 + sizeof(int)) * (size_t)((kSSeg + W + 2 * kSBlk) / kSBlk + 1) + 16;
+}
+constexpr size_t kStripLdsMax = 160 * 1024 - 256;      // dynamic share: the kernel's static arrays take 80 bytes of the 160 KB
+constexpr int kStripMaxW = (int)((kStripLdsMax - kStripLds - 16) / (sizeof(double) * 2 + sizeof(int)) - 1) * kSBlk - kSSeg - 2 * kSBlk;
+static_assert(strip_lds(kStripMaxW) <= kStripLdsMax && kStripMaxW >= 131072, "strip form: LDS budget");
+
+// inclusive scan inside each 32-lane half of the wave (the 16-lane row steps of wave_scan3, then row_bcast:15 into rows 1
+// and 3 only): a fixed order; every lane of the wave must be active
+__device__ __forceinline__ void half_wave_scan3(double &a, double &b, int &c) {
+#define MST_SCAN_STEP(CTRL, MASK)               \
+    {                                           \
+        const double ua = dpp_d<CTRL, MASK>(a); \
+        const double ub = dpp_d<CTRL, MASK>(b); \
+        const int uc = dpp_i<CTRL, MASK>(c);    \
+        a = a + ua;                             \
+        b = b + ub;                             \
+        c += uc;                                \
+    }
+    MST_SCAN_STEP(0x111, 0xf)   // row_shr:1
+    MST_SCAN_STEP(0x112, 0xf)   // row_shr:2
+    MST_SCAN_STEP(0x114, 0xf)   // row_shr:4
+    MST_SCAN_STEP(0x118, 0xf)   // row_shr:8
+    MST_SCAN_STEP(0x142, 0xa)   // row_bcast:15 -> rows 1 and 3
+#undef MST_SCAN_STEP
+}
+
+// (count, sum, sum of squares) of the shifted samples (v + 0.001, 0 where there is no contact or i >= n - d) of every aligned
+// 32-sample block of every diagonal: bs*[d * nbk + q] for block q = samples [32 q, 32 q + 32).  Each half-wave takes one block;
+// the sum is the inclusive 32-lane scan at its last lane.
+__global__ void __launch_bounds__(kThreads)
+band_block_sums_kernel(const double *__restrict__ band_in, int64_t n, int64_t nbk, double *__restrict__ bs1,
+                       double *__restrict__ bs2, int *__restrict__ bsc) {
+    constexpr int U = 4;                                 // blocks' worth of loads in flight per lane
+    const int d = blockIdx.y;
+    const int64_t L = n - d;
+    const double *row = band_in + (int64_t)d * n;
+    const int64_t span = nbk * kSBlk;                   // a multiple of 32: half-waves are wholly inside or outside
+    const int64_t stride = (int64_t)gridDim.x * kThreads * U;
+    for (int64_t i0 = (int64_t)blockIdx.x * kThreads * U + threadIdx.x; i0 - threadIdx.x < span; i0 += stride) {
+        double v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = i0 + (int64_t)u * kThreads;
+            const double r = i < L ? row[i] : 0.0;
+            v[u] = r != 0.0 ? r + 0.001 : 0.0;          // vals[x] = v + 0.001   (:635)
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = i0 + (int64_t)u * kThreads;
+            double a = v[u], b = v[u] * v[u];           // vals ** 2  (:649)
+            int c = v[u] != 0.0 ? 1 : 0;
+            half_wave_scan3(a, b, c);
+            if ((threadIdx.x & 31) == 31 && i < span) {
+                const int64_t q = (int64_t)d * nbk + i / kSBlk;
+                bs1[q] = a;
+                bs2[q] = b;
+                bsc[q] = c;
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kThreads)
+normalize_strips_kernel(const double *__restrict__ band_in, double *__restrict__ band_out, int64_t n, int W,
+                        const double *__restrict__ diag_stats, const double *__restrict__ bs1, const double *__restrict__ bs2,
+                        const int *__restrict__ bsc, int64_t nbk) {
+    extern __shared__ __align__(16) double lds[];
+    __shared__ double w1[kThreads / 64], w2[kThreads / 64];
+    __shared__ int wc[kThreads / 64];
+    const int d = blockIdx.y;
+    const int64_t L = n - d;
+    const int64_t seg0 = (int64_t)blockIdx.x * kSSeg;
+    const int tid = threadIdx.x;
+    double *orow = band_out + (int64_t)d * n;
+    if (seg0 >= L) {                                     // past the end of this diagonal: the output band is zero there
+        for (int k = tid; k < kSSeg; k += kThreads)
+            if (seg0 + k < n) orow[seg0 + k] = 0.0;
+        return;
+    }
+    const int left = W / 2;                             // np.convolve(..., 'same'): window = [i - W/2, i - W/2 + W - 1]
+    const int64_t first = seg0 - left;
+    const int64_t base = (first >= 0 ? first : first - (kSBlk - 1)) / kSBlk * kSBlk;        // head strip: floor to 32
+    const int f = (int)(first - base);                  // 0 .. 31
+    const int toff = (f + W) / kSBlk * kSBlk;           // tail strip start - base
+    const int tile = f + kSSeg - 1 + W + 1;             // tile elements [0, tile) cover every window
+    const int nblk = (tile + kSBlk - 1) / kSBlk;
+    const int np = nblk + 1;                            // exclusive prefixes of the tile's blocks, and their total
+    double *H1 = lds, *H2 = H1 + kSStrip, *T1 = H2 + kSStrip, *T2 = T1 + kSStrip, *P1 = T2 + kSStrip, *P2 = P1 + np;
+    int *Hc = reinterpret_cast<int *>(P2 + np), *Tc = Hc + kSStrip, *Pc = Tc + kSStrip;
+    const double *row = band_in + (int64_t)d * n;
+    // the tile's block sums (0 outside the diagonal), coalesced
+    const int64_t q0 = base / kSBlk;                    // exact: base is a multiple of 32
+    {
+        const double *r1 = bs1 + (int64_t)d * nbk, *r2 = bs2 + (int64_t)d * nbk;
+        const int *rc = bsc + (int64_t)d * nbk;
+        for (int k = tid; k < np; k += kThreads) {
+            const int64_t q = q0 + k;
+            const bool in = k < nblk && q >= 0 && q < nbk;
+            P1[k] = in ? r1[q] : 0.0;
+            P2[k] = in ? r2[q] : 0.0;
+            Pc[k] = in ? rc[q] : 0;
+        }
+    }
+    // the strips' in-block partial sums: lane j of a half-wave takes sample 31 - j of its block in the head strip (inclusive
+    // scan = sum from the sample to the block's end) and sample j in the tail strip (sum from the block's start)
+    for (int g = tid; g < kSStripPad; g += kThreads) {
+        const int gh = (g & ~(kSBlk - 1)) | (kSBlk - 1 - (g & (kSBlk - 1)));
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int e = s == 0 ? gh : g;
+            const int64_t i = base + (s == 0 ? 0 : toff) + e;
+            double r = 0.0;
+            if (e < kSStrip && i >= 0 && i < L) r = row[i];
+            double a = r != 0.0 ? r + 0.001 : 0.0;      // vals[x] = v + 0.001   (:635)
+            double b = a * a;                           // vals ** 2  (:649)
+            int c = a != 0.0 ? 1 : 0;
+            half_wave_scan3(a, b, c);
+            if (e < kSStrip) {
+                (s == 0 ? H1 : T1)[e] = a;
+                (s == 0 ? H2 : T2)[e] = b;
+                (s == 0 ? Hc : Tc)[e] = c;
+            }
+        }
+    }
+    __syncthreads();
+    // block sums -> exclusive prefixes over the tile: thread-serial chunks of CH entries, the chunk totals scanned across the
+    // workgroup (DPP inside the wave, the waves in index order)
+    {
+        const int CH = (np + kThreads - 1) / kThreads, k0 = tid * CH;
+        double a1 = 0.0, a2 = 0.0;
+        int ac = 0;
+        for (int j = 0; j < CH; ++j) {
+            const int k = k0 + j;
+            if (k < np) {
+                a1 = a1 + P1[k];
+                a2 = a2 + P2[k];
+                ac += Pc[k];
+            }
+        }
+        double s1 = a1, s2 = a2, o1, o2, t1, t2;
+        int sc = ac, oc, tc;
+        block_totals3<kThreads>(s1, s2, sc, w1, w2, wc, o1, o2, oc, t1, t2, tc);
+        double p1 = o1 + lane_before(s1), p2 = o2 + lane_before(s2);
+        int pc = oc + lane_before_i(sc);
+        for (int j = 0; j < CH; ++j) {
+            const int k = k0 + j;
+            if (k < np) {
+                const double v1 = P1[k], v2 = P2[k];
+                const int vc = Pc[k];
+                P1[k] = p1;
+                P2[k] = p2;
+                Pc[k] = pc;
+                p1 = p1 + v1;
+                p2 = p2 + v2;
+                pc += vc;
+            }
+        }
+    }
+    __syncthreads();
+    const double mean = diag_stats[4 * d + 0], sd = diag_stats[4 * d + 1], wgt = diag_stats[4 * d + 2];
+    const double std2 = sd * sd;
+    for (int k = tid; k < kSSeg; k += kThreads) {
+        const int64_t i = seg0 + k;
+        if (i >= n) break;
+        double z = 0.0;
+        const double r = i < L ? row[i] : 0.0;
+        const double x = r != 0.0 ? r + 0.001 : 0.0;
+        if (x != 0.0) {
+            const int ra = f + k, rb = ra + W;              // window = tile elements [ra, rb)
+            const int rA = (ra + kSBlk - 1) / kSBlk * kSBlk, rB = rb / kSBlk * kSBlk;
+            double s1, s2;
+            int c;
+            if (rA <= rB) {
+                const bool hh = ra != rA, ht = rb != rB;
+                c = (hh ? Hc[ra] : 0) + (Pc[rB / kSBlk] - Pc[rA / kSBlk]) + (ht ? Tc[rb - 1 - toff] : 0);
+                s1 = hh ? H1[ra] : 0.0;                      // head
+                s2 = hh ? H2[ra] : 0.0;
+                s1 = s1 + (P1[rB / kSBlk] - P1[rA / kSBlk]);    // whole aligned blocks: one difference of tile prefixes
+                s2 = s2 + (P2[rB / kSBlk] - P2[rA / kSBlk]);
+                if (ht) {                                    // tail
+                    s1 = s1 + T1[rb - 1 - toff];
+                    s2 = s2 + T2[rb - 1 - toff];
+                }
+            } else {                                         // window inside one aligned block (W < 32)
+                c = Hc[ra] - Hc[rb];
+                s1 = H1[ra] - H1[rb];
+                s2 = H2[ra] - H2[rb];
+            }
+            const double cnt = (double)c;
+            double var = (s2 - s1 * s1 / cnt) / (cnt - 1.0);        // (:650)
+            if (!isfinite(var)) var = std2;                          // (:653-654)
+            double mu = s1 / cnt;                                    // (:656)
+            if (c < 30) {                                            // (:657-658)
+                mu = mean;
+                var = std2;
+            }
+            if (!isfinite(mu)) mu = mean;                            // (:660-661)
+            z = (x - mu) / sqrt(var);                                // (:663-665)
+            if (!isfinite(z)) z = 0.0;                               // (:666)
+            z = z * wgt;                                             // (:667)
+        }
+        orow[i] = z;                                                 // positions past the diagonal's end receive 0
+    }
+}
+
 // Branch B (mustache.py:671-685): plain per-diagonal z-score for d < min(dpx, n); other diagonals pass through
 // (after the nan_to_num at :673).
 __global__ void __launch_bounds__(kThreads)
@@ -956,9 +1184,9 @@ extern "C" int mst_normalize_band(const double *band_in, double *band_out, int64
     if (!band_in || !band_out || !diag_stats || band_in == band_out || n <= 0 || dpx < 0 || dpx + 2 > 65535)
         return mst::fail(MST_E_ARG, "mst_normalize_band: bad argument (out of place, dpx + 2 <= 65535)");
 #ifndef MST_PROFILE
-    if (local != 0 && local != 1)
+    if (local != 0 && local != 1 && local != 4)
         return mst::fail(MST_E_ARG, "mst_normalize_band: local = %d selects a cross-check kernel that only PROFILE builds "
-                         "carry (make PROFILE=1 -> libmustache_hip_profile.so); the product library takes 0 or 1", local);
+                         "carry (make PROFILE=1 -> libmustache_hip_profile.so); the product library takes 0, 1 or 4", local);
 #endif
     hipStream_t s = mst::as_stream(stream);
     const int nd = dpx + 2;
@@ -1027,6 +1255,32 @@ extern "C" int mst_normalize_band(const double *band_in, double *band_out, int64
         };
         const size_t lds = window < 2 ? 0 : lds_need(kBlk, 2), lds_wide = window < 2 ? 0 : lds_need(kBlkWide, 1);
         const bool wide = lds > 160 * 1024;
+        // local == 4, or a window beyond what the LDS-resident forms hold (> 16384 bins, resolutions below ~125 bp): the strip form
+        if (window >= 2 && (local == 4 || (local == 1 && wide && lds_wide > 160 * 1024))) {
+            if (window > kStripMaxW)
+                return mst::fail(MST_E_ARG,
+                                 "mst_normalize_band: window of %d bins (= 2 Mb / resolution) is outside [2, %d]: the sliding-window "
+                                 "normalisation supports resolutions down to ~%d bp",
+                                 window, kStripMaxW, (int)(2000000 / kStripMaxW) + 1);
+            const int64_t nbk = (n + kSBlk - 1) / kSBlk;
+            double *bs = nullptr;                        // block sums: [nd][nbk] sum, [nd][nbk] sum of squares, [nd][nbk] count
+            const size_t nbs = (size_t)nd * nbk;
+            MST_HIP(hipMallocAsync((void **)&bs, (sizeof(double) * 2 + sizeof(int)) * nbs, s));
+            const int64_t per_diag = (nbk * kSBlk + 4 * kThreads - 1) / (4 * kThreads);
+            const int64_t gx = (8192 + nd - 1) / nd;           // ~8 k workgroups in all, each walking its share of a diagonal
+            band_block_sums_kernel<<<dim3((unsigned)(per_diag < gx ? per_diag : gx), nd), kThreads, 0, s>>>(
+                band_in, n, nbk, bs, bs + nbs, reinterpret_cast<int *>(bs + 2 * nbs));
+            MST_LAUNCH_CHECK();
+            static unsigned long long lds_allowed_strips = 0;
+            MST_HIP(mst::allow_dynamic_lds(reinterpret_cast<const void *>(&normalize_strips_kernel), (int)kStripLdsMax,
+                                           &lds_allowed_strips));
+            // every output position, the zero tails past each diagonal's end included, is written by the kernel
+            normalize_strips_kernel<<<dim3((unsigned)((n + kSSeg - 1) / kSSeg), nd), kThreads, strip_lds(window), s>>>(
+                band_in, band_out, n, window, diag_stats, bs, bs + nbs, reinterpret_cast<const int *>(bs + 2 * nbs), nbk);
+            MST_LAUNCH_CHECK();
+            MST_HIP(hipFreeAsync(bs, s));
+            return MST_OK;
+        }
         if (window < 2 || (wide && lds_wide > 160 * 1024))
             return mst::fail(MST_E_ARG,
                              "mst_normalize_band: window of %d bins (= 2 Mb / resolution) is outside [2, 16384]: the sliding-window "

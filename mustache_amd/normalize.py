@@ -426,14 +426,15 @@ def band_to_coo(band, x, y, v_out, n, dpx):
     return v_out
 
 
-_KERNELS = {"auto": 1, "blocked": 2, "segment": 3}
+_KERNELS = {"auto": 1, "blocked": 2, "segment": 3, "strips": 4}
 
 
 def normalize_band(band, n, dpx, resolution, blocked=False, kernel=None):
     """Returns (normalised band, diag_stats [dpx+2, 4] = mean, std, weight, count).  Branch selection and window
     size follow mustache.py:628, :631.  `kernel` ("blocked" / "segment"; `blocked=True` is short for the former) asks for one
     of the two cross-check formulations of branch A's window sums -- only a PROFILE build of the library carries them
-    (make PROFILE=1, MUSTACHE_HIP_LIB=.../libmustache_hip_profile.so); the product library picks its kernel itself."""
+    (make PROFILE=1, MUSTACHE_HIP_LIB=.../libmustache_hip_profile.so); the product library picks its kernel itself, and
+    also takes "strips": the strip form, which serves windows beyond 16 384 bins (resolutions below ~125 bp), at any window."""
     lib = require_gpu()
     local = (n - dpx) * resolution > 2000000
     window = int(2000000 / resolution)
