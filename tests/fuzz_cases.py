@@ -217,15 +217,18 @@ def genome_case(rng, pipe, max_n=5200, max_chroms=5, plan=None):
                            bad=bad)
 
 
-def diff_case(rng, eng):
+def diff_case(rng, eng, octaves=None):
     """One random block pair through the two-sample path: the band-direct route in both forms (selected records only + device
     look-ups = what the driver runs; whole found sets) and the dense drop-in diff_mustache(), against the oracle's
-    restatement of the reference's diff_mustache(): the four loop lists identical in coordinates and scales, q within 1e-6."""
+    restatement of the reference's diff_mustache(): the four loop lists identical in coordinates and scales, q within 1e-6.
+    `octaves`: the octave list (default OCT); `eng` must be a ScaleSpaceEngine built for it."""
     import torch
     import oracle
     from mustache_amd.diff_mustache import _pair_tail, diff_mustache
     from mustache_amd.normalize import band_from_coo
     from mustache_amd.synth import synth_coo
+
+    octs = OCT if octaves is None else [float(o) for o in octaves]
 
     def key(lists):
         return [[(int(a), int(b), float(s)) for a, b, _, s in l] for l in lists]
@@ -242,7 +245,7 @@ def diff_case(rng, eng):
         c = np.zeros((n, n))
         c[x, y] = v
         cs.append(c)
-    exp = oracle.diff_block(cs[0].copy(), cs[1].copy(), start, dpx, OCT, st, pt, pt2)
+    exp = oracle.diff_block(cs[0].copy(), cs[1].copy(), start, dpx, octs, st, pt, pt2)
     bands = []
     for c in cs:
         xx, yy = np.nonzero(np.triu(c))
@@ -252,7 +255,7 @@ def diff_case(rng, eng):
     got_band = _pair_tail(batch, 0, 1, start, pt, pt2, st, True)
     full = _pair_tail(eng.run_band_pairs(bands, n, dpx, [0], n), 0, 1, start, pt, pt2, st, True)
     forms_agree = [[tuple(l) for l in ls] for ls in full] == [[tuple(l) for l in ls] for ls in got_band]
-    got_dense = diff_mustache(cs[0].copy(), cs[1].copy(), "1", "1", 5000, start, start + n, 0, dpx, OCT, st, pt, pt2)
+    got_dense = diff_mustache(cs[0].copy(), cs[1].copy(), "1", "1", 5000, start, start + n, 0, dpx, octs, st, pt, pt2)
     ok = key(got_band) == key(exp) and key(got_dense) == key(exp)
     qe = 0.0
     if ok:
@@ -260,7 +263,7 @@ def diff_case(rng, eng):
             for a, b in zip(g, e):
                 qe = max(qe, abs(a[2] - b[2]) / max(b[2], 1e-300))
     return bool(ok and forms_agree and qe <= 1e-6), sum(len(l) for l in exp), dict(
-        kind="block pair", n=n, dpx=dpx, st=st, pt=pt, pt2=pt2, lists=[len(l) for l in exp], forms_agree=forms_agree, qerr=qe)
+        kind="block pair", octaves=octs, n=n, dpx=dpx, st=st, pt=pt, pt2=pt2, lists=[len(l) for l in exp], forms_agree=forms_agree, qerr=qe)
 
 
 def geometry_case(pipe, n, dpx, res, depth, st=0.88, pt=0.1, share_modes=(True,), plan=None):

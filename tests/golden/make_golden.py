@@ -323,10 +323,12 @@ def make_regulator(ref, name="regulator_3blocks", n=4200, dpx=200, res=10000, se
 
 
 def make_diff(name="diff_320", n=320, dpx=80, start=640, res=50000, nloops=30, pt=0.3, pt2=0.3, compact=False,
-              normalize=True):
+              normalize=True, octaves=OCTAVES):
     """Two-sample path: run the reference's diff_mustache() on one block pair and keep its locals.  `diff_320`: a small
     pair with full inputs and locals; `diff_2000` (compact=True): BASELINE config 5's 5 kb block geometry (2000 x 2000,
-    distance limit 400 px), inputs regenerated from the seeds by the tests, outputs as checksums + the four loop lists."""
+    distance limit 400 px), inputs regenerated from the seeds by the tests, outputs as checksums + the four loop lists.
+    `octaves` (stored in the fixture): the octave list handed to the reference; its largest sigma_2 / sigma_3 blur radius picks
+    the difference kernel's tile."""
     ref = load_reference("mustache")
     dref = load_reference("diff_mustache")
     xa, ya, va = synth_coo(n, dpx, depth=300.0, seed=51, nloops=nloops)
@@ -361,7 +363,7 @@ def make_diff(name="diff_320", n=320, dpx=80, start=640, res=50000, nloops=30, p
     dref.norm.fit = nfit
     sys.settrace(tracer)
     try:
-        out = dref.diff_mustache(c1.copy(), c2.copy(), "1", "1", 5000, start, start + n, 0, dpx, OCTAVES, 0.8, pt, pt2)
+        out = dref.diff_mustache(c1.copy(), c2.copy(), "1", "1", 5000, start, start + n, 0, dpx, list(octaves), 0.8, pt, pt2)
     finally:
         sys.settrace(None)
         dref.norm.fit = fit0
@@ -386,7 +388,8 @@ def make_diff(name="diff_320", n=320, dpx=80, start=640, res=50000, nloops=30, p
         np.savez_compressed(os.path.join(HERE, name + ".npz"), xa=xa.astype(np.int32), ya=ya.astype(np.int32), va=va,
                             xb=xb.astype(np.int32), yb=yb.astype(np.int32), vb=vb, n=n, dpx=dpx, start=start,
                             st=0.8, pt=pt, pt2=pt2, norm_fit=np.array(fits), **lists,
-                            **{"loc_" + k: v for k, v in locs.items()})
+                            **{"loc_" + k: v for k, v in locs.items()},
+                            **({} if list(octaves) == OCTAVES else {"octaves": np.array(octaves, dtype=np.float64)}))
     print(name, [len(o) for o in out], {k: v.shape for k, v in locs.items()})
 
 
@@ -578,8 +581,14 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["readers"]:
         make_readers_ref()
         sys.exit(0)
-    if sys.argv[1:] == ["diff"]:
-        make_diff()
+    if sys.argv[1:2] == ["diff"]:
+        # `diff`: the default octaves (diff_320); `diff wide`: the same pair at octaves whose blur radii select the difference
+        # kernel's two wider tiles -- [2.0, 4.0] (radius 10: the 14 tile) and [3.2, 6.4] (radius 15: the 28 tile)
+        if sys.argv[2:] in ([], ["default"]):
+            make_diff()
+        if sys.argv[2:] == ["wide"]:
+            make_diff("diff_320_oc2", octaves=[2.0, 4.0])
+            make_diff("diff_320_sz32", octaves=[3.2, 6.4])
         sys.exit(0)
     if sys.argv[1:] == ["diffregulator"]:   # the two-sample regulator() at config 5's geometry (~4 min in the reference)
         make_diff_regulator()

@@ -78,6 +78,18 @@ def test_fuzz_block_pairs_seeded_slice(pipe):
     assert loops > 100
 
 
+def test_fuzz_block_pairs_wide_tiles_seeded_slice():
+    """the same block-pair cases at octave lists whose difference kernel runs its two wider tiles: [2.0, 4.0] (largest
+    sigma_2 / sigma_3 radius 10: the 14 tile), [3.2, 6.4] and [1.6, 3.2, 6.4] (radius 15: the 28 tile)"""
+    from mustache_amd.engine import ScaleSpaceEngine
+    loops = 0
+    for seed, octs in ((20271, [2.0, 4.0]), (20272, [3.2, 6.4]), (20273, [1.6, 3.2, 6.4])):
+        rng = np.random.default_rng(seed)
+        eng = ScaleSpaceEngine(octs)
+        loops += _report([fuzz_cases.diff_case(rng, eng, octaves=octs) for _ in range(4)])
+    assert loops > 30
+
+
 def test_large_geometry_odd_distance_limit(pipe):
     """dpx 3011 -> blocks of 6022 x 6022 whose overlap is not a multiple of anything (tile lattice phase differs per block),
     both share modes."""
