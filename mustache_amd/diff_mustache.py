@@ -195,10 +195,11 @@ def run_pair_genome(pipe, pairs, distance_in_px, st, pt, pt2):
 
 def run_pair_layout(pipe, lay, gbands, st, pt, pt2):
     """run_pair_genome's body on a prepared layout + the two samples' genome bands."""
+    from .engine import default_found_cap
     eng = pipe.engine
     CH, distance_in_px, pairs = lay.CH, lay.dpx, lay.ns
     # per block pair in HBM: D_2 of the difference image for every octave + the two samples' record buffers
-    per_pair = len(eng.levels.octave_values) * CH * CH * 8 + 2 * max(4096, CH * CH // 32) * 48
+    per_pair = len(eng.levels.octave_values) * CH * CH * 8 + 2 * default_found_cap(CH) * 48
     # groups of block pairs: two are in flight at a time (the device work of group i + 1 runs under the host tail of group i),
     # each at least ~256 Mpix per sample so that its launches fill the chip
     bs = max(1, min(int(pipe.max_batch_bytes // (2 * per_pair)), max(pipe.blocks_per_launch(CH), -(-len(lay.blocks) // 4))))

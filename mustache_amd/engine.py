@@ -4,7 +4,9 @@ PyTorch is plumbing here (device memory, streams); every number is produced by l
 library or a missing GPU is an error -- there is no CPU path in this package.
 """
 import ctypes
+import itertools
 import os
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -47,6 +49,52 @@ def require_gpu():
 def _off(t, n):
     """Device pointer of element n of tensor t."""
     return ctypes.c_void_p(t.data_ptr() + n * t.element_size())
+
+
+def default_found_cap(CH):
+    """Record capacity per block of CH x CH before any launch overflowed: one record per 32 pixels, at least 4096."""
+    return max(4096, (CH * CH) // 32)
+
+
+def _event_pair(timing):
+    """(start, end) timing events around a launch, the start recorded on the current stream; None without a timing list."""
+    if timing is None:
+        return None
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    ev[0].record()
+    return ev
+
+
+@dataclass(slots=True, eq=False)
+class _Launch:
+    """One fused scale-space launch -- or one group's stage of a staged launch (a view) -- as ScaleSpaceEngine._ss_launch
+    enqueued it, and what its finish (_ss_finish) brought back.  An overflow re-enqueues the same record (_grow)."""
+    B: int
+    CH: int
+    cap: int                    # record capacity per block
+    flags: int                  # MST_FLAG_* word of the launch
+    nzc: object = None          # tested-pixel counts [B] int32 (device): input of the dense kernel, output of the band kernels
+    own_nzc: bool = False       # nzc is one of the launch's buffers (allocated with them)
+    blocks: tuple = None        # (c, nz): dense blocks and their masks
+    band_src: tuple = None      # (band, n, dpx, ctypes array of the B block origins): windows of a band
+    band2: tuple = None         # (second band, split): blocks [split, B) are windows of the second band
+    stages: list = None         # staged launch: block counts of its groups, one stage each
+    views: list = None          # staged launch: one record per group (views of the buffers), set by _enqueue
+    timing: list = None         # receives `ev` once the finish has synchronised
+    ev: tuple = None            # (start, end) events around the launch
+    reuse: object = None        # _carve slot of the launch's buffers and of its finish's staging; None = not kept
+    graph: bool = False         # the finish is replayed as a hipGraph (MST_FLAG_GRAPH)
+    done: object = None         # event behind the launch (a staged group: behind its stage)
+    ws: object = None           # the launch's buffers
+    stats: object = None
+    fit: object = None
+    count: object = None
+    found: object = None
+    pval: object = None
+    count_h: object = None      # set by the finish: record counts, tested-pixel counts, fits (host), prefetched records
+    nz_h: object = None
+    fit_h: object = None
+    prefetched: object = None
 
 
 class _MultiGather:
@@ -215,53 +263,13 @@ class BlockBatch(_MultiGather):
 
 class BandBatch(_MultiGather):
     """Same interface as BlockBatch for blocks that exist only as windows of the band (mst_scale_space_band): the tail's
-    gathers read the band directly, no dense block is ever built."""
+    gathers read the band directly, no dense block is ever built.  Blocks [0, P) read bands[0], blocks [P, B) bands[1]
+    (PairBandBatch); the batched gathers make one launch per run of consecutive blocks of the same band."""
 
     def __init__(self, engine, band, n, dpx, starts, CH, nz_count, found, fit):
-        self.engine, self.band, self.n, self.dpx, self.starts, self.CH = engine, band, int(n), int(dpx), list(starts), CH
-        self.B = len(self.starts)
-        self.nz_count, self.found, self.fit = nz_count, found, fit
-
-    def _device(self):
-        return self.band.device
-
-    def _features_launch(self, b, pix, half, m, cnt1, cnt2, cval):
-        _lib.check(self.engine.lib.mst_candidate_features_band(_ptr(self.band), self.n, self.dpx, int(self.starts[b]),
-                                                               self.CH, pix, half, m, cnt1, cnt2, cval, _stream()))
-
-    def _diagonals_launch(self, b, ks, m, out):
-        _lib.check(self.engine.lib.mst_gather_diagonals_band(_ptr(self.band), self.n, self.dpx, int(self.starts[b]),
-                                                             self.CH, ks, m, out, _stream()))
-
-    def _features_one_launch(self, bs, sizes, d_pix, d_half, total, cnt, cval):
-        starts = np.repeat(np.array([int(self.starts[b]) for b in bs], dtype=np.int64), sizes)
-        d_s = torch.from_numpy(starts).to(self.band.device)
-        _lib.check(self.engine.lib.mst_candidate_features_band_multi(_ptr(self.band), self.n, self.dpx, _ptr(d_s), self.CH,
-                                                                     _ptr(d_pix), _ptr(d_half), int(total), _ptr(cnt),
-                                                                     _off(cnt, total), _ptr(cval), _stream()))
-        return True
-
-    def _diag_means_one_launch(self, bs, sizes, d_k, out):
-        starts = np.repeat(np.array([int(self.starts[b]) for b in bs], dtype=np.int64), sizes)
-        d_s = torch.from_numpy(starts).to(self.band.device)
-        _lib.check(self.engine.lib.mst_diag_means_band_multi(_ptr(self.band), self.n, self.dpx, _ptr(d_s), self.CH,
-                                                             _ptr(d_k), int(starts.size), _ptr(out), _stream()))
-        return True
-
-    def _diag_means_launch(self, b, ks, m, out):
-        _lib.check(self.engine.lib.mst_diag_means_band(_ptr(self.band), self.n, self.dpx, int(self.starts[b]), self.CH,
-                                                       ks, m, out, _stream()))
-
-
-class PairBandBatch(_MultiGather):
-    """The two-sample caller's batch: blocks [0, P) are windows of sample 1's band, blocks [P, 2P) the same windows of
-    sample 2's band (reference diff_mustache.py:671-674 builds the two dense blocks; here neither exists)."""
-
-    def __init__(self, engine, bands, n, dpx, starts, CH, nz_count, found, fit):
-        self.engine, self.bands, self.n, self.dpx, self.CH = engine, bands, int(n), int(dpx), CH
-        self.starts = list(starts) + list(starts)
-        self.P = len(starts)
-        self.B = 2 * self.P
+        self.engine, self.n, self.dpx, self.starts, self.CH = engine, int(n), int(dpx), list(starts), CH
+        self.B = self.P = len(self.starts)
+        self.bands = (band,)
         self.nz_count, self.found, self.fit = nz_count, found, fit
 
     def _device(self):
@@ -270,54 +278,50 @@ class PairBandBatch(_MultiGather):
     def _band(self, b):
         return self.bands[0] if b < self.P else self.bands[1]
 
-    def _diag_means_one_launch(self, bs, sizes, d_k, out):
-        """one launch per run of consecutive blocks of the same sample"""
-        starts = np.repeat(np.array([int(self.starts[b]) for b in bs], dtype=np.int64), sizes)
-        d_s = torch.from_numpy(starts).to(self.bands[0].device)
-        off = 0
-        i = 0
+    def _runs(self, bs, sizes):
+        """(band, first entry, entries) per run of consecutive blocks of bs on the same band, empty runs left out"""
+        off = i = 0
         while i < len(bs):
             j = i
             while j < len(bs) and (bs[j] < self.P) == (bs[i] < self.P):
                 j += 1
             m = int(sum(sizes[i:j]))
             if m:
-                _lib.check(self.engine.lib.mst_diag_means_band_multi(_ptr(self._band(bs[i])), self.n, self.dpx, _off(d_s, off),
-                                                                     self.CH, _off(d_k, off), m, _off(out, off), _stream()))
+                yield self._band(bs[i]), off, m
             off += m
             i = j
-        return True
+
+    def _entry_starts(self, bs, sizes):
+        starts = np.repeat(np.array([int(self.starts[b]) for b in bs], dtype=np.int64), sizes)
+        return torch.from_numpy(starts).to(self._device())
 
     def _features_one_launch(self, bs, sizes, d_pix, d_half, total, cnt, cval):
-        """one launch per run of consecutive blocks of the same sample (callers list sample 1's blocks first, then sample 2's)"""
-        starts = np.repeat(np.array([int(self.starts[b]) for b in bs], dtype=np.int64), sizes)
-        d_s = torch.from_numpy(starts).to(self.bands[0].device)
-        off = 0
-        i = 0
-        while i < len(bs):
-            j = i
-            while j < len(bs) and (bs[j] < self.P) == (bs[i] < self.P):
-                j += 1
-            m = int(sum(sizes[i:j]))
-            if m:
-                _lib.check(self.engine.lib.mst_candidate_features_band_multi(
-                    _ptr(self._band(bs[i])), self.n, self.dpx, _off(d_s, off), self.CH, _off(d_pix, off), _off(d_half, off), m,
-                    _off(cnt, off), _off(cnt, total + off), _off(cval, off), _stream()))
-            off += m
-            i = j
+        d_s = self._entry_starts(bs, sizes)
+        for band, off, m in self._runs(bs, sizes):
+            _lib.check(self.engine.lib.mst_candidate_features_band_multi(
+                _ptr(band), self.n, self.dpx, _off(d_s, off), self.CH, _off(d_pix, off), _off(d_half, off), m,
+                _off(cnt, off), _off(cnt, total + off), _off(cval, off), _stream()))
         return True
 
-    def _features_launch(self, b, pix, half, m, cnt1, cnt2, cval):
-        _lib.check(self.engine.lib.mst_candidate_features_band(_ptr(self._band(b)), self.n, self.dpx, int(self.starts[b]),
-                                                               self.CH, pix, half, m, cnt1, cnt2, cval, _stream()))
+    def _diag_means_one_launch(self, bs, sizes, d_k, out):
+        d_s = self._entry_starts(bs, sizes)
+        for band, off, m in self._runs(bs, sizes):
+            _lib.check(self.engine.lib.mst_diag_means_band_multi(_ptr(band), self.n, self.dpx, _off(d_s, off), self.CH,
+                                                                 _off(d_k, off), m, _off(out, off), _stream()))
+        return True
 
     def _diagonals_launch(self, b, ks, m, out):
         _lib.check(self.engine.lib.mst_gather_diagonals_band(_ptr(self._band(b)), self.n, self.dpx, int(self.starts[b]),
                                                              self.CH, ks, m, out, _stream()))
 
-    def _diag_means_launch(self, b, ks, m, out):
-        _lib.check(self.engine.lib.mst_diag_means_band(_ptr(self._band(b)), self.n, self.dpx, int(self.starts[b]), self.CH,
-                                                       ks, m, out, _stream()))
+
+class PairBandBatch(BandBatch):
+    """The two-sample caller's batch: blocks [0, P) are windows of sample 1's band, blocks [P, 2P) the same windows of
+    sample 2's band (reference diff_mustache.py:671-674 builds the two dense blocks; here neither exists)."""
+
+    def __init__(self, engine, bands, n, dpx, starts, CH, nz_count, found, fit):
+        super().__init__(engine, bands[0], n, dpx, list(starts) + list(starts), CH, nz_count, found, fit)
+        self.bands, self.P = tuple(bands), len(starts)
 
 
 _GC_SETTLED = False
@@ -436,117 +440,121 @@ class ScaleSpaceEngine:
         `timing`: optional list; receives a (start, end) torch.cuda.Event pair bracketing the mst_scale_space launch
         on the launch stream.  `band_src` = (band, n, dpx, starts, CH) selects the band-direct kernel (c, nz unused;
         nz_count is then an OUTPUT)."""
-        st = self._ss_launch(c, nz, nz_count, skip_empty, found_cap, timing, fma, band_src)
+        L = self._ss_launch(self._flags(skip_empty, fma), nzc=nz_count, blocks=None if band_src is not None else (c, nz),
+                            band_src=band_src, found_cap=found_cap, timing=timing)
         packed = download and select_below is None and not sort
-        return self._ss_results(self._ss_finish(st, packed=packed), download, sort, with_value, with_q, select_below)
+        return self._ss_results(self._ss_finish(L, packed=packed), download, sort, with_value, with_q, select_below)
 
-    def _ss_launch(self, c, nz, nz_count, skip_empty, found_cap, timing, fma, band_src, reuse=None, graph=False, out=None, band2=None):
-        """Allocate the outputs and enqueue the fused kernel on the current stream (no synchronisation).  `reuse`: see _carve.
-        `out`: the caller's own buffers instead (dict ws, stats, fit, count, found, pval -- e.g. one sample's rows of buffers
-        that hold both samples of a two-sample call, so that ONE mst_found_finish serves both launches).
-        `band2` = (second band, split): ONE launch over the blocks of two bands (the two samples of a two-sample call; band_src's
-        starts list holds all B origins, blocks [split, B) read the second band)."""
-        if band_src is not None:
-            band, bn, bdpx, bstarts, CH = band_src
-            B = len(bstarts)
-            skey = tuple(bstarts)
-            st_arr = self._starts_arrays.get(skey)          # repeated launches of the same blocks: no re-marshalling
-            if st_arr is None:
-                if len(self._starts_arrays) > 64:
-                    self._starts_arrays.clear()
-                st_arr = self._starts_arrays[skey] = (ctypes.c_int64 * B)(*bstarts)
-        else:
-            B, CH, _ = c.shape
-        if found_cap is None:
-            found_cap = self._found_cap.get(CH, max(4096, (CH * CH) // 32))
-        lv = ctypes.byref(self._lv_struct)
+    # ---- one fused launch: its record, buffers, enqueue, overflow rule and finish ------------------------------------
+    def _found_cap_for(self, CH):
+        """record capacity per block of the next launch of CH x CH blocks: the default, or what an overflow taught (_grow)"""
+        return self._found_cap.get(CH, default_found_cap(CH))
+
+    def _workspace_bytes(self, B, CH):
         ws_bytes = self._ws_bytes.get((B, CH))
         if ws_bytes is None:
-            ws_bytes = self._ws_bytes[(B, CH)] = int(self.lib.mst_scale_space_workspace_bytes(B, CH, lv))
-        with torch.cuda.device(self.device):
-            # the six launch buffers (kept between calls for small launches, see _carve)
-            T = _lib.MST_MAX_TESTED
-            ws, stats, fit, count, found, pval = (out[k] for k in ("ws", "stats", "fit", "count", "found", "pval")) \
-                if out is not None else self._carve(
-                (ws_bytes, torch.uint8, (ws_bytes,)), (B * T * 16, torch.float64, (B, T, 2)),
-                (B * T * 16, torch.float64, (B, T, 2)), (B * 4, torch.int32, (B,)),
-                (B * found_cap * 16, torch.int64, (B, found_cap, 2)),            # 16-byte records
-                (B * found_cap * 8, torch.float64, (B, found_cap)), reuse=None if reuse is None else ("launch", reuse))
-            ev = None
-            if timing is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
-            # MST_FLAG_NO_SHARE (4): every tile once per block; default: tiles inside two consecutive blocks computed once
-            # MST_FLAG_GRAPH (8): a launch that repeats with identical arguments is replayed as one hipGraph
-            flags = (1 if skip_empty else 0) | (2 if fma else 0) | (0 if self.share_tiles else 4) | (8 if graph else 0)
-            if band2 is not None:
-                # two-sample launch: blocks [split, B) are windows of the second band (mst_scale_space_band_pair)
-                _lib.check(self.lib.mst_scale_space_band_pair(_ptr(band), _ptr(band2[0]), int(band2[1]), bn, bdpx, st_arr, B, CH, lv,
-                                                              _ptr(found), found_cap, _ptr(count), _ptr(stats), _ptr(nz_count),
-                                                              flags, _ptr(ws), ws_bytes, _stream()))
-            elif band_src is not None:
-                _lib.check(self.lib.mst_scale_space_band(_ptr(band), bn, bdpx, st_arr, B, CH, lv, _ptr(found),
-                                                         found_cap, _ptr(count), _ptr(stats), _ptr(nz_count), flags,
-                                                         _ptr(ws), ws_bytes, _stream()))
-            else:
-                _lib.check(self.lib.mst_scale_space(_ptr(c), _ptr(nz), B, CH, lv, _ptr(found), found_cap,
-                                                    _ptr(count), _ptr(stats), flags, _ptr(ws), ws_bytes, _stream()))
-            if ev is not None:
-                ev[1].record()
-        return dict(args=(c, nz, nz_count, skip_empty, timing, fma, band_src), B=B, CH=CH, found_cap=found_cap, ws=ws,
-                    stats=stats, fit=fit, count=count, found=found, pval=pval, ev=ev, reuse=reuse, graph=graph, band2=band2)
+            ws_bytes = self._ws_bytes[(B, CH)] = int(self.lib.mst_scale_space_workspace_bytes(B, CH, ctypes.byref(self._lv_struct)))
+        return ws_bytes
 
-    def _ss_launch_staged(self, groups, band_src_all, skip_empty, found_cap, timing, fma):
-        """ONE fused launch over the blocks of all `groups` (consecutive lists of block origins), enqueued on the current stream
-        in one stage per group (mst_scale_space_band_stage): the work list is the whole launch's, so tiles shared by the last
-        block of a group and the first block of the next are still computed once -- separate launches per group recompute them
-        (0.4 ms per cut on 4000 x 4000 blocks) -- and after stage i the blocks of groups 0 .. i are final.  Returns one state
-        per group in the form _ss_finish takes: views of the launch's buffers for the group's blocks, with `done` = the event
-        behind the group's stage."""
-        band, bn, bdpx, CH = band_src_all
-        starts = [int(v) for g in groups for v in g]
-        B = len(starts)
-        cuts, acc = [], 0
-        for g in groups[:-1]:
-            acc += len(g)
-            cuts.append(acc)
-        st_arr = (ctypes.c_int64 * B)(*starts)
-        cut_arr = (ctypes.c_int32 * max(1, len(cuts)))(*cuts)
-        if found_cap is None:
-            found_cap = self._found_cap.get(CH, max(4096, (CH * CH) // 32))
-        lv = ctypes.byref(self._lv_struct)
-        ws_bytes = self._ws_bytes.get((B, CH))
-        if ws_bytes is None:
-            ws_bytes = self._ws_bytes[(B, CH)] = int(self.lib.mst_scale_space_workspace_bytes(B, CH, lv))
+    def _launch_buffers(self, B, CH, cap, reuse, nzc=False):
+        """ws, stats, fit, count, found (16-byte records), pval -- and with nzc=True the tested-pixel counts -- of one launch
+        (kept between calls for small launches when `reuse` names a slot, see _carve)"""
         T = _lib.MST_MAX_TESTED
-        flags = (1 if skip_empty else 0) | (2 if fma else 0) | (0 if self.share_tiles else 4)
-        out = []
+        ws_bytes = self._workspace_bytes(B, CH)
+        parts = [(ws_bytes, torch.uint8, (ws_bytes,)), (B * T * 16, torch.float64, (B, T, 2)), (B * T * 16, torch.float64, (B, T, 2)),
+                 (B * 4, torch.int32, (B,)), (B * cap * 16, torch.int64, (B, cap, 2)), (B * cap * 8, torch.float64, (B, cap))]
+        if nzc:
+            parts.append((B * 4, torch.int32, (B,)))
+        return self._carve(*parts, reuse=None if reuse is None else ("launch", reuse))
+
+    def _flags(self, skip_empty, fma, graph=False):
+        # MST_FLAG_NO_SHARE (4): every tile once per block; default: tiles inside two consecutive blocks computed once
+        # MST_FLAG_GRAPH (8): a launch that repeats with identical arguments is replayed as one hipGraph
+        return (1 if skip_empty else 0) | (2 if fma else 0) | (0 if self.share_tiles else 4) | (8 if graph else 0)
+
+    def _starts_array(self, starts):
+        key = tuple(starts)
+        arr = self._starts_arrays.get(key)          # repeated launches of the same blocks: no re-marshalling
+        if arr is None:
+            if len(self._starts_arrays) > 64:
+                self._starts_arrays.clear()
+            arr = self._starts_arrays[key] = (ctypes.c_int64 * len(key))(*key)
+        return arr
+
+    def _ss_launch(self, flags, nzc=None, blocks=None, band_src=None, band2=None, stages=None, found_cap=None, timing=None,
+                   reuse=None, graph=False):
+        """Record one fused launch and enqueue it on the current stream (no synchronisation).  Source: `blocks` = (c, nz),
+        dense blocks and their masks, or `band_src` = (band, n, dpx, starts, CH), windows of a band; `band2` = (second band,
+        split): ONE launch over the blocks of two bands (the two samples of a two-sample call; blocks [split, B) read the
+        second band).  `nzc`: the tested-pixel counts (input of the dense kernel, output of the band kernel); None = one of
+        the launch's own buffers.  `stages`: block counts of the groups of a staged launch (_enqueue).  `reuse`: the _carve slot
+        of the launch's buffers and its finish's staging.  `graph`: the finish is replayed as a hipGraph too."""
+        if band_src is not None:
+            band, n, dpx, starts, CH = band_src
+            B, src = len(starts), (band, n, dpx, self._starts_array(starts))
+        else:
+            (B, CH, _), src = blocks[0].shape, None
+        L = _Launch(B, CH, self._found_cap_for(CH) if found_cap is None else found_cap, flags, nzc=nzc, own_nzc=nzc is None,
+                    blocks=blocks, band_src=src, band2=band2, stages=stages, timing=timing, reuse=reuse, graph=graph)
+        return self._enqueue(L)
+
+    def _enqueue(self, L):
+        """(Re)allocate L's buffers at capacity L.cap and enqueue its fused launch on the current stream.
+        A staged launch (L.stages) is enqueued in one stage per group (mst_scale_space_band_stage): the work list is the whole
+        launch's, so tiles shared by the last block of a group and the first block of the next are still computed once --
+        separate launches per group recompute them (0.4 ms per cut on 4000 x 4000 blocks) -- and after stage i the blocks of
+        groups 0 .. i are final.  L.views then holds one record per group in the form _ss_finish takes: views of the launch's
+        buffers for the group's blocks, with `done` = the event behind the group's stage."""
+        B, CH, cap = L.B, L.CH, L.cap
+        lv = ctypes.byref(self._lv_struct)
+        ws_bytes = self._workspace_bytes(B, CH)
         with torch.cuda.device(self.device):
-            ws, stats, fit, count, found, pval, nzc = self._carve(
-                (ws_bytes, torch.uint8, (ws_bytes,)), (B * T * 16, torch.float64, (B, T, 2)),
-                (B * T * 16, torch.float64, (B, T, 2)), (B * 4, torch.int32, (B,)),
-                (B * found_cap * 16, torch.int64, (B, found_cap, 2)), (B * found_cap * 8, torch.float64, (B, found_cap)),
-                (B * 4, torch.int32, (B,)), reuse=("staged", 0))
-            cur = torch.cuda.current_stream(self.device)
-            b0 = 0
-            for gi, g in enumerate(groups):
-                ev = None
-                if timing is not None:
-                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    ev[0].record()
-                _lib.check(self.lib.mst_scale_space_band_stage(_ptr(band), bn, bdpx, st_arr, B, CH, lv, _ptr(found), found_cap,
-                                                               _ptr(count), _ptr(stats), _ptr(nzc), flags, _ptr(ws), ws_bytes,
-                                                               cut_arr, len(cuts), gi, _stream()))
-                if ev is not None:
-                    ev[1].record()
-                b1 = b0 + len(g)
-                sub_src = (band, bn, bdpx, [int(v) for v in g], CH)
-                out.append(dict(args=(None, None, nzc[b0:b1], skip_empty, timing, fma, sub_src), B=b1 - b0, CH=CH,
-                                found_cap=found_cap, ws=ws, stats=stats[b0:b1], fit=fit[b0:b1], count=count[b0:b1],
-                                found=found[b0:b1], pval=pval[b0:b1], ev=ev, reuse=1 + gi % 2, graph=False, band2=None,
-                                done=cur.record_event(), staged=True))
-                b0 = b1
-        return out
+            bufs = self._launch_buffers(B, CH, cap, L.reuse, nzc=L.own_nzc)
+            L.ws, L.stats, L.fit, L.count, L.found, L.pval = bufs[:6]
+            if L.own_nzc:
+                L.nzc = bufs[6]
+            tail = (_ptr(L.found), cap, _ptr(L.count), _ptr(L.stats))
+            if L.stages is not None:
+                band, n, dpx, st_arr = L.band_src
+                cuts = list(itertools.accumulate(L.stages))[:-1]
+                cut_arr = (ctypes.c_int32 * max(1, len(cuts)))(*cuts)
+                cur = torch.cuda.current_stream(self.device)
+                L.views, b0 = [], 0
+                for gi, nb in enumerate(L.stages):
+                    ev = _event_pair(L.timing)
+                    _lib.check(self.lib.mst_scale_space_band_stage(_ptr(band), n, dpx, st_arr, B, CH, lv, *tail, _ptr(L.nzc),
+                                                                   L.flags, _ptr(L.ws), ws_bytes, cut_arr, len(cuts), gi, _stream()))
+                    if ev is not None:
+                        ev[1].record()
+                    b1 = b0 + nb
+                    L.views.append(_Launch(nb, CH, cap, L.flags, nzc=L.nzc[b0:b1], timing=L.timing, ev=ev, reuse=1 + gi % 2,
+                                           done=cur.record_event(), stats=L.stats[b0:b1], fit=L.fit[b0:b1],
+                                           count=L.count[b0:b1], found=L.found[b0:b1], pval=L.pval[b0:b1]))
+                    b0 = b1
+                return L
+            L.ev = _event_pair(L.timing)
+            if L.blocks is not None:
+                c, nz = L.blocks
+                _lib.check(self.lib.mst_scale_space(_ptr(c), _ptr(nz), B, CH, lv, *tail, L.flags, _ptr(L.ws), ws_bytes,
+                                                    _stream()))
+            elif L.band2 is not None:
+                band, n, dpx, st_arr = L.band_src
+                _lib.check(self.lib.mst_scale_space_band_pair(_ptr(band), _ptr(L.band2[0]), int(L.band2[1]), n, dpx, st_arr, B, CH,
+                                                              lv, *tail, _ptr(L.nzc), L.flags, _ptr(L.ws), ws_bytes, _stream()))
+            else:
+                band, n, dpx, st_arr = L.band_src
+                _lib.check(self.lib.mst_scale_space_band(_ptr(band), n, dpx, st_arr, B, CH, lv, *tail, _ptr(L.nzc), L.flags,
+                                                         _ptr(L.ws), ws_bytes, _stream()))
+            if L.ev is not None:
+                L.ev[1].record()
+        return L
+
+    def _grow(self, L, relaunch=True):
+        """THE record-capacity overflow rule (rare: a block with an unusually dense set of local maxima): four times the
+        capacity, kept for every later launch of blocks of this size, and the same launch again on the current stream --
+        unless the caller redoes the work another way (relaunch=False)."""
+        L.cap = self._found_cap[L.CH] = L.cap * 4
+        return self._enqueue(L) if relaunch else L
 
     def _carve(self, *parts, reuse=None):
         """Device buffers for one launch: parts = (bytes, dtype, shape).  `reuse` (a hashable key, or None): SMALL sets (< 256 MB)
@@ -583,19 +591,19 @@ class ScaleSpaceEngine:
         return (h[16:16 + 4 * B].view(np.uint32).astype(np.int64), h[16 + cw:16 + cw + 4 * B].view(np.uint32).astype(np.int64),
                 h[16 + 2 * cw:16 + 2 * cw + 16 * _lib.MST_MAX_TESTED * B].view(np.float64).reshape(B, _lib.MST_MAX_TESTED, 2).copy())
 
-    def _ss_finish(self, st, packed=False, relaunch=True):
+    def _ss_finish(self, L, packed=False, relaunch=True):
         """p-values of the found pixels (ONE synchronisation of the launch stream: mst_found_finish brings the overflow flag, the
         record counts, the tested-pixel counts and the fits back in the same round trip); a record-capacity overflow re-runs the
-        kernel.  packed=True additionally leaves the records' pixel indices / levels as narrow device arrays (st["pix"], st["lvl"])
-        for a caller that downloads whole found sets."""
+        launch (_grow), or with relaunch=False is the caller's to handle.  packed=True: for a caller that downloads whole found
+        sets, the records may come back inside the same call (L.prefetched)."""
         nt = self.levels.n_tested
         with torch.cuda.device(self.device):
             while True:
-                B, cap = st["B"], st["found_cap"]
+                B, cap = L.B, L.cap
                 # whole-found-set downloads: the first `pitch` records of every block also come out as narrow, densely
                 # pitched arrays and are copied to the host inside the same call; pitch = the largest count the last launch of
                 # this block size saw + 5 % (the first launch of a size has no guess and takes the two-step download)
-                pitch = min(cap, self._prefetch_guess.get(st["CH"], 0)) if packed else 0
+                pitch = min(cap, self._prefetch_guess.get(L.CH, 0)) if packed else 0
                 summ = self._summary_pin(B)
                 dev3 = host3 = None
                 if pitch > 0:
@@ -603,54 +611,48 @@ class ScaleSpaceEngine:
                                                               (B * pitch * 4, torch.int32, (B, pitch)),
                                                               (B * pitch, torch.uint8, (B, pitch)),
                                                               (B * pitch * 8, torch.float64, (B, pitch)),
-                                                              reuse=None if st.get("reuse") is None else ("finish", st["reuse"]))
+                                                              reuse=None if L.reuse is None else ("finish", L.reuse))
                     dev3 = (d_pix, d_lvl, d_pv)
                     self._pin_flip ^= 1
                     host3 = (self._pinned("pix", (B, pitch), torch.int32), self._pinned("lvl", (B, pitch), torch.uint8),
                              self._pinned("pv", (B, pitch), torch.float64))
                 else:
                     scratch = torch.empty(summ.numel(), dtype=torch.uint8, device=self.device)
-                vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
                 try:
-                    _lib.check(self.lib.mst_found_finish(_ptr(st["found"]), cap, _ptr(st["count"]), _ptr(st["args"][2]),
-                                                         _ptr(st["stats"]), B, nt, _ptr(st["pval"]), _ptr(st["fit"]), pitch,
-                                                         *(vp(t) for t in (dev3 or (None, None, None))), _ptr(scratch),
-                                                         vp(summ), *(vp(t) for t in (host3 or (None, None, None))),
-                                                         8 if st.get("graph") else 0, _stream()))
+                    _lib.check(self.lib.mst_found_finish(_ptr(L.found), cap, _ptr(L.count), _ptr(L.nzc), _ptr(L.stats), B, nt,
+                                                         _ptr(L.pval), _ptr(L.fit), pitch,
+                                                         *(_ptr(t) for t in (dev3 or (None, None, None))), _ptr(scratch),
+                                                         _ptr(summ), *(_ptr(t) for t in (host3 or (None, None, None))),
+                                                         8 if L.graph else 0, _stream()))
                     break
                 except _lib.MstOverflow:
                     if not relaunch:            # the caller owns the launches (several of them behind this one finish)
                         raise
-                    c, nz, nz_count, skip_empty, timing, fma, band_src = st["args"]
-                    cap = st["found_cap"] * 4   # rare: a block with an unusually dense set of local maxima
-                    self._found_cap[st["CH"]] = cap
-                    st = self._ss_launch(c, nz, nz_count, skip_empty, cap, timing, fma, band_src, reuse=st.get("reuse"),
-                                         band2=st.get("band2"))
-        if st["ev"] is not None:
-            st["args"][4].append(st["ev"])      # mst_found_finish synchronised the stream: the events are complete
-        st["count_h"], st["nz_h"], st["fit_h"] = self._parse_summary(summ, B)
-        st["prefetched"] = None
+                    self._grow(L)
+        if L.ev is not None:
+            L.timing.append(L.ev)      # mst_found_finish synchronised the stream: the events are complete
+        L.count_h, L.nz_h, L.fit_h = self._parse_summary(summ, B)
+        L.prefetched = None
         if packed:
-            mx = int(st["count_h"].max(initial=0))
+            mx = int(L.count_h.max(initial=0))
             if host3 is not None:
                 # the records are on the host already when the guess held; False = tried (the staging set is already flipped)
-                st["prefetched"] = host3 if mx <= pitch else False
+                L.prefetched = host3 if mx <= pitch else False
             # next guess: 10 % above this launch's largest count, but never much below the last guess -- the launches of a run
             # differ (a genome's chromosomes, a chromosome's ends), and a guess that fails costs a second download
-            self._prefetch_guess[st["CH"]] = max(mx + mx // 10 + 64, int(0.995 * self._prefetch_guess.get(st["CH"], 0)))
-        return st
+            self._prefetch_guess[L.CH] = max(mx + mx // 10 + 64, int(0.995 * self._prefetch_guess.get(L.CH, 0)))
+        return L
 
-    def _ss_results(self, st, download, sort, with_value, with_q, select_below):
-        found, pval, count, fit, found_cap = st["found"], st["pval"], st["count"], st["fit"], st["found_cap"]
+    def _ss_results(self, L, download, sort, with_value, with_q, select_below):
         nt = self.levels.n_tested
         if not download:
-            return found, pval, count, fit, found_cap
-        host = (st.get("count_h"), st.get("fit_h"))
+            return L.found, L.pval, L.count, L.fit, L.cap
+        host = (L.count_h, L.fit_h)
         if select_below is not None:
-            return self._download_selected(found, pval, count, fit, nt, found_cap, float(select_below), host=host)
-        extra = {"q": self.fdr(pval, count, found_cap)} if with_q else None
-        return self._download(found, pval, count, fit, nt, sort=sort, with_value=with_value, extra=extra, host=host,
-                              prefetched=st.get("prefetched"))
+            return self._download_selected(L.found, L.pval, L.count, L.fit, nt, L.cap, float(select_below), host=host)
+        extra = {"q": self.fdr(L.pval, L.count, L.cap)} if with_q else None
+        return self._download(L.found, L.pval, L.count, L.fit, nt, sort=sort, with_value=with_value, extra=extra, host=host,
+                              prefetched=L.prefetched)
 
     def sigma_loop_band_overlapped(self, band, n, dpx, groups, CH, skip_empty=True, timing=None, fma=False, download=True,
                                    sort=True, with_value=True, with_q=True, select_below=None):
@@ -661,6 +663,15 @@ class ScaleSpaceEngine:
         (_pinned) -- valid until the group AFTER NEXT is fetched.  Consume each group as it is yielded (the pipeline's tail does)
         and copy what has to outlive that; `list(...)` over three or more groups leaves the first group's views showing the
         third group's bytes (scripts/staged_stress.py checks the path that way)."""
+        packed = download and select_below is None and not sort
+        src = lambda starts: (band, int(n), int(dpx), [int(v) for v in starts], int(CH))
+
+        def result(L):
+            res = self._ss_results(L, download, sort, with_value, with_q, select_below)
+            # the tested-pixel counts came back with the finish's round trip: hand them out as a HOST tensor (callers' .cpu() is
+            # then free) unless the caller asked for device buffers
+            return res + ((torch.from_numpy(L.nz_h.astype(np.uint32).view(np.int32)) if download else L.nzc),)
+
         if len(groups) == 1:
             # nothing to overlap: run on the caller's stream, without the side streams' events (a small launch -- six blocks of
             # 2000 x 2000 are 1.75 ms of kernel -- pays for every host-side call)
@@ -668,25 +679,18 @@ class ScaleSpaceEngine:
             # benchmark step, the same chromosome again -- presents identical arguments and the library replays it as ONE
             # hipGraph launch (MST_FLAG_GRAPH).  A graph cannot be captured on the legacy default stream: run on the first
             # side stream then.
-            starts = groups[0]
             cur = torch.cuda.current_stream(self.device)
             side = None
             if download and cur.cuda_stream == 0:
                 side = device_streams(self.device)[0]
                 side.wait_stream(cur)                       # the band was produced on the caller's stream
             with torch.cuda.stream(side if side is not None else cur):
-                if download:
-                    nzc, = self._carve((len(starts) * 4, torch.int32, (len(starts),)), reuse=("nzc", 0))
-                else:
-                    nzc = torch.empty(len(starts), dtype=torch.int32, device=self.device)
-                st = self._ss_launch(None, None, nzc, skip_empty, None, timing, fma,
-                                     (band, int(n), int(dpx), [int(v) for v in starts], int(CH)),
-                                     reuse=0 if download else None, graph=download)
-                st2 = self._ss_finish(st, packed=download and select_below is None and not sort)
-                res = self._ss_results(st2, download, sort, with_value, with_q, select_below)
+                L = self._ss_launch(self._flags(skip_empty, fma, graph=download), band_src=src(groups[0]), timing=timing,
+                                    reuse=0 if download else None, graph=download)
+                res = result(self._ss_finish(L, packed=packed))
             if side is not None:
                 cur.wait_stream(side)           # explicit: the caller's stream is ordered behind the side stream whatever the finish did
-            yield res + ((torch.from_numpy(st2["nz_h"].astype(np.uint32).view(np.int32)) if download else st2["args"][2]),)
+            yield res
             return
         cur = torch.cuda.current_stream(self.device)
         ready = cur.record_event()              # the band was produced on the caller's stream
@@ -700,7 +704,7 @@ class ScaleSpaceEngine:
             # (a launch's record lists, p-values and per-tile statistics are allocated for all of its blocks at once: 24 B x
             #  CH^2 / 32 per block and ~2.6 MB of statistics per 4000 x 4000 block -- 1.9 GB for chr1 at 1 kb.  Whole genomes at fine
             #  resolutions go through several staged launches of at most MUSTACHE_STAGED_GB, default 32, of such buffers each.)
-            per_block = 24 * self._found_cap.get(int(CH), max(4096, (int(CH) * int(CH)) // 32)) + \
+            per_block = 24 * self._found_cap_for(int(CH)) + \
                 (int(CH) // 30 + 2) * (int(CH) // 62 + 2) * (20 + 16 * self.levels.n_tested)
             budget = float(os.environ.get("MUSTACHE_STAGED_GB", "32")) * (1 << 30)
             chunks, acc = [[]], 0
@@ -711,57 +715,48 @@ class ScaleSpaceEngine:
                 chunks[-1].append(g)
                 acc += len(g)
             for chunk in chunks:
-                cap = None
-                done_groups = 0
-                while True:
-                    with torch.cuda.stream(ks), _lib.stage("scale-space launch"):
-                        sts = self._ss_launch_staged(chunk, (band, int(n), int(dpx), int(CH)), skip_empty, cap, timing, fma)
+                with torch.cuda.stream(ks), _lib.stage("scale-space launch"):
+                    L = self._ss_launch(self._flags(skip_empty, fma), band_src=src([v for g in chunk for v in g]),
+                                        stages=[len(g) for g in chunk], timing=timing, reuse="staged")
+                gi = 0
+                while gi < len(chunk):
+                    view = L.views[gi]
+                    fs.wait_event(view.done)
                     try:
-                        for gi in range(done_groups, len(chunk)):
-                            st = sts[gi]
-                            fs.wait_event(st["done"])
-                            with torch.cuda.stream(fs), _lib.stage("scale-space finish"):
-                                st2 = self._ss_finish(st, packed=select_below is None and not sort, relaunch=False)
-                                res = self._ss_results(st2, download, sort, with_value, with_q, select_below)
-                            yield res + (torch.from_numpy(st2["nz_h"].astype(np.uint32).view(np.int32)),)
-                            done_groups = gi + 1
-                        break
+                        with torch.cuda.stream(fs), _lib.stage("scale-space finish"):
+                            res = result(self._ss_finish(view, packed=packed, relaunch=False))
                     except _lib.MstOverflow:
-                        # rare (a block with an unusually dense set of local maxima): the whole launch again with four times the
-                        # record capacity; the groups already handed out stay as they are (their records were complete)
+                        # the whole launch again with more room; the groups already handed out stay as they are (their records
+                        # were complete)
                         ks.synchronize()
-                        cap = self._found_cap[int(CH)] = sts[0]["found_cap"] * 4
+                        with torch.cuda.stream(ks), _lib.stage("scale-space launch"):
+                            self._grow(L)
+                        continue
+                    yield res
+                    gi += 1
             cur.wait_stream(ks)
             cur.wait_stream(fs)
             return
 
-        def finish(st):
-            with torch.cuda.stream(st["stream"]):
-                st2 = self._ss_finish(st, packed=download and select_below is None and not sort)
-                res = self._ss_results(st2, download, sort, with_value, with_q, select_below)
-            # the tested-pixel counts came back with the finish's round trip: hand them out as a HOST tensor (callers' .cpu() is
-            # then free) unless the caller asked for device buffers
-            nzc = torch.from_numpy(st2["nz_h"].astype(np.uint32).view(np.int32)) if download else st2["args"][2]
-            return res + (nzc,)
+        def finish(s, L):
+            with torch.cuda.stream(s):
+                return result(self._ss_finish(L, packed=packed))
 
         pending = None
         for gi, starts in enumerate(groups):
             s = self._side_streams[gi % 2]
             s.wait_event(ready)
             if pending is not None:
-                s.wait_event(pending["kernel_done"])        # one fused kernel at a time
+                s.wait_event(pending[1].done)               # one fused kernel at a time
             with torch.cuda.stream(s):
-                nzc = torch.empty(len(starts), dtype=torch.int32, device=self.device)
-                st = self._ss_launch(None, None, nzc, skip_empty, None, timing, fma,
-                                     (band, int(n), int(dpx), [int(v) for v in starts], int(CH)),
-                                     reuse=(1 + gi % 2) if download else None)     # two launches in flight: two buffer sets
-                st["kernel_done"] = s.record_event()
-            st["stream"], st["nzc"] = s, nzc
+                L = self._ss_launch(self._flags(skip_empty, fma), band_src=src(starts), timing=timing,
+                                    reuse=(1 + gi % 2) if download else None)     # two launches in flight: two buffer sets
+                L.done = s.record_event()
             if pending is not None:
-                yield finish(pending)
-            pending = st
+                yield finish(*pending)
+            pending = (s, L)
         if pending is not None:
-            yield finish(pending)
+            yield finish(*pending)
         cur.wait_stream(self._side_streams[0])
         cur.wait_stream(self._side_streams[1])
 
@@ -777,38 +772,33 @@ class ScaleSpaceEngine:
             _lib.check(self.lib.mst_bh_fdr(_ptr(pval), _ptr(count), B, found_cap, _ptr(q), _ptr(ws), ws_bytes, _stream()))
         return q
 
-    def _download_selected(self, found, pval, count, fit, nt, found_cap, pt, full_sort=False, pair=None, host=None):
-        """BH-FDR and the selection q < pt on the device; only the selected records come back.  Default: mst_bh_select
-        (sorts only the records that can be selected -- same selected set, bit-identical q); full_sort=True runs mst_bh_fdr
-        over all records and then mst_select_below (kept as the cross-check).  pair = (ppair [2P, found_cap], P), two-sample
-        path: the selected records also carry `pair`, `value` and `v_other` (mst_pair_gather)."""
+    def _download_selected(self, found, pval, count, fit, nt, found_cap, pt, pair=None, host=None):
+        """BH-FDR and the selection q < pt on the device; only the selected records come back.  mst_bh_select sorts only the
+        records that can be selected (same selected set and bit-identical q as mst_bh_fdr over all records followed by
+        mst_select_below).  pair = (ppair [2P, found_cap], P), two-sample path: the selected records also carry `pair`, `value`
+        and `v_other` (mst_pair_gather)."""
         B = count.shape[0]
         cap = self._select_cap
         ws_bytes = int(self.lib.mst_bh_workspace_bytes(B, found_cap))
         if ws_bytes == 0:
             raise ValueError("too many found records for one BH launch (B * capacity must fit in int32)")
         with torch.cuda.device(self.device):
-            q = self.fdr(pval, count, found_cap) if full_sort else None
-            ws = None if full_sort else torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
             while True:
                 pix = torch.empty((B, cap), dtype=torch.int32, device=self.device)
                 lvl = torch.empty((B, cap), dtype=torch.int32, device=self.device)
                 qs = torch.empty((B, cap), dtype=torch.float64, device=self.device)
                 n_sel = torch.empty(B, dtype=torch.int32, device=self.device)
-                if full_sort:
-                    _lib.check(self.lib.mst_select_below(_ptr(found), _ptr(q), _ptr(count), B, found_cap, pt, cap,
-                                                         _ptr(pix), _ptr(lvl), _ptr(qs), _ptr(n_sel), _stream()))
-                else:
-                    # without the library's own look at the subset sizes (mst_bh_select_nowait: the in-LDS sort for every
-                    # block): the counts are read right below anyway, and a block whose subset does not fit it says so there
-                    idx = torch.empty((B, cap), dtype=torch.int32, device=self.device) if pair is not None else None
-                    args = (_ptr(found), _ptr(pval), _ptr(count), B, found_cap, pt, cap, _ptr(pix), _ptr(lvl), _ptr(qs),
-                            None if idx is None else _ptr(idx), _ptr(n_sel), _ptr(ws), ws_bytes, _stream())
-                    # the sort's LDS request: 1024 records (14 KB) until a launch of this engine needed more -- this kernel runs
-                    # next to the following group's fused kernel, which leaves little LDS free
-                    _lib.check(self.lib.mst_bh_select_nowait(*(args[:12] + (self._bh_lds_records,) + args[12:])))
+                # without the library's own look at the subset sizes (mst_bh_select_nowait: the in-LDS sort for every
+                # block): the counts are read right below anyway, and a block whose subset does not fit it says so there
+                idx = torch.empty((B, cap), dtype=torch.int32, device=self.device) if pair is not None else None
+                args = (_ptr(found), _ptr(pval), _ptr(count), B, found_cap, pt, cap, _ptr(pix), _ptr(lvl), _ptr(qs),
+                        None if idx is None else _ptr(idx), _ptr(n_sel), _ptr(ws), ws_bytes, _stream())
+                # the sort's LDS request: 1024 records (14 KB) until a launch of this engine needed more -- this kernel runs
+                # next to the following group's fused kernel, which leaves little LDS free
+                _lib.check(self.lib.mst_bh_select_nowait(*(args[:12] + (self._bh_lds_records,) + args[12:])))
                 n_h = n_sel.cpu().numpy().view(np.uint32).astype(np.int64)
-                if not full_sort and (n_h == 0xFFFFFFFF).any():       # MST_BH_RETRY: this launch through the synchronising form
+                if (n_h == 0xFFFFFFFF).any():       # MST_BH_RETRY: this launch through the synchronising form
                     self._bh_lds_records = min(4096, self._bh_lds_records * 2)
                     if idx is not None:
                         _lib.check(self.lib.mst_bh_select_records(*args))
@@ -976,6 +966,40 @@ class ScaleSpaceEngine:
                                                      P, CH, n_oct, tpo, off, _ptr(ppair), _stream()))
         return ppair, fit
 
+    def _pair_launch(self, bands, n, dpx, starts, CH, skip_empty, reuse=None, graph=False):
+        """Enqueue a two-sample call's device work on the current stream: both samples' sigma loops in ONE fused launch over 2P
+        blocks (mst_scale_space_band_pair: rows [0, P) sample 1, [P, 2P) the same windows of sample 2's band -- one set of
+        record buffers, so ONE mst_found_finish serves both) and, right behind it, the difference kernel (mst_diff_dog_band: it
+        needs the bands only).  `graph`: the fused launch is replayed as a hipGraph.  Returns (launch, dog, norm.fit, keep);
+        `keep` holds the difference kernel's other buffers until the caller is done."""
+        P = len(starts)
+        starts = [int(v) for v in starts]
+        L = self._ss_launch(self._flags(skip_empty, False, graph=graph), band_src=(bands[0], int(n), int(dpx), starts + starts, int(CH)),
+                            band2=(bands[1], P), reuse=reuse)
+        lv = ctypes.byref(self._lv_struct)
+        dev = self.device
+        with torch.cuda.device(dev):
+            st_arr = (ctypes.c_int64 * P)(*starts)
+            dog = torch.empty((len(self.levels.octave_values), P, CH, CH), dtype=torch.float64, device=dev)
+            nfit = torch.empty((len(self.levels.octave_values), P, 2), dtype=torch.float64, device=dev)
+            mcount = torch.empty(P, dtype=torch.int32, device=dev)
+            ws_bytes = int(self.lib.mst_diff_dog_workspace_bytes(P, CH, lv))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(self.lib.mst_diff_dog_band(_ptr(bands[0]), _ptr(bands[1]), int(n), int(dpx), st_arr, P, CH, lv, _ptr(dog),
+                                                  _ptr(nfit), _ptr(mcount), _ptr(ws), ws_bytes, _stream()))
+        return L, dog, nfit, (ws, mcount, st_arr)
+
+    def _pair_pvalues(self, L, P, dog, nfit, ppair=None):
+        """Differential p-values of a two-sample launch's records (mst_pair_pvalues_dog over rows [0, P), then [P, 2P))
+        -> ppair [2P, cap] (device; allocated here unless given)."""
+        if ppair is None:
+            ppair = torch.empty((2 * P, L.cap), dtype=torch.float64, device=self.device)
+        n_oct, tpo = len(self.levels.octave_values), self.levels.s - 1
+        for off in (0, P):
+            _lib.check(self.lib.mst_pair_pvalues_dog(_ptr(L.found), L.cap, _ptr(L.count), _ptr(dog), _ptr(nfit), P, L.CH, n_oct, tpo,
+                                                     off, _ptr(ppair), _stream()))
+        return ppair
+
     def run_band_pairs(self, bands, n, dpx, starts, CH, skip_empty=True, select_below=None):
         """Both samples' sigma loops straight from their bands + the pair p-values: PairBandBatch over 2P blocks whose
         records carry `pair` and `q`.  select_below = pt (what the per-chromosome driver passes): BH, the selection q < pt and
@@ -983,94 +1007,57 @@ class ScaleSpaceEngine:
         `value` and `v_other` (the partner sample's winning value at that pixel, NaN if it did not find it); without it the
         whole found sets are downloaded, sorted by pixel (the cross-check form)."""
         P = len(starts)
-        lt = self.levels
-        n_oct, tpo = len(lt.octave_values), lt.s - 1
-        lv = ctypes.byref(self._lv_struct)
-        T, nt = _lib.MST_MAX_TESTED, lt.n_tested
-        starts_i = [int(v) for v in starts]
-        st_arr = (ctypes.c_int64 * P)(*starts_i)
-        cap = self._found_cap.get(CH, max(4096, (CH * CH) // 32))
-        ws_bytes = self._ws_bytes.get((2 * P, CH))
-        if ws_bytes is None:
-            ws_bytes = self._ws_bytes[(2 * P, CH)] = int(self.lib.mst_scale_space_workspace_bytes(2 * P, CH, lv))
+        nt = self.levels.n_tested
         # A SMALL call (its buffers are kept between calls, _carve) repeats with identical arguments when the caller repeats it: the
         # two fused launches are then replayed as hipGraphs (MST_FLAG_GRAPH: uploads, counter zeroing, kernel, reduction in one
         # launch each, no dispatch gaps -- ~40 us of idle device before each kernel otherwise).  A graph cannot be captured on the
         # legacy default stream: such a call runs on the first side stream.
-        small = 2 * P * cap * 24 + ws_bytes < (200 << 20)
+        small = 2 * P * self._found_cap_for(CH) * 24 + self._workspace_bytes(2 * P, CH) < (200 << 20)
         cur = torch.cuda.current_stream(self.device)
         side = None
         if small and cur.cuda_stream == 0:
             side = device_streams(self.device)[0]
             side.wait_stream(cur)                           # the bands were produced on the caller's stream
         with torch.cuda.device(self.device), torch.cuda.stream(side if side is not None else cur):
-            dog = None
+            L, dog, nfit, _keep = self._pair_launch(bands, n, dpx, starts, CH, skip_empty, reuse="pairs", graph=small)
             while True:
-                # ONE set of record buffers for both samples (sample 1 in rows [0, P), sample 2 in [P, 2P)): the two fused
-                # launches write their halves, one mst_found_finish (one synchronisation) serves both, and nothing has to be
-                # concatenated afterwards.  Small sets are kept between calls (_carve).
-                found, pval, count, stats, fit, nzc, ws = self._carve(
-                    (2 * P * cap * 16, torch.int64, (2 * P, cap, 2)), (2 * P * cap * 8, torch.float64, (2 * P, cap)),
-                    (2 * P * 4, torch.int32, (2 * P,)), (2 * P * T * 16, torch.float64, (2 * P, T, 2)),
-                    (2 * P * T * 16, torch.float64, (2 * P, T, 2)), (2 * P * 4, torch.int32, (2 * P,)),
-                    (ws_bytes, torch.uint8, (ws_bytes,)), reuse=("pairs", 0))
-                # ... filled by ONE fused launch over the 2P blocks (mst_scale_space_band_pair: sample 2's blocks read its own band)
-                self._ss_launch(None, None, nzc, skip_empty, cap, None, False, (bands[0], int(n), int(dpx), starts_i + starts_i, int(CH)),
-                                out=dict(ws=ws, stats=stats, fit=fit, count=count, found=found, pval=pval), graph=small,
-                                band2=(bands[1], P))
-                if dog is None:
-                    # the difference kernel needs the bands only: queued behind the sigma loops, before anything is waited for
-                    dog = torch.empty((n_oct, P, CH, CH), dtype=torch.float64, device=self.device)
-                    nfit = torch.empty((n_oct, P, 2), dtype=torch.float64, device=self.device)
-                    mcount = torch.empty(P, dtype=torch.int32, device=self.device)
-                    dws_bytes = int(self.lib.mst_diff_dog_workspace_bytes(P, CH, lv))
-                    dws = torch.empty(dws_bytes, dtype=torch.uint8, device=self.device)
-                    _lib.check(self.lib.mst_diff_dog_band(_ptr(bands[0]), _ptr(bands[1]), int(n), int(dpx), st_arr, P, CH, lv,
-                                                          _ptr(dog), _ptr(nfit), _ptr(mcount), _ptr(dws), dws_bytes, _stream()))
-                st = dict(args=(None, None, nzc, skip_empty, None, False, None), B=2 * P, CH=CH, found_cap=cap, stats=stats,
-                          fit=fit, count=count, found=found, pval=pval, ev=None, reuse=None, graph=False)
                 try:
-                    if select_below is not None:
-                        # the per-chromosome driver's form: everything behind the kernels is queued at once and waited for ONCE
-                        done = self._pairs_one_wait(st, P, dog, nfit, n_oct, tpo, float(select_below))
-                        if done is not None:
-                            recs, fits, nz_h, norm_fit = done
-                            batch = PairBandBatch(self, bands, n, dpx, starts, CH, nz_h, recs, fits)
-                            batch.norm_fit = norm_fit
-                            return batch
-                    st = self._ss_finish(st, relaunch=False)
+                    # the per-chromosome driver's form (select_below): everything behind the kernels is queued at once and waited
+                    # for ONCE; None = it takes the step-by-step path below
+                    done = None if select_below is None else self._pairs_one_wait(L, P, dog, nfit, float(select_below))
+                    if done is None:
+                        self._ss_finish(L, relaunch=False)
                     break
-                except _lib.MstOverflow:        # rare: a block with an unusually dense set of local maxima -- both samples again
-                    cap = cap * 4
-                    self._found_cap[CH] = cap
-            ppair = torch.empty((2 * P, cap), dtype=torch.float64, device=self.device)
-            for off in (0, P):
-                _lib.check(self.lib.mst_pair_pvalues_dog(_ptr(found), cap, _ptr(count), _ptr(dog), _ptr(nfit), P, CH, n_oct, tpo,
-                                                         off, _ptr(ppair), _stream()))
-            nfit_p = self._pinned("pair_nfit", tuple(nfit.shape), torch.float64)      # lands with the downloads' synchronisation
-            nfit_p.copy_(nfit, non_blocking=True)
-            host = (st["count_h"], st["fit_h"])
-            if select_below is not None:
-                recs, fits = self._download_selected(found, pval, count, fit, nt, cap, float(select_below), pair=(ppair, P),
-                                                     host=host)
+                except _lib.MstOverflow:        # both samples again (the difference kernel's results stay valid)
+                    self._grow(L)
+            if done is not None:
+                recs, fits, nz_h, norm_fit = done
             else:
-                recs, fits = self._download(found, pval, count, fit, nt, sort=True,
-                                            extra={"pair": ppair, "q": self.fdr(pval, count, cap)}, host=host)
-            torch.cuda.current_stream().synchronize()
-            norm_fit = nfit_p.numpy().copy()
-        batch = PairBandBatch(self, bands, n, dpx, starts, CH, st["nz_h"], recs, fits)
+                ppair = self._pair_pvalues(L, P, dog, nfit)
+                nfit_p = self._pinned("pair_nfit", tuple(nfit.shape), torch.float64)      # lands with the downloads' synchronisation
+                nfit_p.copy_(nfit, non_blocking=True)
+                host = (L.count_h, L.fit_h)
+                if select_below is not None:
+                    recs, fits = self._download_selected(L.found, L.pval, L.count, L.fit, nt, L.cap, float(select_below),
+                                                         pair=(ppair, P), host=host)
+                else:
+                    recs, fits = self._download(L.found, L.pval, L.count, L.fit, nt, sort=True,
+                                                extra={"pair": ppair, "q": self.fdr(L.pval, L.count, L.cap)}, host=host)
+                torch.cuda.current_stream().synchronize()
+                nz_h, norm_fit = L.nz_h, nfit_p.numpy().copy()
+        batch = PairBandBatch(self, bands, n, dpx, starts, CH, nz_h, recs, fits)
         batch.norm_fit = norm_fit
         return batch
 
-    def _pairs_one_wait(self, st, P, dog, nfit, n_oct, tpo, pt):
+    def _pairs_one_wait(self, L, P, dog, nfit, pt):
         """Behind the two sigma loops and the difference kernel of a two-sample launch: p-values (mst_found_finish, no wait), pair
         p-values, BH + selection q < pt (mst_bh_select_nowait), the differential test's look-ups for the selected records
         (mst_pair_gather) and the downloads -- all queued back to back, ONE synchronisation, then the checks that used to cost a
         round trip each (record capacity: MstOverflow to the caller; selection capacity / oversized BH subset: None, the caller
         takes the step-by-step path).  A call on six block pairs of 2000 x 2000 is 1.4 ms of kernels: three more waits of
         ~45 us each were 10 % of it.  Returns (records, fits, tested-pixel counts, norm.fit) or None."""
-        B, cap, CH = st["B"], st["found_cap"], st["CH"]
-        found, pval, count, fit, stats, nzc = st["found"], st["pval"], st["count"], st["fit"], st["stats"], st["args"][2]
+        B, cap = L.B, L.cap
+        found, pval, count, fit, stats, nzc = L.found, L.pval, L.count, L.fit, L.stats, L.nzc
         nt = self.levels.n_tested
         sel = self._pair_sel_cap = getattr(self, "_pair_sel_cap", 256)
         ws_bytes = int(self.lib.mst_bh_workspace_bytes(B, cap))
@@ -1090,9 +1077,7 @@ class ScaleSpaceEngine:
         none3 = (None, None, None)
         _lib.check(self.lib.mst_found_finish(_ptr(found), cap, _ptr(count), _ptr(nzc), _ptr(stats), B, nt, _ptr(pval), _ptr(fit), 0,
                                              *none3, _ptr(scratch), ctypes.c_void_p(summ.data_ptr()), *none3, 16, _stream()))
-        for off in (0, P):
-            _lib.check(self.lib.mst_pair_pvalues_dog(_ptr(found), cap, _ptr(count), _ptr(dog), _ptr(nfit), P, CH, n_oct, tpo, off,
-                                                     _ptr(ppair), _stream()))
+        self._pair_pvalues(L, P, dog, nfit, ppair)
         _lib.check(self.lib.mst_bh_select_nowait(_ptr(found), _ptr(pval), _ptr(count), B, cap, pt, sel, _ptr(pix), _ptr(lvl), _ptr(qs),
                                                  _ptr(idx), _ptr(n_sel), self._bh_lds_records, _ptr(ws), ws_bytes, _stream()))
         _lib.check(self.lib.mst_pair_gather(_ptr(found), cap, _ptr(count), _ptr(ppair), int(P), _ptr(idx), _ptr(pix), _ptr(n_sel), sel,
@@ -1148,53 +1133,31 @@ class ScaleSpaceEngine:
         cur = torch.cuda.current_stream(self.device)
         ready = cur.record_event()
         streams = device_streams(self.device)[:2]
-        lt = self.levels
-        n_oct, tpo = len(lt.octave_values), lt.s - 1
-        lv = ctypes.byref(self._lv_struct)
 
         def launch(gi, starts):
             s = streams[gi % 2]
             s.wait_event(ready)
             if gi:
                 s.wait_event(launch.prev_done)                   # one group's kernels at a time
-            P = len(starts)
-            with torch.cuda.stream(s), torch.cuda.device(self.device):
-                cap = self._found_cap.get(CH, max(4096, (CH * CH) // 32))
-                nzc = torch.empty(2 * P, dtype=torch.int32, device=self.device)
-                st2 = [int(v) for v in starts]
-                # both samples' blocks in ONE fused launch (rows [0, P) sample 1, [P, 2P) sample 2: mst_scale_space_band_pair)
-                sst = self._ss_launch(None, None, nzc, skip_empty, cap, None, False, (bands[0], int(n), int(dpx), st2 + st2, int(CH)),
-                                      band2=(bands[1], P))
-                # the difference kernel needs the bands only: queue it behind the sigma loops right away
-                st_arr = (ctypes.c_int64 * P)(*[int(v) for v in starts])
-                dog = torch.empty((n_oct, P, CH, CH), dtype=torch.float64, device=self.device)
-                nfit = torch.empty((n_oct, P, 2), dtype=torch.float64, device=self.device)
-                mcount = torch.empty(P, dtype=torch.int32, device=self.device)
-                ws_bytes = int(self.lib.mst_diff_dog_workspace_bytes(P, CH, lv))
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-                _lib.check(self.lib.mst_diff_dog_band(_ptr(bands[0]), _ptr(bands[1]), int(n), int(dpx), st_arr, P, CH, lv,
-                                                      _ptr(dog), _ptr(nfit), _ptr(mcount), _ptr(ws), ws_bytes, _stream()))
+            with torch.cuda.stream(s):
+                work = self._pair_launch(bands, n, dpx, starts, CH, skip_empty)
                 launch.prev_done = s.record_event()
-            return dict(stream=s, starts=starts, cap=cap, nzc=nzc, sst=sst, dog=dog, nfit=nfit, keep=(ws, mcount, st_arr))
+            return s, starts, work
 
-        def collect(g):
-            P = len(g["starts"])
-            with torch.cuda.stream(g["stream"]), torch.cuda.device(self.device):
-                st = self._ss_finish(g["sst"])
-                if st["found_cap"] != g["cap"]:
-                    # a record-capacity overflow re-ran the launch with more room: redo this group the plain way
-                    return self.run_band_pairs(bands, n, dpx, g["starts"], CH, skip_empty=skip_empty, select_below=select_below)
-                cap = g["cap"]
-                found, pval, count, fit = st["found"], st["pval"], st["count"], st["fit"]
-                ppair = torch.empty((2 * P, cap), dtype=torch.float64, device=self.device)
-                for off in (0, P):
-                    _lib.check(self.lib.mst_pair_pvalues_dog(_ptr(found), cap, _ptr(count), _ptr(g["dog"]), _ptr(g["nfit"]), P, CH,
-                                                             n_oct, tpo, off, _ptr(ppair), _stream()))
-                recs, fits = self._download_selected(found, pval, count, fit, self.levels.n_tested, cap, float(select_below),
-                                                     pair=(ppair, P))
-                nz_h = st["nz_h"]
-                norm_fit = g["nfit"].cpu().numpy()
-            batch = PairBandBatch(self, bands, n, dpx, g["starts"], CH, nz_h, recs, fits)
+        def collect(s, starts, work):
+            P = len(starts)
+            L, dog, nfit, _keep = work
+            with torch.cuda.stream(s), torch.cuda.device(self.device):
+                try:
+                    self._ss_finish(L, relaunch=False)
+                except _lib.MstOverflow:
+                    # more room from now on, and this group redone the plain way
+                    self._grow(L, relaunch=False)
+                    return self.run_band_pairs(bands, n, dpx, starts, CH, skip_empty=skip_empty, select_below=select_below)
+                recs, fits = self._download_selected(L.found, L.pval, L.count, L.fit, self.levels.n_tested, L.cap,
+                                                     float(select_below), pair=(self._pair_pvalues(L, P, dog, nfit), P))
+                norm_fit = nfit.cpu().numpy()
+            batch = PairBandBatch(self, bands, n, dpx, starts, CH, L.nz_h, recs, fits)
             batch.norm_fit = norm_fit
             return batch
 
@@ -1202,9 +1165,9 @@ class ScaleSpaceEngine:
         for gi, starts in enumerate(groups):
             g = launch(gi, starts)
             if pending is not None:
-                yield collect(pending)
+                yield collect(*pending)
             pending = g
-        yield collect(pending)
+        yield collect(*pending)
         cur.wait_stream(streams[0])
         cur.wait_stream(streams[1])
 

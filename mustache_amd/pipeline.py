@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import ScaleSpaceEngine, BlockBatch, BandBatch, _ptr, _stream
+from .engine import ScaleSpaceEngine, BlockBatch, BandBatch, default_found_cap, _ptr, _stream
 from .normalize import band_from_coo, band_from_host_coo, normalize_band
 from .sharding import shard_blocks, gather_loops, world
 from .tail import batch_tail
@@ -31,8 +31,9 @@ def split_groups(items, per, px_per_item=16e6):
     return groups
 
 
-# what the last run_band / run_layout of this process measured: blocks, Mpix, seconds in the scale-space stage and in the tail,
-# the fused kernel's own time (HIP events) -- the command line's verbose summary prints it (mustache.main, `-v`)
+# what the last run_band / run_layout of this process measured: blocks, Mpix, launches, seconds in the scale-space stage and in
+# the tail, the fused kernel's own time (HIP events; band path only) -- the command line's verbose summary prints it
+# (mustache.main, `-v`).  Every run replaces it.
 LAST_RUN = {}
 
 
@@ -126,7 +127,7 @@ class ChromosomePipeline:
         return c, nz, nzc
 
     def batches(self, idx, CH, dense=True):
-        per_block = (CH * CH * 9 if dense else 0) + max(4096, CH * CH // 32) * 48
+        per_block = (CH * CH * 9 if dense else 0) + default_found_cap(CH) * 48
         bs = max(1, int(self.max_batch_bytes // per_block))
         return [idx[i:i + bs] for i in range(0, len(idx), bs)]
 
@@ -134,25 +135,17 @@ class ChromosomePipeline:
                  dense=False):
         """band: normalised band on the device.  Returns this chromosome's loops (all ranks, after the gather).
         `shard=(rank, world_size)` runs one rank's share without a process group (no gather) -- used by tests."""
+        global LAST_RUN
         CH, start, end = block_tiling(n, dpx)
         rank, ws = world() if distributed else (0, 1)
         if shard is not None:
             rank, ws, distributed = shard[0], shard[1], False
         mine = shard_blocks(len(start), rank, ws)
-        loops = []
-        t_dev = t_tail = 0.0
-
-        def tail(batch, group, starts_g):
-            with _lib.stage("tail"):
-                tails = batch_tail(batch, list(range(len(group))), starts_g, pt, st, intra=True)
-            for j, i in enumerate(group):
-                mask = block_mask_size(i, start, end, dpx)
-                for lp in tails[j]:
-                    if lp[0] >= start[i] + mask or lp[1] >= start[i] + mask:      # mustache.py:957-959
-                        loops.append([lp[0], lp[1], lp[2], lp[3]])
-
+        loops = [[]]
         if dense:           # materialise [B, CH, CH] blocks first (what mustache() gets from its caller) -- cross-check path
-            for group in self.batches(mine, CH, dense):
+            t_dev = t_tail = 0.0
+            groups = self.batches(mine, CH, dense)
+            for group in groups:
                 t0 = time.time()
                 starts_g = [start[i] for i in group]
                 c, nz, nzc = self.blocks_from_band(band, n, dpx, starts_g, CH)
@@ -161,31 +154,52 @@ class ChromosomePipeline:
                 batch = BlockBatch(self.engine, c, nz, CH, len(group),
                                    nzc.cpu().numpy().view(np.uint32).astype(np.int64), found, fits)
                 t1 = time.time()
-                tail(batch, group, starts_g)
+                self._tail(batch, [(0, i, s, s) for i, s in zip(group, starts_g)], [(CH, start, end)], dpx, st, pt, loops)
                 t_dev += t1 - t0
                 t_tail += time.time() - t1
                 del c, nz, batch
+            run = dict(scale_space_s=t_dev, tail_s=t_tail, launches=len(groups))
         else:
             # default: blocks are windows of the band, cut inside the fused kernel.  The blocks go through it in groups of
             # `overlap_blocks`; BH + selection + download AND the host tail of one group run under the kernel of the next
-            groups = split_groups(mine, self.overlap_blocks, float(CH) * CH)
-            starts = [[start[i] for i in g] for g in groups]
-            t0 = time.time()
-            kev = []                               # (start, end) events of the fused kernel's launches / stages
-            for group, starts_g, (found, fits, nzc) in zip(groups, starts, self.engine.sigma_loop_band_overlapped(
-                    band, n, dpx, starts, CH, skip_empty=skip_empty, with_value=False, select_below=pt, timing=kev)):
-                t1 = time.time()
-                batch = BandBatch(self.engine, band, n, dpx, starts_g, CH,
-                                  nzc.cpu().numpy().view(np.uint32).astype(np.int64), found, fits)
-                tail(batch, group, starts_g)
-                t_tail += time.time() - t1
-                del batch
-            t_dev = time.time() - t0 - t_tail
-            LAST_RUN.update(kernel_ms=sum(a.elapsed_time(b) for a, b in kev))
-        LAST_RUN.update(scale_space_s=t_dev, tail_s=t_tail, blocks=len(mine), chunk=CH, mpix=len(mine) * CH * CH / 1e6)
+            groups = split_groups([(0, i, start[i], start[i]) for i in mine], self.overlap_blocks, float(CH) * CH)
+            run = self._run_band_groups(band, n, dpx, CH, groups, [(CH, start, end)], st, pt, skip_empty, loops)
+        run.update(blocks=len(mine), chunk=CH, mpix=len(mine) * CH * CH / 1e6)
+        LAST_RUN = run
         if timings is not None:
-            timings.update(LAST_RUN)
-        return gather_loops(loops, device=self.device) if (distributed and ws > 1) else loops
+            timings.update(run)
+        return gather_loops(loops[0], device=self.device) if (distributed and ws > 1) else loops[0]
+
+    def _tail(self, batch, group, tiling, dpx, st, pt, loops):
+        """The host tail of one batch and the overlap mask (mustache.py:957-959).  group: (chromosome, block index, origin in
+        the chromosome, origin in the band) per block of the batch; tiling[c] = block_tiling of chromosome c; the loops of
+        chromosome c go to loops[c], in chromosome coordinates."""
+        with _lib.stage("tail"):
+            tails = batch_tail(batch, list(range(len(group))), [g[2] for g in group], pt, st, intra=True)
+        for j, (c, i, s_loc, _) in enumerate(group):
+            _, start, end = tiling[c]
+            mask = block_mask_size(i, start, end, dpx)
+            for lp in tails[j]:
+                if lp[0] >= s_loc + mask or lp[1] >= s_loc + mask:
+                    loops[c].append([lp[0], lp[1], lp[2], lp[3]])
+
+    def _run_band_groups(self, band, n, dpx, CH, groups, tiling, st, pt, skip_empty, loops):
+        """The band path of run_band and run_layout: the groups' fused launches (engine.sigma_loop_band_overlapped), each
+        group's host tail (_tail) under the next group's kernel.  Returns the run's timings."""
+        t0 = time.time()
+        t_tail = 0.0
+        kev = []                               # (start, end) events of the fused kernel's launches / stages
+        for group, (found, fits, nzc) in zip(groups, self.engine.sigma_loop_band_overlapped(
+                band, n, dpx, [[g[3] for g in grp] for grp in groups], CH, skip_empty=skip_empty, with_value=False,
+                select_below=pt, timing=kev)):
+            t1 = time.time()
+            batch = BandBatch(self.engine, band, n, dpx, [g[3] for g in group], CH,
+                              nzc.cpu().numpy().view(np.uint32).astype(np.int64), found, fits)
+            self._tail(batch, group, tiling, dpx, st, pt, loops)
+            t_tail += time.time() - t1
+            del batch
+        return dict(scale_space_s=time.time() - t0 - t_tail, tail_s=t_tail, launches=len(groups),
+                    kernel_ms=sum(a.elapsed_time(b) for a, b in kev))
 
     def blocks_per_launch(self, CH):
         """Blocks per fused-kernel launch on the band path: 16 of 4000 x 4000, 64 of 2000 x 2000 (>= 256 Mpix per launch)."""
@@ -203,34 +217,15 @@ class ChromosomePipeline:
 
     def run_layout(self, lay, gband, st, pt, skip_empty=True, timings=None):
         """run_genome's body on a prepared layout + genome band."""
-        CH, dpx, ns = lay.CH, lay.dpx, lay.ns
-        per = self.blocks_per_launch(CH)
-        groups = split_groups(lay.blocks, per, float(CH) * CH)
-        loops = [[] for _ in ns]
-        t0 = time.time()
-        t_tail = 0.0
-        kev = []
-        for group, (found, fits, nzc) in zip(groups, self.engine.sigma_loop_band_overlapped(
-                gband, lay.N, dpx, [[g[3] for g in grp] for grp in groups], CH, skip_empty=skip_empty, with_value=False,
-                select_below=pt, timing=kev)):
-            t1 = time.time()
-            batch = BandBatch(self.engine, gband, lay.N, dpx, [g[3] for g in group], CH,
-                              nzc.cpu().numpy().view(np.uint32).astype(np.int64), found, fits)
-            with _lib.stage("tail"):
-                tails = batch_tail(batch, list(range(len(group))), [g[2] for g in group], pt, st, intra=True)
-            for j, (c, i, s_loc, _) in enumerate(group):
-                _, start, end = lay.tiling[c]
-                mask = block_mask_size(i, start, end, dpx)
-                for lp in tails[j]:
-                    if lp[0] >= s_loc + mask or lp[1] >= s_loc + mask:            # mustache.py:957-959
-                        loops[c].append([lp[0], lp[1], lp[2], lp[3]])
-            t_tail += time.time() - t1
-            del batch
-        LAST_RUN.update(scale_space_s=time.time() - t0 - t_tail, tail_s=t_tail, blocks=len(lay.blocks), chunk=CH,
-                        mpix=len(lay.blocks) * CH * CH / 1e6, launches=len(groups),
-                        kernel_ms=sum(a.elapsed_time(b) for a, b in kev))
+        global LAST_RUN
+        CH = lay.CH
+        loops = [[] for _ in lay.ns]
+        groups = split_groups(lay.blocks, self.blocks_per_launch(CH), float(CH) * CH)
+        run = self._run_band_groups(gband, lay.N, lay.dpx, CH, groups, lay.tiling, st, pt, skip_empty, loops)
+        run.update(blocks=len(lay.blocks), chunk=CH, mpix=len(lay.blocks) * CH * CH / 1e6)
+        LAST_RUN = run
         if timings is not None:
-            timings.update(LAST_RUN)
+            timings.update(run)
         return loops
 
     def normalized_band_packed(self, pc, dpx, normalized=False):

@@ -32,7 +32,7 @@ def launch(eng, variant, stream, skip):
     os.environ["MST_ABLATE"] = str(variant)
     with torch.cuda.stream(stream):                 # the launch only (no finish: it would wait for the kernel)
         nzc = torch.empty(len(start), dtype=torch.int32, device=dev)
-        keep.append(eng._ss_launch(None, None, nzc, skip, None, None, False, (band, int(n), int(dpx), [int(v) for v in start], int(CH))))
+        keep.append(eng._ss_launch(eng._flags(skip, False), nzc=nzc, band_src=(band, int(n), int(dpx), [int(v) for v in start], int(CH))))
 
 
 def timed(jobs, skip, reps=5):

@@ -43,13 +43,13 @@ with torch.cuda.stream(side):
             c["nzc"] = torch.empty(c["B"], dtype=torch.int32, device=dev)
             c["summ"] = torch.empty(int(eng.lib.mst_found_summary_bytes(c["B"])), dtype=torch.uint8, pin_memory=True)
             c["scratch"] = torch.empty(c["summ"].numel(), dtype=torch.uint8, device=dev)
-        st = eng._ss_launch(None, None, c["nzc"], True, None, None, False, (c["band"], c["n"], c["dpx"], c["starts"], CH),
-                            reuse=("stress", k), graph=use_graph)
+        L = eng._ss_launch(eng._flags(True, False, graph=use_graph), nzc=c["nzc"], band_src=(c["band"], c["n"], c["dpx"], c["starts"], CH),
+                           reuse=("stress", k))
         c["scratch"].fill_(0xFF)
         c["summ"].fill_(0x55)
-        B, cap = st["B"], st["found_cap"]
-        rc = eng.lib.mst_found_finish(_ptr(st["found"]), cap, _ptr(st["count"]), _ptr(c["nzc"]), _ptr(st["stats"]), B, nt,
-                                      _ptr(st["pval"]), _ptr(st["fit"]), 0, None, None, None, _ptr(c["scratch"]),
+        B, cap = L.B, L.cap
+        rc = eng.lib.mst_found_finish(_ptr(L.found), cap, _ptr(L.count), _ptr(c["nzc"]), _ptr(L.stats), B, nt,
+                                      _ptr(L.pval), _ptr(L.fit), 0, None, None, None, _ptr(c["scratch"]),
                                       ctypes.c_void_p(c["summ"].data_ptr()), None, None, None, 8 if use_graph else 0, _stream())
         h = c["summ"].numpy()
         cw = 8 * ((B + 1) // 2)
