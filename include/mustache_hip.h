@@ -418,6 +418,47 @@ MST_STABLE int mst_pair_gather(const mst_found *found, uint32_t found_cap, const
                     const uint32_t *sel_index, const uint32_t *sel_pixel, const uint32_t *sel_count, uint32_t out_cap,
                     uint32_t max_selected, double *out_pair, double *out_value, double *out_other, void *stream);
 
+/* ---- ICE balancing (mustache_amd/balance.py; the algorithm is stated there) -------------------------------------------------
+ * The matrix is the full symmetric CSR of one chromosome's kept pixels: row_ptr dev [n + 1] int64, col dev [nnz] int32,
+ * val dev [nnz] float64, sorted by (row, column); an off-diagonal pixel appears in both rows.  Each row is cut into chunks of
+ * 1024 entries counted from its first entry: chunk_ptr dev [n + 1] int64 (the chunks of row r are [chunk_ptr[r],
+ * chunk_ptr[r + 1])), chunk_row dev [n_chunks] int32 (the row of each chunk).  Every sum runs in a fixed order that depends only
+ * on absolute row and entry positions (no float atomics): results are bit-identical from run to run, under any permutation of
+ * the pixels that built the CSR, and for any n (appended empty rows change nothing).  workspace: dev, at least
+ * mst_balance_workspace_bytes(n, n_chunks) bytes, shared by the calls of one balancing (the iteration keeps nothing in it
+ * between calls that the caller must preserve). */
+typedef struct mst_balance_state {
+    double variance;      /* population variance of r over the non-zero marginals, last iteration */
+    double mean;          /* mean of the non-zero marginals, last iteration (1 when none is non-zero) */
+    int32_t iterations;   /* iterations run */
+    int32_t converged;    /* 1 once variance < tol */
+    int32_t done;         /* 1 once converged or iterations == max_iter: later iterations are no-ops */
+    int32_t _pad;
+} mst_balance_state;
+
+MST_STABLE uint64_t mst_balance_workspace_bytes(int64_t n, int64_t n_chunks);
+/* m[i] = w[i] * sum_c A_ic w[c]; nnz[i] (optional, may be NULL) = #{c : A_ic != 0, w[c] != 0}.  w, m: dev [n] f64; nnz: dev [n]. */
+MST_STABLE int mst_balance_marginals(const int64_t *row_ptr, const int32_t *col, const double *val, const int32_t *chunk_row,
+                          const int64_t *chunk_ptr, int64_t n, int64_t n_chunks, const double *w, double *m, int32_t *nnz,
+                          void *workspace, uint64_t workspace_bytes, void *stream);
+/* `steps` ICE iterations on w (dev [n] f64, updated in place): s = w * (A w); mu = mean(s[s != 0]); r = s / mu there, 1
+ * elsewhere; w /= r; variance = var(r[s != 0]) (0 when no s is non-zero); stop when variance < tol or after max_iter iterations.  state: dev, zeroed by
+ * the caller before the first call; an iteration enqueued after state->done is set does nothing, so a caller may enqueue several
+ * and read state back once. */
+MST_STABLE int mst_balance_iterate(const int64_t *row_ptr, const int32_t *col, const double *val, const int32_t *chunk_row,
+                        const int64_t *chunk_ptr, int64_t n, int64_t n_chunks, double *w, int32_t steps, int32_t max_iter,
+                        double tol, mst_balance_state *state, void *workspace, uint64_t workspace_bytes, void *stream);
+/* kappa = sqrt(sum_{i <= j} A_ij w_i w_j / sum_{i <= j} A_ij) (the balanced total equals the raw total), bias[i] = kappa / w[i]
+ * where w[i] != 0, NaN elsewhere.  bias: dev [n] f64; kappa: dev f64 [1] or NULL. */
+MST_STABLE int mst_balance_bias(const int64_t *row_ptr, const int32_t *col, const double *val, const int32_t *chunk_row,
+                     const int64_t *chunk_ptr, int64_t n, int64_t n_chunks, const double *w, double *bias, double *kappa,
+                     void *workspace, uint64_t workspace_bytes, void *stream);
+/* A bias vector applied to packed records as read_pd applies a -b vector (mustache.py read_bias): out[e] =
+ * (v[e] / b[x[e]]) / b[x[e] + dist[e]], where b[i] = bias[i] when bias[i] >= 0.2, +inf when it is NaN or below 0.2, and 1 for
+ * a bin at or past n_bias.  x, dist: dev [nnz] int32; v: dev [nnz] f32; bias: dev [n_bias] f64; out: dev [nnz] f64. */
+MST_STABLE int mst_balance_apply_packed(const int32_t *x, const int32_t *dist, const float *v, int64_t nnz, const double *bias,
+                             int64_t n_bias, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,11 @@ _SIGNATURES = {
     "mst_pair_pvalues_dog": (ctypes.c_int, [_p, _u32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     "mst_pair_gather": (ctypes.c_int, [_p, _u32, _p, _p, _i32, _p, _p, _p, _u32, _u32, _p, _p, _p, _p]),
     "mst_pair_pvalues": (ctypes.c_int, [_p, _u32, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    "mst_balance_workspace_bytes": (_u64, [_i64, _i64]),
+    "mst_balance_marginals": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _u64, _p]),
+    "mst_balance_iterate": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _i32, _i32, ctypes.c_double, _p, _p, _u64, _p]),
+    "mst_balance_bias": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _u64, _p]),
+    "mst_balance_apply_packed": (ctypes.c_int, [_p, _p, _p, _i64, _p, _i64, _p, _p]),
 }
 
 _lib = None

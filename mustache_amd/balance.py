@@ -1,0 +1,311 @@
+"""ICE balancing (iterative correction) of one chromosome's intra-chromosomal map on the GPU, for maps that come without a
+bias vector: `--balance ICE` on both command lines, `ice()` in Python.
+
+The algorithm (modelled on the defaults of `cooler balance --cis-only`; tests/balance_reference.py restates it in NumPy):
+
+Input: the chromosome's whole upper-triangular pixel set (i <= j; entries with v <= 0 or a non-finite v are dropped) and the
+bin count n.  A repeated pixel (same (min, max) in either orientation) counts once, the last entry in input order wins.
+Every step runs on the full symmetric matrix A (an off-diagonal pixel is in row i and in row j).
+  1. drop the pixels with j - i < ignore_diags;
+  2. mask the bins whose row has fewer than min_nnz non-zeros;
+  3. m = the row sums with the masked rows and columns removed;
+  4. over the bins with m > 0: l = log m, med = median(l), mad = median(|l - med|); mask the bins with
+     m < exp(med - mad_max * mad) and the bins with m = 0;
+  5. w = 1 on unmasked bins, 0 on masked; for k = 1 .. max_iter: s = w * (A w); mu = mean(s[s != 0]); r = s / mu where
+     s != 0, 1 elsewhere; w /= r; var = population variance of r[s != 0] (0 when no s is non-zero); stop when var < tol;
+  6. b = kappa / w on unmasked bins, NaN on masked, kappa = sqrt(sum A_ij w_i w_j / sum A_ij) over the kept pixels i <= j: the
+     balanced total equals the raw total (Juicer's scale, so read_bias' 0.2 cut-off means what it means for a KR vector).
+The bias is applied exactly as a `-b` vector (mustache.read_pd): v' = (v / b[bin of pos1]) / b[bin of pos2], NaN or b < 0.2
+count as +inf, v' > 0 kept.
+
+Device work (mustache_amd/csrc/mst_balance.hip): the filter-stage row sums and non-zero counts, the iteration with its mean,
+variance and convergence test, kappa and the bias, and the application to `.hic` records.  Every sum has a fixed order that
+depends only on absolute bin and pixel positions, so the bias is bit-identical from run to run, under any permutation of the
+records, for any n, and whichever reader the pixels came from.  torch does the one-off sort and the CSR offsets; the median
+of step 4 runs on the host (NumPy).
+"""
+import ctypes
+import math
+
+import numpy as np
+
+METHODS = ("ICE",)
+CHUNK = 1024                 # entries per chunk of a CSR row (kChunk in mst_balance.hip)
+STEPS_PER_READ = 8           # iterations enqueued between two reads of the device's convergence flag
+
+
+class BalanceError(ValueError):
+    """A --balance request that conflicts with another option."""
+
+
+def check_request(method, path=None, bias=None, norm_method=None, world=1, bias_flag="-b"):
+    """Raise BalanceError naming the conflict when `--balance method` cannot be honoured; return the method (upper case)."""
+    m = str(method).upper()
+    if m not in METHODS:
+        raise BalanceError("--balance %s: unknown method (supported: %s)" % (method, ", ".join(METHODS)))
+    if bias:
+        raise BalanceError("--balance %s and %s: give either a bias file or --balance, not both" % (m, bias_flag))
+    if norm_method and str(norm_method).upper() != "NONE":
+        raise BalanceError("--balance %s and -norm %s: --balance reads raw counts; leave -norm unset or NONE"
+                           % (m, norm_method))
+    for p in ([path] if isinstance(path, str) else list(path or [])):
+        if str(p).endswith((".cool", ".mcool")):
+            raise BalanceError("--balance %s and %s: .cool/.mcool files carry their own `weight` column; "
+                               "--balance is for text and .hic input" % (m, p))
+    if world > 1:
+        raise BalanceError("--balance %s in a multi-rank run (world size %d): balancing runs on one GPU; "
+                           "start a single process" % (m, world))
+    return m
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# bias vectors as files and as read_pd's lookup
+# ----------------------------------------------------------------------------------------------------------------------
+def write_bias(path, chrom, res, bias):
+    """The 3-column bias file read_bias reads: `chrom<TAB>start_bp<TAB>repr(value)`, one line per bin, `nan` on masked bins.
+    repr() round-trips every float64, so read_bias reads back exactly these values."""
+    res = int(res)
+    with open(path, "w") as f:
+        f.write("".join("%s\t%d\t%r\n" % (chrom, i * res, float(b)) for i, b in enumerate(np.asarray(bias, np.float64))))
+
+
+def bias_lookup(bias):
+    """bin -> factor exactly as read_bias builds it from a file holding `bias` (NaN or < 0.2 -> +inf, other bins 1.0)."""
+    from collections import defaultdict
+    d = defaultdict(lambda: 1.0)
+    for i, val in enumerate(np.asarray(bias, np.float64).tolist()):
+        d[float(i)] = val if (not np.isnan(val) and val >= 0.2) else np.inf
+    return d
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the device balancing
+# ----------------------------------------------------------------------------------------------------------------------
+class _State(ctypes.Structure):            # mst_balance_state
+    _fields_ = [("variance", ctypes.c_double), ("mean", ctypes.c_double), ("iterations", ctypes.c_int32),
+                ("converged", ctypes.c_int32), ("done", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
+def _as_tensor(a, dtype, device):
+    import torch
+    if isinstance(a, torch.Tensor):
+        return a.to(device=device, dtype=dtype)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(device=device, dtype=dtype)
+
+
+class BalanceCSR:
+    """The kept pixels of one map as the full symmetric CSR the kernels take (see include/mustache_hip.h)."""
+
+    def __init__(self, x, y, v, n, ignore_diags=2, device=None):
+        import torch
+        from .engine import require_gpu
+        require_gpu()
+        if device is None:
+            device = v.device if isinstance(v, torch.Tensor) and v.is_cuda else \
+                torch.device("cuda", torch.cuda.current_device())
+        self.device, self.n = torch.device(device), int(n)
+        n = self.n
+        with torch.cuda.device(self.device):
+            xd, yd = _as_tensor(x, torch.int64, device), _as_tensor(y, torch.int64, device)
+            vd = _as_tensor(v, torch.float64, device)
+            ok = (vd > 0) & torch.isfinite(vd)
+            lo, hi = torch.minimum(xd, yd), torch.maximum(xd, yd)
+            ok &= (lo >= 0) & (hi < n)
+            lo, hi, vd = lo[ok], hi[ok], vd[ok]
+            # a repeated pixel counts once: the last entry in input order wins (stable sort, last of each run of equal keys)
+            key = lo * n + hi
+            key, order = torch.sort(key, stable=True)
+            last = torch.ones_like(key, dtype=torch.bool)
+            if key.numel() > 1:
+                last[:-1] = key[1:] != key[:-1]
+            sel = order[last]
+            lo, hi, vd = lo[sel], hi[sel], vd[sel]        # sorted by (lo, hi)
+            del key, order, last, sel, xd, yd, ok
+            far = (hi - lo) >= int(ignore_diags)
+            lo, hi, vd = lo[far], hi[far], vd[far]
+            self.kept = int(vd.numel())
+            off = hi != lo
+            rows = torch.cat([lo, hi[off]])
+            cols = torch.cat([hi, lo[off]])
+            vals = torch.cat([vd, vd[off]])
+            del lo, hi, vd, off
+            _, order = torch.sort(rows * n + cols)        # unique keys
+            self.col = cols[order].to(torch.int32)
+            self.val = vals[order]
+            counts = torch.bincount(rows, minlength=n)
+            del rows, cols, vals, order
+            zero = torch.zeros(1, dtype=torch.int64, device=device)
+            self.row_ptr = torch.cat([zero, torch.cumsum(counts, 0)])
+            nch = (counts + (CHUNK - 1)) // CHUNK
+            self.chunk_ptr = torch.cat([zero, torch.cumsum(nch, 0)])
+            self.n_chunks = int(self.chunk_ptr[-1].item())
+            self.chunk_row = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=device), nch)
+            self.nnz = int(self.val.numel())
+            from . import _lib
+            lib = _lib.load()
+            self.ws = torch.empty(int(lib.mst_balance_workspace_bytes(n, self.n_chunks)), dtype=torch.uint8, device=device)
+
+    def _args(self):
+        from .engine import _ptr
+        return (_ptr(self.row_ptr), _ptr(self.col), _ptr(self.val), _ptr(self.chunk_row), _ptr(self.chunk_ptr), self.n,
+                self.n_chunks)
+
+    def marginals(self, w, with_nnz=False):
+        """(m = w * (A w), row non-zero counts or None) as device tensors."""
+        import torch
+        from . import _lib
+        from .engine import _ptr, _stream
+        lib = _lib.load()
+        m = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        nnz = torch.empty(self.n, dtype=torch.int32, device=self.device) if with_nnz else None
+        _lib.check(lib.mst_balance_marginals(*self._args(), _ptr(w), _ptr(m), _ptr(nnz), _ptr(self.ws), self.ws.numel(),
+                                             _stream()))
+        return m, nnz
+
+    def iterate(self, w, max_iter, tol):
+        """Run the ICE iteration on w (in place) -> (iterations, variance, converged)."""
+        import torch
+        from . import _lib
+        from .engine import _ptr, _stream
+        lib = _lib.load()
+        state = torch.zeros(ctypes.sizeof(_State), dtype=torch.uint8, device=self.device)
+        launched = 0
+        st = _State()
+        while launched < max_iter:
+            k = min(STEPS_PER_READ, max_iter - launched)
+            _lib.check(lib.mst_balance_iterate(*self._args(), _ptr(w), int(k), int(max_iter), float(tol), _ptr(state),
+                                               _ptr(self.ws), self.ws.numel(), _stream()))
+            launched += k
+            host = state.cpu().numpy()
+            ctypes.memmove(ctypes.addressof(st), host.ctypes.data, ctypes.sizeof(_State))
+            if st.done:
+                break
+        return int(st.iterations), float(st.variance), bool(st.converged)
+
+    def bias(self, w):
+        """(bias device tensor [n], kappa)"""
+        import torch
+        from . import _lib
+        from .engine import _ptr, _stream
+        lib = _lib.load()
+        b = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        kappa = torch.empty(1, dtype=torch.float64, device=self.device)
+        _lib.check(lib.mst_balance_bias(*self._args(), _ptr(w), _ptr(b), _ptr(kappa), _ptr(self.ws), self.ws.numel(),
+                                        _stream()))
+        return b, float(kappa.item())
+
+
+def mad_mask(m, mad_max):
+    """Step 4 on host values m (float64 [n]): True where the bin is masked."""
+    m = np.asarray(m, np.float64)
+    pos = m > 0
+    if not pos.any():
+        return np.ones(len(m), bool)
+    logm = np.log(m[pos])
+    med = np.median(logm)
+    mad = np.median(np.abs(logm - med))
+    return (m < np.exp(med - mad_max * mad)) | (m == 0)
+
+
+def ice(x, y, v, n, *, ignore_diags=2, min_nnz=10, mad_max=5.0, tol=1e-5, max_iter=200, device=None, timings=None):
+    """ICE bias of one chromosome's map.  x, y: bin indices (host arrays or device tensors, either orientation); v: raw
+    counts; n: bin count.  Returns (bias float64[n] on the host, info) with info = {"iterations", "variance", "converged",
+    "masked" (bool[n]), "kappa"}.  `timings` (a dict) receives "prepare_s" and "iterate_s" when given."""
+    import time
+    import torch
+    if int(max_iter) < 1:
+        raise ValueError("ice(): max_iter must be >= 1")
+    n = int(n)
+    t0 = time.perf_counter()
+    csr = BalanceCSR(x, y, v, n, ignore_diags=ignore_diags, device=device)
+    with torch.cuda.device(csr.device):
+        w = torch.ones(n, dtype=torch.float64, device=csr.device)
+        _, nnz = csr.marginals(w, with_nnz=True)
+        w = (nnz >= int(min_nnz)).to(torch.float64)
+        m, _ = csr.marginals(w)
+        masked = mad_mask(m.cpu().numpy(), float(mad_max))
+        w = torch.from_numpy((~masked).astype(np.float64)).to(csr.device)
+        torch.cuda.synchronize(csr.device)
+        t1 = time.perf_counter()
+        if masked.all():
+            iterations, variance, converged, kappa = 0, math.nan, True, math.nan
+            bias = np.full(n, np.nan)
+        else:
+            iterations, variance, converged = csr.iterate(w, int(max_iter), float(tol))
+            b, kappa = csr.bias(w)
+            bias = b.cpu().numpy()
+        t2 = time.perf_counter()
+    if timings is not None:
+        timings["prepare_s"], timings["iterate_s"], timings["kept"], timings["nnz"] = t1 - t0, t2 - t1, csr.kept, csr.nnz
+    del csr
+    return bias, {"iterations": iterations, "variance": variance, "converged": converged, "masked": masked, "kappa": kappa}
+
+
+def report(info, label):
+    """The CLI's line about one balancing; a warning when the iteration limit was reached."""
+    if not info["converged"]:
+        print("Warning: ICE balancing of %s did not converge in %d iterations (variance %r)"
+              % (label, info["iterations"], info["variance"]))
+    else:
+        print("ICE balancing of %s: %d iterations, %d of %d bins masked"
+              % (label, info["iterations"], int(info["masked"].sum()), len(info["masked"])))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# readers under --balance
+# ----------------------------------------------------------------------------------------------------------------------
+def balance_text(p1, p2, cnt, res, **kw):
+    """Raw text records (positions in bp, counts) -> (bias, info) over bins 0 .. max bin."""
+    a = np.floor_divide(np.asarray(p1, np.float64), res)
+    b = np.floor_divide(np.asarray(p2, np.float64), res)
+    cnt = np.asarray(cnt, np.float64)
+    ok = np.isfinite(a) & np.isfinite(b) & (a >= 0) & (b >= 0)
+    a, b, cnt = a[ok].astype(np.int64), b[ok].astype(np.int64), cnt[ok]
+    n = int(max(a.max(), b.max())) + 1 if len(a) else 0
+    if n == 0:
+        return np.zeros(0), {"iterations": 0, "variance": math.nan, "converged": True, "masked": np.zeros(0, bool),
+                             "kappa": math.nan}
+    return ice(a, b, cnt, n, **kw)
+
+
+def read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res, device=None, **kw):
+    """`.hic` under --balance: every raw record of the chromosome (norm NONE, no distance limit), ICE on the device, the
+    bias applied on the device, then the reader's distance rule -> (x, y, v) host arrays, None when nothing is left."""
+    import torch
+    from .engine import _ptr, _stream, require_gpu
+    from .hicfile import read_intra_packed
+    from .readers import _HIC_LOCK, _hic_handle
+    from . import _lib
+    lib = require_gpu()
+    with _HIC_LOCK:
+        h = _hic_handle(f)
+        if not CHRM_SIZE:
+            sizes = {"chr" + name.replace("chr", ''): length for name, length in h.chromosomes()[1:]}
+            key = "chr" + str(chromosome).replace("chr", '')
+            if key not in sizes:
+                raise NameError('wrong chromosome name!')
+            CHRM_SIZE = sizes[key]
+        print("reading %s through the native .hic reader, raw counts for ICE balancing" % str(f).rsplit("/", 1)[-1])
+        pc = read_intra_packed(h, chromosome, res, "NONE", -1, int(CHRM_SIZE))
+    if len(pc) == 0:
+        print(f'There is no contact in chrmosome {chromosome} to work on.')
+        return None
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    with torch.cuda.device(dev):
+        xd = torch.from_numpy(pc.x[:pc.count]).to(dev)
+        dd = torch.from_numpy(pc.dist[:pc.count]).to(dev)
+        vd = torch.from_numpy(pc.v[:pc.count]).to(dev)
+        yd = xd.to(torch.int64) + dd.to(torch.int64)
+        n = int(yd.max().item()) + 1
+        bias, info = ice(xd, yd, vd.to(torch.float64), n, device=dev, **kw)
+        report(info, "chromosome %s" % chromosome)
+        bd = torch.from_numpy(bias).to(dev)
+        out = torch.empty(pc.count, dtype=torch.float64, device=dev)
+        _lib.check(lib.mst_balance_apply_packed(_ptr(xd), _ptr(dd), _ptr(vd), int(pc.count), _ptr(bd), int(n), _ptr(out),
+                                                _stream()))
+        keep = (out > 0) & (dd <= int(distance_in_bp // res))
+        x, y, v = xd[keep].to(torch.int64).cpu().numpy(), yd[keep].cpu().numpy(), out[keep].cpu().numpy()
+    if len(v) == 0:
+        print(f'There is no contact in chrmosome {chromosome} to work on.')
+        return None
+    return x, y, v

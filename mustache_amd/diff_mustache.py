@@ -252,8 +252,11 @@ def _pairs_from_filled(eng, pipe, dbands, n, dpx, starts, CH, dense=False, pt=No
     return batch
 
 
-def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2, chromosome, chromosome2, verbose=True):
-    """The reading half of regulator() (diff_mustache.py:591-626): -> (coo1, coo2, res) or None when a sample is empty."""
+def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2, chromosome, chromosome2, verbose=True,
+              balance=None):
+    """The reading half of regulator() (diff_mustache.py:591-626): -> (coo1, coo2, res) or None when a sample is empty.
+    balance="ICE": each sample's raw map is balanced on its own on the GPU (mustache_amd.balance), as mustache.read_contacts
+    does for one sample; bias1 / bias2 and a stored normalisation are then not used."""
     if not chromosome2 or chromosome2 == 'n':
         chromosome2 = chromosome
     if chromosome != chromosome2:
@@ -261,7 +264,16 @@ def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2,
     if verbose:
         print("Reading contact map...")
     coos = []
-    for f, bias in ((f1, bias1), (f2, bias2)):
+    if balance:
+        from .balance import check_request, read_hic_balanced
+        from .mustache import read_pd_balanced
+        check_request(balance, [f1, f2], bias1 or bias2, norm_method, bias_flag="-b1/-b2")
+        for f in (f1, f2):
+            if f.endswith(".hic"):             # raw counts through the native reader, whatever MUSTACHE_HIC_BACKEND says
+                coos.append(read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res))
+            else:
+                coos.append(read_pd_balanced(f, distance_in_bp, chromosome, res))
+    for f, bias in ((f1, bias1), (f2, bias2)) if not balance else ():
         if f.endswith(".hic"):
             from .readers import hic_backend, read_hic_file, read_hic_packed
             if hic_backend() == "native":
@@ -291,10 +303,12 @@ def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2,
 
 def regulator(f1, f2, norm_method, CHRM_SIZE, outdir, bed1="", bed2="", res=5000, sigma0=1.6, s=10, pt=0.1, pt2=0.1,
               st=0.88, octaves=2, verbose=True, nprocesses=4, distance_filter=2000000, bias1=False, bias2=False,
-              chromosome='n', chromosome2=None):
-    """Two-sample loop calling for one chromosome (diff_mustache.py:572-690); returns [x, y, fdr, sigma, tag] rows."""
+              chromosome='n', chromosome2=None, balance=None):
+    """Two-sample loop calling for one chromosome (diff_mustache.py:572-690); returns [x, y, fdr, sigma, tag] rows.
+    `balance="ICE"` (not in the reference): balance each sample's raw map on the GPU instead of applying bias1 / bias2."""
     octave_values = [sigma0 * (2 ** i) for i in range(octaves)]
-    got = read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_filter, bias1, bias2, chromosome, chromosome2, verbose)
+    got = read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_filter, bias1, bias2, chromosome, chromosome2, verbose,
+                    balance=balance)
     if got is None:
         return []
     coo1, coo2, res = got
@@ -329,6 +343,8 @@ def parse_args(args):
     p.add_argument("-ch", "--chromosome", dest="chromosome", nargs='+', default='n', required=False)
     p.add_argument("-ch2", "--chromosome2", dest="chromosome2", nargs='+', default='n', required=False)
     p.add_argument("-v", "--verbose", dest="verbose", type=bool, default=True, required=False)
+    p.add_argument("--balance", dest="balance", default=None, metavar="ICE", required=False,
+                   help="OPTIONAL: balance each raw contact map on the GPU (ICE) instead of -b1/-b2 / -norm")
     return p.parse_args(args)
 
 
@@ -397,6 +413,14 @@ def main(argv=None):
     # reads and runs its own, ONE gather of (chromosome, x, y, fdr, sigma, list tag) records, rank 0 writes the four files
     from .sharding import assign_chromosomes, gather_records, init_from_env
     rank, world_size = init_from_env()
+    if args.balance is not None:
+        from .balance import BalanceError, check_request
+        try:
+            args.balance = check_request(args.balance, [f1, f2], args.biasfile1 or args.biasfile2, args.norm_method,
+                                         world_size, bias_flag="-b1/-b2")
+        except BalanceError as e:
+            print("Error: %s" % e)
+            return
     mine = list(range(len(pairs)))
     if world_size > 1:
         from .readers import chromosome_sizes
@@ -464,10 +488,10 @@ def main(argv=None):
             emit(i, regulator(f1, f2, args.norm_method, False, args.outdir, bed1=args.bed1, bed2=args.bed2, res=res,
                               sigma0=args.s_z, s=args.s, verbose=args.verbose, pt=args.pt, pt2=args.pt2, st=args.st,
                               distance_filter=distFilter, nprocesses=args.nprocesses, bias1=biasf1, bias2=biasf2,
-                              chromosome=chromosome, chromosome2=chromosome2, octaves=args.octaves))
+                              chromosome=chromosome, chromosome2=chromosome2, octaves=args.octaves, balance=args.balance))
             continue
         got = read_pair(f1, f2, args.norm_method, False, res, distFilter, biasf1, biasf2, chromosome, chromosome2,
-                        args.verbose)
+                        args.verbose, balance=args.balance)
         if got is None:
             flush()                               # keeps the output in chromosome order
             emit(i, [])

@@ -187,6 +187,61 @@ def _parse_contacts_native(f, sep, chromosome):
         raise
 
 
+def _finish_text(p1, p2, cnt, distance_in_bp, bias, res):
+    """read_pd after the parse: distance filter, bins, counts divided by bias[pos1 bin] then bias[pos2 bin] (`bias` = what
+    read_bias returns, or False), non-positive rows dropped."""
+    keep = np.abs(p1 - p2) <= ((distance_in_bp / res + 1) * res)           # (:267, :283)
+    a = np.floor_divide(p1[keep], res)                                     # df[1] //= res
+    b = np.floor_divide(p2[keep], res)
+    cnt = cnt[keep]
+    if bias:
+        cnt = np.divide(cnt, np.vectorize(bias.get)(a, 1)) if len(a) else cnt
+        cnt = np.divide(cnt, np.vectorize(bias.get)(b, 1)) if len(b) else cnt
+    pos = cnt > 0
+    a, b, cnt = a[pos].astype(np.int64), b[pos].astype(np.int64), cnt[pos]
+    return np.minimum(a, b), np.maximum(a, b), cnt
+
+
+def _text_records(f, sep, chromosome):
+    """(pos1, pos2, count) float64 of every record read_pd reads, before its distance filter; None when a 5-column file has
+    no record of the chromosome."""
+    native = _parse_contacts_native(f, sep, chromosome)
+    if native is not None:
+        ncols, p1, p2, cnt = native
+        if ncols == 5 and len(cnt) == 0:
+            return None
+        return p1, p2, cnt
+    import pandas as pd
+    df = pd.read_csv(f, sep=sep, header=None)
+    df.dropna(inplace=True)
+    if df.shape[1] == 5:
+        df = df[np.vectorize(is_chr)(df[0], chromosome)]
+        if df.shape[0] == 0:
+            return None
+        df = df[np.vectorize(is_chr)(df[2], chromosome)]
+        a, b, cnt = 1, 3, 4
+    elif df.shape[1] == 3:
+        a, b, cnt = 0, 1, 2
+    else:
+        raise ValueError("contact text file must have 3 or 5 columns")
+    return (np.asarray(df[a], np.float64), np.asarray(df[b], np.float64), np.asarray(df[cnt], np.float64))
+
+
+def read_pd_balanced(f, distance_in_bp, chromosome, res, device=None, **ice_args):
+    """read_pd under `--balance ICE`: every record of the chromosome, before the distance filter, is balanced on the GPU
+    (balance.ice); the bias is then applied as read_pd applies a -b vector.  Returns read_pd's triple, or None."""
+    from .balance import balance_text, bias_lookup, report
+    recs = _text_records(f, get_sep(f), chromosome)
+    if recs is None:
+        print('Could\'t read any interaction for this chromosome!')
+        return
+    p1, p2, cnt = recs
+    bias, info = balance_text(p1, p2, cnt, res, device=device, **ice_args)
+    if len(bias):
+        report(info, "chromosome %s" % chromosome)
+    return _finish_text(p1, p2, cnt, distance_in_bp, bias_lookup(bias), res)
+
+
 def read_pd(f, distance_in_bp, bias, chromosome, res):
     """3-column (pos1 pos2 count) or 5-column (chr1 pos1 chr2 pos2 count) text -> upper-triangular COO in bin
     units, counts divided by bias[x]*bias[y], non-positive rows dropped (reference mustache.py:254-297)."""
@@ -197,17 +252,7 @@ def read_pd(f, distance_in_bp, bias, chromosome, res):
         if ncols == 5 and len(cnt) == 0:
             print('Could\'t read any interaction for this chromosome!')
             return
-        keep = np.abs(p1 - p2) <= ((distance_in_bp / res + 1) * res)       # (:267, :283)
-        a = np.floor_divide(p1[keep], res)                                 # df[1] //= res
-        b = np.floor_divide(p2[keep], res)
-        cnt = cnt[keep]
-        bias = read_bias(bias, chromosome, res)
-        if bias:
-            cnt = np.divide(cnt, np.vectorize(bias.get)(a, 1)) if len(a) else cnt
-            cnt = np.divide(cnt, np.vectorize(bias.get)(b, 1)) if len(b) else cnt
-        pos = cnt > 0
-        a, b, cnt = a[pos].astype(np.int64), b[pos].astype(np.int64), cnt[pos]
-        return np.minimum(a, b), np.maximum(a, b), cnt
+        return _finish_text(p1, p2, cnt, distance_in_bp, read_bias(bias, chromosome, res), res)
     import pandas as pd
     df = pd.read_csv(f, sep=sep, header=None)
     df.dropna(inplace=True)
@@ -270,15 +315,27 @@ def _check_pair(f, chromosome, chromosome2):
 
 
 def read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromosome, chromosome2, verbose=True,
-                  packed=False, part=(0, 1), device=None):
+                  packed=False, part=(0, 1), device=None, balance=None):
     """The reading half of regulator() (reference mustache.py:866-889): host I/O only, so main() can fetch the next
     chromosome while the GPU works on the current one.  Returns (x, y, v, res) or None when nothing was read.
     packed=True: a `.hic` file read by the native reader comes back as hicfile.PackedContacts (12 bytes per record, what
-    the GPU loader takes) instead of the int64 / float64 triple."""
+    the GPU loader takes) instead of the int64 / float64 triple.
+    balance="ICE": the map's raw counts are balanced on the GPU (mustache_amd.balance) instead of using a bias file or a
+    stored normalisation; the result is always the int64 / float64 triple."""
     chromosome2 = _check_pair(f, chromosome, chromosome2)
     distance_in_bp = distance_filter
     if verbose:
         print("Reading contact map...")
+    if balance:
+        from .balance import check_request, read_hic_balanced
+        check_request(balance, f, bias, norm_method, world=part[1])
+        if f.endswith(".hic"):                 # raw counts through the native reader, whatever MUSTACHE_HIC_BACKEND says
+            r = read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res, device=device)
+        else:
+            r = read_pd_balanced(f, distance_in_bp, chromosome, res, device=device)
+        if r is None or len(r[2]) == 0:
+            return None
+        return np.asarray(r[0]), np.asarray(r[1]), np.asarray(r[2], dtype=np.float64), res
     if f.endswith(".hic") and packed:
         from .readers import hic_backend, read_hic_packed
         if hic_backend() == "native":
@@ -305,15 +362,17 @@ def read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromos
 
 def regulator(f, norm_method, CHRM_SIZE, outdir, bed="", res=5000, sigma0=1.6, s=10, pt=0.1, st=0.88, octaves=2,
               verbose=True, nprocesses=4, distance_filter=2000000, bias=False, chromosome='n', chromosome2=None,
-              contacts=None, shard_blocks=True):
+              contacts=None, shard_blocks=True, balance=None):
     """Loop calling for one chromosome (reference mustache.py:853-942).  `s` is accepted and ignored like in the
     reference (s = 10 is hard-wired at :711); `nprocesses` is ignored: all blocks run as one GPU batch.
     `contacts` (not in the reference): what read_contacts() returned for this chromosome, when the caller read ahead;
-    `shard_blocks=False`: in a multi-GPU job this rank runs the whole chromosome alone (whole-genome sharding by chromosome)."""
+    `shard_blocks=False`: in a multi-GPU job this rank runs the whole chromosome alone (whole-genome sharding by chromosome).
+    `balance="ICE"` (not in the reference): balance the raw map on the GPU instead of applying `bias` (read_contacts)."""
     chromosome2 = _check_pair(f, chromosome, chromosome2)
     octave_values = [sigma0 * (2 ** i) for i in range(octaves)]
     if contacts is None:
-        contacts = read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromosome, chromosome2, verbose)
+        contacts = read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromosome, chromosome2, verbose,
+                                 balance=balance)
         if contacts is None:
             return []
     from .hicfile import PackedContacts
@@ -364,6 +423,8 @@ def parse_args(args):
     p.add_argument("-ch2", "--chromosome2", dest="chromosome2", nargs='+', default='n', required=False,
                    help="Optional: second chromosome (inter-chromosomal mode is non-functional upstream).")
     p.add_argument("-v", "--verbose", dest="verbose", type=bool, default=True, help="OPTIONAL: verbosity")
+    p.add_argument("--balance", dest="balance", default=None, metavar="ICE",
+                   help="OPTIONAL: balance the raw contact map on the GPU (ICE) instead of -b / -norm; text and .hic input")
     return p.parse_args(args)
 
 
@@ -469,6 +530,13 @@ def main(argv=None):
         print("Error: Couldn't find specified bias file")
         return
     biasf = args.biasfile if args.biasfile else False
+    if args.balance is not None:
+        from .balance import BalanceError, check_request
+        try:
+            args.balance = check_request(args.balance, f, args.biasfile, args.norm_method, _world)
+        except BalanceError as e:
+            print("Error: %s" % e)
+            return
     pairs = list(zip(chr_list, chr_list2))
 
     try:                                     # the reader thread below must upload to THIS thread's device, not to GPU 0
@@ -485,7 +553,7 @@ def main(argv=None):
             with stage("read %s" % chromosome):
                 return read_contacts(f, args.norm_method, CHRM_SIZE, res, distFilter, biasf, chromosome, chromosome2,
                                      verbose=args.verbose, packed=True, part=(0, 1) if by_chromosome else (rank, _world),
-                                     device=my_device)
+                                     device=my_device, balance=args.balance)
         except BaseException as e:          # re-raised in the main thread, at this chromosome's turn
             return e
 
