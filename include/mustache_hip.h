@@ -459,6 +459,33 @@ MST_STABLE int mst_balance_bias(const int64_t *row_ptr, const int32_t *col, cons
 MST_STABLE int mst_balance_apply_packed(const int32_t *x, const int32_t *dist, const float *v, int64_t nnz, const double *bias,
                              int64_t n_bias, double *out, void *stream);
 
+/* ---- inter-chromosomal pairs (mustache_amd/trans.py states the rules; tests/trans_reference.py restates them) --------------
+ * A pair (A, B) is one rectangular map, x = bin of A, y = bin of B, cut into square CH x CH tiles with separate row and column
+ * origins.  The tiles go through mst_scale_space (dense source: no band geometry, every tile with a tested pixel is computed)
+ * and the dense tail (mst_candidate_features, mst_cluster_representatives -- its clustering clips at the tile edges). */
+/* `.hic` rows of a trans matrix (mst_hic_rawstream_open_trans, include/mustache_io.h) -> COO: per record (a, b) = (binX, binY),
+ * or (binY, binX) when transposed != 0 (the file stores the pair as (B, A)); value = (float)(count / (norm_x[a] * norm_y[b]))
+ * with both vectors, or the raw count with neither; dropped when a bin lies outside its vector or the value is NaN, inf or
+ * <= 0.  x, y: dev int32 [capacity]; v: dev f64 [capacity]; count: dev uint64, ACCUMULATED with one atomic per kept record
+ * (the caller zeroes it; slabs may be decoded in any order and the record order is unspecified).  A count above capacity means
+ * records were dropped: the caller re-runs with room for count records. */
+MST_STABLE int mst_trans_decode_hic_rows(const void *payload, const void *rows, int32_t n_rows, const double *norm_x, int64_t n_norm_x,
+                              const double *norm_y, int64_t n_norm_y, int32_t transposed, int32_t *x, int32_t *y, double *v,
+                              int64_t capacity, uint64_t *count, void *stream);
+/* The pair's z-score over its n records: mean = sum v / n, std = sqrt(sum (v - mean)^2 / n), out = (v - mean) / std with NaN /
+ * inf -> 0 (out may alias v).  Both sums are exact (fixed-point integer pieces), so stats and out are bit-identical under any
+ * permutation of the records.  stats: dev f64 [4] = {mean, std, n, 0}; mean / std are NaN when a value is not finite.
+ * n < 2^31.  workspace: dev, mst_trans_zscore_workspace_bytes() bytes. */
+MST_STABLE uint64_t mst_trans_zscore_workspace_bytes(void);
+MST_STABLE int mst_trans_zscore(const double *v, int64_t n, double *out, double *stats, void *workspace, uint64_t workspace_bytes,
+                     void *stream);
+/* Records -> B tiles: c dev [B][CH][CH] f64, zeroed, then c[b][x - row0[b]][y - col0[b]] = v for every record inside tile b's
+ * window (a record lands in every tile that holds it).  row0, col0: dev int64 [B], 1 <= B <= 4096.  Pixels are unique. */
+MST_STABLE int mst_trans_scatter_tiles(const int32_t *x, const int32_t *y, const double *v, int64_t n, const int64_t *row0,
+                            const int64_t *col0, int32_t B, int32_t CH, double *c, void *stream);
+/* The trans prologue: nz[b] = c[b] != 0 over the whole tile, no fills; nz_count dev [B] uint32, overwritten. */
+MST_STABLE int mst_trans_prologue(const double *c, uint8_t *nz, uint32_t *nz_count, int32_t B, int32_t CH, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/mustache_io.h"
+#include "../../include/mustache_io_trans.h"
 #include "mst_inflate.h"
 
 namespace {
@@ -1275,8 +1276,9 @@ struct mst_hic_rawstream {
     mst_hic *h = nullptr;
     std::vector<const BlockRef *> todo;
     ZoomData zoom;
-    std::vector<double> norm_vec;
+    std::vector<double> norm_vec, norm_vec2;                          // trans: the vectors of A and of B
     bool use_norm = false;
+    int64_t chrom_length2 = 0;
     uint8_t *base = nullptr;
     int32_t n_slabs = 0;
     int64_t slab_bytes = 0;
@@ -1523,6 +1525,98 @@ extern "C" int mst_hic_rawstream_open(mst_hic *h, const char *chrom, int32_t res
         delete s;
         return fail(MST_IO_E_FORMAT, "unreadable file (out of memory?)");
     }
+}
+
+// ---- trans matrices: every block of the pair's matrix, rows delivered as for the intra stream ---------------------------------
+static int norm_vector_of(mst_hic *h, const char *norm, int ci, int32_t resolution, std::vector<double> &out) {
+    read_norm_index(h);
+    auto nit = h->norm_index.find(norm_key(norm, ci, "BP", resolution));
+    if (nit == h->norm_index.end())
+        return fail(MST_IO_E_NOTFOUND, "no %s normalisation vector for %s at %d bp", norm, h->chroms[(size_t)ci].name.c_str(),
+                    resolution);
+    out = read_norm_vector(h, nit->second);
+    return MST_IO_OK;
+}
+
+extern "C" int mst_hic_rawstream_open_trans(mst_hic *h, const char *chrom_a, const char *chrom_b, int32_t resolution,
+                                            const char *norm, int32_t n_threads, void *slab_memory, int32_t n_slabs,
+                                            int64_t slab_bytes, int32_t *transposed, mst_hic_rawstream **out) {
+    if (!h || !chrom_a || !chrom_b || !out || !transposed || resolution <= 0 || !slab_memory || n_slabs < 2 || slab_bytes < 4096 ||
+        (slab_bytes & 15) || slab_bytes > ((int64_t)1 << 32) || (reinterpret_cast<uintptr_t>(slab_memory) & 15))
+        return fail(MST_IO_E_ARG, "mst_hic_rawstream_open_trans: bad argument (slab_bytes: a multiple of 16 in [4096, 2^32]; "
+                                  "slab_memory 16-byte aligned)");
+    *out = nullptr;
+    if (h->version < 7)
+        return fail(MST_IO_E_FORMAT, "mst_hic_rawstream_open_trans: version %d blocks are plain records, not rows (versions 7-9 "
+                                     "are read)", h->version);
+    mst_hic_rawstream *s = nullptr;
+    try {
+        const int ca = find_chromosome(h, chrom_a), cb = find_chromosome(h, chrom_b);
+        if (ca < 0) return fail(MST_IO_E_NOTFOUND, "chromosome %s is not in the file", chrom_a);
+        if (cb < 0) return fail(MST_IO_E_NOTFOUND, "chromosome %s is not in the file", chrom_b);
+        if (ca == cb) return fail(MST_IO_E_ARG, "mst_hic_rawstream_open_trans: %s and %s are one chromosome", chrom_a, chrom_b);
+        const int lo = ca < cb ? ca : cb, hi = ca < cb ? cb : ca;
+        auto it = h->matrices.find(std::to_string(lo) + "_" + std::to_string(hi));
+        if (it == h->matrices.end()) return fail(MST_IO_E_NOTFOUND, "no matrix for the pair %s, %s", chrom_a, chrom_b);
+        s = new mst_hic_rawstream();
+        s->h = h;
+        s->zoom = read_zoom(h, it->second.first, resolution);
+        if (!s->zoom.found) {
+            delete s;
+            return fail(MST_IO_E_NOTFOUND, "resolution %d is not in the file", resolution);
+        }
+        s->use_norm = norm && *norm && strcmp(norm, "NONE") != 0;
+        if (s->use_norm) {
+            int rc = norm_vector_of(h, norm, ca, resolution, s->norm_vec);
+            if (rc == MST_IO_OK) rc = norm_vector_of(h, norm, cb, resolution, s->norm_vec2);
+            if (rc != MST_IO_OK) {
+                delete s;
+                return rc;
+            }
+        }
+        for (const BlockRef &b : s->zoom.blocks) {
+            if (b.size <= 0) continue;
+            if (b.pos < 0 || (uint64_t)b.pos + (uint64_t)b.size > h->size) throw FormatError{"block outside the file"};
+            s->todo.push_back(&b);
+        }
+        s->blocks_total = (int32_t)s->todo.size();
+        s->chrom_length = h->chroms[(size_t)ca].length;
+        s->chrom_length2 = h->chroms[(size_t)cb].length;
+        *transposed = ca > cb ? 1 : 0;
+        s->base = static_cast<uint8_t *>(slab_memory);
+        s->n_slabs = n_slabs;
+        s->slab_bytes = slab_bytes;
+        s->pay_bytes.assign((size_t)n_slabs, 0);
+        s->row_count.assign((size_t)n_slabs, 0);
+        for (int32_t i = 0; i < n_slabs; ++i) s->free_q.push_back(i);
+        int nt = n_threads > 0 ? n_threads : default_threads();
+        if (nt < 1) nt = 1;
+        if ((size_t)nt > s->todo.size()) nt = s->todo.empty() ? 1 : (int)s->todo.size();
+        if (nt > n_slabs - 1) nt = n_slabs - 1;
+        s->active = nt;
+        for (int t = 0; t < nt; ++t) s->workers.emplace_back([s] { s->work(); });
+        *out = s;
+        return MST_IO_OK;
+    } catch (const FormatError &e) {
+        delete s;
+        return fail(MST_IO_E_FORMAT, "%s", e.what);
+    } catch (...) {
+        delete s;
+        return fail(MST_IO_E_FORMAT, "unreadable file (out of memory?)");
+    }
+}
+
+extern "C" int mst_hic_rawstream_info_trans(mst_hic_rawstream *s, const double **norm_a, int64_t *count_a, const double **norm_b,
+                                            int64_t *count_b, int64_t *length_a_bp, int64_t *length_b_bp) {
+    if (!s || !norm_a || !count_a || !norm_b || !count_b || !length_a_bp || !length_b_bp)
+        return fail(MST_IO_E_ARG, "mst_hic_rawstream_info_trans: bad argument");
+    *norm_a = s->use_norm ? s->norm_vec.data() : nullptr;
+    *count_a = s->use_norm ? (int64_t)s->norm_vec.size() : -1;
+    *norm_b = s->use_norm ? s->norm_vec2.data() : nullptr;
+    *count_b = s->use_norm ? (int64_t)s->norm_vec2.size() : -1;
+    *length_a_bp = s->chrom_length;
+    *length_b_bp = s->chrom_length2;
+    return MST_IO_OK;
 }
 
 extern "C" int mst_hic_rawstream_info(mst_hic_rawstream *s, const double **norm_values, int64_t *norm_count,

@@ -63,6 +63,12 @@ _SIGNATURES = {
     "mst_hic_rawstream_release": (ctypes.c_int, [_P, ctypes.c_int32]),
     "mst_hic_rawstream_close": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "mst_hic_rawstream_open_trans": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32, ctypes.c_char_p,
+                                                    ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int64,
+                                                    ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_P)]),
+    "mst_hic_rawstream_info_trans": (ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_P),
+                                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                                    ctypes.POINTER(ctypes.c_int64)]),
     "mst_text_read_contacts": (ctypes.c_int64, [ctypes.c_char_p, ctypes.c_char, ctypes.c_char_p, ctypes.c_int32,
                                                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_P), ctypes.POINTER(_P),
                                                 ctypes.POINTER(_P)]),
@@ -242,6 +248,38 @@ class HicRawStream:
             self.blocks_total, self.blocks_mine = int(bt.value), int(bm.value)
 
     __del__ = close
+
+
+class HicTransRawStream(HicRawStream):
+    """mst_hic_rawstream_open_trans: the raw rows of EVERY block of the inter-chromosomal matrix of (chrom_a, chrom_b), delivered
+    as HicRawStream delivers an intra matrix's; `transposed` is True when the file stores the pair as (chrom_b, chrom_a).  The
+    rows are decoded on the GPU (mst_trans_decode_hic_rows).  Versions 7-9 only."""
+
+    def __init__(self, hic, chrom_a, chrom_b, resolution, norm, memory_ptr, n_slabs, slab_bytes, threads=0):
+        self._lib, self._hic = hic._lib, hic
+        self._s = _P()
+        self.slab_bytes, self.n_slabs = int(slab_bytes), int(n_slabs)
+        tr = ctypes.c_int32()
+        _check(self._lib, self._lib.mst_hic_rawstream_open_trans(hic._h, str(chrom_a).encode(), str(chrom_b).encode(),
+                                                                 int(resolution), str(norm).encode(), int(threads), _P(memory_ptr),
+                                                                 int(n_slabs), int(slab_bytes), ctypes.byref(tr),
+                                                                 ctypes.byref(self._s)))
+        self.transposed = bool(tr.value)
+        self.rows_total = self.bytes_total = self.blocks_total = self.blocks_mine = None
+
+    def info(self):
+        """(norm vector of chrom_a, of chrom_b -- float64 copies, or None for norm NONE --, length of chrom_a, of chrom_b in bp)"""
+        va, na, vb, nb, la, lb = _P(), ctypes.c_int64(), _P(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _check(self._lib, self._lib.mst_hic_rawstream_info_trans(self._s, ctypes.byref(va), ctypes.byref(na), ctypes.byref(vb),
+                                                                 ctypes.byref(nb), ctypes.byref(la), ctypes.byref(lb)))
+
+        def vec(p, n):
+            if n.value < 0:
+                return None
+            if n.value == 0:
+                return np.zeros(0, np.float64)
+            return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_double)), shape=(n.value,)).copy()
+        return vec(va, na), vec(vb, nb), int(la.value), int(lb.value)
 
 
 class PackedContacts:

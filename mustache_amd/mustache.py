@@ -309,9 +309,15 @@ def _check_pair(f, chromosome, chromosome2):
     if (chromosome != chromosome2) and not (('.hic' in f) or ('.cool' in f) or ('.mcool' in f)):
         print("Interchromosomal analysis is only supported for .hic and .cool input formats.")
         raise FileNotFoundError
-    if chromosome != chromosome2:
-        raise NotImplementedError("inter-chromosomal mode is non-functional in the reference (mustache.py:939-942)")
     return chromosome2
+
+
+def call_trans_coo(x, y, v, octave_values, st, pt, verbose=True, label=""):
+    """The trans pair's body after the reader (mustache_amd/trans.py rules 2-6): z-score, square tiles with row / column
+    origins, the sigma loop and the tail per tile, ownership.  x = bins of the first chromosome, y = bins of the second, v > 0
+    (host arrays or device tensors).  Returns [[x, y, fdr, sigma], ...] sorted by (x, y)."""
+    from .trans import call_trans_coo as _call
+    return _call(x, y, v, octave_values, st, pt, verbose=verbose, label=label)
 
 
 def read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromosome, chromosome2, verbose=True,
@@ -326,6 +332,13 @@ def read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromos
     distance_in_bp = distance_filter
     if verbose:
         print("Reading contact map...")
+    if chromosome != chromosome2:          # a trans pair: every record of the matrix, no distance limit (trans.py rule 1)
+        from .trans import TransError, read_trans_contacts
+        if balance:
+            raise TransError("--balance does not apply to inter-chromosomal pairs")
+        if part[1] > 1:
+            raise TransError("inter-chromosomal pairs run on one GPU only")
+        return read_trans_contacts(f, norm_method, chromosome, chromosome2, res, device=device)
     if balance:
         from .balance import check_request, read_hic_balanced
         check_request(balance, f, bias, norm_method, world=part[1])
@@ -370,6 +383,14 @@ def regulator(f, norm_method, CHRM_SIZE, outdir, bed="", res=5000, sigma0=1.6, s
     `balance="ICE"` (not in the reference): balance the raw map on the GPU instead of applying `bias` (read_contacts)."""
     chromosome2 = _check_pair(f, chromosome, chromosome2)
     octave_values = [sigma0 * (2 ** i) for i in range(octaves)]
+    if chromosome != chromosome2:          # chromosome2 = B: the trans pair (A, B), mustache_amd/trans.py
+        if contacts is None:
+            contacts = read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromosome, chromosome2, verbose,
+                                     balance=balance)
+            if contacts is None:
+                return []
+        x, y, v, _res = contacts
+        return call_trans_coo(x, y, v, octave_values, st, pt, verbose=verbose, label="%s,%s" % (chromosome, chromosome2))
     if contacts is None:
         contacts = read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromosome, chromosome2, verbose,
                                  balance=balance)
@@ -421,7 +442,9 @@ def parse_args(args):
     p.add_argument("-ch", "--chromosome", dest="chromosome", nargs='+', default='n', required=False,
                    help="REQUIRED: chromosome(s) to run on. Optional for cooler files.")
     p.add_argument("-ch2", "--chromosome2", dest="chromosome2", nargs='+', default='n', required=False,
-                   help="Optional: second chromosome (inter-chromosomal mode is non-functional upstream).")
+                   help="OPTIONAL: second chromosome of each pair, zipped with -ch (same count).  A pair of two different "
+                        "chromosomes is called inter-chromosomally on the GPU (.hic / .cool / .mcool input, one GPU, no "
+                        "--balance); a pair of one chromosome runs the intra-chromosomal path.")
     p.add_argument("-v", "--verbose", dest="verbose", type=bool, default=True, help="OPTIONAL: verbosity")
     p.add_argument("--balance", dest="balance", default=None, metavar="ICE",
                    help="OPTIONAL: balance the raw contact map on the GPU (ICE) instead of -b / -norm; text and .hic input")
@@ -538,6 +561,20 @@ def main(argv=None):
             print("Error: %s" % e)
             return
     pairs = list(zip(chr_list, chr_list2))
+    # inter-chromosomal pairs (mustache_amd/trans.py) run after every intra-chromosomal pair, in pair order
+    trans_pairs = [p for p in pairs if p[0] != p[1]]
+    pairs = [p for p in pairs if p[0] == p[1]]
+    if trans_pairs:
+        refusal = None
+        if not args.chromosome or args.chromosome == 'n':
+            refusal = "inter-chromosomal pairs need -ch and -ch2 (all-pairs runs are not supported)"
+        elif _world > 1:
+            refusal = "inter-chromosomal pairs run on one GPU only (this run has %d ranks)" % _world
+        elif args.balance is not None:
+            refusal = "--balance does not apply to inter-chromosomal pairs"
+        if refusal:
+            print("Error: %s" % refusal)
+            return
 
     try:                                     # the reader thread below must upload to THIS thread's device, not to GPU 0
         import torch
@@ -666,6 +703,21 @@ def main(argv=None):
                               octaves=args.octaves, contacts=contacts, shard_blocks=not by_chromosome)
             emit(i, o)
         flush()
+    first = not pairs                        # the header is written with the first pair's rows
+    for chromosome, chromosome2 in trans_pairs:
+        start_time = time.time()
+        _check_pair(f, chromosome, chromosome2)          # text input: the reference's refusal
+        contacts = read_contacts(f, args.norm_method, False, res, distFilter, biasf, chromosome, chromosome2,
+                                 verbose=args.verbose, device=my_device)
+        o = [] if contacts is None else regulator(
+            f, args.norm_method, False, args.outdir, res=contacts[3], sigma0=args.s_z, verbose=args.verbose, pt=args.pt,
+            st=args.st, distance_filter=distFilter, chromosome=chromosome, chromosome2=chromosome2, octaves=args.octaves,
+            contacts=contacts)
+        print("{0} loops found for chrmosome pair={1},{2}, fdr<{3} in {4}sec".format(
+            len(o), chromosome, chromosome2, args.pt, "%.2f" % (time.time() - start_time)))
+        if first or o:
+            write_loops(args.outdir, chromosome, chromosome2, res, o, first=first)
+            first = False
     if by_chromosome:
         # one gather of (chromosome index, x, y, fdr, sigma) records; rank 0 writes the chromosomes in their order
         from .sharding import gather_records

@@ -258,6 +258,25 @@ def read_mcooler(f, distance_in_bp, chr1, chr2, res, cooler_balance):
         raise NameError('Reading from the file failed!') from e
 
 
+def read_cooler_trans(f, chr1, chr2, res, cooler_balance):
+    """Every pixel of the (chr1, chr2) block of a `.cool` / `.mcool` file (mustache_amd/trans.py rule 1): x = bin of chr1,
+    y = bin of chr2, balanced by the cooler weights unless cooler_balance names another column; non-finite and non-positive
+    values dropped.  Returns (x, y, v, res)."""
+    cooler = _need("cooler")
+    if f.endswith(".mcool"):
+        clr = cooler.Cooler('%s::/resolutions/%s' % (f, res))
+    else:
+        clr = cooler.Cooler(f)
+        res = clr.binsize
+    if chr1 not in clr.chromnames or chr2 not in clr.chromnames:
+        raise NameError('wrong chromosome name!')
+    balance = True if not cooler_balance else cooler_balance
+    m = clr.matrix(balance=balance, sparse=True).fetch(chr1, chr2).tocoo()
+    v = np.asarray(m.data, dtype=np.float64)
+    keep = np.isfinite(v) & (v > 0)
+    return m.row[keep].astype(np.int64), m.col[keep].astype(np.int64), v[keep], res
+
+
 def chromosome_sizes(f, res):
     """{name: length in bp} for a .hic / .cool / .mcool file ({} when it cannot be told) -- only used to balance a
     whole-genome run over several GPUs."""

@@ -1,0 +1,237 @@
+"""Inter-chromosomal (trans) loop calling for one chromosome pair (A, B) on the GPU.
+
+The reference's trans branch is dead code (mustache.py:939-942 calls inter_normalize_map with the wrong arguments and never
+tiles), so the semantics are fixed here; tests/trans_reference.py restates them in NumPy / SciPy.
+
+1. Input: every record of the A x B matrix, x = bin of A, y = bin of B, value > 0 and finite (readers.py / read_hic_trans).
+2. Normalisation: over the N records, mean = sum v / N, std = sqrt(sum (v - mean)^2 / N), v' = (v - mean) / std, NaN / inf
+   -> 0 (mst_trans_zscore; exact sums, bit-identical under record permutation).  N = 0 or std = 0: no loops.
+3. Tiling: n1 = max(x) + 1, n2 = max(y) + 1, square tiles of C = min(2000, max(n1, n2)); per axis the reference's cis start
+   formula with CHUNK = C and overlap 256 (trans_axis_tiles); tile (i, j) OWNS rows [end_{i-1}, end_i) and columns
+   [end_{j-1}, end_j): every map pixel is owned by exactly one tile.  Cells outside the map are 0.
+4. Per tile: nz = c != 0 over the whole tile (mst_trans_prologue: no triangle masks, no fills); the reference's sigma loop on
+   nz (mst_scale_space, dense source); BH over the tile's found set, q < pt; fewer than 50 or 10 000 tested pixels: no loops;
+   the cis sparsity filter (x != 0, the same window arithmetic); no diagonal-mean filter.
+5. Clustering: 8-connected components of the selected pixels each dilated by its 3 x 3 neighbourhood, clipped at the tile
+   edges; the representative is the component's lowest q (o = q at found pixels, >= 1 elsewhere), ties to the first pixel in
+   row-major order (mst_cluster_representatives does exactly this for any tile; its halo never wraps).  A representative
+   is kept only if its tile owns it.
+6. Output rows sorted by (x, y): [x, y, fdr, sigma] in map coordinates.
+"""
+import os
+
+import numpy as np
+
+TRANS_CHUNK = 2000
+TRANS_OVERLAP = 256
+
+
+class TransError(RuntimeError):
+    """A trans request this package refuses (the CLI prints it as an `Error:` line)."""
+
+
+def trans_axis_tiles(n, chunk, overlap=TRANS_OVERLAP):
+    """(start[], end[]) of one axis: the reference's cis tiling formula (mustache.py:896-910) with CHUNK = chunk."""
+    n = int(n)
+    if n <= chunk:
+        return [0], [n]
+    start, end = [0], [chunk]
+    while end[-1] < n:
+        start.append(end[-1] - overlap)
+        end.append(start[-1] + chunk)
+    end[-1] = n
+    start[-1] = max(0, n - chunk)
+    return start, end
+
+
+def trans_tiling(n1, n2, chunk=TRANS_CHUNK):
+    """(C, rows, cols): tile size and the (start, end) lists of both axes."""
+    C = min(int(chunk), max(int(n1), int(n2)))
+    return C, trans_axis_tiles(n1, C), trans_axis_tiles(n2, C)
+
+
+def owned_range(ends, i):
+    """[lo, hi) that tile i of an axis owns: [end_{i-1}, end_i), end_{-1} = 0."""
+    return (ends[i - 1] if i > 0 else 0), ends[i]
+
+
+def _ptr(t):
+    import ctypes
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _stream():
+    import ctypes
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def zscore_device(v, device=None):
+    """v' of rule 2 for a float64 device (or host) vector: (v', mean, std, n).  mean / std come back to the host."""
+    import torch
+    from . import _lib
+    from .engine import require_gpu
+    lib = require_gpu()
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    v = torch.as_tensor(v, dtype=torch.float64).to(dev).contiguous()
+    out = torch.empty_like(v)
+    stats = torch.empty(4, dtype=torch.float64, device=dev)
+    ws_bytes = int(lib.mst_trans_zscore_workspace_bytes())
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mst_trans_zscore(_ptr(v), int(v.numel()), _ptr(out), _ptr(stats), _ptr(ws), ws_bytes, _stream()))
+    mean, std, n, _ = (float(a) for a in stats.cpu().numpy())
+    return out, mean, std, int(v.numel())
+
+
+def read_hic_trans(f, norm_method, chr_a, chr_b, res, device=None, slab_bytes=4 << 20, n_slabs=8, threads=0):
+    """Every record of the (chr_a, chr_b) matrix of a `.hic` file as DEVICE tensors (x int32, y int32, v float64): the host
+    inflates the zlib blocks (mst_hic_rawstream_open_trans), mst_trans_decode_hic_rows decodes the rows, divides by both
+    normalisation vectors (KR by default) and transposes a pair the file stores as (chr_b, chr_a)."""
+    import torch
+    from . import _lib
+    from .engine import require_gpu
+    from .hicfile import HicTransRawStream
+    from .readers import _HIC_LOCK, _hic_handle
+    lib = require_gpu()
+    norm = "KR" if not norm_method else str(norm_method)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    pool = torch.empty(n_slabs * slab_bytes, dtype=torch.uint8, pin_memory=True)
+    xs, ys, vs = [], [], []
+    with _HIC_LOCK, torch.cuda.device(dev):
+        h = _hic_handle(f)
+        st = HicTransRawStream(h, chr_a, chr_b, res, norm, pool.data_ptr(), n_slabs, slab_bytes, threads=threads)
+        try:
+            na, nb, _, _ = st.info()
+            d_na = None if na is None else torch.from_numpy(na).to(dev)
+            d_nb = None if nb is None else torch.from_numpy(nb).to(dev)
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            while True:
+                got = st.next(-1)
+                if got is False:
+                    break
+                if got is None:
+                    continue
+                slab, nbytes, rows = got
+                base = slab * slab_bytes
+                pay = pool[base:base + max(nbytes, 2)].to(dev)
+                dr = pool[base + slab_bytes - 16 * rows:base + slab_bytes].to(dev)
+                torch.cuda.current_stream().synchronize()           # the slab is free once its bytes are on the device
+                st.release(slab)
+                cap = nbytes // 2 + rows
+                x = torch.empty(cap, dtype=torch.int32, device=dev)
+                y = torch.empty(cap, dtype=torch.int32, device=dev)
+                v = torch.empty(cap, dtype=torch.float64, device=dev)
+                count.zero_()
+                _lib.check(lib.mst_trans_decode_hic_rows(_ptr(pay), _ptr(dr), int(rows), _ptr(d_na), -1 if na is None else len(na),
+                                                         _ptr(d_nb), -1 if nb is None else len(nb), 1 if st.transposed else 0,
+                                                         _ptr(x), _ptr(y), _ptr(v), cap, _ptr(count), _stream()))
+                k = int(count.item())
+                if k > cap:
+                    raise RuntimeError("mst_trans_decode_hic_rows: %d records in a slab of capacity %d" % (k, cap))
+                xs.append(x[:k])
+                ys.append(y[:k])
+                vs.append(v[:k])
+        finally:
+            st.close()
+    if not xs:
+        z = torch.zeros(0, dtype=torch.int32, device=dev)
+        return z, z.clone(), torch.zeros(0, dtype=torch.float64, device=dev)
+    return torch.cat(xs), torch.cat(ys), torch.cat(vs)
+
+
+def read_trans_contacts(f, norm_method, chr_a, chr_b, res, device=None):
+    """(x, y, v, res) of the pair: `.hic` through read_hic_trans (device tensors), `.cool` / `.mcool` through cooler (host
+    arrays); None when the pair has no record."""
+    if f.endswith(".hic"):
+        x, y, v = read_hic_trans(f, norm_method, chr_a, chr_b, res, device=device)
+    elif f.endswith(".cool") or f.endswith(".mcool"):
+        from .readers import read_cooler_trans
+        x, y, v, res = read_cooler_trans(f, chr_a, chr_b, res, norm_method)
+    else:
+        raise TransError("Interchromosomal analysis is only supported for .hic and .cool input formats.")
+    if len(v) == 0:
+        return None
+    return x, y, v, res
+
+
+class TransCaller:
+    """Rules 2-6 on the GPU for one pair's records.  `tiles_per_launch` tiles go through one scatter, one prologue and one
+    fused scale-space launch (mst_scale_space over dense tiles) and one batched tail."""
+
+    def __init__(self, octave_values=(1.6, 3.2), device=None, tiles_per_launch=None, chunk=TRANS_CHUNK):
+        from .mustache import _engine
+        self.chunk = int(chunk)            # rule 3's 2000; smaller values only to exercise many tiles on small maps
+        self.eng = _engine(octave_values)
+        self.device = self.eng.device if device is None else device
+        self.tiles_per_launch = int(tiles_per_launch or os.environ.get("MUSTACHE_TRANS_TILES", "64"))
+
+    def normalize(self, x, y, v):
+        """device (x int32, y int32, v' float64) and (mean, std, n) of rule 2"""
+        import torch
+        dev = self.device
+        x = torch.as_tensor(x).to(dev, dtype=torch.int32).contiguous()
+        y = torch.as_tensor(y).to(dev, dtype=torch.int32).contiguous()
+        vz, mean, std, n = zscore_device(v, dev)
+        return x, y, vz, (mean, std, n)
+
+    def run_tiles(self, x, y, vz, n1, n2, st, pt):
+        """rules 3-6 on normalised device records: loops [x, y, fdr, sigma] sorted by (x, y)"""
+        import torch
+        from . import _lib
+        from .engine import BlockBatch
+        from .tail import batch_tail
+        eng, dev = self.eng, self.device
+        lib = eng.lib
+        C, (rs, re), (cs, ce) = trans_tiling(n1, n2, self.chunk)
+        tiles = [(i, j) for i in range(len(rs)) for j in range(len(cs))]
+        out = []
+        for g0 in range(0, len(tiles), self.tiles_per_launch):
+            group = tiles[g0:g0 + self.tiles_per_launch]
+            B = len(group)
+            row0 = torch.tensor([rs[i] for i, _ in group], dtype=torch.int64, device=dev)
+            col0 = torch.tensor([cs[j] for _, j in group], dtype=torch.int64, device=dev)
+            c = torch.empty((B, C, C), dtype=torch.float64, device=dev)
+            nz = torch.empty((B, C, C), dtype=torch.uint8, device=dev)
+            nzc = torch.empty(B, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.mst_trans_scatter_tiles(_ptr(x), _ptr(y), _ptr(vz), int(vz.numel()), _ptr(row0), _ptr(col0), B, C,
+                                                       _ptr(c), _stream()))
+                _lib.check(lib.mst_trans_prologue(_ptr(c), _ptr(nz), _ptr(nzc), B, C, _stream()))
+                found, fits = eng.sigma_loop(c, nz, nzc, with_value=False, select_below=pt)
+            batch = BlockBatch(eng, c, nz, C, B, nzc.cpu().numpy().view(np.uint32).astype(np.int64), found, fits)
+            loops = batch_tail(batch, list(range(B)), [0] * B, pt, st, intra=False)
+            for (i, j), lp in zip(group, loops):
+                rlo, rhi = owned_range(re, i)
+                clo, chi = owned_range(ce, j)
+                for lx, ly, q, sg in lp:
+                    gx, gy = int(lx) + rs[i], int(ly) + cs[j]
+                    if rlo <= gx < rhi and clo <= gy < chi:
+                        out.append([np.int64(gx), np.int64(gy), q, sg])
+            del c, nz
+        out.sort(key=lambda r: (int(r[0]), int(r[1])))
+        return out
+
+    def run(self, x, y, v, st, pt, verbose=False, label=""):
+        """rules 2-6 on a pair's records (host arrays or device tensors)"""
+        import torch
+        if len(v) == 0:
+            print("There is no contact in the chromosome pair %s to work on." % label)
+            return []
+        x, y, vz, (mean, std, n) = self.normalize(x, y, v)
+        if not (np.isfinite(mean) and np.isfinite(std)) or std == 0:
+            print("There is no contact in the chromosome pair %s to work on." % label)
+            return []
+        n1 = int(torch.max(x).item()) + 1
+        n2 = int(torch.max(y).item()) + 1
+        if verbose:
+            C, (rs, _), (cs, _) = trans_tiling(n1, n2, self.chunk)
+            print("Loop calling (trans %s: %d x %d bins, %d tiles of %d)..." % (label, n1, n2, len(rs) * len(cs), C))
+        return self.run_tiles(x, y, vz, n1, n2, st, pt)
+
+
+def call_trans_coo(x, y, v, octave_values, st, pt, verbose=False, label="", tiles_per_launch=None, chunk=TRANS_CHUNK):
+    """Loops of one chromosome pair from its records (x = bins of A, y = bins of B, v > 0): rules 2-6 of this module.
+    Returns [[x, y, fdr, sigma], ...] sorted by (x, y)."""
+    return TransCaller(octave_values, tiles_per_launch=tiles_per_launch, chunk=chunk).run(x, y, v, st, pt, verbose=verbose,
+                                                                                          label=label)
