@@ -14,15 +14,21 @@ p-values of the found pixels -> compacted found records on the host.  The step i
 N ranks = STRONG scaling, the reference's own partition (one process per block of ONE chromosome, mustache.py:913-937):
 the 124 blocks are split into N contiguous ranges, no data-path collective; the step time is the MAX over ranks between
 two barriers and `value` = 1,984 Mpix / that time, whole job, at every N.  (`--scaling weak` = one whole chromosome per
-rank, the genome partition; the mode that is not the headline is timed in the same run and reported as `other_scaling`.)
+rank, the genome partition.)
 
-On the same JSON line: `roofline` (the fused kernel, HIP events on the launch stream, against the FP64 vector pipe WITHOUT
-FMA -- bit-exactness with SciPy forbids contraction: 1152 flops per pixel over 39.3 TFLOP/s; `hbm_model` = SURVEY 8d's
-592 B / pixel model beside the PMC traffic), `cpu_baseline` (the CPU oracle: one block on 1 core, `p4` = 8 blocks in 4 processes
-as the reference's default -p 4, and the first / middle / last block's whole found sets checked against the HIP path),
-`band_skip` (empty tiles skipped: the product mode) and `tile_sharing` / `no_share` (separate speed-ups), `chr21_5kb` /
-`diff_chr21_5kb`, `end_to_end` / `end_to_end_from_file`, `ranks` (at N = 1 with a labelled single-GPU projection of the strong
-split: every rank's block range of N = 2, 4, 8 timed alone on this GPU).  `--extra` adds the side legs of scripts/bench_extra.py.
+A plain run does only what the headline needs: set-up, the warm-up and timed steps, `--dump-outputs`, and the JSON line with
+what those steps measured -- `config`, `ranks` (the step of the slowest and fastest rank) and `roofline` (the fused kernel of
+the timed steps, HIP events on the launch stream, against the FP64 vector pipe WITHOUT FMA -- bit-exactness with SciPy
+forbids contraction: 1152 flops per pixel over 39.3 TFLOP/s; `hbm_model` = SURVEY 8d's 592 B / pixel model beside the PMC
+traffic).
+
+`--full` adds the legs that take runs of their own: `band_skip` (empty tiles skipped: the product mode) and `tile_sharing` /
+`no_share` (separate speed-ups), at N > 1 the scaling mode that is not the headline (`other_scaling`), and at N = 1
+`cpu_baseline` (the CPU oracle: one block on 1 core, `p4` = 8 blocks in 4 processes as the reference's default -p 4, and the
+first / middle / last block's whole found sets checked against the HIP path), `chr21_5kb` / `diff_chr21_5kb`, `end_to_end`,
+and a labelled single-GPU projection of the strong split in `ranks` (every rank's block range of N = 2, 4, 8 timed alone on
+this GPU); `end_to_end_from_file` at every N.  `--no-cpu`, `--no-file` and `--core` leave legs out of a `--full` run;
+`--extra` (implies `--full`) adds the side legs of scripts/bench_extra.py.
 """
 import argparse
 import json
@@ -131,10 +137,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-file", action="store_true", help="skip the end-to-end-from-a-.hic-file leg")
-    ap.add_argument("--core", action="store_true", help="no file or CPU legs (what the PMC passes of scripts/profile_bench.sh run)")
-    ap.add_argument("--extra", action="store_true", help="add the side legs of scripts/bench_extra.py (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the legs that take runs of their own: band skip / tile sharing, the other "
+                         "scaling mode, the share projection, end to end, chr21 @ 5 kb, the file leg and the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline leg")
+    ap.add_argument("--no-file", action="store_true", help="--full without the end-to-end-from-a-.hic-file leg")
+    ap.add_argument("--core", action="store_true",
+                    help="--full without the file or CPU legs (what the PMC passes of scripts/profile_bench.sh run)")
+    ap.add_argument("--extra", action="store_true", help="add the side legs of scripts/bench_extra.py (N = 1 only; implies --full)")
     ap.add_argument("--small", action="store_true", help="debug: 12 blocks instead of 124")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="N > 1: strong (default, the metric) = ONE chromosome's blocks in contiguous ranges over the ranks; weak "
@@ -146,6 +156,7 @@ def parse():
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
     a.no_cpu, a.no_file = a.no_cpu or a.core, a.no_file or a.core
+    a.full = a.full or a.extra
     return a
 
 
@@ -585,6 +596,101 @@ def small_shape_legs(device):
                                   "p-values, BH + selection + partner look-ups on the device, selected records to the host)"}})
 
 
+def sharing_legs(cx, dt, value, kernel_ms_per_step, wi):
+    """--full: the headline step again with empty tiles skipped (`band_skip`), with every tile computed once per block
+    (`no_share`), and the speed-up of tile sharing (`tile_sharing`); `dt` = the headline's timed seconds, `value` its rate,
+    `wi` its work_items."""
+    w, args = cx.w, cx.args
+    # the same step with empty tiles skipped (the product mode: identical results, a separate speed-up, never `value`)
+    hs = max(1, args.steps // 2)
+    frac = w.pipe.engine.band_tile_fraction(w.CH, w.dpx)
+    dt_s, kms_s, _, _ = cx.timed(True, hs, 1)
+    wis = work_items(w, True)
+    bs_credit = len(w.mine) * w.CH * w.CH * frac * FLOPS_PER_PIXEL / (sum(kms_s) / hs * 1e-3) / 1e12
+    band_skip = {"value": round(w.total_mpix / (dt_s / hs), 1), "unit": "Mpix/s", "speedup": round((dt / args.steps) / (dt_s / hs), 3),
+                 "kernel_ms_per_step": round(sum(kms_s) / hs, 3), "launched_tile_fraction": round(frac, 4),
+                 "roofline": {"bound": "fp64_valu", "peak": PEAK_TF, "unit": "TFLOP/s",
+                              "achieved": round(bs_credit * wis[0] / wis[1], 3), "frac": round(bs_credit * wis[0] / wis[1] / PEAK_TF, 4),
+                              "work_items": wis[0], "tiles": wis[1], "shared_tiles": wis[2], "work_items_per_launch": wis[3],
+                              "block_pixel_view": {"achieved": round(bs_credit, 3), "frac": round(bs_credit / PEAK_TF, 4)},
+                              "note": "1152 flops per pixel of the band tiles the workgroups really computed over the kernel time"},
+                 "note": "only the tiles that can reach the tested band are launched; `value` / `roofline` are always the dense run"}
+
+    # both again with every tile computed once PER BLOCK (MST_FLAG_NO_SHARE): identical records; the kernel's own rate
+    w.pipe.engine.share_tiles = False
+    dt_n, kms_n, _, _ = cx.timed(False, hs, 1)
+    dt_ns, kms_ns, _, _ = cx.timed(True, hs, 1)
+    w.pipe.engine.share_tiles = True
+    kn, kns = sum(kms_n) / hs, sum(kms_ns) / hs
+    tf_n = len(w.mine) * w.CH * w.CH * FLOPS_PER_PIXEL / (kn * 1e-3) / 1e12
+    tf_ns = len(w.mine) * w.CH * w.CH * frac * FLOPS_PER_PIXEL / (kns * 1e-3) / 1e12
+    no_share = {"value": round(w.total_mpix / (dt_n / hs), 1), "unit": "Mpix/s", "kernel_ms_per_step": round(kn, 3),
+                "roofline": {"bound": "fp64_valu", "achieved": round(tf_n, 3), "peak": PEAK_TF, "unit": "TFLOP/s", "frac": round(tf_n / PEAK_TF, 4)},
+                "band_skip": {"value": round(w.total_mpix / (dt_ns / hs), 1), "unit": "Mpix/s", "kernel_ms_per_step": round(kns, 3),
+                              "roofline": {"bound": "fp64_valu", "achieved": round(tf_ns, 3), "peak": PEAK_TF, "unit": "TFLOP/s",
+                                           "frac": round(tf_ns / PEAK_TF, 4)}},
+                "work_items_per_launch": {"dense": work_items(w, False, share=False)[3], "band_skip": work_items(w, True, share=False)[3]},
+                "note": "MST_FLAG_NO_SHARE: every workgroup's flops are algorithmic flops of one block -- the kernel's own efficiency"}
+    tile_sharing = {"speedup": round(value / no_share["value"], 4), "kernel_speedup": round(kn / kernel_ms_per_step, 4),
+                    "band_skip_speedup": round(band_skip["value"] / no_share["band_skip"]["value"], 4),
+                    "work_items": wi[0], "tiles": wi[1], "shared_tiles": wi[2],
+                    "note": "blocks overlap by half their edge at 1 kb (mustache.py:899-908); a tile inside two blocks of a launch is "
+                            "computed once, its records / statistics delivered to both.  `value` is WITH sharing, no_share without"}
+    return {"tile_sharing": tile_sharing, "band_skip": band_skip, "no_share": no_share}
+
+
+def full_legs(cx, out, value, ms_per_step, no_share):
+    """--full, after the headline (`value`, `ms_per_step`) and sharing_legs (`no_share`): the legs that add keys of their own
+    to the line `out`"""
+    import torch
+    w, args, rank, world = cx.w, cx.args, cx.rank, cx.world
+    strong = args.scaling == "strong"
+    if world > 1:
+        # the other partitioning, timed after the headline (every rank takes part): same step, same timed region, max over ranks
+        other = "weak" if strong else "strong"
+        w.set_scaling(other)
+        dt_o, _, _, owns_o = cx.timed(False, args.steps, 2)
+        out["other_scaling"] = {"scaling": other, "value": round(w.total_mpix / (dt_o / args.steps), 1), "unit": "Mpix/s",
+                                "ms_per_step": round(dt_o / args.steps * 1e3, 3), "megapixels_per_step": round(w.total_mpix, 1),
+                                "blocks_on_this_rank": len(w.mine),
+                                "ms_per_step_max": round(max(owns_o) / args.steps * 1e3, 3),
+                                "ms_per_step_min": round(min(owns_o) / args.steps * 1e3, 3),
+                                "note": "weak = a whole chromosome per rank (a genome run); strong = ONE chromosome's blocks over the ranks"}
+        w.set_scaling(args.scaling)
+
+    solo = rank == 0 and world == 1
+    if solo:
+        out["ranks"].update(share_projection(w, ms_per_step))
+    if solo:
+        # informational: the whole per-chromosome run from the normalised band (rows 2-9, product mode) -- NOT part of `value`
+        w.pipe.run_band(w.band, w.n, w.dpx, 0.88, 0.1, distributed=False)      # first call: staging buffers, allocator
+        runs = []
+        for _ in range(3):
+            tm = {}
+            torch.cuda.synchronize()
+            t0 = time.time()
+            loops = w.pipe.run_band(w.band, w.n, w.dpx, 0.88, 0.1, timings=tm, distributed=False)
+            torch.cuda.synchronize()
+            runs.append((time.time() - t0, tm.get("tail_s", 0.0)))
+        runs.sort()
+        out["end_to_end"] = {"rows_2_to_9_s": round(runs[1][0], 3), "normalize_s": round(w.normalize_s, 3),
+                             "tail_s": round(runs[1][1], 3), "loops": len(loops), "all_runs_s": [round(r[0], 3) for r in runs],
+                             "note": "synthetic chr1@1kb from the normalised band to the final loop list, 1 GPU (median of 3)"}
+        out["chr21_5kb"], out["diff_chr21_5kb"] = small_shape_legs(cx.device)
+    extra = None
+    if args.extra and solo:
+        extra = __import__("scripts.bench_extra", fromlist=["Extra"]).Extra(sys.modules[__name__], cx, out, value, no_share)
+        extra.before_file_leg()
+    if not args.no_file:
+        # every rank takes part (N > 1: each inflates its share of the file, the shares are exchanged); rank 0 reports
+        out["end_to_end_from_file"] = fl = file_leg(cx, on_band=extra.sparse_step if extra else None)
+        out["ranks"]["read_s"] = fl["read_s_per_rank"]
+    if solo and not args.no_cpu:
+        out["cpu_baseline"], out["speedup_vs_cpu_1core"], out["speedup_vs_cpu_p4"] = cpu_baseline(w, value)
+        if extra:
+            extra.cpu_pools()
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -672,42 +778,7 @@ def main():
                           "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac_of_model_roofline": round(achieved_gbs / HBM_PEAK_GBS, 4),
                           "note": "SURVEY 8d's level-streaming model: the rate the kernel WOULD need if it wrote and re-read every "
                                   "level -- it holds all levels on chip instead, see traffic"}}
-
-    # the same step with empty tiles skipped (the product mode: identical results, a separate speed-up, never `value`)
-    hs = max(1, args.steps // 2)
-    frac = w.pipe.engine.band_tile_fraction(w.CH, w.dpx)
-    dt_s, kms_s, _, _ = cx.timed(True, hs, 1)
-    wis = work_items(w, True)
-    bs_credit = len(w.mine) * w.CH * w.CH * frac * FLOPS_PER_PIXEL / (sum(kms_s) / hs * 1e-3) / 1e12
-    band_skip = {"value": round(w.total_mpix / (dt_s / hs), 1), "unit": "Mpix/s", "speedup": round((dt / args.steps) / (dt_s / hs), 3),
-                 "kernel_ms_per_step": round(sum(kms_s) / hs, 3), "launched_tile_fraction": round(frac, 4),
-                 "roofline": {"bound": "fp64_valu", "peak": PEAK_TF, "unit": "TFLOP/s",
-                              "achieved": round(bs_credit * wis[0] / wis[1], 3), "frac": round(bs_credit * wis[0] / wis[1] / PEAK_TF, 4),
-                              "work_items": wis[0], "tiles": wis[1], "shared_tiles": wis[2], "work_items_per_launch": wis[3],
-                              "block_pixel_view": {"achieved": round(bs_credit, 3), "frac": round(bs_credit / PEAK_TF, 4)},
-                              "note": "1152 flops per pixel of the band tiles the workgroups really computed over the kernel time"},
-                 "note": "only the tiles that can reach the tested band are launched; `value` / `roofline` are always the dense run"}
-
-    # both again with every tile computed once PER BLOCK (MST_FLAG_NO_SHARE): identical records; the kernel's own rate
-    w.pipe.engine.share_tiles = False
-    dt_n, kms_n, _, _ = cx.timed(False, hs, 1)
-    dt_ns, kms_ns, _, _ = cx.timed(True, hs, 1)
-    w.pipe.engine.share_tiles = True
-    kn, kns = sum(kms_n) / hs, sum(kms_ns) / hs
-    tf_n = len(w.mine) * w.CH * w.CH * FLOPS_PER_PIXEL / (kn * 1e-3) / 1e12
-    tf_ns = len(w.mine) * w.CH * w.CH * frac * FLOPS_PER_PIXEL / (kns * 1e-3) / 1e12
-    no_share = {"value": round(w.total_mpix / (dt_n / hs), 1), "unit": "Mpix/s", "kernel_ms_per_step": round(kn, 3),
-                "roofline": {"bound": "fp64_valu", "achieved": round(tf_n, 3), "peak": PEAK_TF, "unit": "TFLOP/s", "frac": round(tf_n / PEAK_TF, 4)},
-                "band_skip": {"value": round(w.total_mpix / (dt_ns / hs), 1), "unit": "Mpix/s", "kernel_ms_per_step": round(kns, 3),
-                              "roofline": {"bound": "fp64_valu", "achieved": round(tf_ns, 3), "peak": PEAK_TF, "unit": "TFLOP/s",
-                                           "frac": round(tf_ns / PEAK_TF, 4)}},
-                "work_items_per_launch": {"dense": work_items(w, False, share=False)[3], "band_skip": work_items(w, True, share=False)[3]},
-                "note": "MST_FLAG_NO_SHARE: every workgroup's flops are algorithmic flops of one block -- the kernel's own efficiency"}
-    tile_sharing = {"speedup": round(value / no_share["value"], 4), "kernel_speedup": round(kn / (k_ms * launches_per_step), 4),
-                    "band_skip_speedup": round(band_skip["value"] / no_share["band_skip"]["value"], 4),
-                    "work_items": wi[0], "tiles": wi[1], "shared_tiles": wi[2],
-                    "note": "blocks overlap by half their edge at 1 kb (mustache.py:899-908); a tile inside two blocks of a launch is "
-                            "computed once, its records / statistics delivered to both.  `value` is WITH sharing, no_share without"}
+    legs = sharing_legs(cx, dt, value, k_ms * launches_per_step, wi) if args.full else {}
 
     strong = args.scaling == "strong"
     ranges = [shard_blocks(nb, r, world) for r in range(world)]
@@ -729,53 +800,9 @@ def main():
                      "efficiency_bound": round(sum(per_rank) / float(world * max(per_rank)), 4),
                      "efficiency_bound_at": {str(k): round(nb / (k * -(-nb // k)), 4) for k in (1, 2, 4, 8)},
                      "note": "contiguous split: the slowest rank carries ceil(blocks / ranks) blocks -> efficiency_bound_at"},
-           "roofline": roof, "tile_sharing": tile_sharing, "band_skip": band_skip, "no_share": no_share,
-           "normalize_ms_untimed": round(w.normalize_s * 1e3, 2)}
-
-    if world > 1:
-        # the other partitioning, timed after the headline (every rank takes part): same step, same timed region, max over ranks
-        other = "weak" if strong else "strong"
-        w.set_scaling(other)
-        dt_o, _, _, owns_o = cx.timed(False, args.steps, 2)
-        out["other_scaling"] = {"scaling": other, "value": round(w.total_mpix / (dt_o / args.steps), 1), "unit": "Mpix/s",
-                                "ms_per_step": round(dt_o / args.steps * 1e3, 3), "megapixels_per_step": round(w.total_mpix, 1),
-                                "blocks_on_this_rank": len(w.mine),
-                                "ms_per_step_max": round(max(owns_o) / args.steps * 1e3, 3),
-                                "ms_per_step_min": round(min(owns_o) / args.steps * 1e3, 3),
-                                "note": "weak = a whole chromosome per rank (a genome run); strong = ONE chromosome's blocks over the ranks"}
-        w.set_scaling(args.scaling)
-
-    solo = rank == 0 and world == 1
-    if solo:
-        out["ranks"].update(share_projection(w, ms_per_step))
-    if solo:
-        # informational: the whole per-chromosome run from the normalised band (rows 2-9, product mode) -- NOT part of `value`
-        w.pipe.run_band(w.band, w.n, w.dpx, 0.88, 0.1, distributed=False)      # first call: staging buffers, allocator
-        runs = []
-        for _ in range(3):
-            tm = {}
-            torch.cuda.synchronize()
-            t0 = time.time()
-            loops = w.pipe.run_band(w.band, w.n, w.dpx, 0.88, 0.1, timings=tm, distributed=False)
-            torch.cuda.synchronize()
-            runs.append((time.time() - t0, tm.get("tail_s", 0.0)))
-        runs.sort()
-        out["end_to_end"] = {"rows_2_to_9_s": round(runs[1][0], 3), "normalize_s": round(w.normalize_s, 3),
-                             "tail_s": round(runs[1][1], 3), "loops": len(loops), "all_runs_s": [round(r[0], 3) for r in runs],
-                             "note": "synthetic chr1@1kb from the normalised band to the final loop list, 1 GPU (median of 3)"}
-        out["chr21_5kb"], out["diff_chr21_5kb"] = small_shape_legs(device)
-    extra = None
-    if args.extra and solo:
-        extra = __import__("scripts.bench_extra", fromlist=["Extra"]).Extra(sys.modules[__name__], cx, out, value, no_share)
-        extra.before_file_leg()
-    if not args.no_file:
-        # every rank takes part (N > 1: each inflates its share of the file, the shares are exchanged); rank 0 reports
-        out["end_to_end_from_file"] = fl = file_leg(cx, on_band=extra.sparse_step if extra else None)
-        out["ranks"]["read_s"] = fl["read_s_per_rank"]
-    if solo and not args.no_cpu:
-        out["cpu_baseline"], out["speedup_vs_cpu_1core"], out["speedup_vs_cpu_p4"] = cpu_baseline(w, value)
-        if extra:
-            extra.cpu_pools()
+           "roofline": roof, **legs, "normalize_ms_untimed": round(w.normalize_s * 1e3, 2)}
+    if args.full:
+        full_legs(cx, out, value, ms_per_step, legs["no_share"])
     if rank == 0:
         print(json.dumps(out))
     if grouped:

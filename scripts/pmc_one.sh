@@ -6,7 +6,7 @@ OUT=$REPO/gpurun_out/pmc1
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$REPO
-env "$@" rocprofv3 --pmc $C --kernel-trace -d $OUT/g -o pmc --output-format csv -- python $REPO/bench.py --small --steps 1 --warmup 0 --no-cpu > $OUT/log.txt 2>&1
+env "$@" rocprofv3 --pmc $C --kernel-trace -d $OUT/g -o pmc --output-format csv -- python $REPO/bench.py --small --steps 1 --warmup 0 --full --no-cpu > $OUT/log.txt 2>&1
 python - <<PY
 import csv, glob, collections
 per = collections.defaultdict(dict)

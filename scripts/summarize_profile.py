@@ -15,9 +15,9 @@ out_md = os.path.join(src, tag + "_summary.md")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 lines = ["# rocprofv3 summary `%s`" % tag, "",
-         "Command: `rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1 --no-cpu --no-file` "
+         "Command: `rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1 --full --no-cpu --no-file` "
          "(scripts/profile_bench.sh); PMC passes: `rocprofv3 --pmc <counters> --kernel-trace -- python bench.py --small "
-         "--steps 1 --warmup 0 --core` with `MST_BENCH_OVERLAP=1` (12 blocks of 4000x4000 in ONE launch), one pass per counter "
+         "--steps 1 --warmup 0 --full --core` with `MST_BENCH_OVERLAP=1` (12 blocks of 4000x4000 in ONE launch), one pass per counter "
          "group, all in the same session as the trace.  The traced run uses bench.py's default: ONE launch per step in three stages (mst_scale_space_band_stage: three kernel invocations over one work list), the finish of a stage under the next stage's kernel.", ""]
 
 # ---- kernel stats ------------------------------------------------------------------------------------------------
@@ -271,7 +271,7 @@ if "diag_stats_kernel" in extra and "normalize_walk_kernel" in extra:
               16.0 * samples / tot / 1e6 / 8000.0)]
 open(out_md, "w").write("\n".join(lines) + "\n")
 if traffic:
-    traffic["command"] = "MST_BENCH_OVERLAP=1 rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python bench.py --small --steps 1 --warmup 0 --no-cpu"
+    traffic["command"] = "MST_BENCH_OVERLAP=1 rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python bench.py --small --steps 1 --warmup 0 --full --no-cpu"
     traffic["other_kernels"] = extra
     json.dump(traffic, open(os.path.join(src, tag + "_pmc_traffic.json"), "w"), indent=1)
 # keep the raw stats csv next to the summary

@@ -463,6 +463,22 @@ def test_bench_stage_cuts():
         assert c[0] == 0 and c[-1] == nb and all(b > a for a, b in zip(c[:-1], c[1:]))
 
 
+def test_bench_plain_run_unless_full(monkeypatch):
+    """bench.parse: a plain run by default; --full turns the other legs on, --extra implies it, --core trims it"""
+    import sys
+    import bench
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+        return bench.parse()
+    a = parse("--gpus", "1", "--steps", "3", "--warmup", "1")
+    assert not a.full and not a.extra and a.steps == 3 and a.warmup == 1
+    assert parse("--full").full and not parse("--full").no_cpu and not parse("--full").no_file
+    assert parse("--extra").full
+    a = parse("--full", "--core")
+    assert a.full and a.no_cpu and a.no_file
+
+
 def test_bench_dump_outputs_orders_records_and_samples_above_the_cap(tmp_path, monkeypatch):
     """bench.py --dump-outputs on host data shaped like Workload.step's: blocks in block order whatever the stage split, records
     by pixel and level inside each block, and above the size cap a seeded sample that is the same on every call"""
