@@ -22,7 +22,8 @@ import time
 
 import numpy as np
 
-from .mustache import (_engine, block_tiling, block_mask_size, parseBP, read_pd)
+from .mustache import (_engine, block_tiling, block_mask_size, chromosome_pairs, owned_chromosomes, parseBP,
+                       read_sample)
 from .tail import (fdr_candidates_multi, diag_mean_filter_multi, cluster_representatives, loops_from_reps,
                    _features_multi)
 
@@ -185,9 +186,12 @@ def run_pair_genome(pipe, pairs, distance_in_px, st, pt, pt2):
     call_diff_loops_coo on each chromosome alone."""
     from .pipeline import GenomeLayout
     lay = GenomeLayout([n for _, n in pairs], distance_in_px)
-    # `pairs` is consumed: each sample's chromosome bands are released one by one as they are copied into that sample's
-    # genome band (the caller holds no other reference), so the peak is the genome bands + the bands not yet copied
+    # `pairs` is consumed down to the bands: each chromosome's list of the two bands is emptied, so that whatever other
+    # reference to those lists the caller still holds, each sample's chromosome bands are released one by one as they are
+    # copied into that sample's genome band -- the peak is the genome bands + the bands not yet copied
     per_sample = [[d[s_] for d, _ in pairs] for s_ in (0, 1)]
+    for d, _ in pairs:
+        d.clear()
     del pairs[:]
     gbands = [lay.band(per_sample[s_], pipe.device, consume=True) for s_ in (0, 1)]
     return run_pair_layout(pipe, lay, gbands, st, pt, pt2)
@@ -263,38 +267,18 @@ def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2,
         raise NotImplementedError("inter-chromosomal mode is non-functional in the reference (diff_mustache.py:687-690)")
     if verbose:
         print("Reading contact map...")
-    coos = []
     if balance:
-        from .balance import check_request, read_hic_balanced
-        from .mustache import read_pd_balanced
+        from .balance import check_request
         check_request(balance, [f1, f2], bias1 or bias2, norm_method, bias_flag="-b1/-b2")
-        for f in (f1, f2):
-            if f.endswith(".hic"):             # raw counts through the native reader, whatever MUSTACHE_HIC_BACKEND says
-                coos.append(read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res))
-            else:
-                coos.append(read_pd_balanced(f, distance_in_bp, chromosome, res))
-    for f, bias in ((f1, bias1), (f2, bias2)) if not balance else ():
-        if f.endswith(".hic"):
-            from .readers import hic_backend, read_hic_file, read_hic_packed
-            if hic_backend() == "native":
-                # the packed / streamed form the single-sample CLI uses: same record set as read_hic_file (pinned on the
-                # reference's, tests/test_readers_ref.py) without the int64 / float64 triple; None = no contact
-                coo = read_hic_packed(f, norm_method, CHRM_SIZE, distance_in_bp, chromosome, res)
-            else:
-                coo = read_hic_file(f, norm_method, CHRM_SIZE, distance_in_bp, chromosome, chromosome2, res)
-        elif f.endswith(".cool"):
-            from .readers import read_cooler
-            x, y, v, r2 = read_cooler(f, distance_in_bp, chromosome, chromosome2, norm_method)
-            if coos and r2 != res:
-                raise ValueError('Both contact maps should have the same resolution.')
-            res, coo = r2, (x, y, v)
-        elif f.endswith(".mcool"):
-            from .readers import read_mcooler
-            coo = read_mcooler(f, distance_in_bp, chromosome, chromosome2, res, norm_method)
-        else:
-            coo = read_pd(f, distance_in_bp, bias, chromosome, res)
-        coos.append(coo)
     from .hicfile import PackedContacts
+    coos = []
+    for f, bias in ((f1, bias1), (f2, bias2)):
+        coo = read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome, balance=balance)
+        if coo is not None and not isinstance(coo, PackedContacts):
+            if coos and coo[3] != res:                # only a `.cool` file brings a resolution of its own
+                raise ValueError('Both contact maps should have the same resolution.')
+            res, coo = coo[3], coo[:3]
+        coos.append(coo)
     empty = lambda c: c is None or (len(c) == 0 if isinstance(c, PackedContacts) else len(c[2]) == 0)
     if empty(coos[0]) or empty(coos[1]):
         return None
@@ -385,18 +369,9 @@ def main(argv=None):
     if not res:
         print("Error: Invalid resolution")
         return
-    if not args.chromosome or args.chromosome == 'n':
-        if f1.endswith((".cool", ".mcool", ".hic")):
-            from .readers import list_chromosomes
-            chr_list = list_chromosomes(f1, res)
-        else:
-            print("Error: Please enter the chromosome name.")
-            return
-    else:
-        chr_list = list(args.chromosome)
-    chr_list2 = list(args.chromosome2) if isinstance(args.chromosome2, list) else list(chr_list)
-    if len(chr_list) != len(chr_list2):
-        print("Error: the same number of chromosome1 and chromosome2 should be provided.")
+    pairs = chromosome_pairs(f1, res, args.chromosome, args.chromosome2)
+    if isinstance(pairs, str):
+        print(pairs)
         return
     distFilter = resolve_distance_filter(args.distFilter, res)
     if args.biasfile1 and not os.path.exists(args.biasfile1):
@@ -407,11 +382,10 @@ def main(argv=None):
         return
     biasf1 = False            # reference quirk (:824-827): -b1 is checked for existence but never passed on
     biasf2 = args.biasfile2 if args.biasfile2 else False
-    pairs = list(zip(chr_list, chr_list2))
 
     # multi-GPU (`torchrun -m mustache_amd.diff_mustache ...`): chromosomes are dealt to the ranks largest first, each rank
     # reads and runs its own, ONE gather of (chromosome, x, y, fdr, sigma, list tag) records, rank 0 writes the four files
-    from .sharding import assign_chromosomes, gather_records, init_from_env
+    from .sharding import gather_chromosome_rows, init_from_env
     rank, world_size = init_from_env()
     if args.balance is not None:
         from .balance import BalanceError, check_request
@@ -421,13 +395,7 @@ def main(argv=None):
         except BalanceError as e:
             print("Error: %s" % e)
             return
-    mine = list(range(len(pairs)))
-    if world_size > 1:
-        from .readers import chromosome_sizes
-        sizes = chromosome_sizes(f1, res)
-        weights = [sizes.get(str(c), sizes.get("chr" + str(c).replace("chr", ""), 1)) for c, _ in pairs]
-        owner = assign_chromosomes(weights, world_size)
-        mine = [i for i in range(len(pairs)) if owner[i] == rank]
+    mine = owned_chromosomes(f1, res, pairs, rank, world_size) if world_size > 1 else list(range(len(pairs)))
 
     def write(i, o):
         chromosome, chromosome2 = pairs[i]
@@ -468,19 +436,10 @@ def main(argv=None):
     # collected in HBM and the block pairs of ALL chromosomes go through the same launches (run_pair_genome); the reference
     # runs chromosome after chromosome (diff_mustache.py:858-906).  Same rows, in the same chromosome order.
     batched = len(mine) > 1
-    genome_budget = None                 # bytes of held bands (both samples); pipeline.genome_batch_budget at the first band
-    held, held_bytes, pipe = [], 0, None
-
-    def flush():
-        nonlocal held, held_bytes
-        if held:
-            idx, dpx_h = [h[0] for h in held], held[0][3]
-            prs = [(list(h[1]), h[2]) for h in held]
-            held, held_bytes = [], 0             # `prs` holds the only references: run_pair_genome releases them as it copies
-            rows = run_pair_genome(pipe, prs, dpx_h, args.st, args.pt, args.pt2)
-            for i, o in zip(idx, rows):
-                emit(i, o)
-        held, held_bytes = [], 0
+    from .pipeline import GenomeBatcher
+    pipe = None
+    run_many = lambda items, ns, dpx: run_pair_genome(pipe, list(zip(items, ns)), dpx, args.st, args.pt, args.pt2)
+    genome = GenomeBatcher(lambda: pipe.device, run_many, lambda dbands, n, dpx: run_many([dbands], [n], dpx)[0], emit)
 
     for i in mine:
         chromosome, chromosome2 = pairs[i]
@@ -493,8 +452,7 @@ def main(argv=None):
         got = read_pair(f1, f2, args.norm_method, False, res, distFilter, biasf1, biasf2, chromosome, chromosome2,
                         args.verbose, balance=args.balance)
         if got is None:
-            flush()                               # keeps the output in chromosome order
-            emit(i, [])
+            genome.skip(i)
             continue
         if pipe is None:
             from .pipeline import ChromosomePipeline
@@ -506,30 +464,13 @@ def main(argv=None):
         if args.verbose:
             print("Normalizing contact map...")
         dbands, n = normalized_pair_bands(pipe, coo1, coo2, res_c, dpx)
-        nbytes = sum(b.numel() * 8 for b in dbands)
-        if genome_budget is None:
-            from .pipeline import genome_batch_budget
-            genome_budget = genome_batch_budget(pipe.device)
-        if held and (held[0][3] != dpx or held_bytes + nbytes > genome_budget):
-            flush()
-        if nbytes > genome_budget:               # this chromosome alone is over the budget: run it by itself, no second copy
-            flush()
-            alone = [(list(dbands), n)]
-            del dbands
-            emit(i, run_pair_genome(pipe, alone, dpx, args.st, args.pt, args.pt2)[0])
-            continue
-        held.append((i, dbands, n, dpx))
-        held_bytes += nbytes
-    flush()
+        genome.add(i, dbands, n, dpx, sum(b.numel() * 8 for b in dbands))
+    genome.flush()
     if world_size > 1:
-        rec = np.array([[i, float(r[0]), float(r[1]), float(r[2]), float(r[3]), float(r[4])]
-                        for i, o in results.items() for r in o], dtype=np.float64).reshape(-1, 6)
-        parts = gather_records(rec)
-        if rank == 0:
-            allrec = np.concatenate(parts)
-            for i in range(len(pairs)):
-                rows = allrec[allrec[:, 0] == i]
-                write(i, [[np.int64(a), np.int64(b), np.float64(q), np.float64(sg), int(t)] for _, a, b, q, sg, t in rows])
+        # one gather of (chromosome, x, y, fdr, sigma, list tag) records; rank 0 writes the four files
+        per_chromosome = gather_chromosome_rows(results, len(pairs), 5)
+        for i, rows in enumerate(per_chromosome or []):
+            write(i, [[np.int64(a), np.int64(b), np.float64(q), np.float64(sg), int(t)] for a, b, q, sg, t in rows])
 
 
 if __name__ == '__main__':

@@ -340,36 +340,45 @@ def read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromos
             raise TransError("inter-chromosomal pairs run on one GPU only")
         return read_trans_contacts(f, norm_method, chromosome, chromosome2, res, device=device)
     if balance:
-        from .balance import check_request, read_hic_balanced
+        from .balance import check_request
         check_request(balance, f, bias, norm_method, world=part[1])
-        if f.endswith(".hic"):                 # raw counts through the native reader, whatever MUSTACHE_HIC_BACKEND says
+    r = read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome, packed=packed, part=part,
+                    device=device, balance=balance)
+    if isinstance(r, tuple) and len(r[2]) == 0:
+        return None
+    return r
+
+
+def read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome, packed=True, part=(0, 1), device=None,
+                balance=None):
+    """One sample's intra-chromosomal records by file type, for read_contacts and diff_mustache.read_pair.  Returns
+    (x, y, v, res) host arrays (res: the file's own for `.cool`), possibly empty; hicfile.PackedContacts for a `.hic` file
+    when `packed` and the native reader serves it (a rank's share of `part` may be empty and is still returned: every
+    rank takes part in the exchange); None when a text reader finds no record of the chromosome.
+    balance="ICE": the raw counts balanced on the GPU (`.hic` through the native reader whatever MUSTACHE_HIC_BACKEND says,
+    text otherwise); the caller has already checked the request (balance.check_request)."""
+    if balance:
+        from .balance import read_hic_balanced
+        if f.endswith(".hic"):
             r = read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res, device=device)
         else:
             r = read_pd_balanced(f, distance_in_bp, chromosome, res, device=device)
-        if r is None or len(r[2]) == 0:
-            return None
-        return np.asarray(r[0]), np.asarray(r[1]), np.asarray(r[2], dtype=np.float64), res
-    if f.endswith(".hic") and packed:
-        from .readers import hic_backend, read_hic_packed
-        if hic_backend() == "native":
-            # part = (rank, ranks): several GPUs on ONE chromosome -- each rank inflates its share of the blocks only
+    elif f.endswith(".hic"):
+        from .readers import hic_backend, read_hic_file, read_hic_packed
+        if packed and hic_backend() == "native":
             return read_hic_packed(f, norm_method, CHRM_SIZE, distance_in_bp, chromosome, res, part=part, device=device)
-    if f.endswith(".hic"):
-        from .readers import read_hic_file
-        x, y, v = read_hic_file(f, norm_method, CHRM_SIZE, distance_in_bp, chromosome, chromosome2, res)
+        r = read_hic_file(f, norm_method, CHRM_SIZE, distance_in_bp, chromosome, chromosome, res)
     elif f.endswith(".cool"):
         from .readers import read_cooler
-        x, y, v, res = read_cooler(f, distance_in_bp, chromosome, chromosome2, norm_method)
+        *r, res = read_cooler(f, distance_in_bp, chromosome, chromosome, norm_method)
     elif f.endswith(".mcool"):
         from .readers import read_mcooler
-        x, y, v = read_mcooler(f, distance_in_bp, chromosome, chromosome2, res, norm_method)
+        r = read_mcooler(f, distance_in_bp, chromosome, chromosome, res, norm_method)
     else:
         r = read_pd(f, distance_in_bp, bias, chromosome, res)
-        if r is None:
-            return None
-        x, y, v = r
-    if len(v) == 0:
+    if r is None:
         return None
+    x, y, v = r
     return np.asarray(x), np.asarray(y), np.asarray(v, dtype=np.float64), res
 
 
@@ -512,6 +521,31 @@ def _scalar_text(v):
     return repr(float(v)) if isinstance(v, (float, np.float64)) else str(v)      # str(np.float32) is NOT repr(float(v)): left to str()
 
 
+def chromosome_pairs(f, res, ch, ch2):
+    """-ch / -ch2 -> [(chromosome, chromosome2)] (without -ch: every chromosome of a `.hic` / `.cool` / `.mcool` file), or the
+    Error: line to print when they cannot be paired (reference mustache.py:1019-1045, diff_mustache.py:781-800)."""
+    if not ch or ch == 'n':
+        if not f.endswith((".cool", ".mcool", ".hic")):
+            return "Error: Please enter the chromosome name."
+        from .readers import list_chromosomes
+        ch = list_chromosomes(f, res)
+    ch2 = ch2 if isinstance(ch2, list) else ch
+    if len(ch) != len(ch2):
+        return "Error: the same number of chromosome1 and chromosome2 should be provided."
+    return list(zip(ch, ch2))
+
+
+def owned_chromosomes(f, res, pairs, rank, world):
+    """Indices of the pairs rank `rank` runs when a multi-GPU run is sharded by chromosome: whole chromosomes, largest
+    first, to the least loaded rank (sharding.assign_chromosomes on the chromosome sizes of `f`)."""
+    from .readers import chromosome_sizes
+    from .sharding import assign_chromosomes
+    sizes = chromosome_sizes(f, res)
+    weights = [sizes.get(str(c), sizes.get("chr" + str(c).replace("chr", ""), 1)) for c, _ in pairs]
+    owner = assign_chromosomes(weights, world)
+    return [i for i in range(len(pairs)) if owner[i] == rank]
+
+
 def main(argv=None):
     start_time = time.time()
     args = parse_args(sys.argv[1:] if argv is None else argv)
@@ -528,19 +562,10 @@ def main(argv=None):
     if not res:
         print("Error: Invalid resolution")
         return
-    if not args.chromosome or args.chromosome == 'n':
-        if f.endswith(".cool") or f.endswith(".mcool") or f.endswith(".hic"):
-            from .readers import list_chromosomes
-            chr_list = list_chromosomes(f, res)
-        else:
-            print("Error: Please enter the chromosome name.")
-            return
-    else:
-        chr_list = list(args.chromosome)
-    if (args.chromosome2 and args.chromosome2 != 'n') and (len(chr_list) != len(args.chromosome2)):
-        print("Error: the same number of chromosome1 and chromosome2 should be provided.")
+    pairs = chromosome_pairs(f, res, args.chromosome, args.chromosome2)
+    if isinstance(pairs, str):
+        print(pairs)
         return
-    chr_list2 = list(args.chromosome2) if isinstance(args.chromosome2, list) else list(chr_list)
     distFilter = resolve_distance_filter(args.distFilter, res)
 
     chrSize_in_bp = False
@@ -560,7 +585,6 @@ def main(argv=None):
         except BalanceError as e:
             print("Error: %s" % e)
             return
-    pairs = list(zip(chr_list, chr_list2))
     # inter-chromosomal pairs (mustache_amd/trans.py) run after every intra-chromosomal pair, in pair order
     trans_pairs = [p for p in pairs if p[0] != p[1]]
     pairs = [p for p in pairs if p[0] == p[1]]
@@ -598,14 +622,7 @@ def main(argv=None):
     # input; a whole-genome run is sharded by CHROMOSOME (largest first, sharding.assign_chromosomes), each rank reading and
     # running only its own -- small chromosomes would otherwise be cut into launches of a few blocks per GPU.
     by_chromosome = _world > 1 and len(pairs) >= _world
-    mine = list(range(len(pairs)))
-    if by_chromosome:
-        from .readers import chromosome_sizes
-        from .sharding import assign_chromosomes
-        sizes = chromosome_sizes(f, res)
-        weights = [sizes.get(str(c), sizes.get("chr" + str(c).replace("chr", ""), 1)) for c, _ in pairs]
-        owner = assign_chromosomes(weights, _world)
-        mine = [i for i in range(len(pairs)) if owner[i] == rank]
+    mine = owned_chromosomes(f, res, pairs, rank, _world) if by_chromosome else list(range(len(pairs)))
 
     # the next chromosome is read (host I/O; the native .hic reader and pandas release the GIL) while the GPU works on
     # the current one -- the reference reads and computes strictly in turn (mustache.py:1057-1080)
@@ -632,21 +649,12 @@ def main(argv=None):
 
     # Several chromosomes on this rank (a whole-genome run): their normalised bands are collected in HBM and ALL their
     # blocks go through one sequence of launches (pipeline.run_genome) -- same loops as chromosome by chromosome, without
-    # the launch-bound tail of 5-31 blocks per chromosome.  `genome_budget` bounds the bands held at once.
+    # the launch-bound tail of 5-31 blocks per chromosome.  pipeline.GenomeBatcher bounds the bands held at once.
     batched = len(mine) > 1 and (_world == 1 or by_chromosome)
-    genome_budget = None                 # bytes; from the device's free memory at the first band (pipeline.genome_batch_budget)
-    held, held_bytes, pipe = [], 0, None
-
-    def flush():
-        nonlocal held, held_bytes
-        if held:
-            dpx = held[0][3]
-            idx, bands, ns = [h[0] for h in held], [h[1] for h in held], [h[2] for h in held]
-            held, held_bytes = [], 0             # `bands` is now the only reference: run_genome releases them as it copies
-            loops = pipe.run_genome(bands, ns, dpx, args.st, args.pt)
-            for i, o in zip(idx, loops):
-                emit(i, o)
-        held, held_bytes = [], 0
+    from .pipeline import GenomeBatcher
+    pipe = None
+    genome = GenomeBatcher(lambda: pipe.device, lambda bands, ns, dpx: pipe.run_genome(bands, ns, dpx, args.st, args.pt),
+                           lambda band, n, dpx: pipe.run_band(band, n, dpx, args.st, args.pt, distributed=False), emit)
 
     with ThreadPoolExecutor(max_workers=1) as pool:
         ahead = pool.submit(fetch, mine[0]) if mine else None
@@ -656,53 +664,36 @@ def main(argv=None):
             ahead = pool.submit(fetch, mine[k + 1]) if k + 1 < len(mine) else None
             if isinstance(contacts, BaseException):
                 raise contacts
-            if batched:
-                if contacts is None:
-                    flush()                       # keeps the output in chromosome order
-                    emit(i, [])
-                    continue
-                if pipe is None:
-                    from .pipeline import ChromosomePipeline
-                    pipe = ChromosomePipeline([args.s_z * (2 ** o_) for o_ in range(args.octaves)])
-                    from .engine import settle_gc
-                    settle_gc()                   # the command-line process only; the library leaves the collector alone
-                _check_pair(f, chromosome, chromosome2)
-                from .hicfile import PackedContacts
-                is_packed = isinstance(contacts, PackedContacts)
-                res_c = contacts.res if is_packed else contacts[3]
-                dpx = int(math.ceil(distFilter // res_c))
-                if args.verbose:
-                    print("Normalizing contact map...")
-                if is_packed:
-                    band, n = pipe.normalized_band_packed(contacts, dpx)
-                else:
-                    band, n = pipe.normalized_band(contacts[0], contacts[1], contacts[2], res_c, dpx)
-                del contacts
-                if genome_budget is None:
-                    from .pipeline import genome_batch_budget
-                    genome_budget = genome_batch_budget(pipe.device)
-                if held and (held[0][3] != dpx or held_bytes + band.numel() * 8 > genome_budget):
-                    flush()
-                if band.numel() * 8 > genome_budget:
-                    # one chromosome alone is over the budget (a second copy of its band would not fit beside it): the
-                    # per-chromosome form, which runs straight from this band
-                    flush()
-                    emit(i, pipe.run_band(band, n, dpx, args.st, args.pt, distributed=False))
-                    del band
-                    continue
-                held.append((i, band, n, dpx))
-                held_bytes += band.numel() * 8
+            if not batched:
+                emit(i, [] if contacts is None else regulator(
+                    f, args.norm_method, False, args.outdir, bed=args.bed, res=getattr(contacts, "res", None) or contacts[3],
+                    sigma0=args.s_z, s=args.s, verbose=args.verbose, pt=args.pt, st=args.st, distance_filter=distFilter,
+                    nprocesses=args.nprocesses, bias=biasf, chromosome=chromosome, chromosome2=chromosome2,
+                    octaves=args.octaves, contacts=contacts, shard_blocks=not by_chromosome))
                 continue
             if contacts is None:
-                o = []
+                genome.skip(i)
+                continue
+            if pipe is None:
+                from .pipeline import ChromosomePipeline
+                pipe = ChromosomePipeline([args.s_z * (2 ** o_) for o_ in range(args.octaves)])
+                from .engine import settle_gc
+                settle_gc()                   # the command-line process only; the library leaves the collector alone
+            _check_pair(f, chromosome, chromosome2)
+            from .hicfile import PackedContacts
+            is_packed = isinstance(contacts, PackedContacts)
+            res_c = contacts.res if is_packed else contacts[3]
+            dpx = int(math.ceil(distFilter // res_c))
+            if args.verbose:
+                print("Normalizing contact map...")
+            if is_packed:
+                band, n = pipe.normalized_band_packed(contacts, dpx)
             else:
-                o = regulator(f, args.norm_method, False, args.outdir, bed=args.bed,
-                              res=getattr(contacts, "res", None) or contacts[3], sigma0=args.s_z,
-                              s=args.s, verbose=args.verbose, pt=args.pt, st=args.st, distance_filter=distFilter,
-                              nprocesses=args.nprocesses, bias=biasf, chromosome=chromosome, chromosome2=chromosome2,
-                              octaves=args.octaves, contacts=contacts, shard_blocks=not by_chromosome)
-            emit(i, o)
-        flush()
+                band, n = pipe.normalized_band(contacts[0], contacts[1], contacts[2], res_c, dpx)
+            del contacts
+            genome.add(i, band, n, dpx, band.numel() * 8)
+            del band                          # the batcher's reference is the only one: run_genome releases it as it copies
+        genome.flush()
     first = not pairs                        # the header is written with the first pair's rows
     for chromosome, chromosome2 in trans_pairs:
         start_time = time.time()
@@ -720,17 +711,12 @@ def main(argv=None):
             first = False
     if by_chromosome:
         # one gather of (chromosome index, x, y, fdr, sigma) records; rank 0 writes the chromosomes in their order
-        from .sharding import gather_records
-        rec = np.array([[i, float(a), float(b), float(q), float(sg)] for i, o in results.items() for a, b, q, sg in o],
-                       dtype=np.float64).reshape(-1, 5)
-        parts = gather_records(rec)
-        if rank == 0:
-            allrec = np.concatenate(parts) if parts else np.zeros((0, 5))
-            for i, (chromosome, chromosome2) in enumerate(pairs):
-                rows = allrec[allrec[:, 0] == i]
-                o = [[np.int64(a), np.int64(b), np.float64(q), np.float64(sg)] for _, a, b, q, sg in rows]
-                if i == 0 or o:
-                    write_loops(args.outdir, chromosome, chromosome2, res, o, first=(i == 0))
+        from .sharding import gather_chromosome_rows
+        per_chromosome = gather_chromosome_rows(results, len(pairs), 4)
+        for i, rows in enumerate(per_chromosome or []):
+            o = [[np.int64(a), np.int64(b), np.float64(q), np.float64(sg)] for a, b, q, sg in rows]
+            if i == 0 or o:
+                write_loops(args.outdir, pairs[i][0], pairs[i][1], res, o, first=(i == 0))
 
 
 if __name__ == '__main__':

@@ -107,6 +107,50 @@ def genome_batch_budget(device=None):
     return int(min(64 << 30, 0.35 * free))
 
 
+class GenomeBatcher:
+    """The command lines' whole-genome batching: the normalised bands of several chromosomes are held in HBM and go through
+    one sequence of launches, `run_many(items, ns, dpx)` -> one output per item (ChromosomePipeline.run_genome,
+    diff_mustache.run_pair_genome).  The held bands are flushed when the distance limit changes or when the next band would
+    take them over genome_batch_budget(get_device()) bytes (taken at the first add, once the caller's pipeline exists); a band
+    over the budget by itself runs alone, `run_alone(item, n, dpx)`, since a second copy of it would not fit beside it.
+    Every output goes to `emit(i, output)` in the order of the indices added or skipped.
+    The list `run_many` receives holds the only references this batcher kept: the callee releases the bands one by one as
+    it copies them into the genome band (GenomeLayout.band(consume=True)), so the peak is not twice the genome."""
+
+    def __init__(self, get_device, run_many, run_alone, emit):
+        self.get_device, self.run_many, self.run_alone, self.emit = get_device, run_many, run_alone, emit
+        self.budget = None
+        self.idx, self.items, self.ns, self.dpx, self.nbytes = [], [], [], None, 0
+
+    def add(self, i, item, n, dpx, nbytes):
+        if self.budget is None:
+            self.budget = genome_batch_budget(self.get_device())
+        if self.items and (self.dpx != dpx or self.nbytes + nbytes > self.budget):
+            self.flush()
+        if nbytes > self.budget:
+            self.flush()
+            self.emit(i, self.run_alone(item, n, dpx))
+            return
+        self.idx.append(i)
+        self.items.append(item)
+        self.ns.append(n)
+        self.dpx = dpx
+        self.nbytes += nbytes
+
+    def skip(self, i):
+        """Chromosome i has nothing to run: its empty output, after those of the chromosomes held before it."""
+        self.flush()
+        self.emit(i, [])
+
+    def flush(self):
+        if not self.items:
+            return
+        idx, items, ns = self.idx, self.items, self.ns
+        self.idx, self.items, self.ns, self.nbytes = [], [], [], 0
+        for i, o in zip(idx, self.run_many(items, ns, self.dpx)):
+            self.emit(i, o)
+
+
 class ChromosomePipeline:
     def __init__(self, octave_values=(1.6, 3.2), device=None, max_batch_bytes=48 << 30):
         self.engine = ScaleSpaceEngine(octave_values, device=device)

@@ -57,6 +57,19 @@ def gather_records(rec, device=None, group=None, force=False):
     return [parts[r][:counts[r]].cpu().numpy() for r in range(ws)]
 
 
+def gather_chromosome_rows(results, count, width):
+    """Whole-genome runs sharded by chromosome: results = {chromosome index: rows of `width` numbers} of this rank.  One
+    gather_records of (index, row) records; rank 0 gets every rank's rows per chromosome, chromosomes 0 .. count - 1 in order
+    (float64 arrays [m, width]), the other ranks None."""
+    rec = np.array([[i] + [float(a) for a in r] for i, o in results.items() for r in o],
+                   dtype=np.float64).reshape(-1, width + 1)
+    parts = gather_records(rec)
+    if world()[0] != 0:
+        return None
+    rec = np.concatenate(parts)
+    return [rec[rec[:, 0] == i, 1:] for i in range(count)]
+
+
 def all_gather_packed(x, dist_, v, n, device, group=None):
     """One process per GPU, each rank holds the packed records of ITS share of a chromosome's `.hic` blocks (host arrays:
     x int32, dist_ int32 or uint16, v float32; `n` = its max(binY) + 1): every rank receives all shares.  Returns

@@ -517,3 +517,135 @@ def test_bench_dump_outputs_orders_records_and_samples_above_the_cap(tmp_path, m
     assert all(np.array_equal(s1[k], s2[k]) for k in s1)
     idx = s1["record_index"].astype(np.int64)
     assert np.all(np.diff(idx) > 0) and np.array_equal(s1["record_pval"], d["record_pval"][idx])
+
+
+class _Item:
+    """A band stand-in: only its identity and its life time matter to the batcher."""
+
+    def __init__(self, name):
+        self.name = name
+
+
+def _batcher(monkeypatch, budget_bytes, log, run_many=None):
+    """pipeline.GenomeBatcher with fake runs that log their calls; the budget through MUSTACHE_GENOME_BATCH_GB."""
+    from mustache_amd.pipeline import GenomeBatcher
+    monkeypatch.setenv("MUSTACHE_GENOME_BATCH_GB", repr(budget_bytes / (1 << 30)))
+
+    def many(items, ns, dpx):
+        log.append(("many", [it.name for it in items], list(ns), dpx))
+        return ["out " + it.name for it in items]
+
+    def alone(item, n, dpx):
+        log.append(("alone", item.name, n, dpx))
+        return "alone " + item.name
+
+    return GenomeBatcher(lambda: None, run_many or many, alone, lambda i, o: log.append(("emit", i, o)))
+
+
+def test_genome_batcher_emits_in_chromosome_order_around_skips(monkeypatch):
+    log = []
+    b = _batcher(monkeypatch, 100, log)
+    b.skip(0)
+    b.add(1, _Item("a"), 10, 4, 30)
+    b.add(2, _Item("b"), 11, 4, 30)
+    b.skip(3)
+    b.add(4, _Item("c"), 12, 4, 30)
+    b.flush()
+    b.flush()                                  # nothing held: no run
+    assert log == [("emit", 0, []),
+                   ("many", ["a", "b"], [10, 11], 4), ("emit", 1, "out a"), ("emit", 2, "out b"), ("emit", 3, []),
+                   ("many", ["c"], [12], 4), ("emit", 4, "out c")]
+
+
+def test_genome_batcher_flushes_when_the_distance_limit_changes(monkeypatch):
+    log = []
+    b = _batcher(monkeypatch, 100, log)
+    b.add(0, _Item("a"), 10, 4, 10)
+    b.add(1, _Item("b"), 10, 4, 10)
+    b.add(2, _Item("c"), 10, 5, 10)
+    assert log == [("many", ["a", "b"], [10, 10], 4), ("emit", 0, "out a"), ("emit", 1, "out b")]
+    b.flush()
+    assert log[3:] == [("many", ["c"], [10], 5), ("emit", 2, "out c")]
+
+
+def test_genome_batcher_flushes_before_the_budget_would_be_exceeded(monkeypatch):
+    log = []
+    b = _batcher(monkeypatch, 100, log)
+    b.add(0, _Item("a"), 1, 4, 40)
+    b.add(1, _Item("b"), 2, 4, 60)             # 100 bytes held: exactly the budget, still one batch
+    assert log == []
+    b.add(2, _Item("c"), 3, 4, 1)
+    assert log == [("many", ["a", "b"], [1, 2], 4), ("emit", 0, "out a"), ("emit", 1, "out b")]
+    assert b.budget == 100
+    b.flush()
+    assert log[3:] == [("many", ["c"], [3], 4), ("emit", 2, "out c")]
+
+
+def test_genome_batcher_runs_a_band_over_the_budget_alone(monkeypatch):
+    log = []
+    b = _batcher(monkeypatch, 100, log)
+    b.add(0, _Item("a"), 1, 4, 50)
+    b.add(1, _Item("big"), 2, 4, 101)          # the held band first, then the big one by itself, nothing held after
+    b.add(2, _Item("c"), 3, 4, 50)
+    b.flush()
+    assert log == [("many", ["a"], [1], 4), ("emit", 0, "out a"), ("alone", "big", 2, 4), ("emit", 1, "alone big"),
+                   ("many", ["c"], [3], 4), ("emit", 2, "out c")]
+    log.clear()
+    b = _batcher(monkeypatch, 0, log)          # MUSTACHE_GENOME_BATCH_GB=0: every chromosome alone
+    b.add(0, _Item("a"), 1, 4, 8)
+    b.add(1, _Item("b"), 1, 4, 8)
+    b.flush()
+    assert log == [("alone", "a", 1, 4), ("emit", 0, "alone a"), ("alone", "b", 1, 4), ("emit", 1, "alone b")]
+
+
+def test_genome_batcher_hands_run_many_the_only_references(monkeypatch):
+    """The memory rule of the whole-genome run: run_genome / run_pair_genome release each band as they copy it into the
+    genome band, which only frees it when the list they were given holds the last reference."""
+    import gc
+    import weakref
+    seen = []
+
+    def many(items, ns, dpx):
+        refs = [weakref.ref(it) for it in items]
+        items.clear()                          # what GenomeLayout.band(consume=True) does entry by entry
+        gc.collect()
+        seen.append([r() is None for r in refs])
+        return [[] for _ in refs]
+
+    b = _batcher(monkeypatch, 100, [], run_many=many)
+    b.add(0, _Item("a"), 1, 4, 10)
+    b.add(1, _Item("b"), 1, 4, 10)
+    b.skip(2)
+    assert seen == [[True, True]]
+
+
+def test_chromosome_pairs(monkeypatch):
+    import mustache_amd.readers as rd
+    from mustache_amd.mustache import chromosome_pairs
+    assert chromosome_pairs("m.txt", 5000, ["1", "2"], "n") == [("1", "1"), ("2", "2")]
+    assert chromosome_pairs("m.hic", 5000, ["1", "2"], ["3", "2"]) == [("1", "3"), ("2", "2")]
+    assert chromosome_pairs("m.txt", 5000, "n", "n") == "Error: Please enter the chromosome name."
+    assert chromosome_pairs("m.txt", 5000, ["1", "2"], ["1"]) == \
+        "Error: the same number of chromosome1 and chromosome2 should be provided."
+    monkeypatch.setattr(rd, "list_chromosomes", lambda f, res: ["chr1", "chrX"])
+    assert chromosome_pairs("m.mcool", 5000, "n", "n") == [("chr1", "chr1"), ("chrX", "chrX")]
+    assert chromosome_pairs("m.cool", 5000, "n", ["chr2", "chr3"]) == [("chr1", "chr2"), ("chrX", "chr3")]
+    assert chromosome_pairs("m.hic", 5000, "n", ["chr2"]).startswith("Error: the same number")
+
+
+@pytest.mark.parametrize("backend", ["native", "pandas"])
+def test_read_sample_on_text_is_read_pd(tmp_path, monkeypatch, backend):
+    from mustache_amd.mustache import read_pd, read_sample
+    monkeypatch.setenv("MUSTACHE_TEXT_BACKEND", backend)
+    res = 5000
+    f5 = tmp_path / "c5.txt"
+    f5.write_text("chr1 0 chr1 5000 10\nchr2 0 chr2 5000 3\nchr1 20000 chr1 5000 4\nchr1 15000 chr1 15000 2.5\n")
+    b = tmp_path / "b.txt"
+    b.write_text("chr1\t0\t1.0\nchr1\t5000\t2.0\nchr1\t20000\t0.5\n")
+    for bias in (False, str(b)):
+        x, y, v, r = read_sample(str(f5), False, False, res, 2000000, bias, "1")
+        ex, ey, ev = read_pd(str(f5), 2000000, bias, "1", res)
+        assert r == res and v.dtype == np.float64
+        assert np.array_equal(x, np.asarray(ex)) and np.array_equal(y, np.asarray(ey)) and np.array_equal(v, np.asarray(ev))
+        assert len(v) == 3
+    assert read_sample(str(f5), False, False, res, 2000000, False, "7") is None
