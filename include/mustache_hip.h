@@ -486,6 +486,30 @@ MST_STABLE int mst_trans_scatter_tiles(const int32_t *x, const int32_t *y, const
 /* The trans prologue: nz[b] = c[b] != 0 over the whole tile, no fills; nz_count dev [B] uint32, overwritten. */
 MST_STABLE int mst_trans_prologue(const double *c, uint8_t *nz, uint32_t *nz_count, int32_t B, int32_t CH, void *stream);
 
+/* ---- aggregate peak analysis (APA) of a loop list (mustache_amd/pileup.py states the rules; tests/pileup_reference.py restates
+ * them).  band: dev f64, the diagonal-major RAW band of one chromosome (band[d * n + i] = pixel (i, i + d), not normalised)
+ * with band_rows >= D + 1 rows; only rows 0 .. D are read.  Every sum has a fixed order that depends only on absolute column
+ * positions and on the caller's loop order (no float atomics): results are bit-identical from run to run. */
+/* workspace bytes of one pile-up (expected pass and reduce, used in turn); 0 for a bad argument or w > 64. */
+MST_STABLE uint64_t mst_pileup_workspace_bytes(int64_t n, int32_t D, int64_t L, int32_t w);
+/* valid[i] (dev uint8 [n], overwritten) = 1 when a non-zero pixel (i, j), |i - j| <= D, touches bin i; expected[d] (dev f64
+ * [D + 1]) = sum of band[d][i] over i with i + d < n and both ends valid, divided by their count (0 when the count is 0). */
+MST_STABLE int mst_pileup_expected(const double *band, int64_t n, int32_t band_rows, int32_t D, uint8_t *valid, double *expected,
+                                   void *workspace, uint64_t workspace_bytes, void *stream);
+/* One window per loop (x, y: dev int64 [L]): obs[l][a + w][b + w] (dev f64 [L][2w+1][2w+1]) = pixel (x + a, y + b), read at
+ * (min, max) below the diagonal; NaN off the chromosome (an index < 0 or >= n) or farther than D from the diagonal.
+ * oe = obs / expected[distance], NaN where expected is 0.  loop_stats dev f64 [L][3] = {obs centre, oe centre, P2LL}: the
+ * centre over the mean of the loop's own non-NaN LL cells (rows 2w-q+1 .. 2w, columns 0 .. q-1), NaN when there is none or
+ * the mean is 0.  0 <= w <= 64, 1 <= q <= 2w + 1; L = 0 launches nothing. */
+MST_STABLE int mst_pileup_windows(const double *band, int64_t n, int32_t band_rows, int32_t D, const double *expected,
+                                  const int64_t *x, const int64_t *y, int64_t L, int32_t w, int32_t q, double *obs, double *oe,
+                                  double *loop_stats, void *stream);
+/* agg dev f64 [4][(2w+1)^2] = per cell: sum of the non-NaN obs, their count, sum of the non-NaN oe, their count, over the
+ * windows order[0 .. L) (dev int32, a permutation of 0 .. L-1; the caller sorts the loops by (x, y)).  The order is cut into
+ * chunks of 512; each chunk's partial sums are added in chunk order.  L = 0 zeroes agg. */
+MST_STABLE int mst_pileup_reduce(const double *obs, const double *oe, const int32_t *order, int64_t L, int32_t w, double *agg,
+                                 void *workspace, uint64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

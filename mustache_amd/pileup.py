@@ -1,0 +1,453 @@
+"""Aggregate peak analysis (APA) of a loop list on the GPU: the map piled up around every loop of a Mustache TSV, with
+Juicer APA's names and defaults (w = 10, q = 6, n = 30).  `python -m mustache_amd.pileup`, `pileup()` / `pileup_band()` in
+Python.  tests/pileup_reference.py restates the arithmetic in NumPy.
+
+Rules:
+  * Loop list: any TSV Mustache writes (`.tsv`, `.loop1`, `.diffloop1`, ...); columns 1-6 are read, later ones are kept as
+    they are.  An anchor's bin is ((start + end) // 2) // res, so a list from another resolution piles up on this map; the
+    two anchors are taken as (x, y) = (min, max).  Chromosome names match with or without a `chr` prefix.
+  * Status of every row: `trans` (two chromosomes), `no_chrom` (not selected, or not in the map), `short` (y - x < n_min),
+    `long` (-x given and y - x > x_max), `off_map` (an anchor >= n), `used` otherwise.
+  * Per chromosome: D = max(y - x) + 2w over its kept loops; the map is read with the distance limit D * res (not the
+    caller's -d clamp ladder) into the RAW band (not normalised) with D + 1 used rows; n is the band width as the caller has it.
+  * Valid bins: touched by a non-zero pixel (i, j), |i - j| <= D.  E[d] = sum band[d, i] / #{i : i and i + d valid,
+    i + d < n} over i with both ends valid; 0 when the count is 0.
+  * Windows: cell [a + w, b + w] = pixel (x + a, y + b), a, b in [-w, w], read at (min, max) below the diagonal; NaN off the
+    chromosome (index < 0 or >= n), excluded from every sum and count.  obs = band value, oe = obs / E[distance] (NaN where
+    E is 0).
+  * Aggregate: the loops sorted by (x, y), per cell the sum and the non-NaN count of obs and oe (chunks of 512 loops added in
+    chunk order); the genome-wide aggregate adds the chromosome partials in the order the chromosomes ran.  Bit-identical
+    under any permutation of the input rows and from run to run.
+  * Metrics on M = sum / count: corners q x q, rows = a index, columns = b index; LL = rows 2w-q+1 .. 2w, columns 0 .. q-1
+    (nearest the diagonal), UL, UR, LR alike; c = M[w, w]; P2X = c / mean(X); ZscoreLL = (c - mean LL) / std LL (population);
+    P2M = c / mean(M without the centre).  Per loop: P2LL = centre / mean of its own non-NaN LL cells (NaN when there is none
+    or the mean is 0).
+Not claimed: agreement with Juicer's own output.
+
+Device work (mustache_amd/csrc/mst_pileup.hip): valid flags and E (two reads of the band), the windows with each loop's
+centre and P2LL, and the reduce; one host wait per chromosome, when the aggregates come back.
+"""
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
+
+MAX_W = 64
+CORNERS = ("LL", "UL", "UR", "LR")
+METRICS = ("P2LL", "P2UL", "P2UR", "P2LR", "ZscoreLL", "P2M")
+STATS_HEADER = "CHR\tROWS_IN\tLOOPS_USED\t" + "\t".join(METRICS) + "\tOE_P2LL\n"
+LOOP_COLUMNS = ("STATUS", "OBS_CENTER", "OE_CENTER", "P2LL")
+DEFAULT_HEADER = "BIN1_CHR\tBIN1_START\tBIN1_END\tBIN2_CHROMOSOME\tBIN2_START\tBIN2_END\tFDR\tDETECTION_SCALE"
+
+
+class PileupError(ValueError):
+    """A pile-up request that cannot be honoured."""
+
+
+def check_window(w, q):
+    if not 0 <= int(w) <= MAX_W:
+        raise PileupError("window half-width w = %d is outside 0 .. %d (a window holds at most %d cells)"
+                          % (w, MAX_W, (2 * MAX_W + 1) ** 2))
+    if not 1 <= int(q) <= 2 * int(w) + 1:
+        raise PileupError("corner size q = %d is outside 1 .. 2w + 1 = %d" % (q, 2 * int(w) + 1))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# metrics (host, on the (2w+1)^2 mean map)
+# ----------------------------------------------------------------------------------------------------------------------
+def corner_slices(w, q):
+    near, far = slice(0, q), slice(2 * w - q + 1, 2 * w + 1)
+    return {"LL": (far, near), "UL": (near, near), "UR": (near, far), "LR": (far, far)}
+
+
+def mean_map(s, c):
+    """sum / count per cell, NaN where the count is 0."""
+    s, c = np.asarray(s, np.float64), np.asarray(c, np.float64)
+    out = np.full(s.shape, np.nan)
+    np.divide(s, c, out=out, where=c > 0)
+    return out
+
+
+def metrics(M, w, q):
+    M = np.asarray(M, np.float64)
+    c = M[w, w]
+    sl = corner_slices(w, q)
+    out = {}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for name in CORNERS:
+            out["P2" + name] = float(c / M[sl[name]].mean())
+        ll = M[sl["LL"]]
+        out["ZscoreLL"] = float((c - ll.mean()) / ll.std())
+        rest = np.delete(M.reshape(-1), w * (2 * w + 1) + w)
+        out["P2M"] = float(c / rest.mean()) if rest.size else math.nan
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the device pile-up of one chromosome
+# ----------------------------------------------------------------------------------------------------------------------
+def _workspace(lib, n, D, L, w, device):
+    import torch
+    return torch.empty(max(int(lib.mst_pileup_workspace_bytes(int(n), int(D), int(L), int(w))), 256), dtype=torch.uint8,
+                       device=device)
+
+
+def expected(band, n, D, ws=None):
+    """(valid uint8 [n], E float64 [D + 1]) device tensors of a raw band (device, [rows >= D + 1, n])."""
+    import torch
+    from . import _lib
+    from .engine import _ptr, _stream, require_gpu
+    lib = require_gpu()
+    n, D = int(n), int(D)
+    if band.dim() != 2 or band.shape[1] != n or band.shape[0] < D + 1 or band.dtype != torch.float64 or not band.is_contiguous():
+        raise PileupError("band must be a contiguous float64 [rows >= D + 1, n] tensor (got %s, n %d, D %d)"
+                          % (tuple(band.shape), n, D))
+    with torch.cuda.device(band.device):
+        if ws is None:
+            ws = _workspace(lib, n, D, 0, 0, band.device)
+        valid = torch.empty(n, dtype=torch.uint8, device=band.device)
+        E = torch.empty(D + 1, dtype=torch.float64, device=band.device)
+        _lib.check(lib.mst_pileup_expected(_ptr(band), n, int(band.shape[0]), D, _ptr(valid), _ptr(E), _ptr(ws), ws.numel(),
+                                           _stream()))
+    return valid, E
+
+
+def windows(band, n, D, E, xd, yd, w, q):
+    """(obs, oe [L, 2w+1, 2w+1], loop stats [L, 3] = obs centre, oe centre, P2LL) device tensors; xd, yd int64 device [L]."""
+    import torch
+    from . import _lib
+    from .engine import _ptr, _stream, require_gpu
+    lib = require_gpu()
+    L, S = int(xd.numel()), 2 * int(w) + 1
+    with torch.cuda.device(band.device):
+        obs = torch.empty((L, S, S), dtype=torch.float64, device=band.device)
+        oe = torch.empty_like(obs)
+        st = torch.empty((L, 3), dtype=torch.float64, device=band.device)
+        _lib.check(lib.mst_pileup_windows(_ptr(band), int(n), int(band.shape[0]), int(D), _ptr(E), _ptr(xd), _ptr(yd), L, int(w),
+                                          int(q), _ptr(obs), _ptr(oe), _ptr(st), _stream()))
+    return obs, oe, st
+
+
+def reduce(obs, oe, order, w, ws):
+    """agg [4, (2w+1)^2] device tensor: sum obs, count obs, sum oe, count oe over the windows in `order` (int32 device)."""
+    import torch
+    from . import _lib
+    from .engine import _ptr, _stream, require_gpu
+    lib = require_gpu()
+    S = 2 * int(w) + 1
+    with torch.cuda.device(obs.device):
+        agg = torch.empty((4, S * S), dtype=torch.float64, device=obs.device)
+        _lib.check(lib.mst_pileup_reduce(_ptr(obs), _ptr(oe), _ptr(order), int(order.numel()), int(w), _ptr(agg), _ptr(ws),
+                                         ws.numel(), _stream()))
+    return agg
+
+
+def _empty_result(w, q):
+    S = 2 * w + 1
+    z = np.zeros((S, S))
+    M = np.full((S, S), np.nan)
+    return {"valid": None, "expected": None, "obs": None, "oe": None, "sum_obs": z, "count_obs": z.copy(), "sum_oe": z.copy(),
+            "count_oe": z.copy(), "apa": M, "apa_oe": M.copy(), "center_obs": np.zeros(0), "center_oe": np.zeros(0),
+            "p2ll": np.zeros(0), "metrics": metrics(M, w, q), "metrics_oe": metrics(M, w, q)}
+
+
+def pileup_band(band, n, D, xs, ys, w=10, q=6):
+    """The pile-up of one chromosome's raw band (device float64 [rows >= D + 1, n]) around the loops (xs, ys) (bins, host
+    arrays or tensors, y - x + 2w <= D).  Returns a dict: "valid", "expected", "obs", "oe" (device tensors), "sum_obs",
+    "count_obs", "sum_oe", "count_oe", "apa" (mean obs), "apa_oe" (host [2w+1, 2w+1]), "center_obs", "center_oe", "p2ll"
+    (host [L], input order), "metrics" and "metrics_oe" (dicts of METRICS).  L = 0 returns empty aggregates without a launch."""
+    import torch
+    w, q = int(w), int(q)
+    check_window(w, q)
+    xs = np.asarray(xs.cpu() if isinstance(xs, torch.Tensor) else xs, np.int64).reshape(-1)
+    ys = np.asarray(ys.cpu() if isinstance(ys, torch.Tensor) else ys, np.int64).reshape(-1)
+    if len(xs) != len(ys):
+        raise PileupError("xs and ys differ in length (%d, %d)" % (len(xs), len(ys)))
+    L, S = len(xs), 2 * w + 1
+    if L == 0:
+        return _empty_result(w, q)
+    from .engine import require_gpu
+    lib = require_gpu()
+    dev = band.device
+    with torch.cuda.device(dev):
+        ws = _workspace(lib, n, D, L, w, dev)
+        valid, E = expected(band, n, D, ws)
+        xd = torch.from_numpy(xs).to(dev, non_blocking=True)
+        yd = torch.from_numpy(ys).to(dev, non_blocking=True)
+        obs, oe, st = windows(band, n, D, E, xd, yd, w, q)
+        order = torch.from_numpy(np.lexsort((ys, xs)).astype(np.int32)).to(dev, non_blocking=True)
+        agg = reduce(obs, oe, order, w, ws)
+        host = torch.cat([agg.view(-1), st.view(-1)]).cpu().numpy()       # the one wait
+    agg_h, st_h = host[:4 * S * S].reshape(4, S, S), host[4 * S * S:].reshape(L, 3)
+    apa, apa_oe = mean_map(agg_h[0], agg_h[1]), mean_map(agg_h[2], agg_h[3])
+    return {"valid": valid, "expected": E, "obs": obs, "oe": oe, "sum_obs": agg_h[0], "count_obs": agg_h[1],
+            "sum_oe": agg_h[2], "count_oe": agg_h[3], "apa": apa, "apa_oe": apa_oe, "center_obs": st_h[:, 0].copy(),
+            "center_oe": st_h[:, 1].copy(), "p2ll": st_h[:, 2].copy(), "metrics": metrics(apa, w, q),
+            "metrics_oe": metrics(apa_oe, w, q)}
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# loop lists
+# ----------------------------------------------------------------------------------------------------------------------
+def _key(c):
+    return str(c).replace("chr", "")
+
+
+class LoopTable:
+    """The rows of a Mustache loop TSV: `header` (without newline), `lines` (each row as read), the six anchor columns."""
+
+    def __init__(self, header, lines, chr1, s1, e1, chr2, s2, e2):
+        self.header, self.lines = header, lines
+        self.chr1, self.chr2 = chr1, chr2
+        self.s1, self.e1 = np.asarray(s1, np.int64), np.asarray(e1, np.int64)
+        self.s2, self.e2 = np.asarray(s2, np.int64), np.asarray(e2, np.int64)
+
+    def __len__(self):
+        return len(self.lines)
+
+    def bins(self, res):
+        """(x, y) = (min, max) of the two anchors' bins, ((start + end) // 2) // res."""
+        a = ((self.s1 + self.e1) // 2) // int(res)
+        b = ((self.s2 + self.e2) // 2) // int(res)
+        return np.minimum(a, b), np.maximum(a, b)
+
+
+def read_loops(path):
+    header, lines, cols = DEFAULT_HEADER, [], [[] for _ in range(6)]
+    with open(path) as fh:
+        for k, raw in enumerate(fh):
+            line = raw.rstrip("\r\n")
+            if not line.strip():
+                continue
+            f = line.split("\t")
+            if k == 0 and f[0] == "BIN1_CHR":
+                header = line
+                continue
+            if len(f) < 6:
+                raise PileupError("%s: row %d has %d columns, a loop row has at least 6" % (path, k + 1, len(f)))
+            lines.append(line)
+            for c in range(6):
+                cols[c].append(f[c])
+    try:
+        return LoopTable(header, lines, cols[0], [int(float(v)) for v in cols[1]], [int(float(v)) for v in cols[2]], cols[3],
+                         [int(float(v)) for v in cols[4]], [int(float(v)) for v in cols[5]])
+    except ValueError as e:
+        raise PileupError("%s: an anchor position is not a number (%s)" % (path, e))
+
+
+def classify(table, res, chromosomes=None, n_min=30, x_max=None):
+    """Statuses before the map is read: (status list, x, y, selected chromosome names).  Rows still eligible have status
+    None; `x_max` is in bins."""
+    x, y = table.bins(res)
+    cis = [_key(a) == _key(b) for a, b in zip(table.chr1, table.chr2)]
+    selected, seen = [], set()
+    for c, ok in (((c, True) for c in chromosomes) if chromosomes else zip(table.chr1, cis)):
+        if ok and _key(c) not in seen:                   # each chromosome once, in order of first appearance
+            seen.add(_key(c))
+            selected.append(c)
+    keys = {_key(c) for c in selected}
+    status = []
+    for k in range(len(table)):
+        sep = int(y[k] - x[k])
+        if not cis[k]:
+            status.append("trans")
+        elif _key(table.chr1[k]) not in keys:
+            status.append("no_chrom")
+        elif sep < n_min:
+            status.append("short")
+        elif x_max is not None and sep > x_max:
+            status.append("long")
+        else:
+            status.append(None)
+    return status, x, y, selected
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the whole run
+# ----------------------------------------------------------------------------------------------------------------------
+def _read_band(f, chromosome, res, D, norm=False, bias=False, balance=None, device=None, verbose=False):
+    """The chromosome's RAW band with distance limit D (device [D + 2, n]) and n, or (None, 0) when the map has no record of
+    it (or no such chromosome)."""
+    import torch
+    from .hicfile import PackedContacts
+    from .mustache import read_contacts
+    from .normalize import band_from_host_coo, band_from_packed
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    try:
+        r = read_contacts(f, norm, False, res, D * res, bias, chromosome, chromosome, verbose=verbose, packed=True, device=dev,
+                          balance=balance)
+    except NameError:                                  # a `.hic` file without this chromosome
+        return None, 0
+    if r is None:
+        return None, 0
+    if isinstance(r, PackedContacts):
+        band = band_from_packed(r, D, dev)
+        return band, int(band.shape[1])
+    x, y, v, _res = r
+    x = np.ascontiguousarray(x, dtype=np.int64)
+    y = np.ascontiguousarray(y, dtype=np.int64)
+    n = int(max(x.max(), y.max())) + 1
+    return band_from_host_coo(x, y, np.ascontiguousarray(v, dtype=np.float64), n, D, dev), n
+
+
+class PileupResult:
+    """What pileup() returns: the table, per row `status`, `obs_center`, `oe_center`, `p2ll`; `chromosomes` = [(name, rows in,
+    loops used, pile-up dict)] in run order; `all` = the genome-wide pile-up dict (sums, counts, means, metrics)."""
+
+    def __init__(self, table, status, w, q):
+        self.table, self.status, self.w, self.q = table, status, w, q
+        L = len(table)
+        self.obs_center, self.oe_center, self.p2ll = np.full(L, np.nan), np.full(L, np.nan), np.full(L, np.nan)
+        self.chromosomes = []
+        self.all = None
+
+
+def pileup(f, loops, res, chromosomes=None, norm=False, bias=False, balance=None, w=10, q=6, n_min=30, x_max=None,
+           device=None, verbose=False):
+    """Pile up map `f` around the loops of `loops` (a TSV path or a LoopTable) at resolution `res` (bp).  The reader
+    arguments (`norm`, `bias`, `balance`) mean what they mean for the caller; `x_max` is in bp.  Returns a PileupResult."""
+    w, q, res = int(w), int(q), int(res)
+    check_window(w, q)
+    table = read_loops(loops) if isinstance(loops, (str, os.PathLike)) else loops
+    status, x, y, selected = classify(table, res, chromosomes, int(n_min), None if x_max is None else int(x_max) // res)
+    out = PileupResult(table, status, w, q)
+    S = 2 * w + 1
+    tot = [np.zeros((S, S)) for _ in range(4)]
+    for chrom in selected:
+        rows = [k for k in range(len(table)) if _key(table.chr1[k]) == _key(chrom) and status[k] != "trans"]
+        cand = [k for k in rows if status[k] is None]
+        part = _empty_result(w, q)
+        used = []
+        if cand:
+            D = int(max(y[k] - x[k] for k in cand)) + 2 * w
+            band, n = _read_band(f, chrom, res, D, norm, bias, balance, device, verbose)
+            if band is None:
+                for k in cand:
+                    status[k] = "no_chrom"
+            else:
+                for k in cand:
+                    status[k] = "off_map" if y[k] >= n else "used"
+                used = [k for k in cand if status[k] == "used"]
+                part = pileup_band(band, n, D, x[used], y[used], w, q)
+                del band
+            for j, k in enumerate(used):
+                out.obs_center[k], out.oe_center[k], out.p2ll[k] = part["center_obs"][j], part["center_oe"][j], part["p2ll"][j]
+        part = {k_: v for k_, v in part.items() if k_ not in ("valid", "expected", "obs", "oe")}   # device arrays freed
+        out.chromosomes.append((chrom, len(rows), len(used), part))
+        for t, name in zip(tot, ("sum_obs", "count_obs", "sum_oe", "count_oe")):
+            t += part[name]                              # genome-wide: in the order the chromosomes ran
+        if verbose:
+            print("pile-up of chromosome %s: %d of %d rows used, P2LL %r" % (chrom, len(used), len(rows),
+                                                                           part["metrics"]["P2LL"]))
+    apa, apa_oe = mean_map(tot[0], tot[1]), mean_map(tot[2], tot[3])
+    out.all = {"sum_obs": tot[0], "count_obs": tot[1], "sum_oe": tot[2], "count_oe": tot[3], "apa": apa, "apa_oe": apa_oe,
+               "metrics": metrics(apa, w, q), "metrics_oe": metrics(apa_oe, w, q)}
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# output files
+# ----------------------------------------------------------------------------------------------------------------------
+def _r(v):
+    return repr(float(v))
+
+
+def write_matrix(path, M):
+    with open(path, "w") as fh:
+        fh.write("".join("\t".join(_r(v) for v in row) + "\n" for row in np.asarray(M)))
+
+
+def write_outputs(prefix, res):
+    """PREFIX.apa.tsv, PREFIX.oe.tsv, PREFIX.stats.tsv, PREFIX.loops.tsv of a PileupResult."""
+    write_matrix(prefix + ".apa.tsv", res.all["apa"])
+    write_matrix(prefix + ".oe.tsv", res.all["apa_oe"])
+
+    def stats_row(name, rows_in, used, p):
+        return "%s\t%d\t%d\t%s\t%s\n" % (name, rows_in, used, "\t".join(_r(p["metrics"][m]) for m in METRICS),
+                                        _r(p["metrics_oe"]["P2LL"]))
+    with open(prefix + ".stats.tsv", "w") as fh:
+        fh.write(STATS_HEADER)
+        for name, rows_in, used, p in res.chromosomes:
+            fh.write(stats_row(name, rows_in, used, p))
+        fh.write(stats_row("all", len(res.table), sum(u for _, _, u, _ in res.chromosomes), res.all))
+    with open(prefix + ".loops.tsv", "w") as fh:
+        fh.write(res.table.header + "\t" + "\t".join(LOOP_COLUMNS) + "\n")
+        fh.write("".join("%s\t%s\t%s\t%s\t%s\n" % (line, s, _r(a), _r(b), _r(c)) for line, s, a, b, c in
+                         zip(res.table.lines, res.status, res.obs_center, res.oe_center, res.p2ll)))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# command line
+# ----------------------------------------------------------------------------------------------------------------------
+def parse_args(args):
+    p = argparse.ArgumentParser(description="Aggregate peak analysis (APA) of a Mustache loop list on the GPU")
+    p.add_argument("-f", "--file", dest="f_path", required=True, help="contact map (text + -b, .hic, .cool, .mcool)")
+    p.add_argument("-l", "--loops", dest="loops", required=True, help="loop list: a TSV written by Mustache")
+    p.add_argument("-r", "--resolution", dest="resolution", required=True, help="resolution of the map")
+    p.add_argument("-o", "--outfile", dest="prefix", required=True, help="output prefix")
+    p.add_argument("-ch", "--chromosome", dest="chromosome", nargs="+", default=None,
+                   help="chromosomes to use (default: those of the cis rows, in order of first appearance)")
+    p.add_argument("-b", "--biases", dest="biasfile", default=None, help="bias vector of a text map")
+    p.add_argument("-norm", "--normalization", dest="norm_method", default=False, help=".hic normalisation (KR, VC, NONE)")
+    p.add_argument("--balance", dest="balance", default=None, metavar="ICE", help="balance the raw map on the GPU (ICE)")
+    p.add_argument("-w", "--window", dest="w", type=int, default=10, help="window half-width in bins (default 10, at most 64)")
+    p.add_argument("-q", "--corner", dest="q", type=int, default=6, help="corner size in bins (default 6)")
+    p.add_argument("-n", "--min-distance", dest="n_min", type=int, default=30,
+                   help="smallest loop size y - x in bins (default 30)")
+    p.add_argument("-x", "--max-distance", dest="x_max", default=None, help="largest loop size in bp (default: none)")
+    return p.parse_args(args)
+
+
+def main(argv=None):
+    args = parse_args(sys.argv[1:] if argv is None else argv)
+    from .mustache import parseBP
+    from .sharding import init_from_env
+    _rank, world = init_from_env()
+    if world > 1:
+        print("Error: pile-ups run on one GPU only (this run has %d ranks); start a single process" % world)
+        return
+    f = args.f_path
+    if not f or not os.path.exists(f):
+        print("Error: Couldn't find the specified contact files")
+        return
+    if not os.path.exists(args.loops):
+        print("Error: Couldn't find the loop list %s" % args.loops)
+        return
+    res = parseBP(args.resolution)
+    if not res:
+        print("Error: Invalid resolution")
+        return
+    if args.biasfile and not os.path.exists(args.biasfile):
+        print("Error: Couldn't find specified bias file")
+        return
+    balance = None
+    if args.balance is not None:
+        from .balance import BalanceError, check_request
+        try:
+            balance = check_request(args.balance, f, args.biasfile, args.norm_method, world)
+        except BalanceError as e:
+            print("Error: %s" % e)
+            return
+    x_max = None
+    if args.x_max is not None:
+        x_max = parseBP(str(args.x_max))
+        if not x_max:
+            print("Error: Invalid -x distance %s" % args.x_max)
+            return
+    try:
+        check_window(args.w, args.q)
+        res_ = pileup(f, args.loops, res, chromosomes=args.chromosome, norm=args.norm_method, bias=args.biasfile or False,
+                      balance=balance, w=args.w, q=args.q, n_min=args.n_min, x_max=x_max, verbose=True)
+    except PileupError as e:
+        print("Error: %s" % e)
+        return
+    write_outputs(args.prefix, res_)
+    a = res_.all["metrics"]
+    print("%d of %d loops piled up: P2LL %r, ZscoreLL %r, P2M %r -> %s.{apa,oe,stats,loops}.tsv"
+          % (sum(u for _, _, u, _ in res_.chromosomes), len(res_.table), a["P2LL"], a["ZscoreLL"], a["P2M"], args.prefix))
+
+
+if __name__ == "__main__":
+    main()
