@@ -120,8 +120,10 @@ __device__ __forceinline__ bool add_exact(double v, unsigned long long *lds) {
     return true;
 }
 
-// the fixed-point total of words[0, kLimbs) (signed 64-bit words of weight 2^(32 i - 1074)) as a double: carries propagated,
-// then the three most significant 32-bit digits of the magnitude (96 bits) added from the top
+// the fixed-point total of words[0, kLimbs) (signed 64-bit words of weight 2^(32 i - 1074)) as a double, rounded ONCE to
+// nearest-even: carries propagated, then the top 53 bits of the magnitude as an integer, a guard bit and a sticky bit OR-ed
+// from every digit below, the rounding in integer arithmetic and one exact ldexp.  A magnitude of at most 53 bits (every
+// subnormal total among them) is exact as it is.
 __device__ double exact_to_double(const unsigned long long *words, long long *w /* LDS [kLimbs + 1] */) {
     long long carry = 0;
     for (int i = 0; i < kLimbs; ++i) {
@@ -143,8 +145,35 @@ __device__ double exact_to_double(const unsigned long long *words, long long *w 
     int top = kLimbs;
     while (top >= 0 && w[top] == 0) --top;
     if (top < 0) return 0.0;
-    double r = 0.0;
-    for (int i = top; i >= 0 && i >= top - 2; --i) r = r + ldexp((double)w[i], 32 * i - 1074);
+    const int hb = 64 - __clzll((unsigned long long)w[top]);      // bits of the top digit, 1 .. 32
+    const int nb = 32 * top + hb;                                 // bits of the magnitude
+    double r;
+    if (nb <= 53) {
+        const unsigned long long m = ((unsigned long long)(top ? w[1] : 0) << 32) | (unsigned long long)w[0];
+        r = ldexp((double)m, -1074);
+    } else {
+        // acc = the two top digits (hb + 32 bits, top >= 1); a top digit narrower than 22 bits takes the rest from the third
+        const unsigned long long acc = ((unsigned long long)w[top] << 32) | (unsigned long long)w[top - 1];
+        unsigned long long m, guard, sticky;
+        int below;                                                // digits [0, below) lie under the guard bit entirely
+        if (hb >= 22) {
+            const int drop = hb + 32 - 53;                        // 1 .. 12 bits of acc under the mantissa
+            m = acc >> drop;
+            guard = (acc >> (drop - 1)) & 1ull;
+            sticky = acc & ((1ull << (drop - 1)) - 1ull);
+            below = top - 1;
+        } else {
+            const int need = 53 - (hb + 32);                      // 0 .. 20 bits of the third digit (top >= 2 here)
+            const unsigned long long d = (unsigned long long)w[top - 2];
+            m = (acc << need) | (d >> (32 - need));
+            guard = (d >> (31 - need)) & 1ull;
+            sticky = d & ((1ull << (31 - need)) - 1ull);
+            below = top - 2;
+        }
+        for (int i = 0; i < below; ++i) sticky |= (unsigned long long)w[i];
+        if (guard && (sticky || (m & 1ull))) ++m;                 // 2^53 at most: still exact as a double
+        r = ldexp((double)m, nb - 53 - 1074);
+    }
     return neg ? -r : r;
 }
 

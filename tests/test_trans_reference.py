@@ -79,6 +79,97 @@ def test_restatement_finds_loops_on_a_rectangular_map():
     assert all(0 <= a < 260 and 0 <= b < 180 for a, b, _, _ in loops)
 
 
+def _synth_trans_whole_map(n1, n2, density=0.3, nloops=12, seed=0):
+    """synth_trans as it was first written: every blob evaluated over the whole map"""
+    rng = np.random.default_rng(seed)
+    m = np.where(rng.random((n1, n2)) < density, np.exp(rng.normal(0.0, 0.5, (n1, n2))), 0.0)
+    gx, gy = np.mgrid[0:n1, 0:n2]
+    for _ in range(nloops):
+        cx, cy = rng.integers(8, n1 - 8), rng.integers(8, n2 - 8)
+        s = rng.uniform(1.2, 3.0)
+        blob = 25.0 * np.exp(-((gx - cx) ** 2 + (gy - cy) ** 2) / (2 * s * s))
+        m = np.where(blob > 0.5, m + blob, m)
+    m[n1 - 1, n2 - 1] = 1.0
+    x, y = np.nonzero(m > 0)
+    return x.astype(np.int64), y.astype(np.int64), m[x, y]
+
+
+@pytest.mark.parametrize("n1,n2,density,nloops,seed", [(260, 180, 0.35, 6, 3), (97, 310, 0.05, 40, 8), (420, 300, 0.3, 10, 1),
+                                                       (40, 40, 0.0, 30, 5)])
+def test_windowed_synth_trans_draws_the_same_map(n1, n2, density, nloops, seed):
+    a = tr.synth_trans(n1, n2, density=density, nloops=nloops, seed=seed)
+    b = _synth_trans_whole_map(n1, n2, density=density, nloops=nloops, seed=seed)
+    for p, q in zip(a, b):
+        assert p.dtype == q.dtype and np.array_equal(p, q)
+    # given blobs come after the random ones and reach the map's edge
+    x, y, v = tr.synth_trans(60, 50, density=0.0, nloops=0, seed=0, blobs=[(0, 49, 2.0)])
+    m = np.zeros((60, 50))
+    m[x, y] = v
+    assert m[0, 49] == 25.0 and m[1, 48] == 25.0 * np.exp(-2 / 8.0) and m[59, 49] == 1.0 and np.count_nonzero(m) == len(v)
+
+
+def test_zscore_exact_is_pinned_by_rational_arithmetic():
+    import math
+    from fractions import Fraction
+    rng = np.random.default_rng(12)
+    cases = [[1.0, 2.0, 4.0, 8.0], [0.1] * 10, [1e16, 1.0, -1e16, 1.0], [2.0 ** -1074, 2.0 ** -1074 * 3, 2.0 ** -1060],
+             [2.0 ** 64, 2.0 ** 11, 1e-300], [2.0 ** 64, 2.0 ** 11, -1e-300], [2.0 ** 64 + 2.0 ** 12, 2.0 ** 11, 0.0],
+             [1e8 + 2.0 ** -20, 1e8 - 2.0 ** -21, 1e8], [-3.5, 2.25, -1e-5, 7.0, 1e5]]
+    cases += [list(rng.uniform(-1, 1, int(rng.integers(1, 12))) * 2.0 ** rng.integers(-300, 300)) for _ in range(200)]
+    cases += [list(rng.uniform(0, 1, 5) * 2.0 ** rng.integers(-60, 60, 5).astype(np.float64)) for _ in range(200)]
+    for v in cases:
+        v = np.array(v, np.float64)
+        assert math.fsum(v.tolist()) == float(sum(Fraction(a) for a in v.tolist()))
+        z, mean, std = tr.zscore_exact(v)
+        # the squares (d * d in float64) are rounded, as in the kernel; their sum is not
+        d = v - np.float64(mean)
+        sq = d * d
+        m_ref = float(sum(Fraction(a) for a in v.tolist())) / len(v)
+        s_ref = math.sqrt(float(sum(Fraction(a) for a in sq.tolist())) / len(v))
+        assert mean == m_ref and std == s_ref
+        if std > 0:
+            assert np.array_equal(z, d / std)
+    assert tr.zscore_exact(np.zeros(0)) is None
+    z, mean, std = tr.zscore_exact([1.0, np.inf, 2.0])
+    assert np.isnan(mean) and np.isnan(std) and (z == 0).all()
+    z, mean, std = tr.zscore_exact([1e200, -1e200, 3.0])                  # a square overflows: std NaN, mean kept
+    assert mean == 1.0 and np.isnan(std) and (z == 0).all()
+    # the tie cases the device test relies on: to even both ways, tie + tiny up
+    assert math.fsum([2.0 ** 64, 2.0 ** 11]) == 2.0 ** 64 and math.fsum([2.0 ** 64, 2.0 ** 11, 1e-300]) == 2.0 ** 64 + 2.0 ** 12
+    assert math.fsum([2.0 ** 64 + 2.0 ** 12, 2.0 ** 11]) == 2.0 ** 64 + 2.0 ** 13
+    # and it agrees with the NumPy form of rule 2 to rounding
+    v = np.exp(rng.normal(0.0, 1.5, 5000))
+    z, mean, std = tr.zscore_exact(v)
+    zn, mn, sn = tr.zscore(v)
+    assert abs(mean - mn) <= 1e-12 * mn and abs(std - sn) <= 1e-12 * sn
+    np.testing.assert_allclose(z, zn, rtol=0, atol=1e-12)
+
+
+@pytest.mark.slow
+def test_smallest_production_case_meets_its_conditions():
+    """C = 2000, 2 x 2 tiles: the restatement alone returns loops, >= 5 in an overlap strip, >= 1 owned by the last tile"""
+    name = "sparse_2x2"
+    c = tr.PRODUCTION_CASES[name]
+    C, (rs, re), (cs, ce) = tr.tiling(c["n1"], c["n2"])
+    assert C == 2000 and len(rs) == 2 and len(cs) == 2
+    x, y, v = tr.production_records(name)
+    per_tile = [int(((x >= r) & (x < r + C) & (y >= q) & (y < q + C)).sum()) for r in rs for q in cs]
+    assert all(10000 <= k < 11000 for k in per_tile), per_tile      # every tile just above rule 4's second threshold
+    loops = tr.production_job(name)
+    tr.assert_production_conditions(name, loops)
+    assert tr.overlap_strips(rs, re) == [(300, 2000)] and tr.overlap_strips(cs, ce) == [(100, 2000)]
+
+
+def test_production_cases_have_the_tilings_they_are_named_for():
+    for name, c in tr.PRODUCTION_CASES.items():
+        C, (rs, re), (cs, ce) = tr.tiling(c["n1"], c["n2"])
+        assert C == 2000, name
+    t = {n: tr.tiling(c["n1"], c["n2"]) for n, c in tr.PRODUCTION_CASES.items()}
+    assert t["short_long_2x2"][1][0] == [0, 1700] and t["short_long_2x2"][2][0] == [0, 300]
+    assert t["three_rows_oc3"][1][0] == [0, 1744, 1900] and t["three_rows_oc3"][2][0] == [0, 200]
+    assert t["dense_2x2"][1][0] == [0, 100] and t["dense_2x2"][2][0] == [0, 50]
+
+
 def test_expected_trans_reading_transposes_and_filters():
     x, y, c = expected_trans([0, 1, 2], [3, 0, 1], [2.0, 0.0, 5.0], np.array([1.0, 2.0, 0.5]), np.array([1.0, 0.5, 2.0, 4.0]))
     assert list(x) == [0, 2] and list(y) == [3, 1]           # the zero count is dropped, rows sorted by (x, y)
