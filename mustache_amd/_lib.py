@@ -10,6 +10,10 @@ MST_ABI_VERSION = 3
 
 MST_OK, MST_E_ARG, MST_E_HIP, MST_E_OVERFLOW, MST_E_NONFINITE = 0, -1, -2, -3, -4
 
+# flag words of the launches and of mst_found_finish (include/mustache_hip.h: same names, same values)
+MST_FLAG_SKIP_EMPTY, MST_FLAG_FMA, MST_FLAG_NO_SHARE, MST_FLAG_GRAPH, MST_FLAG_NO_WAIT = 1, 2, 4, 8, 16
+MST_BH_RETRY = 0xFFFFFFFF      # mst_bh_select_nowait: out_count of a block whose candidate subset exceeds lds_records
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MUSTACHE_HIP_LIB: developer override to A/B alternative builds of the same ABI (still an in-tree HIP library)
 LIB_PATH = os.environ.get("MUSTACHE_HIP_LIB") or os.path.join(_HERE, "libmustache_hip.so")
@@ -145,6 +149,29 @@ def load():
                           % (lib.mst_abi_version(), MST_ABI_VERSION))
     _lib = lib
     return lib
+
+
+def require_gpu():
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("mustache_amd needs a ROCm GPU (MI355X/gfx950); no CPU fallback exists")
+    return load()
+
+
+def ptr(t):
+    """Pointer of tensor t (device or page-locked host memory) as the C ABI takes it; None stays None."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def off(t, n):
+    """Device pointer of element n of tensor t."""
+    return ctypes.c_void_p(t.data_ptr() + n * t.element_size())
+
+
+def stream():
+    """The current torch stream as the C ABI takes it."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def exported_symbols():

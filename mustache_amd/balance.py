@@ -98,7 +98,7 @@ class BalanceCSR:
 
     def __init__(self, x, y, v, n, ignore_diags=2, device=None):
         import torch
-        from .engine import require_gpu
+        from ._lib import require_gpu
         require_gpu()
         if device is None:
             device = v.device if isinstance(v, torch.Tensor) and v.is_cuda else \
@@ -146,7 +146,7 @@ class BalanceCSR:
             self.ws = torch.empty(int(lib.mst_balance_workspace_bytes(n, self.n_chunks)), dtype=torch.uint8, device=device)
 
     def _args(self):
-        from .engine import _ptr
+        from ._lib import ptr as _ptr
         return (_ptr(self.row_ptr), _ptr(self.col), _ptr(self.val), _ptr(self.chunk_row), _ptr(self.chunk_ptr), self.n,
                 self.n_chunks)
 
@@ -154,7 +154,7 @@ class BalanceCSR:
         """(m = w * (A w), row non-zero counts or None) as device tensors."""
         import torch
         from . import _lib
-        from .engine import _ptr, _stream
+        from ._lib import ptr as _ptr, stream as _stream
         lib = _lib.load()
         m = torch.empty(self.n, dtype=torch.float64, device=self.device)
         nnz = torch.empty(self.n, dtype=torch.int32, device=self.device) if with_nnz else None
@@ -166,7 +166,7 @@ class BalanceCSR:
         """Run the ICE iteration on w (in place) -> (iterations, variance, converged)."""
         import torch
         from . import _lib
-        from .engine import _ptr, _stream
+        from ._lib import ptr as _ptr, stream as _stream
         lib = _lib.load()
         state = torch.zeros(ctypes.sizeof(_State), dtype=torch.uint8, device=self.device)
         launched = 0
@@ -186,7 +186,7 @@ class BalanceCSR:
         """(bias device tensor [n], kappa)"""
         import torch
         from . import _lib
-        from .engine import _ptr, _stream
+        from ._lib import ptr as _ptr, stream as _stream
         lib = _lib.load()
         b = torch.empty(self.n, dtype=torch.float64, device=self.device)
         kappa = torch.empty(1, dtype=torch.float64, device=self.device)
@@ -272,7 +272,7 @@ def read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res, device=None
     """`.hic` under --balance: every raw record of the chromosome (norm NONE, no distance limit), ICE on the device, the
     bias applied on the device, then the reader's distance rule -> (x, y, v) host arrays, None when nothing is left."""
     import torch
-    from .engine import _ptr, _stream, require_gpu
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
     from .hicfile import read_intra_packed
     from .readers import _HIC_LOCK, _hic_handle
     from . import _lib

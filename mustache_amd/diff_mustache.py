@@ -199,7 +199,7 @@ def run_pair_genome(pipe, pairs, distance_in_px, st, pt, pt2):
 
 def run_pair_layout(pipe, lay, gbands, st, pt, pt2):
     """run_pair_genome's body on a prepared layout + the two samples' genome bands."""
-    from .engine import default_found_cap
+    from .launch import default_found_cap
     eng = pipe.engine
     CH, distance_in_px, pairs = lay.CH, lay.dpx, lay.ns
     # per block pair in HBM: D_2 of the difference image for every octave + the two samples' record buffers
@@ -240,20 +240,13 @@ def _pairs_from_filled(eng, pipe, dbands, n, dpx, starts, CH, dense=False, pt=No
     if not dense:
         return eng.run_band_pairs(dbands, n, dpx, starts, CH, select_below=pt)
     import torch
-    from .engine import BlockBatch
     c1, nz1, cnt1 = pipe.blocks_from_band(dbands[0], n, dpx, starts, CH)
     c2, nz2, cnt2 = pipe.blocks_from_band(dbands[1], n, dpx, starts, CH)
     c = torch.cat([c1, c2])
     nz = torch.cat([nz1, nz2])
     nzc = torch.cat([cnt1, cnt2])
     del c1, c2, nz1, nz2
-    found, pval, count, fit, cap = eng.sigma_loop(c, nz, nzc, download=False)
-    ppair, nfit = eng.pair_pvalues(c, nz, found, cap, count)
-    recs, fits = eng._download(found, pval, count, fit, eng.levels.n_tested, sort=True,
-                               extra={"pair": ppair, "q": eng.fdr(pval, count, cap)})
-    batch = BlockBatch(eng, c, nz, CH, c.shape[0], nzc.cpu().numpy().view(np.uint32).astype(np.int64), recs, fits)
-    batch.norm_fit = nfit.cpu().numpy()
-    return batch
+    return eng.run_filled_pairs(c, nz, nzc)
 
 
 def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2, chromosome, chromosome2, verbose=True,

@@ -50,14 +50,14 @@ def mustache(c, chromosome, chromosome2, res, pval_weights, start, end, mask_siz
     c = np.asarray(c)
     if c.ndim != 2 or c.shape[0] != c.shape[1] or c.dtype != np.float64:
         raise ValueError("mustache(): c must be a square float64 array")
-    from .engine import BlockBatch
+    from .batches import BlockBatch
     intra = chromosome == chromosome2
     n = c.shape[0]
     dev = torch.from_numpy(np.ascontiguousarray(c)).to(eng.device).unsqueeze(0)
     nz, nzc = eng.prologue(dev, distance_in_px, intra)
     # BH and the selection q < pt on the device, only the selected records come back (what the per-chromosome driver does)
     found, fits = eng.sigma_loop(dev, nz, nzc, with_value=False, select_below=pt)
-    batch = BlockBatch(eng, dev, nz, n, 1, nzc.cpu().numpy().view(np.uint32).astype(np.int64), found, fits)
+    batch = BlockBatch(eng, dev, nz, n, 1, nzc, found, fits)
     if int(batch.nz_count[0]) < 50:
         return []                            # mustache.py:701-702 returns before the fills of :703-706: `c` stays untouched
     # the caller's block gets the fills of mustache.py:703-706 written on the host -- the same values the device copy holds

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream, require_gpu
+from ._lib import ptr as _ptr, stream as _stream, require_gpu
 
 
 def band_from_coo(x, y, v, n, dpx):

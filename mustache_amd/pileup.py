@@ -98,7 +98,7 @@ def expected(band, n, D, ws=None):
     """(valid uint8 [n], E float64 [D + 1]) device tensors of a raw band (device, [rows >= D + 1, n])."""
     import torch
     from . import _lib
-    from .engine import _ptr, _stream, require_gpu
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
     lib = require_gpu()
     n, D = int(n), int(D)
     if band.dim() != 2 or band.shape[1] != n or band.shape[0] < D + 1 or band.dtype != torch.float64 or not band.is_contiguous():
@@ -118,7 +118,7 @@ def windows(band, n, D, E, xd, yd, w, q):
     """(obs, oe [L, 2w+1, 2w+1], loop stats [L, 3] = obs centre, oe centre, P2LL) device tensors; xd, yd int64 device [L]."""
     import torch
     from . import _lib
-    from .engine import _ptr, _stream, require_gpu
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
     lib = require_gpu()
     L, S = int(xd.numel()), 2 * int(w) + 1
     with torch.cuda.device(band.device):
@@ -134,7 +134,7 @@ def reduce(obs, oe, order, w, ws):
     """agg [4, (2w+1)^2] device tensor: sum obs, count obs, sum oe, count oe over the windows in `order` (int32 device)."""
     import torch
     from . import _lib
-    from .engine import _ptr, _stream, require_gpu
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
     lib = require_gpu()
     S = 2 * int(w) + 1
     with torch.cuda.device(obs.device):
@@ -168,7 +168,7 @@ def pileup_band(band, n, D, xs, ys, w=10, q=6):
     L, S = len(xs), 2 * w + 1
     if L == 0:
         return _empty_result(w, q)
-    from .engine import require_gpu
+    from ._lib import require_gpu
     lib = require_gpu()
     dev = band.device
     with torch.cuda.device(dev):

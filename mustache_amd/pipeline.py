@@ -11,7 +11,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import ScaleSpaceEngine, BlockBatch, BandBatch, default_found_cap, _ptr, _stream
+from ._lib import ptr as _ptr, stream as _stream
+from .batches import BandBatch, BlockBatch
+from .engine import ScaleSpaceEngine
+from .launch import default_found_cap
 from .normalize import band_from_coo, band_from_host_coo, normalize_band
 from .sharding import shard_blocks, gather_loops, world
 from .tail import batch_tail
@@ -195,8 +198,7 @@ class ChromosomePipeline:
                 c, nz, nzc = self.blocks_from_band(band, n, dpx, starts_g, CH)
                 found, fits = self.engine.sigma_loop(c, nz, nzc, skip_empty=skip_empty, with_value=False,
                                                      select_below=pt)
-                batch = BlockBatch(self.engine, c, nz, CH, len(group),
-                                   nzc.cpu().numpy().view(np.uint32).astype(np.int64), found, fits)
+                batch = BlockBatch(self.engine, c, nz, CH, len(group), nzc, found, fits)
                 t1 = time.time()
                 self._tail(batch, [(0, i, s, s) for i, s in zip(group, starts_g)], [(CH, start, end)], dpx, st, pt, loops)
                 t_dev += t1 - t0
@@ -237,8 +239,7 @@ class ChromosomePipeline:
                 band, n, dpx, [[g[3] for g in grp] for grp in groups], CH, skip_empty=skip_empty, with_value=False,
                 select_below=pt, timing=kev)):
             t1 = time.time()
-            batch = BandBatch(self.engine, band, n, dpx, [g[3] for g in group], CH,
-                              nzc.cpu().numpy().view(np.uint32).astype(np.int64), found, fits)
+            batch = BandBatch(self.engine, band, n, dpx, [g[3] for g in group], CH, nzc, found, fits)
             self._tail(batch, group, tiling, dpx, st, pt, loops)
             t_tail += time.time() - t1
             del batch

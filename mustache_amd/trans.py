@@ -22,6 +22,8 @@ import os
 
 import numpy as np
 
+from ._lib import ptr as _ptr, stream as _stream
+
 TRANS_CHUNK = 2000
 TRANS_OVERLAP = 256
 
@@ -55,22 +57,11 @@ def owned_range(ends, i):
     return (ends[i - 1] if i > 0 else 0), ends[i]
 
 
-def _ptr(t):
-    import ctypes
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    import ctypes
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def zscore_device(v, device=None):
     """v' of rule 2 for a float64 device (or host) vector: (v', mean, std, n).  mean / std come back to the host."""
     import torch
     from . import _lib
-    from .engine import require_gpu
+    from ._lib import require_gpu
     lib = require_gpu()
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     v = torch.as_tensor(v, dtype=torch.float64).to(dev).contiguous()
@@ -90,7 +81,7 @@ def read_hic_trans(f, norm_method, chr_a, chr_b, res, device=None, slab_bytes=4 
     normalisation vectors (KR by default) and transposes a pair the file stores as (chr_b, chr_a)."""
     import torch
     from . import _lib
-    from .engine import require_gpu
+    from ._lib import require_gpu
     from .hicfile import HicTransRawStream
     from .readers import _HIC_LOCK, _hic_handle
     lib = require_gpu()
@@ -179,7 +170,7 @@ class TransCaller:
         """rules 3-6 on normalised device records: loops [x, y, fdr, sigma] sorted by (x, y)"""
         import torch
         from . import _lib
-        from .engine import BlockBatch
+        from .batches import BlockBatch
         from .tail import batch_tail
         eng, dev = self.eng, self.device
         lib = eng.lib
@@ -199,7 +190,7 @@ class TransCaller:
                                                        _ptr(c), _stream()))
                 _lib.check(lib.mst_trans_prologue(_ptr(c), _ptr(nz), _ptr(nzc), B, C, _stream()))
                 found, fits = eng.sigma_loop(c, nz, nzc, with_value=False, select_below=pt)
-            batch = BlockBatch(eng, c, nz, C, B, nzc.cpu().numpy().view(np.uint32).astype(np.int64), found, fits)
+            batch = BlockBatch(eng, c, nz, C, B, nzc, found, fits)
             loops = batch_tail(batch, list(range(B)), [0] * B, pt, st, intra=False)
             for (i, j), lp in zip(group, loops):
                 rlo, rhi = owned_range(re, i)

@@ -36,8 +36,10 @@ def wrap(obj, name):
     def inner(*a, **k):
         t = time.perf_counter(); r = fn(*a, **k); acc[name] = acc.get(name, 0.0) + time.perf_counter() - t; return r
     setattr(obj, name, inner)
-for nm in ("_ss_launch", "_carve", "_pairs_one_wait"):
-    wrap(eng, nm)
+from mustache_amd import launch as launch_mod
+wrap(launch_mod, "ss_launch")
+wrap(launch_mod, "carve")
+wrap(eng, "_pair_selected")
 for nm in ("mst_diff_dog_band", "mst_found_finish", "mst_pair_pvalues_dog", "mst_bh_select_nowait", "mst_pair_gather", "mst_scale_space_band"):
     pass
 for _ in range(30):

@@ -12,6 +12,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch                                                   # noqa: E402
+from mustache_amd import launch as launch_mod                # noqa: E402
 from mustache_amd.normalize import normalize_band            # noqa: E402
 from mustache_amd.pipeline import ChromosomePipeline, block_tiling   # noqa: E402
 from mustache_amd.synth import band_counts                   # noqa: E402
@@ -32,7 +33,7 @@ def launch(eng, variant, stream, skip):
     os.environ["MST_ABLATE"] = str(variant)
     with torch.cuda.stream(stream):                 # the launch only (no finish: it would wait for the kernel)
         nzc = torch.empty(len(start), dtype=torch.int32, device=dev)
-        keep.append(eng._ss_launch(eng._flags(skip, False), nzc=nzc, band_src=(band, int(n), int(dpx), [int(v) for v in start], int(CH))))
+        keep.append(launch_mod.ss_launch(eng, launch_mod.flags(eng, skip, False), nzc=nzc, band_src=(band, int(n), int(dpx), [int(v) for v in start], int(CH))))
 
 
 def timed(jobs, skip, reps=5):

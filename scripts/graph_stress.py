@@ -13,7 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np      # noqa: E402
 import torch            # noqa: E402
-from mustache_amd.engine import ScaleSpaceEngine, device_streams, _ptr, _stream      # noqa: E402
+from mustache_amd import _lib, launch                                  # noqa: E402
+from mustache_amd._lib import ptr as _ptr, stream as _stream          # noqa: E402
+from mustache_amd.engine import ScaleSpaceEngine, device_streams      # noqa: E402
 
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 500
 graph = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -43,14 +45,14 @@ with torch.cuda.stream(side):
             c["nzc"] = torch.empty(c["B"], dtype=torch.int32, device=dev)
             c["summ"] = torch.empty(int(eng.lib.mst_found_summary_bytes(c["B"])), dtype=torch.uint8, pin_memory=True)
             c["scratch"] = torch.empty(c["summ"].numel(), dtype=torch.uint8, device=dev)
-        L = eng._ss_launch(eng._flags(True, False, graph=use_graph), nzc=c["nzc"], band_src=(c["band"], c["n"], c["dpx"], c["starts"], CH),
-                           reuse=("stress", k))
+        L = launch.ss_launch(eng, launch.flags(eng, True, False, graph=use_graph), nzc=c["nzc"],
+                             band_src=(c["band"], c["n"], c["dpx"], c["starts"], CH), reuse=("stress", k))
         c["scratch"].fill_(0xFF)
         c["summ"].fill_(0x55)
         B, cap = L.B, L.cap
         rc = eng.lib.mst_found_finish(_ptr(L.found), cap, _ptr(L.count), _ptr(c["nzc"]), _ptr(L.stats), B, nt,
                                       _ptr(L.pval), _ptr(L.fit), 0, None, None, None, _ptr(c["scratch"]),
-                                      ctypes.c_void_p(c["summ"].data_ptr()), None, None, None, 8 if use_graph else 0, _stream())
+                                      ctypes.c_void_p(c["summ"].data_ptr()), None, None, None, _lib.MST_FLAG_GRAPH if use_graph else 0, _stream())
         h = c["summ"].numpy()
         cw = 8 * ((B + 1) // 2)
         got = (int(h[:4].view(np.int32)[0]), tuple(h[16:16 + 4 * B].view(np.uint32)), tuple(h[16 + cw:16 + cw + 4 * B].view(np.uint32)))

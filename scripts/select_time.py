@@ -16,6 +16,7 @@ sys.path.insert(0, ROOT)
 def shape(dpx, res, blocks, depth):
     import numpy as np
     import torch
+    from mustache_amd import records
     from mustache_amd.pipeline import ChromosomePipeline, block_tiling
     from mustache_amd.synth import band_counts
     from mustache_amd.normalize import normalize_band
@@ -44,7 +45,7 @@ def shape(dpx, res, blocks, depth):
         for it in range(8):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            sel, fits = eng._download_selected(found, pval, count, fit, nt, cap, pt)
+            sel, fits = records.download_selected(eng, found, pval, count, fit, nt, cap, pt)
             e1.record()
             torch.cuda.synchronize()
             if it:

@@ -2,7 +2,7 @@
 import sys, time, torch, numpy as np
 sys.path.insert(0, ".")
 import bench
-from mustache_amd.engine import BlockBatch
+from mustache_amd import records
 small = "--full" not in sys.argv
 dev = torch.device("cuda", 0)
 n = 4000 + 11 * 2000 if small else 248957
@@ -16,7 +16,7 @@ for rep in range(3):
     sync(); t1 = time.time()
     found, pval, count, fit, cap = eng.sigma_loop(c, nz, nzc, skip_empty=False, download=False)
     sync(); t2 = time.time()
-    out = eng._download(found, pval, count, fit, eng.levels.n_tested)
+    out = records.download_found(eng, found, pval, count, fit, eng.levels.n_tested)
     sync(); t3 = time.time()
     print("blocks_from_band %.2f ms | sigma_loop(+pvalues, alloc) %.2f ms | sort+download+split %.2f ms | total %.2f"
           % ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t3 - t0) * 1e3))

@@ -23,7 +23,7 @@ ranges = [(0, 8), (3, 8), (7, 8), (1, 4), (5, 16), (15, 16)]         # (rank, wo
 
 def digest(w, skip):
     """every group's records are hashed AS THEY ARE HANDED OUT: they are views of two alternating page-locked staging sets, valid
-    until the second-next download (engine._pinned) -- a caller that keeps the first group of three until the end reads the
+    until the second-next download (records.Staging.next_set) -- a caller that keeps the first group of three until the end reads the
     third group's bytes"""
     w.step(skip)                      # (sets up w._group_starts for the current range)
     h = hashlib.sha256()

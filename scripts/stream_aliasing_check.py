@@ -11,15 +11,17 @@ sys.path.insert(0, '.')
 sys.path.insert(0, 'scripts')
 import bench
 import bench_extra
+from mustache_amd import launch, records
 dev = torch.device('cuda:0')
 def instrument(eng):
     acc = {}
-    for name in ("_ss_launch", "_ss_finish", "_ss_results", "_download_selected"):
+    # (the engine calls these through their modules, so wrapping the module attributes catches every call)
+    for mod, name in ((launch, "ss_launch"), (launch, "finish"), (records, "results"), (records, "download_selected")):
         def wrap(fn, key):
             def inner(*a, **k):
                 t = time.perf_counter(); r = fn(*a, **k); acc[key] = acc.get(key, 0.0) + time.perf_counter() - t; return r
             return inner
-        setattr(eng, name, wrap(getattr(eng, name), name))
+        setattr(mod, name, wrap(getattr(mod, name), name))
     return acc
 def run(wg, tag):
     acc = instrument(wg.pipe.engine)

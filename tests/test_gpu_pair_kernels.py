@@ -118,7 +118,7 @@ def _reference(cb1, cb2, dpx, octaves):
 def _launch_band(eng, bands, n, dpx, starts, CH):
     import torch
     from mustache_amd import _lib
-    from mustache_amd.engine import _ptr, _stream
+    from mustache_amd._lib import ptr as _ptr, stream as _stream
     B, n_oct = len(starts), len(eng.levels.octave_values)
     lv = ctypes.byref(eng._lv_struct)
     dog = torch.full((n_oct, B, CH, CH), float("nan"), dtype=torch.float64, device="cuda")
@@ -167,7 +167,7 @@ def _dense_route(eng, case, octaves, band_dog):
     image, G_2 - G_3 bit-identical to the band route's DoG on the addressable pixels, norm.fit within the same bounds"""
     import torch
     from mustache_amd import _lib
-    from mustache_amd.engine import _ptr, _stream
+    from mustache_amd._lib import ptr as _ptr, stream as _stream
     c1, c2, n, dpx, starts, CH = case
     B = len(starts)
     raw = np.stack([_block(c1, n, s, CH) for s in starts] + [_block(c2, n, s, CH) for s in starts])
@@ -277,7 +277,7 @@ def _pvalues(eng, dense, found, count, cap, dog, g3, fit, P, CH, n_oct, tpo):
     """both offsets (sample 1 rows [0, P), sample 2 rows [P, 2P)) into a NaN-poisoned ppair"""
     import torch
     from mustache_amd import _lib
-    from mustache_amd.engine import _ptr, _stream
+    from mustache_amd._lib import ptr as _ptr, stream as _stream
     ppair = torch.full((2 * P, cap), float("nan"), dtype=torch.float64, device="cuda")
     for off in (0, P):
         if dense:

@@ -733,6 +733,7 @@ def test_bh_select_on_crafted_pvalue_distributions():
     histogram's lowest edge (2^-40), a subset just under / over the LDS sort capacity (4096: the radix-sort route), and the
     thresholds 0.05 / 0.1 / 0.5 / 1.0.  Pixels, levels and q-values must be identical bit for bit."""
     import torch
+    from mustache_amd import records
     from mustache_amd.engine import ScaleSpaceEngine
     from mustache_amd.tail import benjamini_hochberg
     eng = ScaleSpaceEngine(OCT)
@@ -770,7 +771,7 @@ def test_bh_select_on_crafted_pvalue_distributions():
             pval[b, :m] = torch.from_numpy(p).to(eng.device)
     for pt in (0.05, 0.1, 0.5, 1.0):
         eng._select_cap = 4096
-        sel, _ = eng._download_selected(found, pval, count, fit, eng.levels.n_tested, cap, pt)
+        sel, _ = records.download_selected(eng, found, pval, count, fit, eng.levels.n_tested, cap, pt)
         for b, p in enumerate(blocks):
             q = benjamini_hochberg(p) if len(p) else np.zeros(0)
             keep = q < pt

@@ -127,7 +127,8 @@ def test_found_capacity_overflow_is_reported_and_recovered():
     re-runs with a larger buffer and gets the same records."""
     import torch
     from mustache_amd import _lib
-    from mustache_amd.engine import ScaleSpaceEngine, _ptr, _stream
+    from mustache_amd.engine import ScaleSpaceEngine
+    from mustache_amd._lib import ptr as _ptr, stream as _stream
     import ctypes
     pipe, c, nz, cnt = _normalised_block(2000, 400, 7, 5000)
     eng = pipe.engine

@@ -649,3 +649,50 @@ def test_read_sample_on_text_is_read_pd(tmp_path, monkeypatch, backend):
         assert np.array_equal(x, np.asarray(ex)) and np.array_equal(y, np.asarray(ey)) and np.array_equal(v, np.asarray(ev))
         assert len(v) == 3
     assert read_sample(str(f5), False, False, res, 2000000, False, "7") is None
+
+
+def test_cut_records_orders_and_slices_per_block():
+    """records.cut_records is the only place where selected records get their order: unordered columns of three blocks
+    (the middle one empty, dead slots behind every block's count holding garbage) must come out per block with the given
+    keys and dtypes, exactly the block's live slots, ascending by pixel; sort=False hands out the live slots as they lie,
+    as views.  launch.parse_summary is the inverse of the summary block's layout (include/mustache_hip.h)."""
+    from mustache_amd import _lib
+    from mustache_amd.launch import parse_summary
+    from mustache_amd.records import cut_records
+    rng = np.random.default_rng(11)
+    B, W, nt = 3, 7, 5
+    counts = np.array([5, 0, 7])
+    pixel = np.stack([rng.permutation(16_000_000)[:W] for _ in range(B)]).astype(np.uint32)
+    pixel[0, 2] = 0xFFFFFFF0                       # a pixel index above 2^31 must not sort as negative
+    cols = {"pixel": pixel, "level": rng.integers(1, 19, (B, W)).astype(np.uint32), "q": rng.random((B, W)),
+            "pair": rng.random((B, W))}
+    fit_h = rng.random((B, _lib.MST_MAX_TESTED, 2))
+    keep = {k: v.copy() for k, v in cols.items()}
+    recs, fits = cut_records(cols, counts, fit_h, nt, sort=True)
+    assert len(recs) == len(fits) == B
+    for b in range(B):
+        m = int(counts[b])
+        order = np.argsort(keep["pixel"][b, :m], kind="stable")
+        assert list(recs[b]) == ["pixel", "level", "q", "pair"]
+        for k in keep:
+            assert recs[b][k].dtype == keep[k].dtype and recs[b][k].shape == (m,), (b, k)
+            assert np.array_equal(recs[b][k], keep[k][b, :m][order]), (b, k)
+        assert np.all(np.diff(recs[b]["pixel"].astype(np.int64)) > 0)
+        assert np.array_equal(fits[b][0], fit_h[b, :nt, 0]) and np.array_equal(fits[b][1], fit_h[b, :nt, 1])
+    assert all(np.array_equal(cols[k], keep[k]) for k in keep), "the columns themselves are left as they were"
+    whole = {"pixel": pixel, "level": cols["level"].astype(np.uint8), "pval": cols["q"]}
+    recs, _ = cut_records(whole, counts, fit_h, nt)
+    for b in range(B):
+        m = int(counts[b])
+        assert list(recs[b]) == ["pixel", "level", "pval"] and recs[b]["level"].dtype == np.uint8
+        for k in whole:
+            assert np.array_equal(recs[b][k], whole[k][b, :m]) and (m == 0 or np.shares_memory(recs[b][k], whole[k]))
+    # the summary block: 16 bytes of flags, the record counts and the tested-pixel counts (uint32, each padded to 8
+    # bytes), the fits [B, MST_MAX_TESTED, 2] float64
+    found_n, nz_n = np.array([5, 0, 0xFFFFFFFE], np.uint32), np.array([9, 1 << 31, 3], np.uint32)
+    pad = np.zeros(1, np.uint32)
+    h = np.concatenate([np.zeros(16, np.uint8), np.concatenate([found_n, pad]).view(np.uint8),
+                        np.concatenate([nz_n, pad]).view(np.uint8), fit_h.view(np.uint8).ravel()])
+    c, z, f = parse_summary(h, B)
+    assert c.dtype == z.dtype == np.int64 and c.tolist() == [5, 0, 0xFFFFFFFE] and z.tolist() == [9, 1 << 31, 3]
+    assert np.array_equal(f, fit_h) and not np.shares_memory(f, h)
