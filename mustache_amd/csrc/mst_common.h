@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdarg>
 #include <cstdio>
+#include <functional>
+#include <memory>
+#include <vector>
 #include "../../include/mustache_hip.h"
 
 namespace mst {
@@ -42,23 +45,82 @@ inline hipError_t allow_dynamic_lds(const void *kernel, int bytes, unsigned long
 // only after the event recorded behind its copy has completed (normally long ago).
 hipError_t upload_small(void *dst, const void *src, size_t bytes, hipStream_t s);
 
+// "Has everything that was enqueued to read or write this resource finished?"  record(s) puts an event behind the work just
+// enqueued on s, wait() blocks the host until every recorded use is over, the destructor waits and destroys.  One event per
+// STREAM that has used the resource (callers alternate two streams), created lazily without timing, recreated when the current
+// device changes (events belong to a device).  Four slots -- a guess, not a measurement; a fifth stream takes a slot over
+// after a HOST wait for that slot's own last use (normally long over, like the former wait for the copy before last).
+class UseFence {
+public:
+    UseFence() = default;
+    UseFence(const UseFence &) = delete;
+    UseFence &operator=(const UseFence &) = delete;
+    ~UseFence();
+    hipError_t record(hipStream_t s);
+    hipError_t wait();
+private:
+    struct Slot {
+        hipStream_t stream = nullptr;
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+    };
+    Slot slot_[4];
+    int dev_ = -1;
+    unsigned turn_ = 0;
+};
+
 // A host list that is uploaded again and again unchanged (the work list of a launch, kept in a per-thread cache of recent
 // launches): ONE page-locked copy made when the list is built (assign), every launch copies straight out of it (upload: no host
 // memcpy, no staging slot), and the memory is released with its owner -- after the last copy out of it has completed.
 struct PinnedList {
     void *p = nullptr;
     size_t cap = 0, bytes = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};                 // behind the last two copies (callers alternate two streams)
-    int dev = -1, turn = 0;
-    bool pending[2] = {false, false};
+    UseFence copied;                                       // behind the copies out of it
     PinnedList() = default;
     PinnedList(const PinnedList &) = delete;
     PinnedList &operator=(const PinnedList &) = delete;
     ~PinnedList();
-    void release();
-    hipError_t wait();
     hipError_t assign(const void *src, size_t n);          // waits for copies still reading the old contents
     hipError_t upload(void *dst, hipStream_t s);
+};
+
+// Graph replay (MST_FLAG_GRAPH), the "second sight" rule: a call whose signature is unknown takes the least recently used entry
+// and runs the ordinary way (one-off calls never pay a capture); the second call with that signature is captured into a
+// hipGraph, instantiated and launched; later ones are one hipGraphLaunch.  An entry's graph is destroyed only after its last
+// launch has completed.  One cache per user and host thread (a thread_local object); never on the legacy default stream (it
+// cannot be captured), never in PROFILE builds.  MUSTACHE_NO_GRAPHS switches users off by `word`.
+class ReplayCache {
+public:
+    enum Sight { kFirst, kCapture, kReplay };
+    ReplayCache(int entries, const char *word);            // word: "launch" or "finish"
+    bool usable(int32_t flags, hipStream_t s) const { return enabled_ && (flags & MST_FLAG_GRAPH) && s != nullptr; }
+    // finds the signature (every scalar / pointer argument, the device, tables as bytes) or claims an entry for it; the call
+    // that follows -- nothing (kFirst), capture or replay -- acts on that entry
+    Sight look(const std::vector<int64_t> &sig);
+    static const char *name(Sight sight);                  // for mst::note: "first sight" / "CAPTURE" / "REPLAY"
+    int replay(hipStream_t s);
+    // body(image) enqueues the call on s between begin and end of the capture; image = image_bytes of page-locked memory the
+    // entry owns (grow-only) for what the graph's copy nodes read, so nothing the graph references can change or go away
+    // under it.  A stream that refuses capture gets body(nullptr), an ordinary launch; the entry stays at second sight, so
+    // the next call tries again.  A failed body, capture or instantiation forgets the signature.
+    int capture(const char *who, hipStream_t s, size_t image_bytes, const std::function<int(char *)> &body);
+private:
+    struct Entry {
+        std::vector<int64_t> sig;
+        hipGraphExec_t exec = nullptr;
+        UseFence done;                                     // behind the launches of exec
+        char *image = nullptr;
+        size_t image_cap = 0;
+        bool seen = false;
+        unsigned long long stamp = 0;
+        void drop_graph();
+        ~Entry();
+    };
+    std::unique_ptr<Entry[]> entry_;
+    Entry *cur_ = nullptr;
+    int n_;
+    unsigned long long stamp_ = 0;
+    bool enabled_;
 };
 
 // PROFILE builds mark the stage every entry point belongs to (read / normalise / launch / finish / tail) as a roctx range, so

@@ -842,13 +842,57 @@ __global__ void fill_stats_kernel(double *level_stats, int n) {
 
 }  // namespace
 
+namespace {
+// The ONE map from a level table's largest blur radius (and MST_FLAG_FMA) to the tile a launch runs: f(TileTag<T>())
+template <class T>
+struct TileTag {
+    using type = T;
+};
+template <class F>
+static auto with_tile(int max_radius, bool fma, F &&f) {
+    if (fma) return f(TileTag<TileDefaultFma>());
+#ifdef MST_EXP_TILE7
+    if (max_radius <= 7 && getenv("MST_EXP_USE_TILE7")) return f(TileTag<TileOct1>());
+#endif
+    if (max_radius <= TileDefault::RMAX) return f(TileTag<TileDefault>());
+    return f(TileTag<TileWide>());
+}
+
+// build_items on the lattice of the level table's tile -- the default tile's or the wide one's: the FMA tile and the experiment's
+// TileOct1 are launched on lists of the default lattice; returns the tile's grid_positions
+static int build_list(int max_radius, const int64_t *starts, int B, int CH, int dpx, bool share, bool band_only,
+                      std::vector<WorkItem> &items, std::vector<int32_t> &sop, int *tiles_total, const int32_t *cuts = nullptr,
+                      int n_cuts = 0, std::vector<int32_t> *stage_begin = nullptr) {
+    if (max_radius > TileDefault::RMAX) {
+        build_items<TileWide>(starts, B, CH, dpx, share, band_only, items, sop, tiles_total, cuts, n_cuts, stage_begin);
+        return grid_positions<TileWide>(CH);
+    }
+    build_items<TileDefault>(starts, B, CH, dpx, share, band_only, items, sop, tiles_total, cuts, n_cuts, stage_begin);
+    return grid_positions<TileDefault>(CH);
+}
+
+// Byte offsets of a launch's tables in its workspace: level table, block origins, work list, position map (slot_of_pos), and
+// behind them the per-item partial statistics.  worst() is what mst_scale_space_workspace_bytes promises and every plain launch
+// carves; a captured launch packs the same layout with its actual counts (enqueue_launch) but keeps the partials where they are.
+struct Workspace {
+    size_t levels = 0, starts, items, sop, partial;
+    Workspace(int B, size_t n_items, size_t n_sop) {
+        starts = align_up(sizeof(DevLevels), 256);
+        items = starts + align_up(sizeof(int64_t) * (size_t)B, 256);
+        sop = items + align_up(sizeof(WorkItem) * n_items, 256);
+        partial = sop + align_up(sizeof(int32_t) * n_sop, 256);
+    }
+    static Workspace worst(int B, int CH) {
+        const size_t n = (size_t)B * positions_max(CH);
+        return Workspace(B, n, n);
+    }
+};
+}  // namespace
+
 extern "C" uint64_t mst_scale_space_workspace_bytes(int32_t B, int32_t CH, const mst_levels *lv) {
     int mr = 0, nt = 0;
     if (B <= 0 || CH <= 0 || check_levels(lv, &mr, &nt) != MST_OK) return 0;
-    const size_t npos = (size_t)positions_max(CH);
-    return align_up(sizeof(DevLevels), 256) + align_up(sizeof(int64_t) * (size_t)B, 256) +
-           align_up(sizeof(WorkItem) * (size_t)B * npos, 256) + align_up(sizeof(int32_t) * (size_t)B * npos, 256) +
-           sizeof(double) * 2 * (size_t)B * npos * nt;
+    return Workspace::worst(B, CH).partial + sizeof(double) * 2 * (size_t)B * positions_max(CH) * nt;
 }
 
 template <class T, bool BAND>
@@ -894,13 +938,11 @@ static int launch_scale_space(const double *c, const uint8_t *nz, BandSrc src, i
 extern "C" int mst_scale_space_band_tiles(int32_t CH, int32_t dpx, const mst_levels *lv, int32_t *tiles_total_out) {
     int mr = 0, nt = 0;
     if (CH <= 0 || dpx < 0 || check_levels(lv, &mr, &nt) != MST_OK) return -1;
-    const bool wide = mr > TileDefault::RMAX;
     std::vector<WorkItem> items;
     std::vector<int32_t> sop;
     const int64_t start = 0;
     int total = 0;
-    if (wide) build_items<TileWide>(&start, 1, CH, dpx, false, true, items, sop, &total);
-    else build_items<TileDefault>(&start, 1, CH, dpx, false, true, items, sop, &total);
+    build_list(mr, &start, 1, CH, dpx, false, true, items, sop, &total);
     if (tiles_total_out) *tiles_total_out = total;
     return (int)items.size();
 }
@@ -909,12 +951,11 @@ extern "C" int mst_scale_space_band_items(const int64_t *starts, int32_t B, int3
                                           int32_t flags, int64_t *tiles_out, int64_t *shared_out) {
     int mr = 0, nt = 0;
     if (!starts || B <= 0 || CH <= 0 || dpx < 0 || check_levels(lv, &mr, &nt) != MST_OK) return -1;
-    const bool wide = mr > TileDefault::RMAX, share = !(flags & MST_FLAG_NO_SHARE), band_only = (flags & MST_FLAG_SKIP_EMPTY) != 0;
+    const bool share = !(flags & MST_FLAG_NO_SHARE), band_only = (flags & MST_FLAG_SKIP_EMPTY) != 0;
     std::vector<WorkItem> items;
     std::vector<int32_t> sop;
     int total = 0;
-    if (wide) build_items<TileWide>(starts, B, CH, dpx, share, band_only, items, sop, &total);
-    else build_items<TileDefault>(starts, B, CH, dpx, share, band_only, items, sop, &total);
+    build_list(mr, starts, B, CH, dpx, share, band_only, items, sop, &total);
     int64_t shared = 0;
     for (const WorkItem &it : items) shared += it.delta2 != 0;
     if (tiles_out) *tiles_out = (int64_t)items.size() + shared;      // tiles the blocks would run one by one
@@ -922,45 +963,251 @@ extern "C" int mst_scale_space_band_items(const int64_t *starts, int32_t B, int3
     return (int)items.size();
 }
 
-// MST_FLAG_GRAPH: a launch whose every argument repeats (same buffers, same blocks, same level table) is captured into a
-// hipGraph the second time it is seen and REPLAYED from then on -- one hipGraphLaunch instead of ~16 runtime calls (four
-// uploads, two memsets, two kernels and their bookkeeping) in front of the fused kernel.  That matters for small launches: six
-// blocks of 2000 x 2000 are 1.75 ms of kernel and the enqueue was 0.07 ms during which the GPU waited.  The graph owns a
-// page-locked image of what its copy nodes read (level table, block origins, work list, position map), so nothing it references
-// can change or go away under it.  Entries live per host thread; an entry's graph is destroyed only after its last launch has
-// completed.
-struct GraphEntry {
-    std::vector<int64_t> sig;                 // every scalar / pointer argument + the block origins
-    mst_levels lv;                            // the level table the graph was captured with
-    hipGraphExec_t exec = nullptr;
-    hipEvent_t done = nullptr;                // behind the last launch
-    char *image = nullptr;                    // page-locked sources of the graph's copy nodes
-    size_t image_cap = 0, image_used = 0;
-    int seen = 0;
-    unsigned long long stamp = 0;
-    void drop_graph() {
-        if (exec) {
-            if (done) (void)hipEventSynchronize(done);
-            (void)hipGraphExecDestroy(exec);
-            exec = nullptr;
-        }
+// level table -> the kernel's form.  first_level[o] = 3 where octave o's first two levels repeat the previous octave's last two
+// (same radius, same taps): the kernel keeps those blurs instead of computing them again
+static int make_dev_levels(const mst_levels *lv, const char *who, DevLevels *h) {
+    if (lv->n_octaves > 16) return mst::fail(MST_E_ARG, "%s: more than 16 octaves", who);
+    memset(h, 0, sizeof(*h));
+    h->n_octaves = lv->n_octaves;
+    h->levels_per_octave = lv->levels_per_octave;
+    for (int l = 0; l < lv->n_octaves * lv->levels_per_octave; ++l) {
+        h->radius[l] = lv->radius[l];
+        for (int j = 0; j <= lv->radius[l]; ++j) h->taps[l][j] = lv->taps[l][j];
     }
-    ~GraphEntry() {
-        drop_graph();
-        if (done) (void)hipEventDestroy(done);
-        if (image) (void)hipHostFree(image);
+    const int lpo = lv->levels_per_octave;
+    for (int o = 0; o < lv->n_octaves; ++o) {
+        h->first_level[o] = 1;
+        if (o == 0) continue;
+#ifdef MST_PROFILE
+        if (getenv("MST_NO_LEVEL_REUSE")) continue;       // PROFILE builds only: time the 24-blur form
+#endif
+        bool same = true;
+        for (int q = 0; q < 2 && same; ++q) {
+            const int a = (o - 1) * lpo + lpo - 2 + q, b = o * lpo + q;      // (prev octave, k = lpo-1+q) vs (this, k = 1+q)
+            same = lv->radius[a] == lv->radius[b] &&
+                   memcmp(lv->taps[a], lv->taps[b], sizeof(double) * (lv->radius[a] + 1)) == 0;
+        }
+        if (same) h->first_level[o] = 3;
+    }
+    return MST_OK;
+}
+
+namespace {
+// The work list of a launch as the launches use it: the list, page-locked copies the uploads read (no host memcpy per launch)
+// and a DEVICE copy, uploaded once per list: a step that repeats its launch (a benchmark loop, the second sample, the same
+// chromosome again) does not send the list -- 17 MB for the 124 blocks of chr1 at 1 kb, 0.4 ms in front of the kernel -- again.
+// The device buffer belongs to the list and only grows.
+struct WorkList {
+    std::vector<int64_t> key;
+    std::vector<WorkItem> items;
+    std::vector<int32_t> sop;
+    std::vector<int32_t> stage_begin;        // staged lists: first item of every stage, then the item count
+    int npos = 0;
+    mst::PinnedList pin_items, pin_sop;
+    char *dbuf = nullptr;
+    size_t dcap = 0;
+    int ddev = -1;
+    bool uploaded = false;
+    hipEvent_t up = nullptr;                 // behind the upload: launches on other streams wait for it on the device
+    mst::UseFence used;                      // behind every launch, on any stream, that read dbuf
+    ~WorkList() {
+        (void)used.wait();
+        if (up) (void)hipEventDestroy(up);
+        if (dbuf) (void)hipFree(dbuf);
+    }
+    // the device copy, for work enqueued on s: uploaded by the first launch that uses the list, read in place afterwards
+    int on_device(hipStream_t s, const WorkItem **d_items, const int32_t **d_sop) {
+        int dev = 0;
+        MST_HIP(hipGetDevice(&dev));
+        const size_t off_sop = align_up(pin_items.bytes, 256), need_dev = off_sop + pin_sop.bytes;
+        if (uploaded && ddev != dev) uploaded = false;
+        if (!uploaded) {
+            MST_HIP(used.wait());            // launches on other streams may still read what is overwritten or freed here
+            if (dcap < need_dev || ddev != dev) {
+                if (dbuf) (void)hipFree(dbuf);
+                dbuf = nullptr;
+                dcap = 0;
+                if (up) (void)hipEventDestroy(up);
+                up = nullptr;
+                const size_t want = need_dev + need_dev / 4;
+                MST_HIP(hipMalloc((void **)&dbuf, want));
+                dcap = want;
+                ddev = dev;
+                MST_HIP(hipEventCreateWithFlags(&up, hipEventDisableTiming));
+            }
+            MST_HIP(pin_items.upload(dbuf, s));
+            MST_HIP(pin_sop.upload(dbuf + off_sop, s));
+            MST_HIP(hipEventRecord(up, s));
+            uploaded = true;
+        } else {
+            MST_HIP(hipStreamWaitEvent(s, up, 0));      // uploaded on another stream, perhaps
+        }
+        *d_items = reinterpret_cast<const WorkItem *>(dbuf);
+        *d_sop = reinterpret_cast<const int32_t *>(dbuf + off_sop);
+        return MST_OK;
     }
 };
 
-// shared body of mst_scale_space (dense blocks) and mst_scale_space_band (blocks cut out of the band on the fly)
+// A few recent lists per host thread: a caller that runs the same blocks again -- a benchmark loop, the second sample of a
+// two-sample run -- does not pay the ~1 ms of host time per 100 k items again.
+//   band source -> tiles on the chromosome's lattice, tiles inside two consecutive blocks computed once (share; without it every
+//   block on its own lattice, every tile once per block: the cross-check form of MST_FLAG_NO_SHARE and the dense source)
+//   dpx < 0: dense source;  staged: the list in the staged order of build_items (cuts, n_cuts)
+struct WorkListCache {
+    WorkList list[4];
+    unsigned turn = 0;
+    int find_or_build(int max_radius, const int64_t *starts, int B, int CH, int dpx, bool share, bool band_only, bool staged,
+                      const int32_t *cuts, int n_cuts, WorkList **out) {
+        std::vector<int64_t> key;
+        key.reserve((size_t)B + 6 + (staged ? n_cuts : 0));
+        key.push_back(B);
+        key.push_back(CH);
+        key.push_back(dpx);
+        key.push_back((share ? 1 : 0) | (band_only ? 2 : 0) | (max_radius > TileDefault::RMAX ? 4 : 0));
+        if (share) key.insert(key.end(), starts, starts + B);     // without sharing the list does not depend on the origins
+        if (staged) {
+            key.push_back(-7);
+            key.insert(key.end(), cuts, cuts + n_cuts);
+        }
+        for (WorkList &wl : list)
+            if (wl.key == key) *out = &wl;
+        if (*out) return MST_OK;
+        WorkList *wl = *out = &list[turn++ % 4];
+        (void)wl->used.wait();              // (a launch four lists ago: long done) its device copy is about to be replaced
+        wl->uploaded = false;
+        wl->key = key;
+        const std::vector<int64_t> zeros(share ? 0 : (size_t)B, 0);
+        wl->npos = build_list(max_radius, share ? starts : zeros.data(), B, CH, dpx < 0 ? 0 : dpx, share, band_only, wl->items,
+                              wl->sop, nullptr, staged ? cuts : nullptr, staged ? n_cuts : 0, &wl->stage_begin);
+        hipError_t pe = wl->pin_items.assign(wl->items.data(), sizeof(WorkItem) * wl->items.size());
+        if (pe == hipSuccess) pe = wl->pin_sop.assign(wl->sop.data(), sizeof(int32_t) * (size_t)B * wl->npos);
+        if (pe != hipSuccess) wl->key.clear();
+        MST_HIP(pe);
+        return MST_OK;
+    }
+};
+
+// Everything a fused launch enqueues, spelled out: enqueue_launch reads nothing else
+struct Launch {
+    const double *c;
+    const uint8_t *nz;
+    BandSrc src;                     // src.starts is set by enqueue_launch
+    const int64_t *starts_host;
+    int B, CH, max_radius, n_tested, skip_empty;
+    bool fma;
+    const DevLevels *levels;         // host copy
+    mst_found *found;
+    uint32_t found_cap;
+    uint32_t *found_count;
+    double *level_stats;
+    char *workspace;
+    WorkList *list;
+    const int32_t *cuts;             // staged form (mst_scale_space_band_stage): stage >= 0 enqueues only the items of blocks
+    int n_cuts, stage;               // [cuts[stage - 1], cuts[stage]) of the launch's ONE work list and the level statistics of
+};                                   // those blocks; stage 0 also uploads the tables and zeroes the counters
+}  // namespace
+
+// image != nullptr: the call is being CAPTURED into a graph whose copy node reads image (mst::ReplayCache)
+template <bool BAND>
+static int enqueue_launch(const Launch &a, char *image, hipStream_t s) {
+    const bool staged = a.stage >= 0, first = a.stage <= 0, captured = image != nullptr;
+    const int B = a.B, nt = a.n_tested, npos = a.list->npos, n_items = (int)a.list->items.size();
+    const size_t items_bytes = sizeof(WorkItem) * (size_t)n_items, sop_bytes = sizeof(int32_t) * (size_t)B * npos;
+    // Captured launches (small, latency-bound): the four tables lie side by side in the workspace -- the tile positions packed
+    // right behind the work list instead of at their worst-case offset -- in the order and alignment of the graph entry's
+    // page-locked image, so ONE copy node uploads them all (four nodes of ~5 us each stood in front of a 0.5 ms kernel).
+    const Workspace worst = Workspace::worst(B, a.CH), at = captured ? Workspace(B, n_items, (size_t)B * npos) : worst;
+    DevLevels *d_lv = reinterpret_cast<DevLevels *>(a.workspace + at.levels);
+    int64_t *d_starts = reinterpret_cast<int64_t *>(a.workspace + at.starts);
+    const WorkItem *d_items = reinterpret_cast<const WorkItem *>(a.workspace + at.items);
+    const int32_t *d_sop = reinterpret_cast<const int32_t *>(a.workspace + at.sop);
+    double *partial = reinterpret_cast<double *>(a.workspace + worst.partial);
+    if (captured) {
+        memcpy(image + at.levels, a.levels, sizeof(DevLevels));
+        if (BAND) memcpy(image + at.starts, a.starts_host, sizeof(int64_t) * (size_t)B);
+        if (n_items) {
+            memcpy(image + at.items, a.list->items.data(), items_bytes);
+            memcpy(image + at.sop, a.list->sop.data(), sop_bytes);
+        }
+        MST_HIP(hipMemcpyAsync(a.workspace, image, n_items ? at.sop + sop_bytes : at.items, hipMemcpyHostToDevice, s));
+    } else if (first) {              // through a pinned staging slot (mst::upload_small): the source may die as soon as this returns
+        MST_HIP(mst::upload_small(d_lv, a.levels, sizeof(DevLevels), s));
+    }
+    if (first) {
+        zero_counts_kernel<<<(B + 255) / 256, 256, 0, s>>>(a.found_count, BAND ? a.src.nz_count : nullptr, B);
+        MST_LAUNCH_CHECK();
+    }
+    BandSrc src = a.src;
+    if (BAND) {
+        if (!captured && first) MST_HIP(mst::upload_small(d_starts, a.starts_host, sizeof(int64_t) * B, s));
+        src.starts = d_starts;
+    }
+    if (n_items == 0) {          // no tile reaches the band: nothing is tested, nothing is found
+        if (first) {
+            fill_stats_kernel<<<(B * MST_MAX_TESTED + 255) / 256, 256, 0, s>>>(a.level_stats, B * MST_MAX_TESTED);
+            MST_LAUNCH_CHECK();
+        }
+        return MST_OK;
+    }
+    if (!captured) {             // (never while capturing: the device copy's path waits on events and allocates)
+        const int drc = a.list->on_device(s, &d_items, &d_sop);
+        if (drc != MST_OK) return drc;
+    }
+    // this call's share of the list and of the blocks (everything, unless staged).  Staged: this stage's run of the list; its
+    // items' slots in `partial` keep their positions in the WHOLE list, which is what the position map refers to -- both
+    // pointers are simply advanced
+    const int it0 = staged ? a.list->stage_begin[a.stage] : 0, it1 = staged ? a.list->stage_begin[a.stage + 1] : n_items;
+    const int blk0 = staged && a.stage > 0 ? a.cuts[a.stage - 1] : 0, blk1 = staged && a.stage < a.n_cuts ? a.cuts[a.stage] : B;
+    if (it1 > it0) {
+        const int lrc = with_tile(a.max_radius, a.fma, [&](auto tag) {
+            return launch_scale_space<typename decltype(tag)::type, BAND>(
+                a.c, a.nz, src, a.CH, d_lv, a.found, a.found_cap, a.found_count, partial + (size_t)it0 * nt * 2, nt, a.skip_empty,
+                d_items + it0, it1 - it0, s);
+        });
+        if (lrc != MST_OK) return lrc;
+    }
+    // a block's tiles are its own items and shared ones of the block before it: complete once its stage has run
+    if (blk1 > blk0) {
+        stats_reduce_kernel<<<dim3(nt, blk1 - blk0), 256, 0, s>>>(partial, npos, d_sop + (size_t)blk0 * npos, nt,
+                                                                a.level_stats + (size_t)blk0 * MST_MAX_TESTED * 2);
+        MST_LAUNCH_CHECK();
+    }
+    if (!captured) MST_HIP(a.list->used.record(s));
+    return MST_OK;
+}
+
+// the signature of a fused launch for graph replay: every scalar / pointer argument, the block origins, the level table
+static std::vector<int64_t> launch_signature(const BandSrc &src, const int64_t *starts, int B, int CH, const mst_levels *lv,
+                                             const void *found, uint32_t found_cap, const void *found_count,
+                                             const void *level_stats, int flags, const void *workspace, uint64_t workspace_bytes,
+                                             int dev) {
+    std::vector<int64_t> sig;
+    const size_t lv_words = (sizeof(mst_levels) + 7) / 8;
+    sig.reserve((size_t)B + 16 + lv_words);
+    for (const void *p : {(const void *)src.band, (const void *)src.band2, found, found_count, level_stats,
+                          (const void *)src.nz_count, workspace})
+        sig.push_back((int64_t)(intptr_t)p);
+    for (int64_t v : {(int64_t)src.n, (int64_t)src.dpx, (int64_t)src.split, (int64_t)B, (int64_t)CH, (int64_t)found_cap,
+                      (int64_t)flags, (int64_t)workspace_bytes, (int64_t)dev})
+        sig.push_back(v);
+    sig.insert(sig.end(), starts, starts + B);
+    sig.resize(sig.size() + lv_words, 0);
+    memcpy(&sig[sig.size() - lv_words], lv, sizeof(mst_levels));
+    return sig;
+}
+
+// MST_FLAG_GRAPH: a launch whose every argument repeats (same buffers, same blocks, same level table) is captured into a
+// hipGraph the second time it is seen and REPLAYED from then on (mst::ReplayCache) -- one hipGraphLaunch instead of ~16 runtime
+// calls (four uploads, two memsets, two kernels and their bookkeeping) in front of the fused kernel.  That matters for small
+// launches: six blocks of 2000 x 2000 are 1.75 ms of kernel and the enqueue was 0.07 ms during which the GPU waited.  Band
+// source only; staged launches are never captured.  This is the shared body of mst_scale_space (dense blocks) and of
+// mst_scale_space_band and its kin (blocks cut out of the band on the fly).
 template <bool BAND>
 static int scale_space_impl(const double *c, const uint8_t *nz, BandSrc src, const int64_t *starts_host, int32_t B,
                             int32_t CH, const mst_levels *lv, mst_found *found, uint32_t found_cap,
                             uint32_t *found_count, double *level_stats, int32_t flags, void *workspace,
                             uint64_t workspace_bytes, void *stream, const char *who, const int32_t *cuts = nullptr,
                             int32_t n_cuts = 0, int32_t stage = -1) {
-    // staged form (mst_scale_space_band_stage): stage >= 0 enqueues only the items of blocks [cuts[stage - 1], cuts[stage]) of the
-    // launch's ONE work list and the level statistics of those blocks; stage 0 also uploads the tables and zeroes the counters
     const bool staged = stage >= 0;
     if (staged) flags &= ~MST_FLAG_GRAPH;
     const int skip_empty = (flags & MST_FLAG_SKIP_EMPTY) ? 1 : 0;
@@ -976,331 +1223,38 @@ static int scale_space_impl(const double *c, const uint8_t *nz, BandSrc src, con
         return mst::fail(MST_E_ARG, "%s: workspace too small (%llu < %llu bytes)", who,
                          (unsigned long long)workspace_bytes, (unsigned long long)need);
     hipStream_t s = mst::as_stream(stream);
-
-    // level table -> device (through a pinned staging slot, mst::upload_small: `h` may die as soon as this returns)
     DevLevels h;
-    memset(&h, 0, sizeof(h));
-    h.n_octaves = lv->n_octaves;
-    h.levels_per_octave = lv->levels_per_octave;
-    for (int l = 0; l < lv->n_octaves * lv->levels_per_octave; ++l) {
-        h.radius[l] = lv->radius[l];
-        for (int j = 0; j <= lv->radius[l]; ++j) h.taps[l][j] = lv->taps[l][j];
-    }
-    if (lv->n_octaves > 16) return mst::fail(MST_E_ARG, "%s: more than 16 octaves", who);
-    const int lpo = lv->levels_per_octave;
-    for (int o = 0; o < lv->n_octaves; ++o) {
-        h.first_level[o] = 1;
-        if (o == 0) continue;
-#ifdef MST_PROFILE
-        if (getenv("MST_NO_LEVEL_REUSE")) continue;       // PROFILE builds only: time the 24-blur form
-#endif
-        bool same = true;
-        for (int q = 0; q < 2 && same; ++q) {
-            const int a = (o - 1) * lpo + lpo - 2 + q, b = o * lpo + q;      // (prev octave, k = lpo-1+q) vs (this, k = 1+q)
-            same = lv->radius[a] == lv->radius[b] &&
-                   memcmp(lv->taps[a], lv->taps[b], sizeof(double) * (lv->radius[a] + 1)) == 0;
-        }
-        if (same) h.first_level[o] = 3;
-    }
+    if ((rc = make_dev_levels(lv, who, &h)) != MST_OK) return rc;
     if (fma && mr > TileDefault::RMAX)
         return mst::fail(MST_E_ARG, "%s: MST_FLAG_FMA is only built for blur radii <= %d", who, TileDefault::RMAX);
-    const bool wide = mr > TileDefault::RMAX;
-    const size_t npos_max = (size_t)positions_max(CH);
-    const int npos = wide ? grid_positions<TileWide>(CH) : grid_positions<TileDefault>(CH);
 
-    char *w = reinterpret_cast<char *>(workspace);
-    DevLevels *d_lv = reinterpret_cast<DevLevels *>(w);
-    w += align_up(sizeof(DevLevels), 256);
-    int64_t *d_starts = reinterpret_cast<int64_t *>(w);
-    w += align_up(sizeof(int64_t) * (size_t)B, 256);
-    WorkItem *d_items = reinterpret_cast<WorkItem *>(w);
-    w += align_up(sizeof(WorkItem) * (size_t)B * npos_max, 256);
-    int32_t *d_sop = reinterpret_cast<int32_t *>(w);
-    w += align_up(sizeof(int32_t) * (size_t)B * npos_max, 256);
-    double *partial = reinterpret_cast<double *>(w);
-
-    // ---- graph replay (MST_FLAG_GRAPH, band source, a stream that can be captured: not the legacy default stream)
-    GraphEntry *gent = nullptr;        // non-null: this call is being CAPTURED into gent
-#ifndef MST_PROFILE
-    static thread_local GraphEntry gcache[4];
-    static thread_local unsigned long long gstamp = 0;
-    static const bool graphs_off = [] {
-        const char *e = getenv("MUSTACHE_NO_GRAPHS");        // diagnostic switch: 1 = no graphs at all, "launch" = none here
-        return e && *e && *e != '0' && *e != 'f';
-    }();
-    if (BAND && (flags & MST_FLAG_GRAPH) && s != nullptr && !graphs_off) {
+    static thread_local mst::ReplayCache graphs(4, "launch");
+    mst::ReplayCache::Sight sight = mst::ReplayCache::kFirst;
+    if (BAND && graphs.usable(flags, s)) {
         int dev = 0;
         MST_HIP(hipGetDevice(&dev));
-        std::vector<int64_t> sig;
-        sig.reserve((size_t)B + 16);
-        for (const void *p : {(const void *)src.band, (const void *)src.band2, (const void *)found, (const void *)found_count,
-                              (const void *)level_stats, (const void *)src.nz_count, (const void *)workspace})
-            sig.push_back((int64_t)(intptr_t)p);
-        for (int64_t v : {(int64_t)src.n, (int64_t)src.dpx, (int64_t)src.split, (int64_t)B, (int64_t)CH, (int64_t)found_cap,
-                          (int64_t)flags, (int64_t)workspace_bytes, (int64_t)dev})
-            sig.push_back(v);
-        sig.insert(sig.end(), starts_host, starts_host + B);
-        GraphEntry *ge = nullptr;
-        for (GraphEntry &e : gcache)
-            if (e.seen && e.sig == sig && memcmp(&e.lv, lv, sizeof(mst_levels)) == 0) ge = &e;
+        sight = graphs.look(launch_signature(src, starts_host, B, CH, lv, found, found_cap, found_count, level_stats, flags,
+                                             workspace, workspace_bytes, dev));
         mst::note("scale_space graph B=%d CH=%d n=%lld dpx=%d cap=%u flags=%d band=%p found=%p count=%p stats=%p nz=%p ws=%p -> %s", B, CH,
                   (long long)src.n, (int)src.dpx, found_cap, flags, (const void *)src.band, (const void *)found, (const void *)found_count,
-                  (const void *)level_stats, (const void *)src.nz_count, workspace, ge && ge->exec ? "REPLAY" : (ge ? "CAPTURE" : "first sight"));
-        if (ge && ge->exec) {
-            ge->stamp = ++gstamp;
-            MST_HIP(hipGraphLaunch(ge->exec, s));
-            MST_HIP(hipEventRecord(ge->done, s));
-            return MST_OK;
-        }
-        if (!ge) {                     // first sight: remember the call, run it the ordinary way (one-off launches never pay a capture)
-            ge = &gcache[0];
-            for (GraphEntry &e : gcache)
-                if (e.stamp < ge->stamp) ge = &e;
-            ge->drop_graph();
-            ge->sig = sig;
-            memcpy(&ge->lv, lv, sizeof(mst_levels));
-            ge->seen = 1;
-            ge->stamp = ++gstamp;
-        } else {
-            ge->stamp = ++gstamp;
-            gent = ge;                 // second sight: capture below
-        }
+                  (const void *)level_stats, (const void *)src.nz_count, workspace, mst::ReplayCache::name(sight));
+        if (sight == mst::ReplayCache::kReplay) return graphs.replay(s);
     }
-#endif
 
-    // the launch's work list: band source -> tiles on the chromosome's lattice, tiles inside two consecutive blocks computed
-    // once (MST_FLAG_NO_SHARE: every block on its own lattice, every tile once per block: the cross-check form)
-    // (a few recent lists are kept per host thread: a caller that runs the same blocks again -- a benchmark loop, the second
-    // sample of a two-sample run -- does not pay the ~1 ms of host time per 100 k items again)
-    struct Cached {
-        std::vector<int64_t> key;
-        std::vector<WorkItem> items;
-        std::vector<int32_t> sop;
-        std::vector<int32_t> stage_begin;        // staged lists: first item of every stage, then the item count
-        mst::PinnedList pin_items, pin_sop;      // page-locked copies the launches upload from (no host memcpy per launch)
-        // ... and a DEVICE copy, uploaded once per list: a step that repeats its launch (a benchmark loop, the second sample, the
-        // same chromosome again) does not send the list -- 17 MB for the 124 blocks of chr1 at 1 kb, 0.4 ms in front of the
-        // kernel -- again.  The buffer belongs to the cache entry and only grows; `used` lies behind the last launch that read it.
-        char *dbuf = nullptr;
-        size_t dcap = 0;
-        int ddev = -1;
-        bool on_device = false;
-        hipEvent_t up = nullptr, used = nullptr;
-        bool used_pending = false;
-        void wait_used() {
-            if (used_pending && used) (void)hipEventSynchronize(used);
-            used_pending = false;
-        }
-        ~Cached() {
-            wait_used();
-            if (up) (void)hipEventDestroy(up);
-            if (used) (void)hipEventDestroy(used);
-            if (dbuf) (void)hipFree(dbuf);
-        }
-    };
-    static thread_local Cached cache[4];
-    static thread_local unsigned cache_turn = 0;
-    const bool share = BAND && !(flags & MST_FLAG_NO_SHARE);
-    const bool band_only = BAND && skip_empty;
-    std::vector<int64_t> key;
-    key.reserve((size_t)B + 6);
-    key.push_back(B);
-    key.push_back(CH);
-    key.push_back(BAND ? src.dpx : -1);
-    key.push_back((share ? 1 : 0) | (band_only ? 2 : 0) | (wide ? 4 : 0));
-    if (share) key.insert(key.end(), starts_host, starts_host + B);     // without sharing the list does not depend on the origins
-    if (staged) {
-        key.push_back(-7);
-        key.insert(key.end(), cuts, cuts + n_cuts);
-    }
-    Cached *hit = nullptr;
-    for (Cached &cd : cache)
-        if (cd.key == key) hit = &cd;
-    if (!hit) {
-        hit = &cache[cache_turn++ % 4];
-        hit->wait_used();                   // (a launch four lists ago: long done) its device copy is about to be replaced
-        hit->on_device = false;
-        hit->key = key;
-        std::vector<int64_t> zeros;
-        const int64_t *st = starts_host;
-        if (!share) {
-            zeros.assign((size_t)B, 0);
-            st = zeros.data();
-        }
-        if (wide) build_items<TileWide>(st, B, CH, BAND ? src.dpx : 0, share, band_only, hit->items, hit->sop, nullptr,
-                                        staged ? cuts : nullptr, staged ? n_cuts : 0, &hit->stage_begin);
-        else build_items<TileDefault>(st, B, CH, BAND ? src.dpx : 0, share, band_only, hit->items, hit->sop, nullptr,
-                                      staged ? cuts : nullptr, staged ? n_cuts : 0, &hit->stage_begin);
-        hipError_t pe = hit->pin_items.assign(hit->items.data(), sizeof(WorkItem) * hit->items.size());
-        if (pe == hipSuccess) pe = hit->pin_sop.assign(hit->sop.data(), sizeof(int32_t) * (size_t)B * npos);
-        if (pe != hipSuccess) {
-            hit->key.clear();
-            MST_HIP(pe);
-        }
-    }
-    const int n_items = (int)hit->items.size();
-    const size_t items_bytes = sizeof(WorkItem) * (size_t)n_items, sop_bytes = sizeof(int32_t) * (size_t)B * npos;
-    // this call's share of the list and of the blocks (everything, unless staged)
-    const int it0 = staged ? hit->stage_begin[stage] : 0, it1 = staged ? hit->stage_begin[stage + 1] : n_items;
-    const int blk0 = staged && stage > 0 ? cuts[stage - 1] : 0, blk1 = staged && stage < n_cuts ? cuts[stage] : B;
-    const bool first = !staged || stage == 0;
-
-    if (gent) {
-        // everything the graph's copy nodes will read, in page-locked memory the entry owns; then the capture begins
-        const size_t need_img = align_up(sizeof(DevLevels), 256) + align_up(sizeof(int64_t) * (size_t)B, 256) +
-                                align_up(items_bytes, 256) + align_up(sop_bytes, 256);
-        if (gent->image_cap < need_img) {
-            if (gent->image) (void)hipHostFree(gent->image);
-            gent->image = nullptr;
-            gent->image_cap = 0;
-            MST_HIP(hipHostMalloc((void **)&gent->image, need_img, hipHostMallocDefault));
-            gent->image_cap = need_img;
-        }
-        gent->image_used = 0;
-        if (!gent->done) MST_HIP(hipEventCreateWithFlags(&gent->done, hipEventDisableTiming));
-        const hipError_t ce = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-        if (ce != hipSuccess) {
-            (void)hipGetLastError();
-            gent = nullptr;            // this stream cannot be captured: ordinary launch
-        }
-    }
-    // host -> device copies of small tables: through the staging ring, or (capturing) from the graph entry's own image
-    auto up = [&](void *dst, const void *from, size_t bytes) -> hipError_t {
-        if (!gent) return mst::upload_small(dst, from, bytes, s);
-        char *p = gent->image + gent->image_used;
-        memcpy(p, from, bytes);
-        gent->image_used += align_up(bytes, 256);
-        return hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, s);
-    };
-    // Captured launches (small, latency-bound): the four tables lie side by side in the workspace -- the tile positions packed
-    // right behind the work list instead of at their worst-case offset -- in the order and alignment of the graph entry's
-    // page-locked image, so ONE copy node uploads them all (four nodes of ~5 us each stood in front of a 0.5 ms kernel).
-    if (gent) d_sop = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(d_items) + align_up(items_bytes, 256));
-    auto enqueue = [&]() -> int {
-        if (gent) {
-            char *img = gent->image;
-            const size_t o1 = align_up(sizeof(DevLevels), 256), o2 = o1 + align_up(sizeof(int64_t) * (size_t)B, 256),
-                         o3 = o2 + align_up(items_bytes, 256);
-            memcpy(img, &h, sizeof(h));
-            if (BAND) memcpy(img + o1, starts_host, sizeof(int64_t) * (size_t)B);
-            if (n_items) {
-                memcpy(img + o2, hit->items.data(), items_bytes);
-                memcpy(img + o3, hit->sop.data(), sop_bytes);
-            }
-            gent->image_used = n_items ? o3 + sop_bytes : o2;
-            MST_HIP(hipMemcpyAsync(d_lv, img, gent->image_used, hipMemcpyHostToDevice, s));
-        } else if (first) {
-            MST_HIP(up(d_lv, &h, sizeof(h)));
-        }
-        if (first) {
-            zero_counts_kernel<<<(B + 255) / 256, 256, 0, s>>>(found_count, BAND ? src.nz_count : nullptr, B);
-            MST_LAUNCH_CHECK();
-        }
-        if (BAND) {
-            if (!gent && first) MST_HIP(up(d_starts, starts_host, sizeof(int64_t) * B));
-            src.starts = d_starts;
-        }
-        if (n_items == 0) {          // no tile reaches the band: nothing is tested, nothing is found
-            if (first) {
-                fill_stats_kernel<<<(B * MST_MAX_TESTED + 255) / 256, 256, 0, s>>>(level_stats, B * MST_MAX_TESTED);
-                MST_LAUNCH_CHECK();
-            }
-            return MST_OK;
-        }
-        if (!gent) {
-            // the list's device copy (struct Cached): uploaded by the first launch that uses the list, read in place afterwards
-            int dev = 0;
-            MST_HIP(hipGetDevice(&dev));
-            const size_t off_sop = align_up(items_bytes, 256), need_dev = off_sop + sop_bytes;
-            if (hit->on_device && hit->ddev != dev) hit->on_device = false;
-            if (!hit->on_device) {
-                hit->wait_used();
-                if (hit->dcap < need_dev || hit->ddev != dev) {
-                    if (hit->dbuf) (void)hipFree(hit->dbuf);
-                    hit->dbuf = nullptr;
-                    hit->dcap = 0;
-                    if (hit->up) (void)hipEventDestroy(hit->up);
-                    if (hit->used) (void)hipEventDestroy(hit->used);
-                    hit->up = hit->used = nullptr;
-                    const size_t want = need_dev + need_dev / 4;
-                    MST_HIP(hipMalloc((void **)&hit->dbuf, want));
-                    hit->dcap = want;
-                    hit->ddev = dev;
-                    MST_HIP(hipEventCreateWithFlags(&hit->up, hipEventDisableTiming));
-                    MST_HIP(hipEventCreateWithFlags(&hit->used, hipEventDisableTiming));
-                }
-                MST_HIP(hit->pin_items.upload(hit->dbuf, s));
-                MST_HIP(hit->pin_sop.upload(hit->dbuf + off_sop, s));
-                MST_HIP(hipEventRecord(hit->up, s));
-                hit->on_device = true;
-            } else {
-                MST_HIP(hipStreamWaitEvent(s, hit->up, 0));          // uploaded on another stream, perhaps
-            }
-            d_items = reinterpret_cast<WorkItem *>(hit->dbuf);
-            d_sop = reinterpret_cast<int32_t *>(hit->dbuf + off_sop);
-        }
-        // (staged: this stage's run of the list; its items' slots in `partial` keep their positions in the WHOLE list, which is
-        //  what the position map refers to -- both pointers are simply advanced)
-        const WorkItem *li = d_items + it0;
-        double *lp = partial + (size_t)it0 * nt * 2;
-        const int ln = it1 - it0;
-        int lrc = MST_OK;
-        if (ln == 0)
-            ;
-        else if (fma)
-            lrc = launch_scale_space<TileDefaultFma, BAND>(c, nz, src, CH, d_lv, found, found_cap, found_count, lp, nt,
-                                                           skip_empty, li, ln, s);
-#ifdef MST_EXP_TILE7
-        else if (mr <= 7 && getenv("MST_EXP_USE_TILE7"))
-            lrc = launch_scale_space<TileOct1, BAND>(c, nz, src, CH, d_lv, found, found_cap, found_count, lp, nt,
-                                                     skip_empty, li, ln, s);
-#endif
-        else if (!wide)
-            lrc = launch_scale_space<TileDefault, BAND>(c, nz, src, CH, d_lv, found, found_cap, found_count, lp, nt,
-                                                        skip_empty, li, ln, s);
-        else
-            lrc = launch_scale_space<TileWide, BAND>(c, nz, src, CH, d_lv, found, found_cap, found_count, lp, nt,
-                                                     skip_empty, li, ln, s);
-        if (lrc != MST_OK) return lrc;
-        // a block's tiles are its own items and shared ones of the block before it: complete once its stage has run
-        if (blk1 > blk0) {
-            stats_reduce_kernel<<<dim3(nt, blk1 - blk0), 256, 0, s>>>(partial, npos, d_sop + (size_t)blk0 * npos, nt,
-                                                                    level_stats + (size_t)blk0 * MST_MAX_TESTED * 2);
-            MST_LAUNCH_CHECK();
-        }
-        if (!gent) {
-            MST_HIP(hipEventRecord(hit->used, s));
-            hit->used_pending = true;
-        }
-        return MST_OK;
-    };
+    static thread_local WorkListCache lists;
+    WorkList *wl = nullptr;
+    rc = lists.find_or_build(mr, starts_host, B, CH, BAND ? src.dpx : -1, BAND && !(flags & MST_FLAG_NO_SHARE), BAND && skip_empty,
+                             staged, cuts, n_cuts, &wl);
+    if (rc != MST_OK) return rc;
     if (!(flags & MST_FLAG_GRAPH))
         mst::note("scale_space plain B=%d CH=%d cap=%u flags=%d found=%p count=%p stats=%p ws=%p items=%d", B, CH, found_cap, flags,
-                  (const void *)found, (const void *)found_count, (const void *)level_stats, workspace, n_items);
-    rc = enqueue();
-    if (gent) {
-        hipGraph_t graph = nullptr;
-        const hipError_t ee = hipStreamEndCapture(s, &graph);        // always: the stream must leave capture mode
-        if (rc != MST_OK) {
-            if (graph) (void)hipGraphDestroy(graph);
-            gent->seen = 0;
-            return rc;
-        }
-        if (ee != hipSuccess || !graph) {
-            gent->seen = 0;
-            return mst::fail(MST_E_HIP, "%s: graph capture failed: %s", who, hipGetErrorString(ee));
-        }
-        hipError_t ie = hipGraphInstantiate(&gent->exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess) {
-            gent->exec = nullptr;
-            gent->seen = 0;
-            return mst::fail(MST_E_HIP, "%s: graph instantiation failed: %s", who, hipGetErrorString(ie));
-        }
-        MST_HIP(hipGraphLaunch(gent->exec, s));
-        MST_HIP(hipEventRecord(gent->done, s));
-    }
-    return rc;
+                  (const void *)found, (const void *)found_count, (const void *)level_stats, workspace, (int)wl->items.size());
+    const Launch a = {c, nz, src, starts_host, B, CH, mr, nt, skip_empty, fma, &h, found, found_cap, found_count, level_stats,
+                      static_cast<char *>(workspace), wl, cuts, n_cuts, stage};
+    if (sight != mst::ReplayCache::kCapture) return enqueue_launch<BAND>(a, nullptr, s);
+    // everything the graph's copy node will read goes into page-locked memory the entry owns: the tables, packed
+    const size_t image_bytes = Workspace(B, wl->items.size(), (size_t)B * wl->npos).partial;
+    return graphs.capture(who, s, image_bytes, [&](char *image) { return enqueue_launch<BAND>(a, image, s); });
 }
 
 extern "C" int mst_scale_space(const double *c, const uint8_t *nz, int32_t B, int32_t CH, const mst_levels *lv,

@@ -429,6 +429,33 @@ extern "C" uint64_t mst_found_summary_bytes(int32_t B) {
     return 16 + 8 * (uint64_t)((B + 1) / 2) * 2 + sizeof(double) * 2 * MST_MAX_TESTED * (uint64_t)B;
 }
 
+// MUSTACHE_GRAPH_DEBUG: what mst_found_finish saw when the flags word was not zero -- the summary image next to the device
+// buffers re-read, then the ring of notes about the recent graph decisions
+static void dump_nonfinite(const void *summary_host, const char *d_sum, const double *level_stats, const uint32_t *nz_count,
+                           int32_t B) {
+    std::vector<double> hs((size_t)B * MST_MAX_TESTED * 2);
+    std::vector<uint32_t> hn((size_t)B);
+    (void)hipMemcpy(hs.data(), level_stats, hs.size() * 8, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(hn.data(), nz_count, hn.size() * 4, hipMemcpyDeviceToHost);
+    unsigned devhdr[4] = {0, 0, 0, 0};
+    (void)hipMemcpy(devhdr, d_sum, 16, hipMemcpyDeviceToHost);
+    const unsigned *hh = static_cast<const unsigned *>(summary_host);
+    fprintf(stderr, "[nonfinite] header host %#x %#x %#x %#x | device now %#x %#x %#x %#x\n", hh[0], hh[1], hh[2], hh[3], devhdr[0],
+            devhdr[1], devhdr[2], devhdr[3]);
+    const char *sh = static_cast<const char *>(summary_host);
+    const size_t cw = 8 * (size_t)((B + 1) / 2);
+    const uint32_t *s_cnt = reinterpret_cast<const uint32_t *>(sh + 16), *s_nz = reinterpret_cast<const uint32_t *>(sh + 16 + cw);
+    const double *s_fit = reinterpret_cast<const double *>(sh + 16 + 2 * cw);
+    for (int b = 0; b < B; ++b) {
+        fprintf(stderr, "[nonfinite] block %d: summary count %u nz %u | memory nz %u\n", b, s_cnt[b], s_nz[b], hn[(size_t)b]);
+        for (int t = 0; t < MST_MAX_TESTED; ++t)
+            fprintf(stderr, "[nonfinite]   level %d: summary loc %g scale %g | memory min %g sum %g\n", t,
+                    s_fit[((size_t)b * MST_MAX_TESTED + t) * 2], s_fit[((size_t)b * MST_MAX_TESTED + t) * 2 + 1],
+                    hs[((size_t)b * MST_MAX_TESTED + t) * 2], hs[((size_t)b * MST_MAX_TESTED + t) * 2 + 1]);
+    }
+    mst::dump_notes();
+}
+
 extern "C" int mst_found_finish(const mst_found *found, uint32_t found_cap, const uint32_t *found_count,
                                 const uint32_t *nz_count, const double *level_stats, int32_t B, int32_t n_tested, double *pval,
                                 double *fit, uint32_t pack_pitch, int32_t *pix_out, uint8_t *lvl_out, double *pv_out,
@@ -471,33 +498,9 @@ extern "C" int mst_found_finish(const mst_found *found, uint32_t found_cap, cons
     // Opt-in because it costs large pipelined launches: with the finish of one group replayed as a graph next to the fused
     // kernel of the next group, that kernel ran 3 % slower (measured A/B on one box: 17.76 -> 17.19 Gpix/s).  Per host thread;
     // not on the legacy default stream (it cannot be captured); not in PROFILE builds.
-    bool done = false;
-#ifndef MST_PROFILE
-    struct FinishGraph {
-        std::vector<int64_t> sig;
-        hipGraphExec_t exec = nullptr;
-        hipEvent_t ev = nullptr;
-        int seen = 0;
-        unsigned long long stamp = 0;
-        void drop() {
-            if (exec) {
-                if (ev) (void)hipEventSynchronize(ev);
-                (void)hipGraphExecDestroy(exec);
-                exec = nullptr;
-            }
-        }
-        ~FinishGraph() {
-            drop();
-            if (ev) (void)hipEventDestroy(ev);
-        }
-    };
-    static thread_local FinishGraph fcache[6];
-    static thread_local unsigned long long fstamp = 0;
-    static const bool graphs_off = [] {
-        const char *e = getenv("MUSTACHE_NO_GRAPHS");        // diagnostic switch: 1 = no graphs at all, "finish" = none here
-        return e && *e && *e != '0' && *e != 'l';
-    }();
-    if ((flags & MST_FLAG_GRAPH) && s != nullptr && !graphs_off) {
+    static thread_local mst::ReplayCache graphs(6, "finish");
+    int erc = MST_OK;
+    if (graphs.usable(flags, s)) {
         int dev = 0;
         MST_HIP(hipGetDevice(&dev));
         std::vector<int64_t> sig;
@@ -508,90 +511,26 @@ extern "C" int mst_found_finish(const mst_found *found, uint32_t found_cap, cons
             sig.push_back((int64_t)(intptr_t)p);
         for (int64_t v : {(int64_t)found_cap, (int64_t)B, (int64_t)n_tested, (int64_t)pack_pitch, (int64_t)dev})
             sig.push_back(v);
-        FinishGraph *g = nullptr;
-        for (FinishGraph &e : fcache)
-            if (e.seen && e.sig == sig) g = &e;
+        const mst::ReplayCache::Sight sight = graphs.look(sig);
         mst::note("found_finish graph B=%d cap=%u pitch=%u found=%p count=%p nz=%p stats=%p fit=%p scratch=%p host=%p -> %s", B, found_cap,
                   pack_pitch, (const void *)found, (const void *)found_count, (const void *)nz_count, (const void *)level_stats,
-                  (const void *)fit, scratch_dev, summary_host, g && g->exec ? "REPLAY" : (g ? "CAPTURE" : "first sight"));
-        if (g && g->exec) {
-            g->stamp = ++fstamp;
-            MST_HIP(hipGraphLaunch(g->exec, s));
-            MST_HIP(hipEventRecord(g->ev, s));
-            done = true;
-        } else if (!g) {
-            g = &fcache[0];
-            for (FinishGraph &e : fcache)
-                if (e.stamp < g->stamp) g = &e;
-            g->drop();
-            g->sig = sig;
-            g->seen = 1;
-            g->stamp = ++fstamp;
-        } else {
-            g->stamp = ++fstamp;
-            if (!g->ev) MST_HIP(hipEventCreateWithFlags(&g->ev, hipEventDisableTiming));
-            if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int erc = enqueue();
-                hipGraph_t graph = nullptr;
-                const hipError_t ee = hipStreamEndCapture(s, &graph);
-                if (erc != MST_OK || ee != hipSuccess || !graph) {
-                    if (graph) (void)hipGraphDestroy(graph);
-                    g->seen = 0;
-                    if (erc != MST_OK) return erc;
-                    return mst::fail(MST_E_HIP, "mst_found_finish: graph capture failed: %s", hipGetErrorString(ee));
-                }
-                const hipError_t ie = hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
-                if (ie != hipSuccess) {
-                    g->exec = nullptr;
-                    g->seen = 0;
-                    return mst::fail(MST_E_HIP, "mst_found_finish: graph instantiation failed: %s", hipGetErrorString(ie));
-                }
-                MST_HIP(hipGraphLaunch(g->exec, s));
-                MST_HIP(hipEventRecord(g->ev, s));
-                done = true;
-            } else {
-                (void)hipGetLastError();
-                g->seen = 0;
-            }
-        }
-    }
-#endif
-    if (!done) {
+                  (const void *)fit, scratch_dev, summary_host, mst::ReplayCache::name(sight));
+        erc = sight == mst::ReplayCache::kReplay    ? graphs.replay(s)
+              : sight == mst::ReplayCache::kCapture ? graphs.capture("mst_found_finish", s, 0, [&](char *) { return enqueue(); })
+                                                    : enqueue();
+    } else {
         if (!(flags & MST_FLAG_GRAPH))
             mst::note("found_finish plain B=%d cap=%u pitch=%u found=%p count=%p nz=%p stats=%p scratch=%p", B, found_cap, pack_pitch,
                       (const void *)found, (const void *)found_count, (const void *)nz_count, (const void *)level_stats, scratch_dev);
-        const int erc = enqueue();
-        if (erc != MST_OK) return erc;
+        erc = enqueue();
     }
+    if (erc != MST_OK) return erc;
     if (flags & MST_FLAG_NO_WAIT) return MST_OK;             // the caller synchronises and asks mst_found_summary_status
     MST_HIP(hipStreamSynchronize(s));
     int dflags = 0;
     memcpy(&dflags, summary_host, sizeof(int));
     mst::note("found_finish summary flags=%d", dflags);
-    if (dflags && getenv("MUSTACHE_GRAPH_DEBUG")) {
-        std::vector<double> hs((size_t)B * MST_MAX_TESTED * 2);
-        std::vector<uint32_t> hn((size_t)B);
-        (void)hipMemcpy(hs.data(), level_stats, hs.size() * 8, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(hn.data(), nz_count, hn.size() * 4, hipMemcpyDeviceToHost);
-        unsigned devhdr[4] = {0, 0, 0, 0};
-        (void)hipMemcpy(devhdr, d_sum, 16, hipMemcpyDeviceToHost);
-        const unsigned *hh = static_cast<const unsigned *>(summary_host);
-        fprintf(stderr, "[nonfinite] header host %#x %#x %#x %#x | device now %#x %#x %#x %#x\n", hh[0], hh[1], hh[2], hh[3], devhdr[0],
-                devhdr[1], devhdr[2], devhdr[3]);
-        const char *sh = static_cast<const char *>(summary_host);
-        const size_t cw = 8 * (size_t)((B + 1) / 2);
-        const uint32_t *s_cnt = reinterpret_cast<const uint32_t *>(sh + 16), *s_nz = reinterpret_cast<const uint32_t *>(sh + 16 + cw);
-        const double *s_fit = reinterpret_cast<const double *>(sh + 16 + 2 * cw);
-        for (int b = 0; b < B; ++b) {
-            fprintf(stderr, "[nonfinite] block %d: summary count %u nz %u | memory nz %u\n", b, s_cnt[b], s_nz[b], hn[(size_t)b]);
-            for (int t = 0; t < MST_MAX_TESTED; ++t)
-                fprintf(stderr, "[nonfinite]   level %d: summary loc %g scale %g | memory min %g sum %g\n", t,
-                        s_fit[((size_t)b * MST_MAX_TESTED + t) * 2], s_fit[((size_t)b * MST_MAX_TESTED + t) * 2 + 1],
-                        hs[((size_t)b * MST_MAX_TESTED + t) * 2], hs[((size_t)b * MST_MAX_TESTED + t) * 2 + 1]);
-        }
-        mst::dump_notes();
-    }
+    if (dflags && getenv("MUSTACHE_GRAPH_DEBUG")) dump_nonfinite(summary_host, d_sum, level_stats, nz_count, B);
     if (dflags & 1)
         return mst::fail(MST_E_OVERFLOW, "found-pixel capacity %u exceeded in at least one block", found_cap);
 #ifdef MST_PROFILE

@@ -984,6 +984,63 @@ def test_graph_replay_gives_identical_records():
     same(step(start), want[1], all_blocks)               # and back to the first graph
 
 
+def test_one_work_list_on_two_streams_then_larger_lists():
+    """The launch-per-group path alternates two streams.  The same block list (same origins: the same cached work list and
+    the same device copy of it) is launched on two side streams back to back without a host wait between them; launches of
+    different, larger block lists follow at once on the SECOND stream -- more of them than the library keeps lists, so the
+    first list's entry is replaced and its device copy overwritten or regrown while the first stream, which the second is
+    not ordered behind, may still read it.  Found counts, tested-pixel counts and found records of every launch are those of
+    a plain single-stream run of its list."""
+    import torch
+    from mustache_amd import launch
+    from mustache_amd.normalize import band_from_host_coo, normalize_band
+    from mustache_amd.pipeline import ChromosomePipeline, block_tiling
+    from mustache_amd.synth import synth_coo
+    n, dpx, res = 9630, 400, 5000
+    x, y, v = synth_coo(n, dpx, depth=150.0, seed=23)
+    pipe = ChromosomePipeline(OCT)
+    eng = pipe.engine
+    band, _, _ = normalize_band(band_from_host_coo(x, y, v, n, dpx, pipe.device), n, dpx, res)
+    CH, start, end = block_tiling(n, dpx)
+    start = list(start)
+    assert len(start) >= 6
+    word = launch.flags(eng, True, False)
+
+    def run(starts):
+        return launch.ss_launch(eng, word, band_src=(band, n, dpx, starts, CH))
+
+    def grab(L):
+        count, nzc, found = L.count.cpu().numpy(), L.nzc.cpu().numpy(), L.found.cpu().numpy()
+        recs = []
+        for b in range(L.B):
+            r = found[b, :count[b]]
+            recs.append(r[np.lexsort((r[:, 1], r[:, 0]))])
+        return count, nzc, recs
+
+    first = start[:3]
+    larger = [start, start[1:], start[:-1], start[2:]]       # four other lists: the library keeps four
+    cur = torch.cuda.current_stream(pipe.device)
+    want = []
+    for st in [first] + larger:                              # plain runs, one at a time
+        L = run(st)
+        cur.synchronize()
+        want.append(grab(L))
+    assert want[0][0].sum() > 300 and max(w[0].max() for w in want) < launch.found_cap_for(eng, CH)
+    s1, s2 = torch.cuda.Stream(pipe.device), torch.cuda.Stream(pipe.device)
+    with torch.cuda.stream(s1):
+        L1 = run(first)
+    with torch.cuda.stream(s2):
+        L2 = run(first)
+        later = [run(st) for st in larger]
+    s1.synchronize()
+    s2.synchronize()
+    for L, exp in zip([L1, L2] + later, [want[0]] + want):
+        count, nzc, recs = grab(L)
+        assert np.array_equal(count, exp[0]) and np.array_equal(nzc, exp[1])
+        for b in range(L.B):
+            assert np.array_equal(recs[b], exp[2][b]), b
+
+
 def test_run_band_in_stages_equals_a_launch_per_group():
     """pipeline.run_band on a chromosome of 40 blocks: its groups of 16 blocks are the stages of ONE launch (tile sharing
     across the groups, the tail of one group under the next stage's kernel) -- the loops are those of the launch-per-group form
