@@ -20,6 +20,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pair_reference as pr      # noqa: E402
+import radius_sweep as rs        # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -49,6 +50,13 @@ def test_octave_lists_cover_every_tile():
         tiles.setdefault(_tile_of(_diff_radius(octs)), []).append(octs)
     print("tile per octave list:", {t: v for t, v in sorted(tiles.items())})
     assert set(tiles) == set(TILE_RADII), tiles
+    # and with the sweep lists every radius each tile is built for: one diff_blur<T, R> per (tile, radius) pair
+    assert tuple(OCTAVE_LISTS) == tuple(rs.DIFF_BASE_LISTS)
+    for octs in OCTAVE_LISTS:
+        assert rs.diff_tile(rs.DiffLevels(octs)) == _tile_of(_diff_radius(octs)), octs
+    wit = rs.diff_witnesses()
+    print("witness of every (tile, radius):", {k: v for k, v in sorted(wit.items())})
+    assert sorted(wit) == [(t, r) for t in sorted(TILE_RADII) for r in range(1, t + 1)] and len(wit) == 50
 
 
 # ---- A: mst_diff_dog_band -----------------------------------------------------------------------------------------------
@@ -95,7 +103,7 @@ def _block(c, n, start, CH):
     return cb
 
 
-def _reference(cb1, cb2, dpx, octaves):
+def _reference(cb1, cb2, dpx, octaves, lt=None):
     """diff_mustache.py:262-276 then D = G(sigma_2) - G(sigma_3) per octave (:315-336), float64 SciPy"""
     import oracle
     from mustache_amd.levels import LevelTable
@@ -108,19 +116,21 @@ def _reference(cb1, cb2, dpx, octaves):
         f[off >= dpx + 1] = 2
     cd = np.zeros((CH, CH))
     cd[nzb] = f1[nzb] - f2[nzb]
-    lt = LevelTable(octaves)
+    lt = LevelTable(octaves) if lt is None else lt
     lpo = lt.levels_per_octave
     D = np.stack([oracle.blur_scipy(cd, lt.sigma[o * lpo + 1], lt.truncate[o * lpo + 1]) -
                   oracle.blur_scipy(cd, lt.sigma[o * lpo + 2], lt.truncate[o * lpo + 2]) for o in range(len(octaves))])
     return cd, nzb, D
 
 
-def _launch_band(eng, bands, n, dpx, starts, CH):
+def _launch_band(eng, bands, n, dpx, starts, CH, lt=None):
+    """lt: a level table of its own (radius_sweep.DiffLevels) instead of the engine's"""
     import torch
     from mustache_amd import _lib
     from mustache_amd._lib import ptr as _ptr, stream as _stream
-    B, n_oct = len(starts), len(eng.levels.octave_values)
-    lv = ctypes.byref(eng._lv_struct)
+    B, n_oct = len(starts), len((eng.levels if lt is None else lt).octave_values)
+    lv_struct = eng._lv_struct if lt is None else lt.as_struct()
+    lv = ctypes.byref(lv_struct)
     dog = torch.full((n_oct, B, CH, CH), float("nan"), dtype=torch.float64, device="cuda")
     fit = torch.full((n_oct, B, 2), float("nan"), dtype=torch.float64, device="cuda")
     cnt = torch.full((B,), -1, dtype=torch.int32, device="cuda")
@@ -129,7 +139,7 @@ def _launch_band(eng, bands, n, dpx, starts, CH):
     st = (ctypes.c_int64 * B)(*starts)
     _lib.check(eng.lib.mst_diff_dog_band(_ptr(bands[0]), _ptr(bands[1]), n, dpx, st, B, CH, lv, _ptr(dog), _ptr(fit), _ptr(cnt),
                                          _ptr(ws), wsb, _stream()))
-    return dog, fit, cnt, (ws, st)
+    return dog, fit, cnt, (ws, st, lv_struct)
 
 
 def _check_fit(got, vals, what):
@@ -144,14 +154,14 @@ def _check_fit(got, vals, what):
     assert el <= pr.LOC_BOUND and es <= pr.SCALE_BOUND, (what, got, (loc_x, scale_x), el, es)
 
 
-def _check_case(eng, octaves, case, results):
+def _check_case(eng, octaves, case, results, lt=None):
     """results = (dog, fit, cnt) of mst_diff_dog_band for case = (c1, c2, n, dpx, starts, CH)"""
     c1, c2, n, dpx, starts, CH = case
     dog, fit, cnt = (t.cpu().numpy() for t in results)
     off = np.arange(CH)[None, :] - np.arange(CH)[:, None]
     addr = (off >= 4) & (off <= dpx + 1)          # every pixel a found record can address
     for b, s in enumerate(starts):
-        cd, nzb, D = _reference(_block(c1, n, s, CH), _block(c2, n, s, CH), dpx, octaves)
+        cd, nzb, D = _reference(_block(c1, n, s, CH), _block(c2, n, s, CH), dpx, octaves, lt)
         what = (octaves, n, dpx, CH, s)
         assert int(cnt[b]) == int(nzb.sum()), what
         for o in range(len(octaves)):
@@ -162,7 +172,7 @@ def _check_case(eng, octaves, case, results):
     return cnt
 
 
-def _dense_route(eng, case, octaves, band_dog):
+def _dense_route(eng, case, octaves, band_dog, lt=None):
     """mst_diff_image -> mst_gauss_blur at sigma_2 / sigma_3 -> mst_masked_normfit on the same blocks: the same difference
     image, G_2 - G_3 bit-identical to the band route's DoG on the addressable pixels, norm.fit within the same bounds"""
     import torch
@@ -178,7 +188,7 @@ def _dense_route(eng, case, octaves, band_dog):
     nzbc = torch.full((B,), -1, dtype=torch.int32, device="cuda")
     _lib.check(eng.lib.mst_diff_image(_ptr(c[:B]), _ptr(c[B:]), _ptr(nz[:B]), _ptr(nz[B:]), B, CH, _ptr(cd), _ptr(nzb), _ptr(nzbc),
                                       _stream()))
-    lt = eng.levels
+    lt = eng.levels if lt is None else lt
     lpo = lt.levels_per_octave
     ws = torch.empty(2048 * B, dtype=torch.uint8, device="cuda")
     off = np.arange(CH)[None, :] - np.arange(CH)[:, None]
@@ -192,7 +202,7 @@ def _dense_route(eng, case, octaves, band_dog):
         d = (g2 - g3).cpu().numpy()
         fit = fit.cpu().numpy()
         for b, s in enumerate(starts):
-            ref_cd, ref_nzb, D = _reference(raw[b], raw[B + b], dpx, octaves)
+            ref_cd, ref_nzb, D = _reference(raw[b], raw[B + b], dpx, octaves, lt)
             if o == 0:
                 assert np.array_equal(nzb[b].cpu().numpy().astype(bool), ref_nzb)
                 assert int(nzbc[b]) == int(ref_nzb.sum())
@@ -241,6 +251,30 @@ def test_diff_dog_band_every_tile_vs_scipy(octaves, cases):
         _dense_route(eng, case, octaves, dog.cpu().numpy())
     assert masked > 10000
     print("worst errors so far (after %s)" % octaves, WORST)
+
+
+@pytest.mark.parametrize("name", list(rs.DIFF_SWEEP))
+def test_diff_dog_band_every_radius_vs_scipy(name, cases):
+    """The sweep lists (radius_sweep.DIFF_SWEEP) through the checks of the test above: with them every diff_blur<T, R>,
+    R = 1 .. RMAX of DiffTile8 / 14 / 28, has run and its DoG is bit-identical to SciPy's.  Their level tables go to the
+    entry point directly (DiffLevels): those of the widest tile hold sigma-loop levels wider than radius 28, which the
+    package refuses.  Cases: the full-size block, the block of 20 x 20 (smaller than the wider radii), the three blocks that continue
+    each other."""
+    from mustache_amd.engine import ScaleSpaceEngine
+    octaves = rs.DIFF_SWEEP[name]
+    lt = rs.DiffLevels(octaves)
+    eng = ScaleSpaceEngine([1.6, 3.2])                 # the library, the prologue and mst_gauss_blur; not its levels
+    masked = 0
+    assert len(cases[6][4]) == 3 and cases[4][5] == 20
+    for case in (cases[0], cases[4], cases[6]):
+        c1, c2, n, dpx, starts, CH = case
+        bands = [_band(c1, n, dpx), _band(c2, n, dpx)]
+        dog, fit, cnt, keep = _launch_band(eng, bands, n, dpx, starts, CH, lt)
+        cnt = _check_case(eng, octaves, case, (dog, fit, cnt), lt)
+        masked += int(cnt.sum())
+        _dense_route(eng, case, octaves, dog.cpu().numpy(), lt)
+    assert masked > 10000
+    print("diff_blur instantiations run by %s: tile %d, radii %s" % (name, rs.diff_tile(lt), sorted(set(lt.diff_radii()))))
 
 
 def test_diff_dog_band_back_to_back_calls(cases):
