@@ -405,7 +405,19 @@ MST_STABLE uint64_t mst_diff_dog_workspace_bytes(int32_t B, int32_t CH, const ms
 MST_STABLE int mst_diff_dog_band(const double *band1, const double *band2, int64_t n, int32_t dpx, const int64_t *starts, int32_t B,
                       int32_t CH, const mst_levels *lv, double *dog, double *fit, uint32_t *mask_count, void *workspace,
                       uint64_t workspace_bytes, void *stream);
-/* mst_pair_pvalues with x read from dog[octave][b][pixel] (the output of mst_diff_dog_band). */
+/* ---- two-sample path, tile-direct (the inter-chromosomal two-sample caller, mustache_amd/diff_trans.py) -----------------------
+ * The same kernel with a dense source.  c1, c2: dev [P][C][C] f64, the two samples' tiles as mst_trans_scatter_tiles left them
+ * (0 = no record).  For tile pair p the difference image
+ *     cd = c1 - c2 where both are non-zero, else 0        (no triangle mask, no fills)
+ * is staged with its reflect halo straight from the two tiles, blurred at sigma_2 and sigma_3 of every octave and only
+ * dog[oct][p] = G_2 - G_3 (dev [n_octaves][P][C][C], EVERY pixel written: all tiles are launched), fit[oct][p] = {loc, scale} of
+ * norm.fit over the pixels set in both samples (dev [n_octaves][P][2]; NaN when there is none) and mask_count[p] = their
+ * number are written.  G_2 - G_3 is bit-identical to mst_diff_image + mst_gauss_blur on the same tiles.  1 <= P <= 65535;
+ * blur radii of sigma_2 / sigma_3 in [1, 28]; C may be smaller than the blur halo.  lv: the sigma loop's level table. */
+MST_STABLE uint64_t mst_diff_dog_tiles_workspace_bytes(int32_t P, int32_t C, const mst_levels *lv);
+MST_STABLE int mst_diff_dog_tiles(const double *c1, const double *c2, int32_t P, int32_t C, const mst_levels *lv, double *dog,
+                       double *fit, uint32_t *mask_count, void *workspace, uint64_t workspace_bytes, void *stream);
+/* mst_pair_pvalues with x read from dog[octave][b][pixel] (the output of mst_diff_dog_band / mst_diff_dog_tiles). */
 MST_STABLE int mst_pair_pvalues_dog(const mst_found *found, uint32_t found_cap, const uint32_t *found_count, const double *dog,
                          const double *fit, int32_t B, int32_t CH, int32_t n_octaves, int32_t tested_per_octave,
                          int32_t sample_offset, double *ppair, void *stream);

@@ -14,6 +14,9 @@
 // tiles straight out of their bands, forms the difference image in LDS, runs the SAME LDS-tiled separable passes as the fused
 // sigma-stack kernel (mst_fir.h: SciPy's tap order, no FMA -> G_2, G_3 bit-identical to gaussian_filter) and writes only
 // D_2 per octave plus the masked sums of norm.fit: no dense blocks, no difference image, no G_2 / G_3 in HBM.
+// Tile-direct (what the inter-chromosomal two-sample caller uses, diff_trans.py): mst_diff_dog_tiles is the SAME kernel with a
+// dense source -- the two samples' tiles [P][C][C] stand in HBM already (the sigma loop reads them), there is no band, so the
+// staging step reads them as they lie (nz_s = c_s != 0, no triangle mask, no fills) and every tile is launched.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -155,17 +158,157 @@ __device__ __forceinline__ void diff_blur_dispatch(int r, const double *ct, doub
 #undef MST_CASE
 }
 
+// Where a workgroup's difference image comes from.  A source stages the (RGR + 2 RMAX) x (RGC + 2 RMAX) window at (Y0, X0) of
+// block pair b with its reflect halo, transposed (ct[col][row]), writes the doubly tested mask of the tile's own pixels to nzb
+// (0 outside the block) and names the tile of a launch slot; everything behind the staging is the kernel's, for every source.
+
+// The two samples' bands (diff_mustache.py:262-276):  tested_s = raw_s != 0 and off >= 4;  filled_s = 2 where off <= 4 or
+// off >= dpx + 1;  cd = filled_1 - filled_2 where tested_1 and tested_2, else 0.  A slot is an entry of the host's list of
+// tiles whose pixels can reach the doubly tested band 4 <= col - row <= dpx + 1: the others hold no pixel of either mask
+// (their sums are zero) and no found pixel ever reads their DoG values.
+struct BandSource {
+    const double *band1, *band2;
+    int64_t n;
+    int dpx;
+    const int64_t *starts;
+    const int32_t *tile_list;
+
+    __device__ __forceinline__ int tile_of(int slot) const { return tile_list[slot]; }
+
+    template <class T>
+    __device__ __forceinline__ void stage(int b, int Y0, int X0, int CH, double *ct, uint8_t *nzb, int tid) const {
+        constexpr int RGR = T::RGR, RGC = T::RGC, RMAX = T::RMAX;
+        const int64_t start = starts[b];
+        const int dpx = this->dpx;
+        const int64_t n = this->n;
+        const bool inner = Y0 >= 0 && X0 >= 0 && Y0 + T::CTR <= CH && X0 + T::CTC <= CH;
+        auto pixel = [&](double r1, double r2, int off, double &val, bool &both) {
+            const bool fill = off <= 4 || off >= dpx + 1;
+            both = r1 != 0.0 && r2 != 0.0 && off >= 4;
+            val = both ? ((fill ? 2.0 : r1) - (fill ? 2.0 : r2)) : 0.0;
+        };
+        if (inner) {
+            constexpr int ND = T::CTR + T::CTC - 1;
+            constexpr int PER = (T::CTR + 63) / 64;
+            constexpr int U = 10 / PER > 0 ? 10 / PER : 1;   // diagonals in flight per wave (two loads each)
+            for (int q0 = tid >> 6; q0 < ND; q0 += T::NW * U) {
+                double a1[U][PER], a2[U][PER];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int q = q0 + u * T::NW;
+                    const int dd = q - (T::CTR - 1);
+                    const int off = X0 - Y0 + dd;
+                    const int i_lo = dd < 0 ? -dd : 0;
+                    const int i_hi = T::CTC - dd < T::CTR ? T::CTC - dd : T::CTR;
+                    const bool in_band = q < ND && off >= 0 && off <= dpx + 1;
+                    const int64_t at = (int64_t)(in_band ? off : 0) * n + start + Y0;
+#pragma unroll
+                    for (int e = 0; e < PER; ++e) {
+                        const int i = i_lo + (tid & 63) + 64 * e;
+                        const bool ok = in_band && i < i_hi && start + X0 + i + dd < n;
+                        a1[u][e] = ok ? band1[at + i] : 0.0;
+                        a2[u][e] = ok ? band2[at + i] : 0.0;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int q = q0 + u * T::NW;
+                    if (q >= ND) break;
+                    const int dd = q - (T::CTR - 1);
+                    const int off = X0 - Y0 + dd;
+                    const int i_lo = dd < 0 ? -dd : 0;
+                    const int i_hi = T::CTC - dd < T::CTR ? T::CTC - dd : T::CTR;
+#pragma unroll
+                    for (int e = 0; e < PER; ++e) {
+                        const int i = i_lo + (tid & 63) + 64 * e;
+                        if (i >= i_hi) continue;
+                        const int j = i + dd;
+                        double val;
+                        bool both;
+                        pixel(a1[u][e], a2[u][e], off, val, both);
+                        ct[j * T::CTP + i] = val;
+                        const int ri = i - RMAX, rj = j - RMAX;
+                        if (ri >= 0 && ri < RGR && rj >= 0 && rj < RGC) nzb[ri * RGC + rj] = both ? 1 : 0;
+                    }
+                }
+            }
+        } else {
+            for (int idx = tid; idx < T::CTR * T::CTC; idx += T::NT) {
+                const int i = idx / T::CTC, j = idx - i * T::CTC;
+                const int uy = Y0 + i, ux = X0 + j;
+                const int by = reflect_idx(uy, CH), bx = reflect_idx(ux, CH);
+                const int off = bx - by;
+                double r1 = 0.0, r2 = 0.0;
+                if (off >= 0 && off <= dpx + 1 && start + bx < n) {
+                    r1 = band1[(int64_t)off * n + start + by];
+                    r2 = band2[(int64_t)off * n + start + by];
+                }
+                double val;
+                bool both;
+                pixel(r1, r2, off, val, both);
+                ct[j * T::CTP + i] = val;
+                const int ri = i - RMAX, rj = j - RMAX;
+                if (ri >= 0 && ri < RGR && rj >= 0 && rj < RGC) {
+                    const bool inside = uy >= 0 && uy < CH && ux >= 0 && ux < CH;
+                    nzb[ri * RGC + rj] = (inside && both) ? 1 : 0;
+                }
+            }
+        }
+    }
+};
+
+// Two dense tile stacks [P][C][C] (an inter-chromosomal tile pair has no band):  nz_s = c_s != 0 over the whole tile, no
+// triangle mask, no fills;  cd = c_1 - c_2 where both are set, else 0.  Every tile is a slot.
+struct DenseSource {
+    const double *c1, *c2;
+
+    __device__ __forceinline__ int tile_of(int slot) const { return slot; }
+
+    template <class T>
+    __device__ __forceinline__ void stage(int b, int Y0, int X0, int CH, double *ct, uint8_t *nzb, int tid) const {
+        constexpr int RGR = T::RGR, RGC = T::RGC, RMAX = T::RMAX;
+        constexpr int N = T::CTR * T::CTC;
+        constexpr int U = 4;                             // pixels in flight per thread (two loads each)
+        const double *p1 = c1 + (int64_t)b * CH * CH, *p2 = c2 + (int64_t)b * CH * CH;
+        const bool inner = Y0 >= 0 && X0 >= 0 && Y0 + T::CTR <= CH && X0 + T::CTC <= CH;
+        // consecutive threads read consecutive columns of a row (coalesced); the transposed store is two-way conflicted
+        for (int i0 = tid; i0 < N; i0 += T::NT * U) {
+            double a1[U], a2[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int idx = i0 + u * T::NT;
+                const int i = idx / T::CTC, j = idx - i * T::CTC;
+                // a window that leaves the block reads SciPy's 'reflect' continuation (any distance: C may be below the halo)
+                const int by = inner ? Y0 + i : reflect_idx(Y0 + i, CH), bx = inner ? X0 + j : reflect_idx(X0 + j, CH);
+                const int64_t at = (int64_t)by * CH + bx;
+                a1[u] = idx < N ? p1[at] : 0.0;
+                a2[u] = idx < N ? p2[at] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int idx = i0 + u * T::NT;
+                if (idx >= N) break;
+                const int i = idx / T::CTC, j = idx - i * T::CTC;
+                const bool both = a1[u] != 0.0 && a2[u] != 0.0;
+                ct[j * T::CTP + i] = both ? a1[u] - a2[u] : 0.0;
+                const int ri = i - RMAX, rj = j - RMAX;
+                if (ri >= 0 && ri < RGR && rj >= 0 && rj < RGC) {
+                    const int uy = Y0 + i, ux = X0 + j;
+                    nzb[ri * RGC + rj] = (uy < CH && ux < CH && both) ? 1 : 0;      // (uy, ux >= 0 on a tile's own pixels)
+                }
+            }
+        }
+    }
+};
+
 // One workgroup = one RGR x RGC tile of one block pair (no ring: nothing here looks at neighbours of the result).
-//   difference image (diff_mustache.py:262-276):  tested_s = raw_s != 0 and off >= 4;  filled_s = 2 where off <= 4 or off >= dpx+1
-//                                                 cd = filled_1 - filled_2 where tested_1 and tested_2, else 0
+//   difference image: the source's (BandSource / DenseSource)
 //   per octave:  D = gaussian_filter(cd, sigma_2) - gaussian_filter(cd, sigma_3)      (:315-336)
-//   out: D [oct][b][CH][CH];  partial[b][tile][oct] = {sum of D, sum of D^2} over the pixels tested in both samples (norm.fit, :371)
-template <class T>
+//   out: D [oct][b][CH][CH];  partial[b][slot][oct] = {sum of D, sum of D^2} over the pixels tested in both samples (norm.fit, :371)
+template <class T, class Src>
 __global__ void __launch_bounds__(T::NT)
-diff_dog_kernel(const double *__restrict__ band1, const double *__restrict__ band2, int64_t n, int dpx,
-                const int64_t *__restrict__ starts, int CH, int B, const DiffLevels *__restrict__ lv,
-                double *__restrict__ dog, double *__restrict__ partial, uint32_t *__restrict__ mask_count, int tiles_x,
-                int n_slots, const int32_t *__restrict__ tile_list) {
+diff_dog_kernel(const Src src, int CH, int B, const DiffLevels *__restrict__ lv, double *__restrict__ dog,
+                double *__restrict__ partial, uint32_t *__restrict__ mask_count, int tiles_x, int n_slots) {
     constexpr int K = T::K, RGR = T::RGR, RGC = T::RGC, RMAX = T::RMAX;
     extern __shared__ __align__(16) double lds[];
     double *ct = lds;
@@ -173,93 +316,17 @@ diff_dog_kernel(const double *__restrict__ band1, const double *__restrict__ ban
     double *red = vb + T::VB_ELEMS;                     // 2 * NT doubles: the masked sums' reduction
     const int tid = threadIdx.x, b = blockIdx.y;
     const int per_xcd = gridDim.x >> 3;                 // XCD-aware order, as in the fused kernel
-    // a slot is an entry of the host's list of tiles whose pixels can reach the doubly tested band 4 <= col - row <= dpx + 1:
-    // the others hold no pixel of either mask (their sums are zero) and no found pixel ever reads their DoG values
     const int slot = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     if (slot >= n_slots) return;
-    const int tile = tile_list[slot];
+    const int tile = src.tile_of(slot);
     const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const int y0 = ty * RGR, x0 = tx * RGC;
     const int rr = tid % RGR, cg = tid / RGR;
     const int gy = y0 + rr;
-    const int64_t start = starts[b];
 
     // ---- stage the difference image with its reflect halo, transposed (ct[col][row]); the mask of the region goes to vb
     uint8_t *nzb = reinterpret_cast<uint8_t *>(vb);
-    const int Y0 = y0 - RMAX, X0 = x0 - RMAX;
-    const bool inner = Y0 >= 0 && X0 >= 0 && Y0 + T::CTR <= CH && X0 + T::CTC <= CH;
-    auto pixel = [&](double r1, double r2, int off, double &val, bool &both) {
-        const bool fill = off <= 4 || off >= dpx + 1;
-        both = r1 != 0.0 && r2 != 0.0 && off >= 4;
-        val = both ? ((fill ? 2.0 : r1) - (fill ? 2.0 : r2)) : 0.0;
-    };
-    if (inner) {
-        constexpr int ND = T::CTR + T::CTC - 1;
-        constexpr int PER = (T::CTR + 63) / 64;
-        constexpr int U = 10 / PER > 0 ? 10 / PER : 1;   // diagonals in flight per wave (two loads each)
-        for (int q0 = tid >> 6; q0 < ND; q0 += T::NW * U) {
-            double a1[U][PER], a2[U][PER];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int q = q0 + u * T::NW;
-                const int dd = q - (T::CTR - 1);
-                const int off = X0 - Y0 + dd;
-                const int i_lo = dd < 0 ? -dd : 0;
-                const int i_hi = T::CTC - dd < T::CTR ? T::CTC - dd : T::CTR;
-                const bool in_band = q < ND && off >= 0 && off <= dpx + 1;
-                const int64_t at = (int64_t)(in_band ? off : 0) * n + start + Y0;
-#pragma unroll
-                for (int e = 0; e < PER; ++e) {
-                    const int i = i_lo + (tid & 63) + 64 * e;
-                    const bool ok = in_band && i < i_hi && start + X0 + i + dd < n;
-                    a1[u][e] = ok ? band1[at + i] : 0.0;
-                    a2[u][e] = ok ? band2[at + i] : 0.0;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int q = q0 + u * T::NW;
-                if (q >= ND) break;
-                const int dd = q - (T::CTR - 1);
-                const int off = X0 - Y0 + dd;
-                const int i_lo = dd < 0 ? -dd : 0;
-                const int i_hi = T::CTC - dd < T::CTR ? T::CTC - dd : T::CTR;
-#pragma unroll
-                for (int e = 0; e < PER; ++e) {
-                    const int i = i_lo + (tid & 63) + 64 * e;
-                    if (i >= i_hi) continue;
-                    const int j = i + dd;
-                    double val;
-                    bool both;
-                    pixel(a1[u][e], a2[u][e], off, val, both);
-                    ct[j * T::CTP + i] = val;
-                    const int ri = i - RMAX, rj = j - RMAX;
-                    if (ri >= 0 && ri < RGR && rj >= 0 && rj < RGC) nzb[ri * RGC + rj] = both ? 1 : 0;
-                }
-            }
-        }
-    } else {
-        for (int idx = tid; idx < T::CTR * T::CTC; idx += T::NT) {
-            const int i = idx / T::CTC, j = idx - i * T::CTC;
-            const int uy = Y0 + i, ux = X0 + j;
-            const int by = reflect_idx(uy, CH), bx = reflect_idx(ux, CH);
-            const int off = bx - by;
-            double r1 = 0.0, r2 = 0.0;
-            if (off >= 0 && off <= dpx + 1 && start + bx < n) {
-                r1 = band1[(int64_t)off * n + start + by];
-                r2 = band2[(int64_t)off * n + start + by];
-            }
-            double val;
-            bool both;
-            pixel(r1, r2, off, val, both);
-            ct[j * T::CTP + i] = val;
-            const int ri = i - RMAX, rj = j - RMAX;
-            if (ri >= 0 && ri < RGR && rj >= 0 && rj < RGC) {
-                const bool inside = uy >= 0 && uy < CH && ux >= 0 && ux < CH;
-                nzb[ri * RGC + rj] = (inside && both) ? 1 : 0;
-            }
-        }
-    }
+    src.template stage<T>(b, y0 - RMAX, x0 - RMAX, CH, ct, nzb, tid);
     __syncthreads();
     uint32_t in_mask = 0, both_mask = 0;
 #pragma unroll
@@ -341,7 +408,7 @@ diff_fit_kernel(const double *__restrict__ partial, int ntiles, int n_slots, con
     double a = 0.0, q = 0.0;
     // summation order fixed by the TILE numbering: a tile that was not launched would have contributed {0, 0}
     for (int i = tid; i < ntiles; i += 256) {
-        const int sl = slot_of_tile[i];
+        const int sl = slot_of_tile ? slot_of_tile[i] : i;     // no list: every tile was launched, in tile order
         if (sl < 0) continue;
         a = a + partial[(((size_t)b * n_slots + sl) * n_oct + o) * 2];
         q = q + partial[(((size_t)b * n_slots + sl) * n_oct + o) * 2 + 1];
@@ -390,6 +457,12 @@ using DiffTile8 = Tile<32, 64, 8>;        // the reference's default octaves: G_
 using DiffTile14 = Tile<32, 64, 14>;
 using DiffTile28 = Tile<32, 64, 28, 4, 1, false, true>;   // 512 threads x 4 pixels, tight pitches: the sigma loop's wide tile
 
+// one tile grid for all three: mst_diff_dog_tiles counts its slots, and both entry points size their workspace, before the
+// tile type is chosen
+static_assert(DiffTile8::RGR == DiffTile14::RGR && DiffTile14::RGR == DiffTile28::RGR && DiffTile8::RGC == DiffTile14::RGC &&
+                  DiffTile14::RGC == DiffTile28::RGC,
+              "the three difference tiles share one region shape");
+
 template <class T>
 size_t diff_lds_bytes() { return sizeof(double) * (size_t)(T::CT_ELEMS + T::VB_ELEMS + 2 * T::NT); }
 template <class T>
@@ -397,10 +470,10 @@ int diff_tiles(int CH) { return ((CH + T::RGR - 1) / T::RGR) * ((CH + T::RGC - 1
 
 size_t diff_align(size_t v) { return (v + 255) / 256 * 256; }
 
-int diff_levels(const mst_levels *lv, DiffLevels *out, int *max_radius) {
+int diff_levels(const char *who, const mst_levels *lv, DiffLevels *out, int *max_radius) {
     if (!lv || lv->n_octaves < 1 || lv->n_octaves > 16 || lv->levels_per_octave < 3 ||
         lv->n_octaves * lv->levels_per_octave > MST_MAX_LEVELS)
-        return mst::fail(MST_E_ARG, "mst_diff_dog_band: bad level table (1..16 octaves, >= 3 levels each)");
+        return mst::fail(MST_E_ARG, "%s: bad level table (1..16 octaves, >= 3 levels each)", who);
     memset(out, 0, sizeof(*out));
     out->n_octaves = lv->n_octaves;
     int mr = 0;
@@ -408,7 +481,7 @@ int diff_levels(const mst_levels *lv, DiffLevels *out, int *max_radius) {
         for (int q = 0; q < 2; ++q) {
             const int l = o * lv->levels_per_octave + 1 + q;          // sigma_2 and sigma_3 of the octave
             const int r = lv->radius[l];
-            if (r < 1 || r > 28) return mst::fail(MST_E_ARG, "mst_diff_dog_band: blur radius %d outside [1, 28]", r);
+            if (r < 1 || r > 28) return mst::fail(MST_E_ARG, "%s: blur radius %d outside [1, 28]", who, r);
             out->radius[o][q] = r;
             for (int j = 0; j <= r; ++j) out->taps[o][q][j] = lv->taps[l][j];
             mr = r > mr ? r : mr;
@@ -436,23 +509,32 @@ int diff_tile_list(int CH, int dpx, int32_t *list) {
     return m;
 }
 
-template <class T>
-int diff_dog_launch(const double *band1, const double *band2, int64_t n, int dpx, const int64_t *d_starts, int CH, int B,
-                    const DiffLevels *d_lv, int n_oct, double *dog, double *partial, int32_t *d_tiles, int m,
-                    uint32_t *mask_count, double *fit, hipStream_t s) {
+// m slots of `src` (slot_of_tile: the inverse of its tile list, or null when every tile is a slot), then the fit
+template <class T, class Src>
+int diff_dog_launch(const Src &src, const int32_t *slot_of_tile, int CH, int B, const DiffLevels *d_lv, int n_oct, double *dog,
+                    double *partial, int m, uint32_t *mask_count, double *fit, hipStream_t s) {
     static unsigned long long lds_allowed = 0;
-    MST_HIP(mst::allow_dynamic_lds(reinterpret_cast<const void *>(&diff_dog_kernel<T>), (int)diff_lds_bytes<T>(),
+    MST_HIP(mst::allow_dynamic_lds(reinterpret_cast<const void *>(&diff_dog_kernel<T, Src>), (int)diff_lds_bytes<T>(),
                                    &lds_allowed));
     const int tx = (CH + T::RGC - 1) / T::RGC, nt = diff_tiles<T>(CH);
     if (m > 0) {
-        diff_dog_kernel<T><<<dim3((m + 7) / 8 * 8, B), T::NT, diff_lds_bytes<T>(), s>>>(band1, band2, n, dpx, d_starts, CH, B,
-                                                                                      d_lv, dog, partial, mask_count, tx, m,
-                                                                                      d_tiles);
+        diff_dog_kernel<T, Src><<<dim3((m + 7) / 8 * 8, B), T::NT, diff_lds_bytes<T>(), s>>>(src, CH, B, d_lv, dog, partial,
+                                                                                           mask_count, tx, m);
         MST_LAUNCH_CHECK();
     }
-    diff_fit_kernel<<<dim3(n_oct, B), 256, 0, s>>>(partial, nt, m, d_tiles + nt, n_oct, B, mask_count, fit);
+    diff_fit_kernel<<<dim3(n_oct, B), 256, 0, s>>>(partial, nt, m, slot_of_tile, n_oct, B, mask_count, fit);
     MST_LAUNCH_CHECK();
     return MST_OK;
+}
+
+// which tile serves the largest radius: 0 / 1 / 2 = DiffTile8 / 14 / 28
+int diff_which(int max_radius) { return max_radius <= DiffTile8::RMAX ? 0 : (max_radius <= DiffTile14::RMAX ? 1 : 2); }
+
+template <class Src, class... A>
+int diff_dog_launch_tile(int which, const Src &src, A... a) {
+    if (which == 0) return diff_dog_launch<DiffTile8>(src, a...);
+    if (which == 1) return diff_dog_launch<DiffTile14>(src, a...);
+    return diff_dog_launch<DiffTile28>(src, a...);
 }
 
 }  // namespace
@@ -473,7 +555,7 @@ extern "C" int mst_diff_dog_band(const double *band1, const double *band2, int64
         return mst::fail(MST_E_ARG, "mst_diff_dog_band: bad argument");
     DiffLevels h;
     int mr = 0;
-    int rc = diff_levels(lv, &h, &mr);
+    int rc = diff_levels("mst_diff_dog_band", lv, &h, &mr);
     if (rc != MST_OK) return rc;
     if (workspace_bytes < mst_diff_dog_workspace_bytes(B, CH, lv))
         return mst::fail(MST_E_ARG, "mst_diff_dog_band: workspace too small");
@@ -484,29 +566,52 @@ extern "C" int mst_diff_dog_band(const double *band1, const double *band2, int64
     int64_t *d_starts = reinterpret_cast<int64_t *>(w);
     w += diff_align(sizeof(int64_t) * (size_t)B);
     int32_t *d_tiles = reinterpret_cast<int32_t *>(w);
-    w += diff_align(sizeof(int32_t) * 2 * (size_t)diff_tiles<DiffTile28>(CH));
+    const int nt = diff_tiles<DiffTile28>(CH);
+    w += diff_align(sizeof(int32_t) * 2 * (size_t)nt);
     double *partial = reinterpret_cast<double *>(w);
     // three uploads, each small enough for the runtime's in-queue blit path.  (Round 5 tried ONE 26 KB upload of the three tables:
     // 15 us less in front of the kernel of a six-pair call, but copies of that size go through the copy engine, where they
     // queue behind this stream's fused kernels and hold up every later small copy of the OTHER streams -- the pipelined
     // two-sample genome run lost its overlap, 0.077 -> 0.090 s; LABBOOK R5.5.)
     static thread_local std::vector<int32_t> tiles_h;
-    tiles_h.resize(2 * (size_t)diff_tiles<DiffTile28>(CH));
-    const int which = mr <= DiffTile8::RMAX ? 0 : (mr <= DiffTile14::RMAX ? 1 : 2);
+    tiles_h.resize(2 * (size_t)nt);
+    const int which = diff_which(mr);
     const int m = which == 0 ? diff_tile_list<DiffTile8>(CH, dpx, tiles_h.data())
                              : (which == 1 ? diff_tile_list<DiffTile14>(CH, dpx, tiles_h.data()) : diff_tile_list<DiffTile28>(CH, dpx, tiles_h.data()));
     MST_HIP(mst::upload_small(d_lv, &h, sizeof(h), s));
     MST_HIP(mst::upload_small(d_starts, starts, sizeof(int64_t) * B, s));
     MST_HIP(mst::upload_small(d_tiles, tiles_h.data(), sizeof(int32_t) * tiles_h.size(), s));
     MST_HIP(hipMemsetAsync(mask_count, 0, sizeof(uint32_t) * B, s));
-    if (which == 0)
-        return diff_dog_launch<DiffTile8>(band1, band2, n, dpx, d_starts, CH, B, d_lv, h.n_octaves, dog, partial, d_tiles, m,
-                                          mask_count, fit, s);
-    if (which == 1)
-        return diff_dog_launch<DiffTile14>(band1, band2, n, dpx, d_starts, CH, B, d_lv, h.n_octaves, dog, partial, d_tiles, m,
-                                           mask_count, fit, s);
-    return diff_dog_launch<DiffTile28>(band1, band2, n, dpx, d_starts, CH, B, d_lv, h.n_octaves, dog, partial, d_tiles, m,
-                                       mask_count, fit, s);
+    const BandSource src{band1, band2, n, dpx, d_starts, d_tiles};
+    return diff_dog_launch_tile(which, src, d_tiles + nt, CH, B, d_lv, h.n_octaves, dog, partial, m, mask_count, fit, s);
+}
+
+extern "C" uint64_t mst_diff_dog_tiles_workspace_bytes(int32_t P, int32_t C, const mst_levels *lv) {
+    if (P <= 0 || C <= 0 || !lv || lv->n_octaves < 1 || lv->n_octaves > 16) return 0;
+    return diff_align(sizeof(DiffLevels)) + sizeof(double) * 2 * (size_t)P * diff_tiles<DiffTile28>(C) * lv->n_octaves;
+}
+
+extern "C" int mst_diff_dog_tiles(const double *c1, const double *c2, int32_t P, int32_t C, const mst_levels *lv, double *dog,
+                                  double *fit, uint32_t *mask_count, void *workspace, uint64_t workspace_bytes,
+                                  void *stream) {
+    MST_RANGE("launch: mst_diff_dog_tiles");
+    if (!c1 || !c2 || !dog || !fit || !mask_count || !workspace || P <= 0 || P > 65535 || C <= 0)
+        return mst::fail(MST_E_ARG, "mst_diff_dog_tiles: bad argument");
+    DiffLevels h;
+    int mr = 0;
+    int rc = diff_levels("mst_diff_dog_tiles", lv, &h, &mr);
+    if (rc != MST_OK) return rc;
+    if (workspace_bytes < mst_diff_dog_tiles_workspace_bytes(P, C, lv))
+        return mst::fail(MST_E_ARG, "mst_diff_dog_tiles: workspace too small");
+    hipStream_t s = mst::as_stream(stream);
+    char *w = reinterpret_cast<char *>(workspace);
+    DiffLevels *d_lv = reinterpret_cast<DiffLevels *>(w);
+    double *partial = reinterpret_cast<double *>(w + diff_align(sizeof(DiffLevels)));
+    MST_HIP(mst::upload_small(d_lv, &h, sizeof(h), s));
+    MST_HIP(hipMemsetAsync(mask_count, 0, sizeof(uint32_t) * P, s));
+    const DenseSource src{c1, c2};
+    return diff_dog_launch_tile(diff_which(mr), src, static_cast<const int32_t *>(nullptr), C, P, d_lv, h.n_octaves, dog, partial,
+                                diff_tiles<DiffTile28>(C), mask_count, fit, s);
 }
 
 extern "C" int mst_pair_pvalues_dog(const mst_found *found, uint32_t found_cap, const uint32_t *found_count,

@@ -7,6 +7,8 @@
     regulator(f1, f2, ...)                               <- diff_mustache.py:572-690
     main()                                               <- diff_mustache.py:720-906   (.loop1/.diffloop1/.loop2/.diffloop2)
 
+A pair of two different chromosomes (-ch A -ch2 B), which the reference's caller cannot run, goes to mustache_amd/diff_trans.py.
+
 Per chromosome both samples' sigma loops run band-direct (mst_scale_space_band on each sample's band) and the difference
 image is formed, blurred and scored inside mst_diff_dog_band -- no dense block of either sample, no difference image and no
 blurred level of it reaches HBM.  diff_mustache() itself receives dense blocks (the reference's seam) and runs them through
@@ -282,8 +284,13 @@ def regulator(f1, f2, norm_method, CHRM_SIZE, outdir, bed1="", bed2="", res=5000
               st=0.88, octaves=2, verbose=True, nprocesses=4, distance_filter=2000000, bias1=False, bias2=False,
               chromosome='n', chromosome2=None, balance=None):
     """Two-sample loop calling for one chromosome (diff_mustache.py:572-690); returns [x, y, fdr, sigma, tag] rows.
+    chromosome2 = B != chromosome: the inter-chromosomal pair (A, B), which the reference cannot run (diff_trans.py).
     `balance="ICE"` (not in the reference): balance each sample's raw map on the GPU instead of applying bias1 / bias2."""
     octave_values = [sigma0 * (2 ** i) for i in range(octaves)]
+    if chromosome2 and chromosome2 != 'n' and chromosome != chromosome2:      # the trans pair (A, B): mustache_amd/diff_trans.py
+        from .diff_trans import regulate
+        return regulate(f1, f2, norm_method, res, octave_values, st, pt, pt2, chromosome, chromosome2, verbose=verbose,
+                        balance=balance)
     got = read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_filter, bias1, bias2, chromosome, chromosome2, verbose,
                     balance=balance)
     if got is None:
@@ -388,7 +395,18 @@ def main(argv=None):
         except BalanceError as e:
             print("Error: %s" % e)
             return
-    mine = owned_chromosomes(f1, res, pairs, rank, world_size) if world_size > 1 else list(range(len(pairs)))
+    # inter-chromosomal pairs (mustache_amd/diff_trans.py) run after every intra-chromosomal pair, in pair order
+    cis_pairs = [p for p in pairs if p[0] == p[1]]
+    trans_pairs = [p for p in pairs if p[0] != p[1]]
+    if trans_pairs:
+        from .diff_trans import refusal
+        why = refusal((f1, f2), args.balance, world_size, bool(args.chromosome) and args.chromosome != 'n')
+        if why:
+            print("Error: %s" % why)
+            return
+    pairs = cis_pairs + trans_pairs
+    n_cis = len(cis_pairs)
+    mine = owned_chromosomes(f1, res, pairs, rank, world_size) if world_size > 1 else list(range(n_cis))
 
     def write(i, o):
         chromosome, chromosome2 = pairs[i]
@@ -421,8 +439,9 @@ def main(argv=None):
             counts = {t: sum(1 for r in o if r[4] == t) for t in (1, 2, 3, 4)}
         else:
             counts = write(i, o)
+        where = chromosome if chromosome == pairs[i][1] else "%s,%s" % pairs[i]
         print(f"({counts[1]},{counts[3]}) loops and ({counts[2]},{counts[4]}) differential-loops found in "
-              f"chrmosome={chromosome} for detection-fdr<{args.pt} and difference-fdr<{args.pt2} in {time.time() - t0:.2f}sec")
+              f"chrmosome={where} for detection-fdr<{args.pt} and difference-fdr<{args.pt2} in {time.time() - t0:.2f}sec")
         t0 = time.time()
 
     # Several chromosomes on this rank (the whole-genome run of BASELINE config 5): both samples' normalised bands are
@@ -459,6 +478,11 @@ def main(argv=None):
         dbands, n = normalized_pair_bands(pipe, coo1, coo2, res_c, dpx)
         genome.add(i, dbands, n, dpx, sum(b.numel() * 8 for b in dbands))
     genome.flush()
+    for i in range(n_cis, len(pairs)):
+        t0 = time.time()
+        emit(i, regulator(f1, f2, args.norm_method, False, args.outdir, res=res, sigma0=args.s_z, verbose=args.verbose,
+                          pt=args.pt, pt2=args.pt2, st=args.st, chromosome=pairs[i][0], chromosome2=pairs[i][1],
+                          octaves=args.octaves))
     if world_size > 1:
         # one gather of (chromosome, x, y, fdr, sigma, list tag) records; rank 0 writes the four files
         per_chromosome = gather_chromosome_rows(results, len(pairs), 5)

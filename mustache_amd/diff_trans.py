@@ -1,0 +1,144 @@
+"""Two-sample (differential) loop calling for one inter-chromosomal pair (A, B) on the GPU.
+
+The reference's two-sample caller is dead on a trans pair (diff_mustache.py:687-690 only prints), so the semantics are fixed
+here, from trans.py's rules for one sample and diff_mustache.py:260-569 for what two samples add;
+tests/diff_trans_reference.py restates them in NumPy / SciPy.
+
+1. Input: each sample contributes every record of its A x B matrix (trans.py rule 1; `.hic`, `.cool`, `.mcool` through
+   read_trans_contacts).
+2. Normalisation: each sample is z-scored on its own (trans.py rule 2, mst_trans_zscore).  A sample that is empty or has
+   std = 0 or a non-finite std: no rows for the pair.
+3. Tiling: n1 = max over both samples of max(x) + 1, n2 likewise (the cis n = max(n1, n2)); trans_tiling(n1, n2) is the one
+   tiling of both samples; ownership as in trans.py rule 3.
+4. Per tile pair:
+   - nz_s = c_s != 0 over the whole tile (no triangle masks, no fills); nz = nz_1 & nz_2; cd = c_1 - c_2 on nz, 0 elsewhere;
+   - either sample with fewer than 50, or fewer than 10 000, tested pixels: the pair's four lists are empty;
+   - per sample the sigma loop on nz_s, BH over its found set, q < pt, the sparsity filter (x != 0, the cis windows), no
+     diagonal-mean filter; a sample without a surviving candidate empties all four lists (diff_mustache.py:507); clustering
+     as in trans.py rule 5;
+   - pair p-value: per octave D_2 = G(sigma_2) - G(sigma_3) of cd -- the reference's quirk kept, EVERY tested level of an
+     octave scores against D_2 (diff_mustache.py:336 vs :363) --, norm.fit over nz, the two-sided normal p-value at each found
+     pixel (mst_diff_dog_tiles, mst_pair_pvalues_dog);
+   - differential subset: the representative has pair < pt2 and v_self > v_other, v_other = 1 off the other sample's nz, its
+     winning DoG value where it found the pixel, 0 where it tested it and did not;
+   - a representative counts only if its tile owns it.
+5. Output rows [x, y, fdr, sigma, tag], tag 1..4 = loops1, diffloops1, loops2, diffloops2, sorted by (tag, x, y) within the
+   pair; the command line writes them to .loop1 / .diffloop1 / .loop2 / .diffloop2 with A in column 1 and B in column 4.
+"""
+import numpy as np
+
+from ._lib import ptr as _ptr, stream as _stream
+from .trans import TRANS_CHUNK, TransCaller, TransError, owned_range, read_trans_contacts, trans_tiling
+
+
+class DiffTransCaller(TransCaller):
+    """Rules 2-5 on the GPU for the records of two samples.  `tiles_per_launch` tile PAIRS go through two scatters, one
+    prologue and one fused scale-space launch over both samples' tiles, one mst_diff_dog_tiles and one batched tail."""
+
+    # tile PAIRS per launch when the caller names none.  A pair of 2000 x 2000 tiles at two octaves holds 2 x 32 MB of tiles,
+    # 2 x 4 MB of masks and 2 x 32 MB of D_2 in HBM, 136 MB before the record buffers: 32 pairs = the 64 tiles of the one-sample
+    # caller's launch, ~4.4 GB.
+    PAIRS_PER_LAUNCH = 32
+
+    def __init__(self, octave_values=(1.6, 3.2), device=None, tiles_per_launch=None, chunk=TRANS_CHUNK):
+        super().__init__(octave_values, device=device, tiles_per_launch=tiles_per_launch or self.PAIRS_PER_LAUNCH, chunk=chunk)
+
+    def run_tiles(self, s1, s2, n1, n2, st, pt, pt2):
+        """rules 3-5 on two samples' normalised device records s = (x, y, vz): rows [x, y, fdr, sigma, tag]"""
+        import torch
+        from . import _lib
+        from .diff_mustache import _pair_tails
+        eng, dev = self.eng, self.device
+        lib = eng.lib
+        C, (rs, re), (cs, ce) = trans_tiling(n1, n2, self.chunk)
+        tiles = [(i, j) for i in range(len(rs)) for j in range(len(cs))]
+        out = []
+        for g0 in range(0, len(tiles), self.tiles_per_launch):
+            group = tiles[g0:g0 + self.tiles_per_launch]
+            P = len(group)
+            row0 = torch.tensor([rs[i] for i, _ in group], dtype=torch.int64, device=dev)
+            col0 = torch.tensor([cs[j] for _, j in group], dtype=torch.int64, device=dev)
+            c = torch.empty((2 * P, C, C), dtype=torch.float64, device=dev)       # sample 1 in [0, P), sample 2 in [P, 2P)
+            nz = torch.empty((2 * P, C, C), dtype=torch.uint8, device=dev)
+            nzc = torch.empty(2 * P, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                for (x, y, vz), half in ((s1, c[:P]), (s2, c[P:])):
+                    _lib.check(lib.mst_trans_scatter_tiles(_ptr(x), _ptr(y), _ptr(vz), int(vz.numel()), _ptr(row0), _ptr(col0),
+                                                           P, C, _ptr(half), _stream()))
+                _lib.check(lib.mst_trans_prologue(_ptr(c), _ptr(nz), _ptr(nzc), 2 * P, C, _stream()))
+                batch = eng.run_filled_pairs(c, nz, nzc, tiles=True)
+            tails = _pair_tails(batch, [(p, P + p, 0) for p in range(P)], pt, pt2, st, False)
+            for (i, j), res4 in zip(group, tails):
+                rlo, rhi = owned_range(re, i)
+                clo, chi = owned_range(ce, j)
+                for tag, loops in enumerate(res4, start=1):
+                    for lx, ly, q, sg in loops:
+                        gx, gy = int(lx) + rs[i], int(ly) + cs[j]
+                        if rlo <= gx < rhi and clo <= gy < chi:
+                            out.append([np.int64(gx), np.int64(gy), q, sg, tag])
+            del batch, c, nz
+        out.sort(key=lambda r: (r[4], int(r[0]), int(r[1])))
+        return out
+
+    def run(self, rec1, rec2, st, pt, pt2, verbose=False, label=""):
+        """rules 2-5 on two samples' records rec = (x, y, v) (host arrays or device tensors)"""
+        import torch
+        samples = []
+        for x, y, v in (rec1, rec2):
+            ok = len(v) > 0
+            if ok:
+                x, y, vz, (mean, std, _) = self.normalize(x, y, v)
+                ok = bool(np.isfinite(mean) and np.isfinite(std)) and std != 0
+            if not ok:
+                print("There is no contact in the chromosome pair %s of one of the samples to work on." % label)
+                return []
+            samples.append((x, y, vz))
+        n1 = max(int(torch.max(s[0]).item()) for s in samples) + 1
+        n2 = max(int(torch.max(s[1]).item()) for s in samples) + 1
+        if verbose:
+            C, (rs, _), (cs, _) = trans_tiling(n1, n2, self.chunk)
+            print("Loop calling (trans %s: %d x %d bins, %d tile pairs of %d)..." % (label, n1, n2, len(rs) * len(cs), C))
+        return self.run_tiles(samples[0], samples[1], n1, n2, st, pt, pt2)
+
+
+def call_diff_trans_coo(rec1, rec2, octave_values, st, pt, pt2, chunk=TRANS_CHUNK, tiles_per_launch=None, verbose=False,
+                        label=""):
+    """Differential loops of one chromosome pair from the two samples' records rec = (x, y, v) (x = bins of A, y = bins of B,
+    v > 0): rules 2-5 of this module.  Returns [[x, y, fdr, sigma, tag], ...] sorted by (tag, x, y)."""
+    return DiffTransCaller(octave_values, tiles_per_launch=tiles_per_launch, chunk=chunk).run(rec1, rec2, st, pt, pt2,
+                                                                                             verbose=verbose, label=label)
+
+
+def refusal(files, balance, world_size, chromosomes_given=True):
+    """Why a two-sample run with an inter-chromosomal pair cannot go ahead (the text of its `Error:` line), or None."""
+    if not chromosomes_given:
+        return "inter-chromosomal pairs need -ch and -ch2 (all-pairs runs are not supported)"
+    if not all(str(f).endswith((".hic", ".cool", ".mcool")) for f in files):
+        return "Interchromosomal analysis is only supported for .hic and .cool input formats."
+    if balance:
+        return "--balance does not apply to inter-chromosomal pairs"
+    if world_size > 1:
+        return "inter-chromosomal pairs run on one GPU only (this run has %d ranks)" % world_size
+    return None
+
+
+def regulate(f1, f2, norm_method, res, octave_values, st, pt, pt2, chromosome, chromosome2, verbose=True, balance=None):
+    """diff_mustache.regulator()'s body for a trans pair: read both samples (rule 1), call.  Rows [x, y, fdr, sigma, tag].
+    Refuses text input and `balance` (TransError).  It runs on the current device alone and knows nothing of ranks: a
+    multi-rank caller (and -ch2 without -ch) is the command line's to refuse, before it gets here (diff_mustache.main)."""
+    why = refusal((f1, f2), balance, 1)
+    if why:
+        raise TransError(why)
+    if verbose:
+        print("Reading contact map...")
+    recs = []
+    for f in (f1, f2):
+        got = read_trans_contacts(f, norm_method, chromosome, chromosome2, res)
+        if got is None:
+            print("There is no contact in the chromosome pair %s,%s of %s to work on." % (chromosome, chromosome2, f))
+            return []
+        if recs and got[3] != recs[0][3]:
+            raise ValueError('Both contact maps should have the same resolution.')
+        recs.append(got)
+    return call_diff_trans_coo(recs[0][:3], recs[1][:3], octave_values, st, pt, pt2, verbose=verbose,
+                               label="%s,%s" % (chromosome, chromosome2))

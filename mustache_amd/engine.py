@@ -332,6 +332,29 @@ class ScaleSpaceEngine:
                                                      P, CH, n_oct, tpo, off, _ptr(ppair), _stream()))
         return ppair, fit
 
+    def pair_pvalues_tiles(self, c, found, found_cap, count):
+        """pair_pvalues for tile pairs whose difference image needs no mask beyond c != 0 (inter-chromosomal tiles,
+        diff_trans.py): mst_diff_dog_tiles stages c[:P] - c[P:] in LDS and writes only D_2 per octave and norm.fit; no
+        difference image, G_2 or G_3 reaches HBM.  Returns (ppair [2P, found_cap], fit) like pair_pvalues."""
+        P2, CH, _ = c.shape
+        P = P2 // 2
+        n_oct, tpo = len(self.levels.octave_values), self.levels.s - 1
+        lv = ctypes.byref(self._lv_struct)
+        dev = self.device
+        with torch.cuda.device(dev):
+            dog = torch.empty((n_oct, P, CH, CH), dtype=torch.float64, device=dev)
+            fit = torch.empty((n_oct, P, 2), dtype=torch.float64, device=dev)
+            mcount = torch.empty(P, dtype=torch.int32, device=dev)
+            ws_bytes = int(self.lib.mst_diff_dog_tiles_workspace_bytes(P, CH, lv))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(self.lib.mst_diff_dog_tiles(_ptr(c[:P]), _ptr(c[P:]), P, CH, lv, _ptr(dog), _ptr(fit), _ptr(mcount),
+                                                   _ptr(ws), ws_bytes, _stream()))
+            ppair = torch.empty((P2, found_cap), dtype=torch.float64, device=dev)
+            for off in (0, P):
+                _lib.check(self.lib.mst_pair_pvalues_dog(_ptr(found), found_cap, _ptr(count), _ptr(dog), _ptr(fit), P, CH,
+                                                         n_oct, tpo, off, _ptr(ppair), _stream()))
+        return ppair, fit
+
     def _pair_launch(self, bands, n, dpx, starts, CH, skip_empty, reuse=None, graph=False):
         """Enqueue a two-sample call's device work on the current stream: both samples' sigma loops in ONE fused launch
         over 2P blocks (mst_scale_space_band_pair: rows [0, P) sample 1, [P, 2P) the same windows of sample 2's band --
@@ -440,12 +463,13 @@ class ScaleSpaceEngine:
         yield from self._ping_pong(
             groups, lambda gi, starts: self._pair_launch(bands, n, dpx, starts, CH, skip_empty), collect)
 
-    def run_filled_pairs(self, c, nz, nz_count, skip_empty=True):
+    def run_filled_pairs(self, c, nz, nz_count, skip_empty=True, tiles=False):
         """The reference's dense two-sample data flow (the cross-check of run_band_pairs): c [2P, CH, CH] filled blocks
         (sample 1 first, then sample 2), nz their masks, nz_count their tested-pixel counts (device).  BlockBatch over
-        all 2P blocks whose records also carry `pair` (the differential p-value) and `q`."""
+        all 2P blocks whose records also carry `pair` (the differential p-value) and `q`.  tiles=True: nz is c != 0
+        (inter-chromosomal tiles) and the pair p-values come from the fused kernel (pair_pvalues_tiles)."""
         found, pval, count, fit, cap = self.sigma_loop(c, nz, nz_count, skip_empty=skip_empty, download=False)
-        ppair, nfit = self.pair_pvalues(c, nz, found, cap, count)
+        ppair, nfit = self.pair_pvalues_tiles(c, found, cap, count) if tiles else self.pair_pvalues(c, nz, found, cap, count)
         recs, fits = records.download_found(self, found, pval, count, fit, self.levels.n_tested, sort=True,
                                             extra={"pair": ppair, "q": records.fdr(self, pval, count, cap)})
         B, CH, _ = c.shape
