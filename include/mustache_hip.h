@@ -498,6 +498,39 @@ MST_STABLE int mst_trans_scatter_tiles(const int32_t *x, const int32_t *y, const
 /* The trans prologue: nz[b] = c[b] != 0 over the whole tile, no fills; nz_count dev [B] uint32, overwritten. */
 MST_STABLE int mst_trans_prologue(const double *c, uint8_t *nz, uint32_t *nz_count, int32_t B, int32_t CH, void *stream);
 
+/* ---- trans pairs of a whole genome in shared launches (mustache_amd/trans_genome.py) ------------------------------------------
+ * The records of P pairs are concatenated: x, y dev int32 [n], v dev f64 [n]; seg_off: dev int64 [P + 1], non-decreasing,
+ * seg_off[0] = 0, seg_off[P] = n; pair p owns records [seg_off[p], seg_off[p + 1]). */
+/* One pair of the batch.  Square tiles of C; K1 x K2 windows; window i of an axis of length n starts at i (C - 256) for
+ * i < K - 1 and at max(0, n - C) for i = K - 1 (trans.trans_axis_tiles); K > 1 needs C > 256.  The pair's tile (i, j) has the
+ * batch index tile_base + i K2 + j (pair-major, then row-major).  A pair that is not tiled (no record, std = 0 or not finite)
+ * has K1 = K2 = 0. */
+typedef struct mst_trans_pair {
+    int32_t C, K1, K2, n1, n2, reserved;
+    int64_t tile_base;
+} mst_trans_pair;
+/* mst_trans_zscore per pair, for all pairs in one sequence of launches: stats dev f64 [4 P] = {mean, std, n, flags} per pair
+ * (flags = 1 when a value or a square was not finite: mean / std are NaN then; a pair without a record keeps 0, 0, 0, 0),
+ * out dev f64 [n] (may alias v), extent dev int32 [2 P] = {max x, max y} per pair (-1, -1 without a record).  Every pair's
+ * mean, std and out are bit-identical to mst_trans_zscore on that pair's records alone.  1 <= P <= 65535, n < 2^31.
+ * workspace: dev, mst_trans_zscore_segmented_workspace_bytes(P) bytes (0 for a bad P). */
+MST_STABLE uint64_t mst_trans_zscore_segmented_workspace_bytes(int32_t P);
+MST_STABLE int mst_trans_zscore_segmented(const int32_t *x, const int32_t *y, const double *v, int64_t n, const int64_t *seg_off,
+                               int32_t P, double *out, double *stats, int32_t *extent, void *workspace,
+                               uint64_t workspace_bytes, void *stream);
+/* counts dev uint32 [T], overwritten: for every tile of the batch the records with v != 0 inside its window (v: the
+ * normalised values).  pairs: dev [P]; T = the batch's tile count < 2^31.  With unique pixels per pair this is the tile's
+ * tested-pixel count, with duplicates an upper bound of it. */
+MST_STABLE int mst_trans_count_tiles(const int32_t *x, const int32_t *y, const double *v, int64_t n, const int64_t *seg_off,
+                          const mst_trans_pair *pairs, int32_t P, int64_t T, uint32_t *counts, void *stream);
+/* Records of the pairs [p0, p1) -> the B tiles of one launch: c dev [B][CH][CH] f64, zeroed, then every record is written into
+ * each tile t that holds it and has slot[t] in [0, B) (slot: dev int32 [T], -1 = not in this launch), at
+ * c[slot[t]][x - row start][y - column start].  Only pairs with C == CH are scattered.  n_range = seg_off[p1] - seg_off[p0]
+ * (sizes the launch).  The same bytes as mst_trans_scatter_tiles writes for the same tiles. */
+MST_STABLE int mst_trans_scatter_worklist(const int32_t *x, const int32_t *y, const double *v, const int64_t *seg_off,
+                               const mst_trans_pair *pairs, int32_t p0, int32_t p1, int64_t n_range, int64_t T,
+                               const int32_t *slot, int32_t B, int32_t CH, double *c, void *stream);
+
 /* ---- aggregate peak analysis (APA) of a loop list (mustache_amd/pileup.py states the rules; tests/pileup_reference.py restates
  * them).  band: dev f64, the diagonal-major RAW band of one chromosome (band[d * n + i] = pixel (i, i + d), not normalised)
  * with band_rows >= D + 1 rows; only rows 0 .. D are read.  Every sum has a fixed order that depends only on absolute column

@@ -111,6 +111,10 @@ _SIGNATURES = {
     "mst_trans_zscore": (ctypes.c_int, [_p, _i64, _p, _p, _p, _u64, _p]),
     "mst_trans_scatter_tiles": (ctypes.c_int, [_p, _p, _p, _i64, _p, _p, _i32, _i32, _p, _p]),
     "mst_trans_prologue": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _p]),
+    "mst_trans_zscore_segmented_workspace_bytes": (_u64, [_i32]),
+    "mst_trans_zscore_segmented": (ctypes.c_int, [_p, _p, _p, _i64, _p, _i32, _p, _p, _p, _p, _u64, _p]),
+    "mst_trans_count_tiles": (ctypes.c_int, [_p, _p, _p, _i64, _p, _p, _i32, _i64, _p, _p]),
+    "mst_trans_scatter_worklist": (ctypes.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i64, _i64, _p, _i32, _i32, _p, _p]),
     "mst_pileup_workspace_bytes": (_u64, [_i64, _i32, _i64, _i32]),
     "mst_pileup_expected": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _u64, _p]),
     "mst_pileup_windows": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p]),

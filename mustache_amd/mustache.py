@@ -457,6 +457,9 @@ def parse_args(args):
     p.add_argument("-v", "--verbose", dest="verbose", type=bool, default=True, help="OPTIONAL: verbosity")
     p.add_argument("--balance", dest="balance", default=None, metavar="ICE",
                    help="OPTIONAL: balance the raw contact map on the GPU (ICE) instead of -b / -norm; text and .hic input")
+    p.add_argument("--trans-all", dest="trans_all", action="store_true",
+                   help="OPTIONAL: call inter-chromosomal loops for every unordered pair of the -ch list (without -ch: of "
+                        "every chromosome of a .hic / .cool / .mcool file) in shared launches; no intra-chromosomal rows.")
     return p.parse_args(args)
 
 
@@ -535,6 +538,58 @@ def chromosome_pairs(f, res, ch, ch2):
     return list(zip(ch, ch2))
 
 
+def trans_all_pairs(f, res, ch, ch2):
+    """--trans-all -> every unordered pair (A, B) of the -ch list in list order (without -ch: of list_chromosomes(f, res)), or
+    the Error: line to print."""
+    if isinstance(ch2, list):
+        return "Error: --trans-all pairs the -ch list with itself; give -ch2 without it"
+    if not f.endswith((".cool", ".mcool", ".hic")):
+        return "Error: Interchromosomal analysis is only supported for .hic and .cool input formats."
+    if not ch or ch == 'n':
+        from .readers import list_chromosomes
+        ch = list_chromosomes(f, res)
+    ch = list(ch)
+    return [(ch[i], ch[j]) for i in range(len(ch)) for j in range(i + 1, len(ch))]
+
+
+def run_trans_all(f, args, res, pairs, device=None):
+    """The --trans-all run: the next pair is read on a reader thread while the current one joins the batch
+    (trans_genome.TransGenomeCaller); rows are written in pair order, the header with the first pair's."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .trans import read_trans_contacts
+    from .trans_genome import TransGenomeCaller
+    state = {"first": True, "t0": time.time()}
+
+    def fetch(k):
+        try:
+            return read_trans_contacts(f, args.norm_method, pairs[k][0], pairs[k][1], res, device=device)
+        except BaseException as e:          # re-raised in the main thread, at this pair's turn
+            return e
+
+    def emit(k, o):
+        chromosome, chromosome2 = pairs[k]
+        print("{0} loops found for chrmosome pair={1},{2}, fdr<{3} in {4}sec".format(
+            len(o), chromosome, chromosome2, args.pt, "%.2f" % (time.time() - state["t0"])))
+        if state["first"] or o:
+            write_loops(args.outdir, chromosome, chromosome2, res, o, first=state["first"])
+            state["first"] = False
+        state["t0"] = time.time()
+
+    caller = TransGenomeCaller([args.s_z * (2 ** i) for i in range(args.octaves)], args.st, args.pt, emit, verbose=args.verbose)
+    with ThreadPoolExecutor(max_workers=1) as pool:
+        ahead = pool.submit(fetch, 0) if pairs else None
+        for k in range(len(pairs)):
+            contacts = ahead.result()
+            ahead = pool.submit(fetch, k + 1) if k + 1 < len(pairs) else None
+            if isinstance(contacts, BaseException):
+                raise contacts
+            if args.verbose:
+                print("Reading contact map (pair %s,%s)..." % pairs[k])
+            caller.add(k, None if contacts is None else contacts[:3], "%s,%s" % pairs[k])
+            del contacts
+        caller.flush()
+
+
 def owned_chromosomes(f, res, pairs, rank, world):
     """Indices of the pairs rank `rank` runs when a multi-GPU run is sharded by chromosome: whole chromosomes, largest
     first, to the least loaded rank (sharding.assign_chromosomes on the chromosome sizes of `f`)."""
@@ -562,6 +617,18 @@ def main(argv=None):
     if not res:
         print("Error: Invalid resolution")
         return
+    if args.trans_all:
+        pairs = trans_all_pairs(f, res, args.chromosome, args.chromosome2)
+        if not isinstance(pairs, str):
+            if _world > 1:
+                pairs = "Error: inter-chromosomal pairs run on one GPU only (this run has %d ranks)" % _world
+            elif args.balance is not None:
+                pairs = "Error: --balance does not apply to inter-chromosomal pairs"
+        if isinstance(pairs, str):
+            print(pairs)
+            return
+        import torch
+        return run_trans_all(f, args, res, pairs, device=torch.device("cuda", torch.cuda.current_device()))
     pairs = chromosome_pairs(f, res, args.chromosome, args.chromosome2)
     if isinstance(pairs, str):
         print(pairs)
