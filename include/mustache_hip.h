@@ -555,6 +555,23 @@ MST_STABLE int mst_pileup_windows(const double *band, int64_t n, int32_t band_ro
 MST_STABLE int mst_pileup_reduce(const double *obs, const double *oe, const int32_t *order, int64_t L, int32_t w, double *agg,
                                  void *workspace, uint64_t workspace_bytes, void *stream);
 
+/* ---- the pile-up of an inter-chromosomal (trans) pair, from its records (rules: the trans part of mustache_amd/pileup.py;
+ * tests/pileup_trans_reference.py restates them).  x, y: dev int32 [N] (bin of A, bin of B), v: dev f64 [N], v > 0 and finite,
+ * N < 2^31; a record outside [0, n1) x [0, n2) is ignored.  No float atomics: every output is bit-identical from run to run and
+ * under any permutation of the records and of the loops. */
+/* workspace bytes of one call (and of the mst_pileup_reduce that follows it); 0 for a bad argument or w > 64. */
+MST_STABLE uint64_t mst_pileup_trans_workspace_bytes(int64_t n1, int64_t n2, int64_t L, int32_t w);
+/* valid_rows[i] (dev uint8 [n1], overwritten) = 1 when a record has x = i, valid_cols[j] (dev uint8 [n2]) alike for y;
+ * expected[0] (dev f64 [1]) = the exact sum of v over all records (one rounding; NaN when a v is not finite) / (#valid rows *
+ * #valid columns), 0 when that product is 0.  One window per loop (lx, ly: dev int64 [L]): obs[l][a + w][b + w] (dev f64
+ * [L][2w+1][2w+1]) = pixel (lx + a, ly + b): the largest v among the records at that pixel, 0.0 where there is none, NaN off
+ * the map (row index < 0 or >= n1, column index < 0 or >= n2).  oe = obs / expected[0], NaN where that is 0 or obs is NaN.
+ * loop_stats as mst_pileup_windows writes it.  0 <= w <= 64, 1 <= q <= 2w + 1; L = 0 and N = 0 are served. */
+MST_STABLE int mst_pileup_trans_windows(const int32_t *x, const int32_t *y, const double *v, int64_t N, int64_t n1, int64_t n2,
+                                        const int64_t *lx, const int64_t *ly, int64_t L, int32_t w, int32_t q, uint8_t *valid_rows,
+                                        uint8_t *valid_cols, double *expected, double *obs, double *oe, double *loop_stats,
+                                        void *workspace, uint64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,9 @@ _SIGNATURES = {
     "mst_pileup_expected": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _u64, _p]),
     "mst_pileup_windows": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p]),
     "mst_pileup_reduce": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _u64, _p]),
+    "mst_pileup_trans_workspace_bytes": (_u64, [_i64, _i64, _i64, _i32]),
+    "mst_pileup_trans_windows": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p,
+                                                _u64, _p]),
 }
 
 _lib = None

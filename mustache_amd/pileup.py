@@ -26,6 +26,30 @@ Not claimed: agreement with Juicer's own output.
 
 Device work (mustache_amd/csrc/mst_pileup.hip): valid flags and E (two reads of the band), the windows with each loop's
 centre and P2LL, and the reduce; one host wait per chromosome, when the aggregates come back.
+
+Inter-chromosomal lists (`--trans`, `pileup(..., trans=True)`, `pileup_trans_records()`; tests/pileup_trans_reference.py
+restates the rules).  Without the switch nothing changes: rows with two chromosomes keep the status `trans`.
+  * Rows: a row with one chromosome gets the status `cis`.  A row with two belongs to the unordered pair {chr1, chr2}; the
+    pair's orientation (A, B) is that of its first row in the file, and a row written (B, A) has its anchors swapped.  Bins:
+    a = ((start + end) // 2) // res on A, b likewise on B -- no min / max across chromosomes.  -ch keeps the pairs whose two
+    chromosomes are both in the list; the other rows get `no_pair`.  Pairs run in order of first appearance.  -n / -x are
+    refused: there is no distance.
+  * Map: trans.read_trans_contacts(f, norm, A, B, res) -- what the trans caller has before its z-score (trans.py rule 1: v > 0
+    and finite, divided by the file's vectors); n1 = max x + 1, n2 = max y + 1; no z-score.  A pair without a record, or not in
+    the file, gives its rows `no_pair`; a row with a >= n1 or b >= n2 is `off_map`; every other row is `used`.  Text input,
+    --balance, -b and `.hic` files of version 6 are refused as the trans caller refuses them.
+  * A pixel that occurs more than once among the records takes the largest of its values (an order-free rule).
+  * Row i of A is valid when some record has x = i, column j of B when some record has y = j.  E = (sum of v over ALL records,
+    a repeated pixel's every record counted) / (#valid rows * #valid columns): one scalar per pair, 0 when the product is 0.
+    The sum is exact (csrc/mst_exact_sum.h: one rounding, equal to math.fsum of the records in any order).
+  * Windows: cell [da + w][db + w] = pixel (a + da, b + db); NaN when an index is < 0, or >= n1 on the A axis or >= n2 on the B
+    axis; 0.0 where the map has no record.  oe = obs / E, NaN where E is 0 or obs is NaN.  Per loop: the obs centre, the oe
+    centre and P2LL with the cis definition (the same row and column index ranges).  In a trans window no corner is nearer a
+    diagonal than another: the four corners are equivalent by symmetry, and "LL" names an index range only.
+  * Aggregate: the loops sorted by (a, b), the same reduce with the same chunks of 512; genome-wide = the pair partials added
+    in run order; the same metrics().  Bit-identical under any permutation of the records and of the rows.
+Device work (mustache_amd/csrc/mst_pileup_trans.hip): one pass over the pair's records finds the valid rows and columns, the
+exact total and the window cells together; one host wait per pair.
 """
 import argparse
 import math
@@ -188,6 +212,56 @@ def pileup_band(band, n, D, xs, ys, w=10, q=6):
             "metrics_oe": metrics(apa_oe, w, q)}
 
 
+def pileup_trans_records(x, y, v, n1, n2, xs, ys, w=10, q=6):
+    """The pile-up of one inter-chromosomal pair's records (x = bins of A, y = bins of B, v > 0; host arrays or device tensors)
+    on the n1 x n2 map around the loops (xs, ys) (bins of A, bins of B).  Returns pileup_band's dict with "expected" the
+    scalar E (a float) and "valid" the pair (rows uint8 [n1], columns uint8 [n2]) of device tensors.  L = 0 still finds the
+    valid flags and E; N = 0 gives E = 0.  One host wait."""
+    import torch
+    from . import _lib
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    w, q, n1, n2 = int(w), int(q), int(n1), int(n2)
+    check_window(w, q)
+    xs = np.asarray(xs.cpu() if isinstance(xs, torch.Tensor) else xs, np.int64).reshape(-1)
+    ys = np.asarray(ys.cpu() if isinstance(ys, torch.Tensor) else ys, np.int64).reshape(-1)
+    if len(xs) != len(ys):
+        raise PileupError("xs and ys differ in length (%d, %d)" % (len(xs), len(ys)))
+    if not (len(x) == len(y) == len(v)):
+        raise PileupError("x, y and v differ in length (%d, %d, %d)" % (len(x), len(y), len(v)))
+    if n1 < 1 or n2 < 1:
+        raise PileupError("a trans map needs n1 >= 1 and n2 >= 1 (got %d x %d)" % (n1, n2))
+    lib = require_gpu()
+    dev = v.device if isinstance(v, torch.Tensor) and v.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    L, S = len(xs), 2 * w + 1
+    with torch.cuda.device(dev):
+        x = torch.as_tensor(x).to(dev, dtype=torch.int32).contiguous()
+        y = torch.as_tensor(y).to(dev, dtype=torch.int32).contiguous()
+        v = torch.as_tensor(v).to(dev, dtype=torch.float64).contiguous()
+        ws = torch.empty(max(int(lib.mst_pileup_trans_workspace_bytes(n1, n2, L, w)), 256), dtype=torch.uint8, device=dev)
+        rows = torch.empty(n1, dtype=torch.uint8, device=dev)
+        cols = torch.empty(n2, dtype=torch.uint8, device=dev)
+        E = torch.empty(1, dtype=torch.float64, device=dev)
+        obs = torch.empty((L, S, S), dtype=torch.float64, device=dev)
+        oe = torch.empty_like(obs)
+        st = torch.empty((L, 3), dtype=torch.float64, device=dev)
+        xd = torch.from_numpy(xs).to(dev, non_blocking=True)
+        yd = torch.from_numpy(ys).to(dev, non_blocking=True)
+        N = int(v.numel())
+        _lib.check(lib.mst_pileup_trans_windows(_ptr(x) if N else None, _ptr(y) if N else None, _ptr(v) if N else None, N, n1, n2,
+                                                _ptr(xd) if L else None, _ptr(yd) if L else None, L, w, q, _ptr(rows), _ptr(cols),
+                                                _ptr(E), _ptr(obs) if L else None, _ptr(oe) if L else None,
+                                                _ptr(st) if L else None, _ptr(ws), ws.numel(), _stream()))
+        order = torch.from_numpy(np.lexsort((ys, xs)).astype(np.int32)).to(dev, non_blocking=True)
+        agg = reduce(obs, oe, order, w, ws)
+        host = torch.cat([agg.view(-1), st.view(-1), E]).cpu().numpy()    # the one wait
+    agg_h, st_h = host[:4 * S * S].reshape(4, S, S), host[4 * S * S:-1].reshape(L, 3)
+    apa, apa_oe = mean_map(agg_h[0], agg_h[1]), mean_map(agg_h[2], agg_h[3])
+    return {"valid": (rows, cols), "expected": float(host[-1]), "obs": obs, "oe": oe, "sum_obs": agg_h[0], "count_obs": agg_h[1],
+            "sum_oe": agg_h[2], "count_oe": agg_h[3], "apa": apa, "apa_oe": apa_oe, "center_obs": st_h[:, 0].copy(),
+            "center_oe": st_h[:, 1].copy(), "p2ll": st_h[:, 2].copy(), "metrics": metrics(apa, w, q),
+            "metrics_oe": metrics(apa_oe, w, q)}
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # loop lists
 # ----------------------------------------------------------------------------------------------------------------------
@@ -237,9 +311,37 @@ def read_loops(path):
         raise PileupError("%s: an anchor position is not a number (%s)" % (path, e))
 
 
-def classify(table, res, chromosomes=None, n_min=30, x_max=None):
+def _classify_trans(table, res, chromosomes):
+    """classify() in trans mode: (status list, a, b, [(A, B)]) with a = bins on A, b = bins on B in the pair's orientation."""
+    a = ((table.s1 + table.e1) // 2) // int(res)
+    b = ((table.s2 + table.e2) // 2) // int(res)
+    keys = None if not chromosomes else {_key(c) for c in chromosomes}
+    pairs, first, status = [], {}, []
+    for k in range(len(table)):
+        k1, k2 = _key(table.chr1[k]), _key(table.chr2[k])
+        if k1 == k2:
+            status.append("cis")
+        elif keys is not None and not (k1 in keys and k2 in keys):
+            status.append("no_pair")
+        else:
+            if frozenset((k1, k2)) not in first:         # the pair's orientation: that of its first row
+                first[frozenset((k1, k2))] = k1
+                pairs.append((table.chr1[k], table.chr2[k]))
+            if first[frozenset((k1, k2))] != k1:
+                a[k], b[k] = b[k], a[k]
+            status.append(None)
+    return status, a, b, pairs
+
+
+def classify(table, res, chromosomes=None, n_min=None, x_max=None, trans=False):
     """Statuses before the map is read: (status list, x, y, selected chromosome names).  Rows still eligible have status
-    None; `x_max` is in bins."""
+    None; `x_max` is in bins; `n_min` = None is the default of 30 bins.  trans=True: (status list, a, b, [(A, B)]), the bins in
+    each pair's orientation and the pairs in order of first appearance; `n_min` and `x_max` are refused."""
+    if trans:
+        if n_min is not None or x_max is not None:
+            raise PileupError("-n / -x do not apply to inter-chromosomal loops: there is no distance")
+        return _classify_trans(table, res, chromosomes)
+    n_min = 30 if n_min is None else int(n_min)
     x, y = table.bins(res)
     cis = [_key(a) == _key(b) for a, b in zip(table.chr1, table.chr2)]
     selected, seen = [], set()
@@ -304,14 +406,77 @@ class PileupResult:
         self.all = None
 
 
-def pileup(f, loops, res, chromosomes=None, norm=False, bias=False, balance=None, w=10, q=6, n_min=30, x_max=None,
-           device=None, verbose=False):
+def _read_pair(f, norm, A, B, res, device):
+    """read_trans_contacts, or None when the file has no such chromosome or no matrix for the pair."""
+    from .hicfile import HicError
+    from .trans import read_trans_contacts
+    try:
+        return read_trans_contacts(f, norm, A, B, res, device=device)
+    except NameError:
+        return None
+    except HicError as e:
+        if e.code == -4 and ("is not in the file" in str(e) and "chromosome" in str(e) or "no matrix for the pair" in str(e)):
+            return None
+        raise
+
+
+def _pileup_trans(f, table, res, chromosomes, norm, bias, balance, w, q, n_min, x_max, device, verbose):
+    """pileup() in trans mode: one pile-up per chromosome pair."""
+    import torch
+    from .diff_trans import refusal
+    why = refusal((f,), balance, 1)
+    if why is None and bias:
+        why = "-b does not apply to inter-chromosomal pairs"
+    if why:
+        raise PileupError(why)
+    status, a, b, pairs = classify(table, res, chromosomes, n_min, x_max, trans=True)
+    out = PileupResult(table, status, w, q)
+    S = 2 * w + 1
+    tot = [np.zeros((S, S)) for _ in range(4)]
+    for A, B in pairs:
+        pair = frozenset((_key(A), _key(B)))
+        rows = [k for k in range(len(table)) if status[k] is None
+                and frozenset((_key(table.chr1[k]), _key(table.chr2[k]))) == pair]
+        part, used = _empty_result(w, q), []
+        got = _read_pair(f, norm, A, B, res, device)
+        if got is None:
+            for k in rows:
+                status[k] = "no_pair"
+        else:
+            x, y, v, _res = got
+            n1 = int(torch.as_tensor(x).max().item()) + 1
+            n2 = int(torch.as_tensor(y).max().item()) + 1
+            for k in rows:
+                status[k] = "off_map" if a[k] >= n1 or b[k] >= n2 else "used"
+            used = [k for k in rows if status[k] == "used"]
+            part = pileup_trans_records(x, y, v, n1, n2, a[used], b[used], w, q)
+            del x, y, v, got
+            for j, k in enumerate(used):
+                out.obs_center[k], out.oe_center[k], out.p2ll[k] = part["center_obs"][j], part["center_oe"][j], part["p2ll"][j]
+        part = {k_: v_ for k_, v_ in part.items() if k_ not in ("valid", "expected", "obs", "oe")}   # device arrays freed
+        out.chromosomes.append(("%s,%s" % (A, B), len(rows), len(used), part))
+        for t, name in zip(tot, ("sum_obs", "count_obs", "sum_oe", "count_oe")):
+            t += part[name]                              # genome-wide: in the order the pairs ran
+        if verbose:
+            print("pile-up of the pair %s,%s: %d of %d rows used, P2M %r" % (A, B, len(used), len(rows), part["metrics"]["P2M"]))
+    apa, apa_oe = mean_map(tot[0], tot[1]), mean_map(tot[2], tot[3])
+    out.all = {"sum_obs": tot[0], "count_obs": tot[1], "sum_oe": tot[2], "count_oe": tot[3], "apa": apa, "apa_oe": apa_oe,
+               "metrics": metrics(apa, w, q), "metrics_oe": metrics(apa_oe, w, q)}
+    return out
+
+
+def pileup(f, loops, res, chromosomes=None, norm=False, bias=False, balance=None, w=10, q=6, n_min=None, x_max=None,
+           device=None, verbose=False, trans=False):
     """Pile up map `f` around the loops of `loops` (a TSV path or a LoopTable) at resolution `res` (bp).  The reader
-    arguments (`norm`, `bias`, `balance`) mean what they mean for the caller; `x_max` is in bp.  Returns a PileupResult."""
+    arguments (`norm`, `bias`, `balance`) mean what they mean for the caller; `n_min` is in bins (None: 30), `x_max` in bp.
+    trans=True piles up the inter-chromosomal rows instead, pair by pair (the module docstring has the rules); in that mode
+    `chromosomes` of the result holds ("A,B", rows in, loops used, pile-up dict).  Returns a PileupResult."""
     w, q, res = int(w), int(q), int(res)
     check_window(w, q)
     table = read_loops(loops) if isinstance(loops, (str, os.PathLike)) else loops
-    status, x, y, selected = classify(table, res, chromosomes, int(n_min), None if x_max is None else int(x_max) // res)
+    if trans:
+        return _pileup_trans(f, table, res, chromosomes, norm, bias, balance, w, q, n_min, x_max, device, verbose)
+    status, x, y, selected = classify(table, res, chromosomes, n_min, None if x_max is None else int(x_max) // res)
     out = PileupResult(table, status, w, q)
     S = 2 * w + 1
     tot = [np.zeros((S, S)) for _ in range(4)]
@@ -394,9 +559,11 @@ def parse_args(args):
     p.add_argument("--balance", dest="balance", default=None, metavar="ICE", help="balance the raw map on the GPU (ICE)")
     p.add_argument("-w", "--window", dest="w", type=int, default=10, help="window half-width in bins (default 10, at most 64)")
     p.add_argument("-q", "--corner", dest="q", type=int, default=6, help="corner size in bins (default 6)")
-    p.add_argument("-n", "--min-distance", dest="n_min", type=int, default=30,
+    p.add_argument("-n", "--min-distance", dest="n_min", type=int, default=None,
                    help="smallest loop size y - x in bins (default 30)")
     p.add_argument("-x", "--max-distance", dest="x_max", default=None, help="largest loop size in bp (default: none)")
+    p.add_argument("--trans", dest="trans", action="store_true",
+                   help="pile up the inter-chromosomal rows, pair by pair (.hic / .cool; -ch keeps the pairs inside the list)")
     return p.parse_args(args)
 
 
@@ -436,12 +603,19 @@ def main(argv=None):
         if not x_max:
             print("Error: Invalid -x distance %s" % args.x_max)
             return
+    from .hicfile import HicError
+    from .trans import TransError
     try:
         check_window(args.w, args.q)
         res_ = pileup(f, args.loops, res, chromosomes=args.chromosome, norm=args.norm_method, bias=args.biasfile or False,
-                      balance=balance, w=args.w, q=args.q, n_min=args.n_min, x_max=x_max, verbose=True)
-    except PileupError as e:
+                      balance=balance, w=args.w, q=args.q, n_min=args.n_min, x_max=x_max, verbose=True, trans=args.trans)
+    except (PileupError, TransError) as e:
         print("Error: %s" % e)
+        return
+    except HicError as e:
+        if not args.trans:
+            raise
+        print("Error: %s" % e)                           # a `.hic` file of version 6: the trans reader's own refusal
         return
     write_outputs(args.prefix, res_)
     a = res_.all["metrics"]

@@ -1,0 +1,140 @@
+"""NumPy restatement of the inter-chromosomal (trans) pile-up of mustache_amd/pileup.py -- the definition the device kernels
+(mustache_amd/csrc/mst_pileup_trans.hip) and the `--trans` run are tested against.  Host arrays only, no GPU.
+
+records: x = bins of A, y = bins of B, v > 0, on the n1 x n2 map.  The map is never made dense: windows are looked up among
+the sorted unique pixels, so a map with a million rows and a handful of records costs nothing.
+"""
+import math
+
+import numpy as np
+
+import pileup_reference as pr
+
+
+def _key(c):
+    return str(c).replace("chr", "")
+
+
+def pixels(x, y, v, n2):
+    """(sorted unique keys x * n2 + y, the largest value at each): a repeated pixel takes the largest of its values."""
+    key = np.asarray(x, np.int64) * int(n2) + np.asarray(y, np.int64)
+    v = np.asarray(v, np.float64)
+    order = np.lexsort((v, key))
+    key, v = key[order], v[order]
+    last = np.ones(len(key), bool)
+    last[:-1] = key[1:] != key[:-1]
+    return key[last], v[last]
+
+
+def valid_bins(x, y, n1, n2):
+    rows, cols = np.zeros(n1, bool), np.zeros(n2, bool)
+    rows[np.asarray(x, np.int64)] = True
+    cols[np.asarray(y, np.int64)] = True
+    return rows, cols
+
+
+def expected(x, y, v, n1, n2):
+    """E = fsum of v over all records (a repeated pixel's every record counted) / (#valid rows * #valid columns); 0 when the
+    product is 0."""
+    rows, cols = valid_bins(x, y, n1, n2)
+    cnt = int(rows.sum()) * int(cols.sum())
+    return math.fsum(np.asarray(v, np.float64).tolist()) / cnt if cnt else 0.0
+
+
+def windows(x, y, v, n1, n2, E, xs, ys, w):
+    """obs, oe [L, 2w+1, 2w+1]: cell [da + w, db + w] = pixel (a + da, b + db), NaN off the map, 0.0 where there is no record;
+    oe = obs / E, NaN where E is 0 or obs is NaN."""
+    key, val = pixels(x, y, v, n2)
+    xs, ys = np.asarray(xs, np.int64), np.asarray(ys, np.int64)
+    off = np.arange(-w, w + 1)
+    I = np.broadcast_to(xs[:, None, None] + off[None, :, None], (len(xs), 2 * w + 1, 2 * w + 1))
+    J = np.broadcast_to(ys[:, None, None] + off[None, None, :], I.shape)
+    on = (I >= 0) & (J >= 0) & (I < n1) & (J < n2)
+    obs = np.full(I.shape, np.nan)
+    want = I[on] * int(n2) + J[on]
+    got = np.zeros(len(want))
+    if len(key):
+        pos = np.minimum(np.searchsorted(key, want), len(key) - 1)
+        hit = key[pos] == want
+        got[hit] = val[pos[hit]]
+    obs[on] = got
+    oe = np.full(I.shape, np.nan)
+    if E != 0:
+        oe[on] = obs[on] / E
+    return obs, oe
+
+
+def aggregate(obs, oe, xs, ys):
+    """pileup_reference.aggregate: the loops sorted by (a, b)."""
+    return pr.aggregate(obs, oe, xs, ys)
+
+
+def pileup_trans_records(x, y, v, n1, n2, xs, ys, w=10, q=6):
+    """The whole pile-up of one pair, in the layout mustache_amd.pileup.pileup_trans_records returns (host arrays)."""
+    if not 0 <= w <= 64:
+        raise ValueError("window half-width w = %d is outside 0 .. 64" % w)
+    if not 1 <= q <= 2 * w + 1:
+        raise ValueError("corner size q = %d is outside 1 .. 2w + 1" % q)
+    xs, ys = np.asarray(xs, np.int64), np.asarray(ys, np.int64)
+    E = expected(x, y, v, n1, n2)
+    obs, oe = windows(x, y, v, n1, n2, E, xs, ys, w)
+    so, co, se, ce = aggregate(obs, oe, xs, ys)
+    c_obs, c_oe, p2ll = pr.per_loop(obs, oe, w, q) if len(xs) else (np.zeros(0), np.zeros(0), np.zeros(0))
+    apa, apa_oe = pr.mean_map(so, co), pr.mean_map(se, ce)
+    return {"valid": valid_bins(x, y, n1, n2), "expected": E, "obs": obs, "oe": oe, "sum_obs": so, "count_obs": co,
+            "sum_oe": se, "count_oe": ce, "apa": apa, "apa_oe": apa_oe, "center_obs": c_obs, "center_oe": c_oe, "p2ll": p2ll,
+            "metrics": pr.metrics(apa, w, q), "metrics_oe": pr.metrics(apa_oe, w, q)}
+
+
+def pileup_trans(rows, records, res, w=10, q=6, chromosomes=None):
+    """A whole `--trans` run restated.  rows: [(chr1, s1, e1, chr2, s2, e2)] in file order; records(A, B) -> (x, y, v) of the
+    pair in THAT orientation, or None when the map has no record of it.  Returns (status per row, per-row obs centre / oe
+    centre / P2LL (NaN where not used), [("A,B", rows in, loops used, pile-up dict)] in run order, the genome-wide dict)."""
+    keys = None if not chromosomes else {_key(c) for c in chromosomes}
+    n = len(rows)
+    status = [None] * n
+    a, b = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    pairs, orient, members = [], {}, {}
+    for k, (c1, s1, e1, c2, s2, e2) in enumerate(rows):
+        k1, k2 = _key(c1), _key(c2)
+        if k1 == k2:
+            status[k] = "cis"
+            continue
+        if keys is not None and not (k1 in keys and k2 in keys):
+            status[k] = "no_pair"
+            continue
+        p = frozenset((k1, k2))
+        if p not in orient:
+            orient[p] = k1
+            pairs.append((p, c1, c2))
+            members[p] = []
+        members[p].append(k)
+        b1, b2 = ((s1 + e1) // 2) // res, ((s2 + e2) // 2) // res
+        a[k], b[k] = (b1, b2) if orient[p] == k1 else (b2, b1)
+    S = 2 * w + 1
+    centre = np.full((n, 3), np.nan)
+    tot = [np.zeros((S, S)) for _ in range(4)]
+    parts = []
+    for p, A, B in pairs:
+        got = records(A, B)
+        used = []
+        if got is None or len(got[2]) == 0:
+            for k in members[p]:
+                status[k] = "no_pair"
+            part = pr.pileup_band(np.zeros((1, 1)), 1, 0, [], [], w, q)
+        else:
+            x, y, v = got
+            n1, n2 = int(np.max(x)) + 1, int(np.max(y)) + 1
+            for k in members[p]:
+                status[k] = "off_map" if a[k] >= n1 or b[k] >= n2 else "used"
+            used = [k for k in members[p] if status[k] == "used"]
+            part = pileup_trans_records(x, y, v, n1, n2, a[used], b[used], w, q)
+            for j, k in enumerate(used):
+                centre[k] = part["center_obs"][j], part["center_oe"][j], part["p2ll"][j]
+        parts.append(("%s,%s" % (A, B), len(members[p]), len(used), part))
+        for t, name in zip(tot, ("sum_obs", "count_obs", "sum_oe", "count_oe")):
+            t += part[name]
+    apa, apa_oe = pr.mean_map(tot[0], tot[1]), pr.mean_map(tot[2], tot[3])
+    whole = {"sum_obs": tot[0], "count_obs": tot[1], "sum_oe": tot[2], "count_oe": tot[3], "apa": apa, "apa_oe": apa_oe,
+             "metrics": pr.metrics(apa, w, q), "metrics_oe": pr.metrics(apa_oe, w, q)}
+    return status, centre, parts, whole
