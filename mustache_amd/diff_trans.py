@@ -28,7 +28,7 @@ tests/diff_trans_reference.py restates them in NumPy / SciPy.
 import numpy as np
 
 from ._lib import ptr as _ptr, stream as _stream
-from .trans import TRANS_CHUNK, TransCaller, TransError, owned_range, read_trans_contacts, trans_tiling
+from .trans import TRANS_CHUNK, TransCaller, TransError, owned_rows, prepared_tiles, read_trans_contacts, trans_tiling
 
 
 class DiffTransCaller(TransCaller):
@@ -50,7 +50,8 @@ class DiffTransCaller(TransCaller):
         from .diff_mustache import _pair_tails
         eng, dev = self.eng, self.device
         lib = eng.lib
-        C, (rs, re), (cs, ce) = trans_tiling(n1, n2, self.chunk)
+        tiling = trans_tiling(n1, n2, self.chunk)
+        C, (rs, _), (cs, _) = tiling
         tiles = [(i, j) for i in range(len(rs)) for j in range(len(cs))]
         out = []
         for g0 in range(0, len(tiles), self.tiles_per_launch):
@@ -58,24 +59,18 @@ class DiffTransCaller(TransCaller):
             P = len(group)
             row0 = torch.tensor([rs[i] for i, _ in group], dtype=torch.int64, device=dev)
             col0 = torch.tensor([cs[j] for _, j in group], dtype=torch.int64, device=dev)
-            c = torch.empty((2 * P, C, C), dtype=torch.float64, device=dev)       # sample 1 in [0, P), sample 2 in [P, 2P)
-            nz = torch.empty((2 * P, C, C), dtype=torch.uint8, device=dev)
-            nzc = torch.empty(2 * P, dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
+
+            def fill(c):                                                         # sample 1 in [0, P), sample 2 in [P, 2P)
                 for (x, y, vz), half in ((s1, c[:P]), (s2, c[P:])):
                     _lib.check(lib.mst_trans_scatter_tiles(_ptr(x), _ptr(y), _ptr(vz), int(vz.numel()), _ptr(row0), _ptr(col0),
                                                            P, C, _ptr(half), _stream()))
-                _lib.check(lib.mst_trans_prologue(_ptr(c), _ptr(nz), _ptr(nzc), 2 * P, C, _stream()))
+            c, nz, nzc = prepared_tiles(eng, dev, 2 * P, C, fill)
+            with torch.cuda.device(dev):
                 batch = eng.run_filled_pairs(c, nz, nzc, tiles=True)
             tails = _pair_tails(batch, [(p, P + p, 0) for p in range(P)], pt, pt2, st, False)
             for (i, j), res4 in zip(group, tails):
-                rlo, rhi = owned_range(re, i)
-                clo, chi = owned_range(ce, j)
                 for tag, loops in enumerate(res4, start=1):
-                    for lx, ly, q, sg in loops:
-                        gx, gy = int(lx) + rs[i], int(ly) + cs[j]
-                        if rlo <= gx < rhi and clo <= gy < chi:
-                            out.append([np.int64(gx), np.int64(gy), q, sg, tag])
+                    out += [row + [tag] for row in owned_rows(loops, tiling, i, j)]
             del batch, c, nz
         out.sort(key=lambda r: (r[4], int(r[0]), int(r[1])))
         return out

@@ -1,4 +1,4 @@
-"""Inter-chromosomal (trans) loop calling for one chromosome pair (A, B) on the GPU.
+"""Inter-chromosomal (trans) loop calling for one chromosome pair (A, B) on the GPU (and what the other trans callers share).
 
 The reference's trans branch is dead code (mustache.py:939-942 calls inter_normalize_map with the wrong arguments and never
 tiles), so the semantics are fixed here; tests/trans_reference.py restates them in NumPy / SciPy.
@@ -32,29 +32,27 @@ class TransError(RuntimeError):
     """A trans request this package refuses (the CLI prints it as an `Error:` line)."""
 
 
+def window_start(i, n, C, K, overlap=TRANS_OVERLAP):
+    """where window i of the K windows of an axis of length n starts: i (C - 256), the last one at max(0, n - C)"""
+    return i * (C - overlap) if i < K - 1 else max(0, n - C)
+
+
 def trans_axis_tiles(n, chunk, overlap=TRANS_OVERLAP):
-    """(start[], end[]) of one axis: the reference's cis tiling formula (mustache.py:896-910) with CHUNK = chunk."""
+    """(start[], end[]) of one axis: the reference's cis tiling formula (mustache.py:896-910) with CHUNK = chunk, closed form."""
     n = int(n)
     if n <= chunk:
         return [0], [n]
-    start, end = [0], [chunk]
-    while end[-1] < n:
-        start.append(end[-1] - overlap)
-        end.append(start[-1] + chunk)
-    end[-1] = n
-    start[-1] = max(0, n - chunk)
-    return start, end
+    if chunk <= overlap:
+        raise ValueError("trans tiles of %d bins cannot overlap by %d" % (chunk, overlap))
+    K = 1 - (chunk - n) // (chunk - overlap)                      # 1 + ceil((n - chunk) / (chunk - overlap))
+    start = [window_start(i, n, chunk, K, overlap) for i in range(K)]
+    return start, [s + chunk for s in start[:-1]] + [n]
 
 
 def trans_tiling(n1, n2, chunk=TRANS_CHUNK):
     """(C, rows, cols): tile size and the (start, end) lists of both axes."""
     C = min(int(chunk), max(int(n1), int(n2)))
     return C, trans_axis_tiles(n1, C), trans_axis_tiles(n2, C)
-
-
-def owned_range(ends, i):
-    """[lo, hi) that tile i of an axis owns: [end_{i-1}, end_i), end_{-1} = 0."""
-    return (ends[i - 1] if i > 0 else 0), ends[i]
 
 
 def zscore_device(v, device=None):
@@ -146,16 +144,60 @@ def read_trans_contacts(f, norm_method, chr_a, chr_b, res, device=None):
     return x, y, v, res
 
 
+def tiles_per_launch_of(tiles_per_launch=None):
+    """the tiles of one launch: the caller's number, else MUSTACHE_TRANS_TILES, else 64"""
+    return int(tiles_per_launch or os.environ.get("MUSTACHE_TRANS_TILES", "64"))
+
+
+def prepared_tiles(eng, dev, B, C, fill):
+    """(c, nz, nzc) of B tiles of C on `dev`: c [B, C, C] float64 as `fill(c)`, the caller's scatter, leaves it; nz = c != 0
+    and its count per tile (mst_trans_prologue: rule 4's first clause)"""
+    import torch
+    from . import _lib
+    c = torch.empty((B, C, C), dtype=torch.float64, device=dev)
+    nz = torch.empty((B, C, C), dtype=torch.uint8, device=dev)
+    nzc = torch.empty(B, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        fill(c)
+        _lib.check(eng.lib.mst_trans_prologue(_ptr(c), _ptr(nz), _ptr(nzc), B, C, _stream()))
+    return c, nz, nzc
+
+
+def tile_loops(eng, dev, B, C, fill, st, pt):
+    """Rules 4-5 on the B tiles of one launch: one scatter (`fill`), one prologue, one fused scale-space launch
+    (mst_scale_space over dense tiles) and one batched tail.  Per tile its loops [x, y, fdr, sigma] in TILE coordinates."""
+    import torch
+    from .batches import BlockBatch
+    from .tail import batch_tail
+    c, nz, nzc = prepared_tiles(eng, dev, B, C, fill)
+    with torch.cuda.device(dev):
+        found, fits = eng.sigma_loop(c, nz, nzc, with_value=False, select_below=pt)
+    batch = BlockBatch(eng, c, nz, C, B, nzc, found, fits)
+    return batch_tail(batch, list(range(B)), [0] * B, pt, st, intra=False)
+
+
+def owned_rows(loops, tiling, i, j):
+    """the map rows [x, y, fdr, sigma] of tile (i, j)'s loops (tile coordinates) that the tile owns (rule 3; end_{-1} = 0)"""
+    _, (rs, re), (cs, ce) = tiling
+    rlo, clo = (re[i - 1] if i else 0), (ce[j - 1] if j else 0)
+    out = []
+    for lx, ly, q, sg in loops:
+        gx, gy = int(lx) + rs[i], int(ly) + cs[j]
+        if rlo <= gx < re[i] and clo <= gy < ce[j]:
+            out.append([np.int64(gx), np.int64(gy), q, sg])
+    return out
+
+
 class TransCaller:
     """Rules 2-6 on the GPU for one pair's records.  `tiles_per_launch` tiles go through one scatter, one prologue and one
-    fused scale-space launch (mst_scale_space over dense tiles) and one batched tail."""
+    fused scale-space launch (mst_scale_space over dense tiles) and one batched tail (tile_loops)."""
 
     def __init__(self, octave_values=(1.6, 3.2), device=None, tiles_per_launch=None, chunk=TRANS_CHUNK):
         from .mustache import _engine
         self.chunk = int(chunk)            # rule 3's 2000; smaller values only to exercise many tiles on small maps
         self.eng = _engine(octave_values)
         self.device = self.eng.device if device is None else device
-        self.tiles_per_launch = int(tiles_per_launch or os.environ.get("MUSTACHE_TRANS_TILES", "64"))
+        self.tiles_per_launch = tiles_per_launch_of(tiles_per_launch)
 
     def normalize(self, x, y, v):
         """device (x int32, y int32, v' float64) and (mean, std, n) of rule 2"""
@@ -170,11 +212,9 @@ class TransCaller:
         """rules 3-6 on normalised device records: loops [x, y, fdr, sigma] sorted by (x, y)"""
         import torch
         from . import _lib
-        from .batches import BlockBatch
-        from .tail import batch_tail
-        eng, dev = self.eng, self.device
-        lib = eng.lib
-        C, (rs, re), (cs, ce) = trans_tiling(n1, n2, self.chunk)
+        dev, lib = self.device, self.eng.lib
+        tiling = trans_tiling(n1, n2, self.chunk)
+        C, (rs, _), (cs, _) = tiling
         tiles = [(i, j) for i in range(len(rs)) for j in range(len(cs))]
         out = []
         for g0 in range(0, len(tiles), self.tiles_per_launch):
@@ -182,24 +222,12 @@ class TransCaller:
             B = len(group)
             row0 = torch.tensor([rs[i] for i, _ in group], dtype=torch.int64, device=dev)
             col0 = torch.tensor([cs[j] for _, j in group], dtype=torch.int64, device=dev)
-            c = torch.empty((B, C, C), dtype=torch.float64, device=dev)
-            nz = torch.empty((B, C, C), dtype=torch.uint8, device=dev)
-            nzc = torch.empty(B, dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
+
+            def fill(c):
                 _lib.check(lib.mst_trans_scatter_tiles(_ptr(x), _ptr(y), _ptr(vz), int(vz.numel()), _ptr(row0), _ptr(col0), B, C,
                                                        _ptr(c), _stream()))
-                _lib.check(lib.mst_trans_prologue(_ptr(c), _ptr(nz), _ptr(nzc), B, C, _stream()))
-                found, fits = eng.sigma_loop(c, nz, nzc, with_value=False, select_below=pt)
-            batch = BlockBatch(eng, c, nz, C, B, nzc, found, fits)
-            loops = batch_tail(batch, list(range(B)), [0] * B, pt, st, intra=False)
-            for (i, j), lp in zip(group, loops):
-                rlo, rhi = owned_range(re, i)
-                clo, chi = owned_range(ce, j)
-                for lx, ly, q, sg in lp:
-                    gx, gy = int(lx) + rs[i], int(ly) + cs[j]
-                    if rlo <= gx < rhi and clo <= gy < chi:
-                        out.append([np.int64(gx), np.int64(gy), q, sg])
-            del c, nz
+            for (i, j), lp in zip(group, tile_loops(self.eng, dev, B, C, fill, st, pt)):
+                out += owned_rows(lp, tiling, i, j)
         out.sort(key=lambda r: (int(r[0]), int(r[1])))
         return out
 

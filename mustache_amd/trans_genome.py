@@ -14,15 +14,13 @@ call_trans_coo returns for that pair alone.  What changes is how the work reache
   could report a loop; a tile it keeps still meets rule 4 in the tail.
 * The kept tiles, in pair-major order, are cut into launch groups: runs of up to `tiles_per_launch` tiles of equal C.  A
   group's pairs are a contiguous range, so its records are one range of the batch; mst_trans_scatter_worklist writes them into
-  the group's tiles, finding the windows that hold a record from its coordinates.  Everything after the scatter is the code of
-  TransCaller.run_tiles: mst_trans_prologue, the sigma loop, the batched tail, ownership.
+  the group's tiles, finding the windows that hold a record from its coordinates.  Everything after the scatter is the code
+  TransCaller.run_tiles runs too: trans.tile_loops (mst_trans_prologue, the sigma loop, the batched tail) and trans.owned_rows.
 """
-import os
-
 import numpy as np
 
 from ._lib import ptr as _ptr, stream as _stream
-from .trans import TRANS_CHUNK, TRANS_OVERLAP, owned_range, trans_axis_tiles, trans_tiling
+from .trans import TRANS_CHUNK, TRANS_OVERLAP, owned_rows, tile_loops, tiles_per_launch_of, trans_tiling, window_start  # noqa: F401
 
 TRANS_MIN_TESTED = 10000          # rule 4's second threshold: below it a tile yields no loops
 RECORD_BYTES = 20                 # x int32, y int32, v float64 + its normalised value (in place): what a held record costs
@@ -43,18 +41,11 @@ def pair_table(dims, chunk=TRANS_CHUNK):
         if d is None:
             continue
         n1, n2 = int(d[0]), int(d[1])
-        C = min(int(chunk), max(n1, n2))
-        if max(n1, n2) > C and C <= TRANS_OVERLAP:                # more than one window: each starts C - 256 after the last
-            raise ValueError("trans tiles of %d bins cannot overlap by %d" % (C, TRANS_OVERLAP))
-        K1, K2 = len(trans_axis_tiles(n1, C)[0]), len(trans_axis_tiles(n2, C)[0])
+        C, (rs, _), (cs, _) = trans_tiling(n1, n2, chunk)         # refuses windows that cannot overlap by 256
+        K1, K2 = len(rs), len(cs)
         table[p] = (C, K1, K2, n1, n2, 0, base)
         base += K1 * K2
     return table, base
-
-
-def window_start(i, n, C, K):
-    """where window i of an axis of length n starts: i (C - 256), the last one at max(0, n - C)"""
-    return i * (C - TRANS_OVERLAP) if i < K - 1 else max(0, n - C)
 
 
 def windows_holding(a, n, C, K):
@@ -110,7 +101,7 @@ class TransGenomeCaller:
         self.eng = _engine(octave_values)
         self.device = self.eng.device
         self.st, self.pt, self.emit, self.chunk, self.verbose = st, pt, emit, int(chunk), verbose
-        self.tiles_per_launch = int(tiles_per_launch or os.environ.get("MUSTACHE_TRANS_TILES", "64"))
+        self.tiles_per_launch = tiles_per_launch_of(tiles_per_launch)
         self.budget = budget_bytes
         self.stats = stats if stats is not None else {}
         for k in ("tiles_total", "tiles_skipped", "launches", "batches"):
@@ -221,40 +212,25 @@ class TransGenomeCaller:
             self.emit(it[0], out[p])
 
     def _run_group(self, x, y, v, seg, seg_d, table, table_d, T, slot, tiles, C, p0, p1, tile_pair, tilings, dims, out):
-        """one launch: TransCaller.run_tiles' body for the tiles of a group"""
+        """one launch: the tiles of a group through trans.tile_loops, scattered from the work list"""
         import torch
         from . import _lib
-        from .batches import BlockBatch
-        from .tail import batch_tail
-        eng, dev = self.eng, self.device
-        lib = eng.lib
+        dev, lib = self.device, self.eng.lib
         B = len(tiles)
         idx = torch.as_tensor(np.asarray(tiles, np.int64)).to(dev)
         slot[idx] = torch.arange(B, dtype=torch.int32, device=dev)
-        c = torch.empty((B, C, C), dtype=torch.float64, device=dev)
-        nz = torch.empty((B, C, C), dtype=torch.uint8, device=dev)
-        nzc = torch.empty(B, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
+
+        def fill(c):
             _lib.check(lib.mst_trans_scatter_worklist(_ptr(x), _ptr(y), _ptr(v), _ptr(seg_d), _ptr(table_d), p0, p1 + 1,
                                                       int(seg[p1 + 1] - seg[p0]), T, _ptr(slot), B, C, _ptr(c), _stream()))
-            _lib.check(lib.mst_trans_prologue(_ptr(c), _ptr(nz), _ptr(nzc), B, C, _stream()))
-            found, fits = eng.sigma_loop(c, nz, nzc, with_value=False, select_below=self.pt)
+        loops = tile_loops(self.eng, dev, B, C, fill, self.st, self.pt)
         slot[idx] = -1
-        batch = BlockBatch(eng, c, nz, C, B, nzc, found, fits)
-        loops = batch_tail(batch, list(range(B)), [0] * B, self.pt, self.st, intra=False)
         for t, lp in zip(tiles, loops):
             p = int(tile_pair[t])
             if p not in tilings:
                 tilings[p] = trans_tiling(dims[p][0], dims[p][1], self.chunk)
-            _, (rs, re), (cs, ce) = tilings[p]
             i, j = divmod(t - int(table[p]["tile_base"]), int(table[p]["K2"]))
-            rlo, rhi = owned_range(re, i)
-            clo, chi = owned_range(ce, j)
-            for lx, ly, q, sg in lp:
-                gx, gy = int(lx) + rs[i], int(ly) + cs[j]
-                if rlo <= gx < rhi and clo <= gy < chi:
-                    out[p].append([np.int64(gx), np.int64(gy), q, sg])
-        del c, nz
+            out[p] += owned_rows(lp, tilings[p], i, j)
 
 
 def call_trans_genome(pairs, octave_values, st, pt, chunk=TRANS_CHUNK, tiles_per_launch=None, budget_bytes=None, stats=None,
