@@ -24,12 +24,17 @@
 #include <zlib.h>
 
 #include <atomic>
+#include <chrono>
 #include <cmath>
+#include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -312,9 +317,37 @@ bool block_near_diagonal(int32_t version, int32_t number, int32_t bbc, int32_t b
     return d == 0 || (d - 1) * (int64_t)bbc + 1 <= max_dist;
 }
 
+// The record filter of every decoder (mustache.py:370-388), whatever the sink: a sink has push(binX, binY, value) and reserve(n).
+template <class Sink>
+inline void emit(Sink &out, int64_t bx, int64_t by, float counts, const std::vector<double> *norm, int64_t max_dist) {
+    if (bx > by) {                                                         // intra blocks store binX <= binY; be lenient
+        const int64_t t = bx;
+        bx = by;
+        by = t;
+    }
+    if (max_dist >= 0 && by - bx > max_dist) return;
+    float c = counts;
+    if (norm) {
+        if (bx < 0 || (size_t)by >= norm->size()) return;                  // straw would index out of range; drop
+        c = (float)((double)counts / ((*norm)[(size_t)bx] * (*norm)[(size_t)by]));
+    }
+    if (std::isnan(c) || !(c > 0.0f)) return;                              // mustache.py:370-373, :385-388
+    out.push(bx, by, c);
+}
+
 struct Records {
     std::vector<int64_t> x, y;
     std::vector<double> v;
+    void push(int64_t bx, int64_t by, float c) {
+        x.push_back(bx);
+        y.push_back(by);
+        v.push_back((double)c);
+    }
+    void reserve(size_t room) {
+        x.reserve(room);
+        y.reserve(room);
+        v.reserve(room);
+    }
 };
 
 // packed sink: binX, binY - binX, float32 value appended to a worker's arena; y_limit = first bin past the caller's size
@@ -330,47 +363,6 @@ struct PackedSink {
     }
     void reserve(size_t) {}
 };
-
-inline void emit(PackedSink &out, int64_t bx, int64_t by, float counts, const std::vector<double> *norm, int64_t max_dist) {
-    if (bx > by) {
-        const int64_t t = bx;
-        bx = by;
-        by = t;
-    }
-    if (max_dist >= 0 && by - bx > max_dist) return;
-    float c = counts;
-    if (norm) {
-        if (bx < 0 || (size_t)by >= norm->size()) return;
-        c = (float)((double)counts / ((*norm)[(size_t)bx] * (*norm)[(size_t)by]));
-    }
-    if (std::isnan(c) || !(c > 0.0f)) return;
-    out.push(bx, by, c);
-}
-
-inline void emit(Records &out, int64_t bx, int64_t by, float counts, const std::vector<double> *norm, int64_t max_dist) {
-    if (bx > by) {                                                         // intra blocks store binX <= binY; be lenient
-        const int64_t t = bx;
-        bx = by;
-        by = t;
-    }
-    if (max_dist >= 0 && by - bx > max_dist) return;
-    float c = counts;
-    if (norm) {
-        if (bx < 0 || (size_t)by >= norm->size()) return;                  // straw would index out of range; drop
-        c = (float)((double)counts / ((*norm)[(size_t)bx] * (*norm)[(size_t)by]));
-    }
-    if (std::isnan(c) || !(c > 0.0f)) return;                              // mustache.py:370-373, :385-388
-    out.x.push_back(bx);
-    out.y.push_back(by);
-    out.v.push_back((double)c);
-}
-
-inline void sink_reserve(Records &out, size_t room) {
-    out.x.reserve(room);
-    out.y.reserve(room);
-    out.v.reserve(room);
-}
-inline void sink_reserve(PackedSink &, size_t) {}
 
 // MUSTACHE_HIC_ZLIB=1: inflate through zlib instead of mst_inflate.h (the cross-check the tests use)
 bool use_zlib() {
@@ -430,12 +422,17 @@ template <class Sink>
 void decode_records(int32_t version, const uint8_t *data, size_t n_out, Sink &out, const std::vector<double> *norm,
                     int64_t max_dist);
 
+// block `b` of the mapped file inflated into buf
+size_t inflate_block(const mst_hic *h, const BlockRef *b, std::vector<uint8_t> &buf, std::vector<uint8_t> &pad) {
+    return inflate_block(h->map + b->pos, (size_t)b->size, h->size - (size_t)b->pos - (size_t)b->size, buf, pad);
+}
+
 template <class Sink>
-void decode_block(int32_t version, const uint8_t *comp, size_t comp_size, size_t readable_past, std::vector<uint8_t> &buf,
-                  Sink &out, const std::vector<double> *norm, int64_t max_dist) {
+void decode_block(const mst_hic *h, const BlockRef *b, std::vector<uint8_t> &buf, Sink &out, const std::vector<double> *norm,
+                  int64_t max_dist) {
     static thread_local std::vector<uint8_t> pad;
-    const size_t n_out = inflate_block(comp, comp_size, readable_past, buf, pad);
-    decode_records(version, buf.data(), n_out, out, norm, max_dist);
+    const size_t n_out = inflate_block(h, b, buf, pad);
+    decode_records(h->version, buf.data(), n_out, out, norm, max_dist);
 }
 
 template <class Sink>
@@ -445,7 +442,7 @@ void decode_records(int32_t version, const uint8_t *data, size_t n_out, Sink &ou
     const int32_t n_rec = c.get<int32_t>();
     if (n_rec < 0) throw FormatError{"negative record count in a block"};
     const size_t room = (size_t)n_rec < n_out ? (size_t)n_rec : n_out;      // a record takes at least one byte
-    sink_reserve(out, room);
+    out.reserve(room);
     if (version < 7) {
         for (int32_t i = 0; i < n_rec; ++i) {
             const int32_t bx = c.get<int32_t>();
@@ -516,24 +513,8 @@ struct SlabSink {
         ++count;
         ymax = by > ymax ? by : ymax;
     }
+    void reserve(size_t) {}
 };
-
-inline void emit(SlabSink &out, int64_t bx, int64_t by, float counts, const std::vector<double> *norm, int64_t max_dist) {
-    if (bx > by) {
-        const int64_t t = bx;
-        bx = by;
-        by = t;
-    }
-    if (max_dist >= 0 && by - bx > max_dist) return;
-    float c = counts;
-    if (norm) {
-        if (bx < 0 || (size_t)by >= norm->size()) return;
-        c = (float)((double)counts / ((*norm)[(size_t)bx] * (*norm)[(size_t)by]));
-    }
-    if (std::isnan(c) || !(c > 0.0f)) return;
-    out.push(bx, by, c);
-}
-inline void sink_reserve(SlabSink &, size_t) {}
 
 // The layout almost every block of a real file has -- version 7-9, list of rows -- decoded with raw pointers: the row's byte
 // extent is checked once, the records go through the same emit() as the general decoder (same filters, same arithmetic).
@@ -742,125 +723,23 @@ static int default_threads() {
     return hw;
 }
 
-// Shared body of the two record readers: every near-diagonal block of the chromosome's intra matrix inflated and decoded on
-// the worker threads, one Records per block in file block order.  Returns 0 or an MST_IO_E_* code (message set).
-static int read_intra_parts(mst_hic *h, const char *chrom, int32_t resolution, const char *norm, int64_t max_dist_bins,
-                            int32_t n_threads, std::vector<Records> &part, int *threads_used) {
-    const int ci = find_chromosome(h, chrom);
-    if (ci < 0) return fail(MST_IO_E_NOTFOUND, "chromosome %s is not in the file", chrom);
-    const std::string key = std::to_string(ci) + "_" + std::to_string(ci);
-    auto it = h->matrices.find(key);
-    if (it == h->matrices.end()) return fail(MST_IO_E_NOTFOUND, "no intra-chromosomal matrix for %s", chrom);
-    ZoomData z = read_zoom(h, it->second.first, resolution);
-    if (!z.found) return fail(MST_IO_E_NOTFOUND, "resolution %d is not in the file", resolution);
-
-    std::vector<double> norm_vec;
-    const bool use_norm = norm && *norm && strcmp(norm, "NONE") != 0;
-    if (use_norm) {
-        read_norm_index(h);
-        auto nit = h->norm_index.find(norm_key(norm, ci, "BP", resolution));
-        if (nit == h->norm_index.end())
-            return fail(MST_IO_E_NOTFOUND, "no %s normalisation vector for %s at %d bp", norm, chrom, resolution);
-        norm_vec = read_norm_vector(h, nit->second);
-    }
-
-    std::vector<const BlockRef *> todo;
-    for (const BlockRef &b : z.blocks) {
-        if (b.size <= 0) continue;
-        if (b.pos < 0 || (uint64_t)b.pos + (uint64_t)b.size > h->size) throw FormatError{"block outside the file"};
-        if (block_near_diagonal(h->version, b.number, z.block_bin_count, z.block_column_count, max_dist_bins))
-            todo.push_back(&b);
-    }
-    int nt = n_threads > 0 ? n_threads : default_threads();
+// The ONE thread-count rule: the caller's request or the default, at least 1, at most one per job, and for a stream at most
+// `slab_bound` = n_slabs - 1 (every worker holds a slab; one more keeps the consumer fed).
+static int worker_count(int32_t requested, size_t jobs, int32_t slab_bound = 0) {
+    int nt = requested > 0 ? requested : default_threads();
     if (nt < 1) nt = 1;
-    if ((size_t)nt > todo.size()) nt = todo.empty() ? 1 : (int)todo.size();
-    part.assign(todo.size(), Records());
-    std::atomic<size_t> next(0);
-    std::atomic<int> bad(0);
-    const char *bad_what = nullptr;
-    auto work = [&]() {
-        std::vector<uint8_t> buf;
-        for (;;) {
-            const size_t i = next.fetch_add(1);
-            if (i >= todo.size() || bad.load()) return;
-            try {
-                decode_block(h->version, h->map + todo[i]->pos, (size_t)todo[i]->size,
-                             h->size - (size_t)todo[i]->pos - (size_t)todo[i]->size, buf, part[i],
-                             use_norm ? &norm_vec : nullptr, max_dist_bins);
-            } catch (const FormatError &e) {
-                bad_what = e.what;
-                bad.store(1);
-                return;
-            } catch (...) {
-                bad_what = "out of memory";
-                bad.store(1);
-                return;
-            }
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nt; ++t) pool.emplace_back(work);
-    work();
-    for (auto &t : pool) t.join();
-    if (bad.load()) return fail(MST_IO_E_ZLIB, "block decode failed: %s", bad_what ? bad_what : "?");
-    *threads_used = nt;
-    return MST_IO_OK;
+    if ((size_t)nt > jobs) nt = jobs ? (int)jobs : 1;
+    if (slab_bound > 0 && nt > slab_bound) nt = slab_bound;
+    return nt;
 }
 
-// run `fn(i)` for i in [0, n) on nt threads (dynamic dealing)
+static int decode_failed(const char *what) { return fail(MST_IO_E_ZLIB, "block decode failed: %s", what); }
+
+// The exception tail of every entry point that parses the file on the calling thread.
 template <class F>
-static void parallel_for(size_t n, int nt, F fn) {
-    std::atomic<size_t> next(0);
-    auto body = [&]() {
-        for (;;) {
-            const size_t i = next.fetch_add(1);
-            if (i >= n) return;
-            fn(i);
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nt; ++t) pool.emplace_back(body);
-    body();
-    for (auto &t : pool) t.join();
-}
-
-extern "C" int64_t mst_hic_read_intra(mst_hic *h, const char *chrom, int32_t resolution, const char *norm,
-                                      int64_t max_dist_bins, int32_t n_threads, int64_t **x, int64_t **y, double **v) {
-    if (!h || !chrom || !x || !y || !v || resolution <= 0) return fail(MST_IO_E_ARG, "mst_hic_read_intra: bad argument");
-    *x = *y = nullptr;
-    *v = nullptr;
+static auto guarded(F body) -> decltype(body()) {
     try {
-        std::vector<Records> part;
-        int nt = 1;
-        const int rc = read_intra_parts(h, chrom, resolution, norm, max_dist_bins, n_threads, part, &nt);
-        if (rc != MST_IO_OK) return rc;
-        std::vector<size_t> offs(part.size() + 1, 0);
-        for (size_t i = 0; i < part.size(); ++i) offs[i + 1] = offs[i] + part[i].v.size();
-        const size_t total = offs[part.size()];
-        int64_t *ox = (int64_t *)malloc((total ? total : 1) * sizeof(int64_t));
-        int64_t *oy = (int64_t *)malloc((total ? total : 1) * sizeof(int64_t));
-        double *ov = (double *)malloc((total ? total : 1) * sizeof(double));
-        if (!ox || !oy || !ov) {
-            free(ox);
-            free(oy);
-            free(ov);
-            return fail(MST_IO_E_FILE, "out of memory for %zu records", total);
-        }
-        // concatenate in file block order (deterministic), the copies spread over the same worker threads
-        parallel_for(part.size(), nt, [&](size_t i) {
-            Records &r = part[i];
-            if (r.v.empty()) return;
-            memcpy(ox + offs[i], r.x.data(), r.v.size() * sizeof(int64_t));
-            memcpy(oy + offs[i], r.y.data(), r.v.size() * sizeof(int64_t));
-            memcpy(ov + offs[i], r.v.data(), r.v.size() * sizeof(double));
-            std::vector<int64_t>().swap(r.x);                      // release the block's buffers as we go
-            std::vector<int64_t>().swap(r.y);
-            std::vector<double>().swap(r.v);
-        });
-        *x = ox;
-        *y = oy;
-        *v = ov;
-        return (int64_t)total;
+        return body();
     } catch (const FormatError &e) {
         return fail(MST_IO_E_FORMAT, "%s", e.what);
     } catch (...) {
@@ -868,30 +747,86 @@ extern "C" int64_t mst_hic_read_intra(mst_hic *h, const char *chrom, int32_t res
     }
 }
 
-// block list + normalisation vector of one chromosome's intra matrix (shared by the record readers)
-static int intra_todo(mst_hic *h, const char *chrom, int32_t resolution, const char *norm, int64_t max_dist_bins,
-                      std::vector<const BlockRef *> &todo, ZoomData &z, std::vector<double> &norm_vec, bool *use_norm) {
-    const int ci = find_chromosome(h, chrom);
-    if (ci < 0) return fail(MST_IO_E_NOTFOUND, "chromosome %s is not in the file", chrom);
-    const std::string key = std::to_string(ci) + "_" + std::to_string(ci);
-    auto it = h->matrices.find(key);
-    if (it == h->matrices.end()) return fail(MST_IO_E_NOTFOUND, "no intra-chromosomal matrix for %s", chrom);
-    z = read_zoom(h, it->second.first, resolution);
-    if (!z.found) return fail(MST_IO_E_NOTFOUND, "resolution %d is not in the file", resolution);
-    *use_norm = norm && *norm && strcmp(norm, "NONE") != 0;
-    if (*use_norm) {
+// The one-shot forms' block runner: body(i, t) for i in [0, n) on nt threads, t = the worker's index (dynamic dealing).  The
+// first exception wins and stops the dealing; returns its text (FormatError texts are literals), or null when all went well.
+template <class F>
+static const char *run_blocks(size_t n, int nt, F body) {
+    std::atomic<size_t> next(0);
+    std::atomic<const char *> bad(nullptr);
+    auto work = [&](int t) {
+        for (;;) {
+            const size_t i = next.fetch_add(1);
+            if (i >= n || bad.load()) return;
+            const char *what = nullptr;
+            try {
+                body(i, t);
+            } catch (const FormatError &e) {
+                what = e.what;
+            } catch (...) {
+                what = "out of memory";
+            }
+            if (what) {
+                const char *none = nullptr;
+                bad.compare_exchange_strong(none, what);
+                return;
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt; ++t) pool.emplace_back(work, t);
+    work(0);
+    for (auto &t : pool) t.join();
+    return bad.load();
+}
+
+// The ONE prologue of every read: what a read needs of one matrix at one resolution.  `todo` points into `zoom.blocks`, so a
+// Matrix is filled where it stays (a stream holds one as a member) and is never copied.
+struct Matrix {
+    ZoomData zoom;
+    std::vector<const BlockRef *> todo;
+    std::vector<double> norm_vec, norm_vec2;                          // pair: the vectors of A and of B
+    bool use_norm = false;
+    int64_t chrom_length = 0, chrom_length2 = 0;
+    int32_t transposed = 0;                                           // pair: the file stores it as (B, A)
+};
+
+// chrom_b == null: the intra matrix of chrom_a, its blocks that can hold a record within max_dist_bins of the diagonal;
+// otherwise the matrix of the pair (chrom_a, chrom_b), every block; `fn` = the entry point, named when the pair is no pair.
+// Returns 0 or an MST_IO_E_* code (message set).
+static int open_matrix(mst_hic *h, const char *chrom_a, const char *chrom_b, int32_t resolution, const char *norm,
+                       int64_t max_dist_bins, Matrix &m, const char *fn = "") {
+    const int ca = find_chromosome(h, chrom_a), cb = chrom_b ? find_chromosome(h, chrom_b) : ca;
+    if (ca < 0) return fail(MST_IO_E_NOTFOUND, "chromosome %s is not in the file", chrom_a);
+    if (cb < 0) return fail(MST_IO_E_NOTFOUND, "chromosome %s is not in the file", chrom_b);
+    if (chrom_b && ca == cb) return fail(MST_IO_E_ARG, "%s: %s and %s are one chromosome", fn, chrom_a, chrom_b);
+    const int lo = ca < cb ? ca : cb, hi = ca < cb ? cb : ca;
+    auto it = h->matrices.find(std::to_string(lo) + "_" + std::to_string(hi));
+    if (it == h->matrices.end())
+        return chrom_b ? fail(MST_IO_E_NOTFOUND, "no matrix for the pair %s, %s", chrom_a, chrom_b)
+                       : fail(MST_IO_E_NOTFOUND, "no intra-chromosomal matrix for %s", chrom_a);
+    m.zoom = read_zoom(h, it->second.first, resolution);
+    if (!m.zoom.found) return fail(MST_IO_E_NOTFOUND, "resolution %d is not in the file", resolution);
+    m.use_norm = norm && *norm && strcmp(norm, "NONE") != 0;
+    if (m.use_norm) {
         read_norm_index(h);
-        auto nit = h->norm_index.find(norm_key(norm, ci, "BP", resolution));
-        if (nit == h->norm_index.end())
-            return fail(MST_IO_E_NOTFOUND, "no %s normalisation vector for %s at %d bp", norm, chrom, resolution);
-        norm_vec = read_norm_vector(h, nit->second);
+        for (int side = 0; side < (chrom_b ? 2 : 1); ++side) {
+            const int ci = side ? cb : ca;
+            auto nit = h->norm_index.find(norm_key(norm, ci, "BP", resolution));
+            if (nit == h->norm_index.end())
+                return fail(MST_IO_E_NOTFOUND, "no %s normalisation vector for %s at %d bp", norm,
+                            chrom_b ? h->chroms[(size_t)ci].name.c_str() : chrom_a, resolution);
+            (side ? m.norm_vec2 : m.norm_vec) = read_norm_vector(h, nit->second);
+        }
     }
-    for (const BlockRef &b : z.blocks) {
+    for (const BlockRef &b : m.zoom.blocks) {
         if (b.size <= 0) continue;
         if (b.pos < 0 || (uint64_t)b.pos + (uint64_t)b.size > h->size) throw FormatError{"block outside the file"};
-        if (block_near_diagonal(h->version, b.number, z.block_bin_count, z.block_column_count, max_dist_bins))
-            todo.push_back(&b);
+        if (chrom_b || block_near_diagonal(h->version, b.number, m.zoom.block_bin_count, m.zoom.block_column_count, max_dist_bins))
+            m.todo.push_back(&b);
     }
+    m.chrom_length = h->chroms[(size_t)ca].length;
+    m.chrom_length2 = h->chroms[(size_t)cb].length;
+    m.transposed = ca > cb ? 1 : 0;
     return MST_IO_OK;
 }
 
@@ -914,6 +849,54 @@ static void split_todo(std::vector<const BlockRef *> &todo, int32_t part, int32_
     todo.swap(own);
 }
 
+extern "C" int64_t mst_hic_read_intra(mst_hic *h, const char *chrom, int32_t resolution, const char *norm,
+                                      int64_t max_dist_bins, int32_t n_threads, int64_t **x, int64_t **y, double **v) {
+    if (!h || !chrom || !x || !y || !v || resolution <= 0) return fail(MST_IO_E_ARG, "mst_hic_read_intra: bad argument");
+    *x = *y = nullptr;
+    *v = nullptr;
+    return guarded([&]() -> int64_t {
+        Matrix m;
+        const int rc = open_matrix(h, chrom, nullptr, resolution, norm, max_dist_bins, m);
+        if (rc != MST_IO_OK) return rc;
+        // one Records per block, in file block order
+        const int nt = worker_count(n_threads, m.todo.size());
+        std::vector<Records> part(m.todo.size());
+        std::vector<std::vector<uint8_t>> bufs((size_t)nt);
+        const char *bad = run_blocks(part.size(), nt, [&](size_t i, int t) {
+            decode_block(h, m.todo[i], bufs[(size_t)t], part[i], m.use_norm ? &m.norm_vec : nullptr, max_dist_bins);
+        });
+        if (bad) return decode_failed(bad);
+        std::vector<size_t> offs(part.size() + 1, 0);
+        for (size_t i = 0; i < part.size(); ++i) offs[i + 1] = offs[i] + part[i].v.size();
+        const size_t total = offs[part.size()];
+        int64_t *ox = (int64_t *)malloc((total ? total : 1) * sizeof(int64_t));
+        int64_t *oy = (int64_t *)malloc((total ? total : 1) * sizeof(int64_t));
+        double *ov = (double *)malloc((total ? total : 1) * sizeof(double));
+        if (!ox || !oy || !ov) {
+            free(ox);
+            free(oy);
+            free(ov);
+            return fail(MST_IO_E_FILE, "out of memory for %zu records", total);
+        }
+        // concatenate in file block order (deterministic), the copies spread over the same worker threads (memcpy and the
+        // release of a vector cannot throw: nothing to report)
+        (void)run_blocks(part.size(), nt, [&](size_t i, int) {
+            Records &r = part[i];
+            if (r.v.empty()) return;
+            memcpy(ox + offs[i], r.x.data(), r.v.size() * sizeof(int64_t));
+            memcpy(oy + offs[i], r.y.data(), r.v.size() * sizeof(int64_t));
+            memcpy(ov + offs[i], r.v.data(), r.v.size() * sizeof(double));
+            std::vector<int64_t>().swap(r.x);                      // release the block's buffers as we go
+            std::vector<int64_t>().swap(r.y);
+            std::vector<double>().swap(r.v);
+        });
+        *x = ox;
+        *y = oy;
+        *v = ov;
+        return (int64_t)total;
+    });
+}
+
 extern "C" int64_t mst_hic_decode_intra_packed(mst_hic *h, const char *chrom, int32_t resolution, const char *norm,
                                                int64_t max_dist_bins, int64_t chrom_size_bp, int32_t n_threads,
                                                int64_t *n_bins) {
@@ -929,19 +912,14 @@ extern "C" int64_t mst_hic_decode_intra_packed_part(mst_hic *h, const char *chro
         return fail(MST_IO_E_ARG, "mst_hic_decode_intra_packed: bad argument");
     *n_bins = 0;
     h->packed_total = -1;
-    try {
-        std::vector<const BlockRef *> todo;
-        ZoomData z;
-        std::vector<double> norm_vec;
-        bool use_norm = false;
-        const int rc = intra_todo(h, chrom, resolution, norm, max_dist_bins, todo, z, norm_vec, &use_norm);
+    return guarded([&]() -> int64_t {
+        Matrix m;
+        const int rc = open_matrix(h, chrom, nullptr, resolution, norm, max_dist_bins, m);
         if (rc != MST_IO_OK) return rc;
-        if (blocks_total) *blocks_total = (int32_t)todo.size();
-        split_todo(todo, part, n_parts);
-        if (blocks_mine) *blocks_mine = (int32_t)todo.size();
-        int nt = n_threads > 0 ? n_threads : default_threads();
-        if (nt < 1) nt = 1;
-        if ((size_t)nt > todo.size()) nt = todo.empty() ? 1 : (int)todo.size();
+        if (blocks_total) *blocks_total = (int32_t)m.todo.size();
+        split_todo(m.todo, part, n_parts);
+        if (blocks_mine) *blocks_mine = (int32_t)m.todo.size();
+        const int nt = worker_count(n_threads, m.todo.size());
         if (h->arenas.size() < (size_t)nt) h->arenas.resize((size_t)nt);
         if (h->inflate_bufs.size() < (size_t)nt) h->inflate_bufs.resize((size_t)nt);
         for (auto &a : h->arenas) {
@@ -949,54 +927,29 @@ extern "C" int64_t mst_hic_decode_intra_packed_part(mst_hic *h, const char *chro
             a.d.clear();
             a.v.clear();
         }
-        h->spans.assign(todo.size(), mst_hic::PackedSpan{0, 0, 0});
+        h->spans.assign(m.todo.size(), mst_hic::PackedSpan{0, 0, 0});
         // straw's window end (mustache.py:320-333): no position at or past the chromosome size the caller gave
         const int64_t y_limit = chrom_size_bp > 0 ? (chrom_size_bp + resolution - 1) / resolution : INT64_MAX;
-        std::atomic<size_t> next(0);
-        std::atomic<int> bad(0);
-        const char *bad_what = nullptr;
-        std::vector<int64_t> ymax((size_t)nt, -1);
-        auto work = [&](int t) {
-            std::vector<uint8_t> &buf = h->inflate_bufs[(size_t)t];
-            PackedSink sink{&h->arenas[(size_t)t], y_limit, -1};
-            for (;;) {
-                const size_t i = next.fetch_add(1);
-                if (i >= todo.size() || bad.load()) break;
-                const size_t before = sink.a->v.size();
-                try {
-                    decode_block(h->version, h->map + todo[i]->pos, (size_t)todo[i]->size,
-                                 h->size - (size_t)todo[i]->pos - (size_t)todo[i]->size, buf, sink,
-                                 use_norm ? &norm_vec : nullptr, max_dist_bins);
-                } catch (const FormatError &e) {
-                    bad_what = e.what;
-                    bad.store(1);
-                    break;
-                } catch (...) {
-                    bad_what = "out of memory";
-                    bad.store(1);
-                    break;
-                }
-                h->spans[i] = mst_hic::PackedSpan{t, before, sink.a->v.size() - before};
-            }
-            ymax[(size_t)t] = sink.ymax;
+        struct alignas(64) Own {                                   // one per worker, a cache line each: ymax moves with every record
+            PackedSink sink;
         };
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nt; ++t) pool.emplace_back(work, t);
-        work(0);
-        for (auto &t : pool) t.join();
-        if (bad.load()) return fail(MST_IO_E_ZLIB, "block decode failed: %s", bad_what ? bad_what : "?");
+        std::vector<Own> sinks;
+        for (int t = 0; t < nt; ++t) sinks.push_back(Own{PackedSink{&h->arenas[(size_t)t], y_limit, -1}});
+        const char *bad = run_blocks(m.todo.size(), nt, [&](size_t i, int t) {
+            PackedSink &sink = sinks[(size_t)t].sink;
+            const size_t before = sink.a->v.size();
+            decode_block(h, m.todo[i], h->inflate_bufs[(size_t)t], sink, m.use_norm ? &m.norm_vec : nullptr, max_dist_bins);
+            h->spans[i] = mst_hic::PackedSpan{t, before, sink.a->v.size() - before};
+        });
+        if (bad) return decode_failed(bad);
         int64_t total = 0, top = -1;
         for (const auto &sp : h->spans) total += (int64_t)sp.count;
-        for (int64_t m : ymax) top = m > top ? m : top;
+        for (const Own &o : sinks) top = o.sink.ymax > top ? o.sink.ymax : top;
         if (top >= INT32_MAX) return fail(MST_IO_E_FORMAT, "bin index %lld does not fit 32 bits", (long long)top);
         h->packed_total = total;
         *n_bins = top + 1;
         return total;
-    } catch (const FormatError &e) {
-        return fail(MST_IO_E_FORMAT, "%s", e.what);
-    } catch (...) {
-        return fail(MST_IO_E_FORMAT, "unreadable file (out of memory?)");
-    }
+    });
 }
 
 extern "C" int mst_hic_fetch_packed(mst_hic *h, int32_t *x, int32_t *dist, float *v, int64_t capacity, int32_t n_threads) {
@@ -1006,11 +959,9 @@ extern "C" int mst_hic_fetch_packed(mst_hic *h, int32_t *x, int32_t *dist, float
                     (long long)h->packed_total);
     std::vector<size_t> offs(h->spans.size() + 1, 0);
     for (size_t i = 0; i < h->spans.size(); ++i) offs[i + 1] = offs[i] + h->spans[i].count;
-    int nt = n_threads > 0 ? n_threads : default_threads();
-    if (nt < 1) nt = 1;
-    if ((size_t)nt > h->spans.size()) nt = h->spans.empty() ? 1 : (int)h->spans.size();
-    // file block order (deterministic whatever thread decoded a block), the copies spread over the worker threads
-    parallel_for(h->spans.size(), nt, [&](size_t i) {
+    // file block order (deterministic whatever thread decoded a block), the copies spread over the worker threads (plain
+    // memcpy: the body cannot throw, nothing to report)
+    (void)run_blocks(h->spans.size(), worker_count(n_threads, h->spans.size()), [&](size_t i, int) {
         const mst_hic::PackedSpan &sp = h->spans[i];
         if (!sp.count) return;
         const mst_hic::PackedArena &a = h->arenas[(size_t)sp.arena];
@@ -1052,25 +1003,13 @@ extern "C" int64_t mst_hic_read_intra_packed(mst_hic *h, const char *chrom, int3
     return total;
 }
 
-// ---- streaming packed read -------------------------------------------------------------------------------------------------
-// Worker threads inflate and decode the chromosome's near-diagonal blocks (this part's share of them) straight into
-// caller-owned slabs; a slab is handed to the consumer as soon as the next block would not fit, so the consumer's H2D copies
-// run while later blocks are still being inflated.  No arena, no second copy, no total count needed in advance.
-#include <condition_variable>
-#include <deque>
-#include <mutex>
-
-struct mst_hic_stream {
-    mst_hic *h = nullptr;
-    std::vector<const BlockRef *> todo;
-    ZoomData zoom;
-    std::vector<double> norm_vec;
-    bool use_norm = false;
-    int64_t max_dist = -1, y_limit = INT64_MAX;
-    uint8_t *base = nullptr;
-    int32_t n_slabs = 0, dist_bytes = 2;
-    int64_t cap = 0;
-    std::vector<int64_t> counts;
+// ---- the slab queue of the streamed reads ------------------------------------------------------------------------------------
+// Slabs of caller-owned memory travel in a circle: free -> a worker fills one -> ready -> the consumer -> released -> free.
+// Worker threads deal the blocks of the stream's `matrix.todo` among themselves; what they do with a block is the stream's
+// Worker (block(b), publish(), and leave() under the lock when the thread ends).  A stream's per-slab metadata and totals are
+// written and read under this queue's lock: publish() and wait_ready() run the caller's `meta` while they hold it.
+struct SlabQueue {
+    struct Cancelled {};
     std::mutex mu;
     std::condition_variable cv_free, cv_ready;
     std::deque<int32_t> free_q, ready_q;
@@ -1079,10 +1018,6 @@ struct mst_hic_stream {
     int active = 0;
     bool failed = false, cancelled = false;
     std::string error;
-    int64_t ymax = -1, total = 0;
-    int32_t blocks_total = 0;
-
-    uint8_t *slab(int32_t i) const { return base + (size_t)i * (size_t)cap * (size_t)(8 + dist_bytes); }
 
     void fail_with(const char *what) {
         std::lock_guard<std::mutex> lk(mu);
@@ -1092,70 +1027,71 @@ struct mst_hic_stream {
         cv_ready.notify_all();
     }
 
-    struct Cancelled {};
+    // a free slab for a worker; waits for one, gives up (Cancelled) when the stream has failed or is being closed
+    int32_t acquire() {
+        std::unique_lock<std::mutex> lk(mu);
+        cv_free.wait(lk, [&] { return !free_q.empty() || failed || cancelled; });
+        if (failed || cancelled) throw Cancelled{};
+        const int32_t slab = free_q.front();
+        free_q.pop_front();
+        return slab;
+    }
 
-    // One worker: blocks are decoded straight into the slab it holds; a slab is handed over exactly when it is FULL (in the
-    // middle of a block if need be: a block may hold more records than a slab) and at the end of the work list, so the
-    // consumer sees a steady flow of full slabs however many workers there are.
-    struct Worker {
-        mst_hic_stream *s;
-        int32_t cur = -1;
-        SlabSink sink;
-        void publish() {
-            if (cur < 0) return;
-            std::lock_guard<std::mutex> lk(s->mu);
-            s->counts[(size_t)cur] = sink.count;
-            s->total += sink.count;
-            if (sink.count > 0) {
-                s->ready_q.push_back(cur);
-                s->cv_ready.notify_one();
-            } else {
-                s->free_q.push_back(cur);
-                s->cv_free.notify_one();
-            }
-            cur = -1;
+    // a worker is done with `slab`: to the consumer when it holds something, straight back to the free slabs when not
+    template <class Meta>
+    void publish(int32_t slab, bool has_content, Meta meta) {
+        std::lock_guard<std::mutex> lk(mu);
+        meta();
+        if (has_content) {
+            ready_q.push_back(slab);
+            cv_ready.notify_one();
+        } else {
+            free_q.push_back(slab);
+            cv_free.notify_one();
         }
-        void next_slab() {
-            publish();
-            std::unique_lock<std::mutex> lk(s->mu);
-            s->cv_free.wait(lk, [&] { return !s->free_q.empty() || s->failed || s->cancelled; });
-            if (s->failed || s->cancelled) throw Cancelled{};
-            cur = s->free_q.front();
-            s->free_q.pop_front();
-            lk.unlock();
-            uint8_t *m = s->slab(cur);
-            sink.x = reinterpret_cast<int32_t *>(m);
-            sink.v = reinterpret_cast<float *>(m + (size_t)s->cap * 4);
-            sink.d = m + (size_t)s->cap * 8;
-            sink.count = 0;
-            sink.cap = s->cap;
-        }
-        static void full(SlabSink &, void *self) { static_cast<Worker *>(self)->next_slab(); }
-    };
+    }
 
-    void work() {
-        std::vector<uint8_t> buf, pad;
-        Worker w{this, -1, SlabSink{nullptr, nullptr, nullptr, dist_bytes, 0, 0, y_limit, -1}};
-        w.sink.on_full = &Worker::full;
-        w.sink.ctx = &w;
+    // the consumer's side: 1 = meta(slab) was called for a filled slab, 2 = nothing yet, 0 = all delivered, < 0 = a worker failed
+    template <class Meta>
+    int wait_ready(int32_t timeout_ms, Meta meta) {
+        std::unique_lock<std::mutex> lk(mu);
+        auto ready = [&] { return !ready_q.empty() || failed || active == 0; };
+        if (timeout_ms < 0) cv_ready.wait(lk, ready);
+        else if (!cv_ready.wait_for(lk, std::chrono::milliseconds(timeout_ms), ready)) return 2;
+        if (failed) return decode_failed(error.c_str());
+        if (ready_q.empty()) return 0;
+        meta(ready_q.front());
+        ready_q.pop_front();
+        return 1;
+    }
+
+    void release(int32_t slab) {
+        std::lock_guard<std::mutex> lk(mu);
+        free_q.push_back(slab);
+        cv_free.notify_one();
+    }
+
+    void cancel_and_join() {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            cancelled = true;
+            cv_free.notify_all();
+        }
+        for (auto &t : workers) t.join();
+    }
+
+    template <class Stream>
+    void work(Stream *s) {
+        typename Stream::Worker w(s);
         try {
             for (;;) {
                 const size_t i = next.fetch_add(1);
-                if (i >= todo.size()) break;
+                if (i >= s->matrix.todo.size()) break;
                 {
                     std::lock_guard<std::mutex> lk(mu);
                     if (failed || cancelled) break;
                 }
-                const BlockRef *b = todo[i];
-                const size_t n_out = inflate_block(h->map + b->pos, (size_t)b->size, h->size - (size_t)b->pos - (size_t)b->size,
-                                                   buf, pad);
-                if (n_out < 4) throw FormatError{"truncated structure"};
-                int32_t n_rec;
-                memcpy(&n_rec, buf.data(), 4);
-                if (n_rec < 0) throw FormatError{"negative record count in a block"};
-                if (w.cur < 0) w.next_slab();
-                if (!decode_rows_fast(h->version, buf.data(), n_out, w.sink, use_norm ? &norm_vec : nullptr, max_dist))
-                    decode_records(h->version, buf.data(), n_out, w.sink, use_norm ? &norm_vec : nullptr, max_dist);
+                w.block(s->matrix.todo[i]);
             }
             w.publish();
         } catch (const Cancelled &) {
@@ -1165,9 +1101,79 @@ struct mst_hic_stream {
             fail_with("out of memory");
         }
         std::lock_guard<std::mutex> lk(mu);
-        ymax = w.sink.ymax > ymax ? w.sink.ymax : ymax;
+        w.leave();
         if (--active == 0) cv_ready.notify_all();
     }
+
+    // every slab free, then the workers: the stream's thread count under the n_slabs - 1 cap
+    template <class Stream>
+    void start(Stream *s, int32_t n_threads, int32_t n_slabs) {
+        for (int32_t i = 0; i < n_slabs; ++i) free_q.push_back(i);
+        const int nt = active = worker_count(n_threads, s->matrix.todo.size(), n_slabs - 1);
+        for (int t = 0; t < nt; ++t) workers.emplace_back([this, s] { work(s); });       // (a worker that ends lowers `active`)
+    }
+};
+
+// ---- streaming packed read -------------------------------------------------------------------------------------------------
+// Worker threads inflate and decode the chromosome's near-diagonal blocks (this part's share of them) straight into
+// caller-owned slabs; a slab is handed to the consumer as soon as the next block would not fit, so the consumer's H2D copies
+// run while later blocks are still being inflated.  No arena, no second copy, no total count needed in advance.
+struct mst_hic_stream {
+    mst_hic *h = nullptr;
+    Matrix matrix;
+    int64_t max_dist = -1, y_limit = INT64_MAX;
+    uint8_t *base = nullptr;
+    int32_t n_slabs = 0, dist_bytes = 2;
+    int64_t cap = 0;
+    std::vector<int64_t> counts;
+    int64_t ymax = -1, total = 0;
+    int32_t blocks_total = 0;
+    SlabQueue q;
+
+    // One worker: blocks are decoded straight into the slab it holds; a slab is handed over exactly when it is FULL (in the
+    // middle of a block if need be: a block may hold more records than a slab) and at the end of the work list, so the
+    // consumer sees a steady flow of full slabs however many workers there are.
+    struct Worker {
+        mst_hic_stream *s;
+        int32_t cur = -1;
+        SlabSink sink;
+        std::vector<uint8_t> buf, pad;
+        explicit Worker(mst_hic_stream *st) : s(st), sink{nullptr, nullptr, nullptr, st->dist_bytes, 0, 0, st->y_limit, -1} {
+            sink.on_full = &Worker::full;
+            sink.ctx = this;
+        }
+        void publish() {
+            if (cur < 0) return;
+            s->q.publish(cur, sink.count > 0, [&] {
+                s->counts[(size_t)cur] = sink.count;
+                s->total += sink.count;
+            });
+            cur = -1;
+        }
+        void next_slab() {
+            publish();
+            cur = s->q.acquire();
+            uint8_t *m = s->base + (size_t)cur * (size_t)s->cap * (size_t)(8 + s->dist_bytes);
+            sink.x = reinterpret_cast<int32_t *>(m);
+            sink.v = reinterpret_cast<float *>(m + (size_t)s->cap * 4);
+            sink.d = m + (size_t)s->cap * 8;
+            sink.count = 0;
+            sink.cap = s->cap;
+        }
+        static void full(SlabSink &, void *self) { static_cast<Worker *>(self)->next_slab(); }
+        void block(const BlockRef *b) {
+            const size_t n_out = inflate_block(s->h, b, buf, pad);
+            if (n_out < 4) throw FormatError{"truncated structure"};
+            int32_t n_rec;
+            memcpy(&n_rec, buf.data(), 4);
+            if (n_rec < 0) throw FormatError{"negative record count in a block"};
+            if (cur < 0) next_slab();
+            const std::vector<double> *norm = s->matrix.use_norm ? &s->matrix.norm_vec : nullptr;
+            if (!decode_rows_fast(s->h->version, buf.data(), n_out, sink, norm, s->max_dist))
+                decode_records(s->h->version, buf.data(), n_out, sink, norm, s->max_dist);
+        }
+        void leave() { s->ymax = sink.ymax > s->ymax ? sink.ymax : s->ymax; }
+    };
 };
 
 extern "C" int mst_hic_stream_open(mst_hic *h, const char *chrom, int32_t resolution, const char *norm, int64_t max_dist_bins,
@@ -1180,20 +1186,13 @@ extern "C" int mst_hic_stream_open(mst_hic *h, const char *chrom, int32_t resolu
     if (dist_bytes == 2 && (max_dist_bins < 0 || max_dist_bins > 65535))
         return fail(MST_IO_E_ARG, "mst_hic_stream_open: 16-bit distances need 0 <= max_dist_bins <= 65535");
     *out = nullptr;
-    mst_hic_stream *s = nullptr;
-    try {
-        s = new mst_hic_stream();
+    return guarded([&]() -> int {
+        std::unique_ptr<mst_hic_stream> s(new mst_hic_stream());
         s->h = h;
-        std::vector<const BlockRef *> todo;
-        const int rc = intra_todo(h, chrom, resolution, norm, max_dist_bins, todo, s->zoom, s->norm_vec, &s->use_norm);
-        if (rc != MST_IO_OK) {
-            delete s;
-            return rc;
-        }
-        // todo points into `zoom.blocks`, which intra_todo filled inside s->zoom: the pointers stay valid with the stream
-        s->blocks_total = (int32_t)todo.size();
-        split_todo(todo, part, n_parts);
-        s->todo.swap(todo);
+        const int rc = open_matrix(h, chrom, nullptr, resolution, norm, max_dist_bins, s->matrix);
+        if (rc != MST_IO_OK) return rc;
+        s->blocks_total = (int32_t)s->matrix.todo.size();
+        split_todo(s->matrix.todo, part, n_parts);
         s->max_dist = max_dist_bins;
         s->y_limit = chrom_size_bp > 0 ? (chrom_size_bp + resolution - 1) / resolution : INT64_MAX;
         s->base = static_cast<uint8_t *>(slab_memory);
@@ -1201,64 +1200,37 @@ extern "C" int mst_hic_stream_open(mst_hic *h, const char *chrom, int32_t resolu
         s->cap = slab_records;
         s->dist_bytes = dist_bytes;
         s->counts.assign((size_t)n_slabs, 0);
-        for (int32_t i = 0; i < n_slabs; ++i) s->free_q.push_back(i);
-        int nt = n_threads > 0 ? n_threads : default_threads();
-        if (nt < 1) nt = 1;
-        if ((size_t)nt > s->todo.size()) nt = s->todo.empty() ? 1 : (int)s->todo.size();
-        if (nt > n_slabs - 1) nt = n_slabs - 1;                 // every worker holds a slab; one more keeps the consumer fed
-        s->active = nt;
-        for (int t = 0; t < nt; ++t) s->workers.emplace_back([s] { s->work(); });
-        *out = s;
+        s->q.start(s.get(), n_threads, n_slabs);
+        *out = s.release();
         return MST_IO_OK;
-    } catch (const FormatError &e) {
-        delete s;
-        return fail(MST_IO_E_FORMAT, "%s", e.what);
-    } catch (...) {
-        delete s;
-        return fail(MST_IO_E_FORMAT, "unreadable file (out of memory?)");
-    }
+    });
 }
 
 extern "C" int mst_hic_stream_next(mst_hic_stream *s, int32_t timeout_ms, int32_t *slab, int64_t *count) {
     if (!s || !slab || !count) return fail(MST_IO_E_ARG, "mst_hic_stream_next: bad argument");
-    std::unique_lock<std::mutex> lk(s->mu);
-    auto ready = [&] { return !s->ready_q.empty() || s->failed || s->active == 0; };
-    if (timeout_ms < 0) s->cv_ready.wait(lk, ready);
-    else if (!s->cv_ready.wait_for(lk, std::chrono::milliseconds(timeout_ms), ready)) return 2;      // nothing yet
-    if (s->failed) return fail(MST_IO_E_ZLIB, "block decode failed: %s", s->error.c_str());
-    if (!s->ready_q.empty()) {
-        *slab = s->ready_q.front();
-        s->ready_q.pop_front();
-        *count = s->counts[(size_t)*slab];
-        return 1;
-    }
-    return 0;                                                                                         // all delivered
+    return s->q.wait_ready(timeout_ms, [&](int32_t i) {
+        *slab = i;
+        *count = s->counts[(size_t)i];
+    });
 }
 
 extern "C" int mst_hic_stream_release(mst_hic_stream *s, int32_t slab) {
     if (!s || slab < 0 || slab >= s->n_slabs) return fail(MST_IO_E_ARG, "mst_hic_stream_release: bad argument");
-    std::lock_guard<std::mutex> lk(s->mu);
-    s->free_q.push_back(slab);
-    s->cv_free.notify_one();
+    s->q.release(slab);
     return MST_IO_OK;
 }
 
 extern "C" int mst_hic_stream_close(mst_hic_stream *s, int64_t *n_bins, int64_t *total, int32_t *blocks_total,
                                     int32_t *blocks_mine) {
     if (!s) return MST_IO_OK;
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        s->cancelled = true;
-        s->cv_free.notify_all();
-    }
-    for (auto &t : s->workers) t.join();
+    s->q.cancel_and_join();
     int rc = MST_IO_OK;
-    if (s->failed) rc = fail(MST_IO_E_ZLIB, "block decode failed: %s", s->error.c_str());
+    if (s->q.failed) rc = decode_failed(s->q.error.c_str());
     else if (s->ymax >= INT32_MAX) rc = fail(MST_IO_E_FORMAT, "bin index %lld does not fit 32 bits", (long long)s->ymax);
     if (n_bins) *n_bins = s->ymax + 1;
     if (total) *total = s->total;
     if (blocks_total) *blocks_total = s->blocks_total;
-    if (blocks_mine) *blocks_mine = (int32_t)s->todo.size();
+    if (blocks_mine) *blocks_mine = (int32_t)s->matrix.todo.size();
     delete s;
     return rc;
 }
@@ -1272,38 +1244,18 @@ extern "C" int mst_hic_stream_close(mst_hic_stream *s, int64_t *n_bins, int64_t 
 // libmustache_hip.so), so no host thread touches a record.  Slab layout: payload from byte 0 upwards, directory entries from
 // the slab's end downwards (entry k at slab_bytes - 16 (k + 1)); a slab is handed over when the next row would not fit.
 // A block may be split between slabs at any row.  v6 blocks (plain records, no rows) are not served: MST_IO_E_FORMAT at open.
+// A trans stream delivers EVERY block of a pair's matrix in the same way.
 struct mst_hic_rawstream {
     mst_hic *h = nullptr;
-    std::vector<const BlockRef *> todo;
-    ZoomData zoom;
-    std::vector<double> norm_vec, norm_vec2;                          // trans: the vectors of A and of B
-    bool use_norm = false;
-    int64_t chrom_length2 = 0;
+    Matrix matrix;
     uint8_t *base = nullptr;
     int32_t n_slabs = 0;
     int64_t slab_bytes = 0;
     std::vector<int64_t> pay_bytes;
     std::vector<int32_t> row_count;
-    std::mutex mu;
-    std::condition_variable cv_free, cv_ready;
-    std::deque<int32_t> free_q, ready_q;
-    std::vector<std::thread> workers;
-    std::atomic<size_t> next{0};
-    int active = 0;
-    bool failed = false, cancelled = false;
-    std::string error;
-    int64_t rows_total = 0, bytes_total = 0, chrom_length = 0;
+    int64_t rows_total = 0, bytes_total = 0;
     int32_t blocks_total = 0;
-
-    struct Cancelled {};
-
-    void fail_with(const char *what) {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!failed) error = what;
-        failed = true;
-        cv_free.notify_all();
-        cv_ready.notify_all();
-    }
+    SlabQueue q;
 
     struct Worker {
         mst_hic_rawstream *s;
@@ -1311,34 +1263,27 @@ struct mst_hic_rawstream {
         uint8_t *m = nullptr;
         int64_t pay = 0;
         int32_t rows = 0;
+        std::vector<uint8_t> buf, pad;
+        double ratio = 2.0;                       // the largest expansion of a block this worker has seen, with a margin
+        explicit Worker(mst_hic_rawstream *st) : s(st) {}
         void publish() {
             if (cur < 0) return;
-            std::lock_guard<std::mutex> lk(s->mu);
-            s->pay_bytes[(size_t)cur] = pay;
-            s->row_count[(size_t)cur] = rows;
-            s->rows_total += rows;
-            s->bytes_total += pay;
-            if (rows > 0) {
-                s->ready_q.push_back(cur);
-                s->cv_ready.notify_one();
-            } else {
-                s->free_q.push_back(cur);
-                s->cv_free.notify_one();
-            }
+            s->q.publish(cur, rows > 0, [&] {
+                s->pay_bytes[(size_t)cur] = pay;
+                s->row_count[(size_t)cur] = rows;
+                s->rows_total += rows;
+                s->bytes_total += pay;
+            });
             cur = -1;
         }
         void next_slab() {
             publish();
-            std::unique_lock<std::mutex> lk(s->mu);
-            s->cv_free.wait(lk, [&] { return !s->free_q.empty() || s->failed || s->cancelled; });
-            if (s->failed || s->cancelled) throw Cancelled{};
-            cur = s->free_q.front();
-            s->free_q.pop_front();
-            lk.unlock();
+            cur = s->q.acquire();
             m = s->base + (size_t)cur * (size_t)s->slab_bytes;
             pay = 0;
             rows = 0;
         }
+        void leave() {}
         // directory entry of a row whose records already lie in this slab at byte `off`
         void list_row(int64_t off, int64_t count, int64_t y, int32_t x_off, uint32_t flags) {
             if (y < INT32_MIN || y > INT32_MAX) throw FormatError{"bin index does not fit 32 bits"};
@@ -1363,312 +1308,198 @@ struct mst_hic_rawstream {
             pay += need + (need & 1);                 // (rec is even for every layout; kept even for the 16-bit loads)
             ++rows;
         }
-    };
 
-    // header + rows of one inflated block (the walk of decode_records, without touching a record): row(p, count, rec, y, x_off, flags)
-    template <class Row>
-    void walk_block(const uint8_t *data, size_t n, Row row) {
-        Cursor c(data, n);
-        if (c.get<int32_t>() < 0) throw FormatError{"negative record count in a block"};
-        const int32_t x_off = c.get<int32_t>();
-        const int32_t y_off = c.get<int32_t>();
-        const bool short_counts = c.get<uint8_t>() == 0;
-        bool short_x = true, short_y = true;
-        if (h->version > 8) {
-            short_x = c.get<uint8_t>() == 0;
-            short_y = c.get<uint8_t>() == 0;
-        }
-        const uint8_t type = c.get<uint8_t>();
-        const uint32_t fc = short_counts ? MST_HIC_ROW_SHORT_COUNTS : 0u;
-        if (type == 1) {
-            const int64_t rec = (short_x ? 2 : 4) + (short_counts ? 2 : 4);
-            const int32_t rows = short_y ? (int32_t)c.get<int16_t>() : c.get<int32_t>();
-            for (int32_t r = 0; r < rows; ++r) {
-                const int32_t y = short_y ? (int32_t)c.get<int16_t>() : c.get<int32_t>();
-                int32_t cols = short_x ? (int32_t)c.get<int16_t>() : c.get<int32_t>();
-                if (cols < 0) cols = 0;                           // the decoder's loop runs zero times as well
-                const uint8_t *p = c.p;
-                c.skip((uint64_t)cols * (uint64_t)rec);
-                if (cols > 0) row(p, (int64_t)cols, rec, (int64_t)y_off + y, x_off, fc | (short_x ? 0u : MST_HIC_ROW_INT_COLUMNS));
+        // header + rows of one inflated block (the walk of decode_records, without touching a record): row(p, count, rec, y, x_off, flags)
+        template <class Row>
+        void walk_block(const uint8_t *data, size_t n, Row row) {
+            Cursor c(data, n);
+            if (c.get<int32_t>() < 0) throw FormatError{"negative record count in a block"};
+            const int32_t x_off = c.get<int32_t>();
+            const int32_t y_off = c.get<int32_t>();
+            const bool short_counts = c.get<uint8_t>() == 0;
+            bool short_x = true, short_y = true;
+            if (s->h->version > 8) {
+                short_x = c.get<uint8_t>() == 0;
+                short_y = c.get<uint8_t>() == 0;
             }
-        } else if (type == 2) {
-            const int32_t n_pts = c.get<int32_t>();
-            const int32_t wd = (int32_t)c.get<int16_t>();
-            if (wd <= 0) throw FormatError{"dense block of width 0"};
-            const int64_t rec = short_counts ? 2 : 4;
-            for (int64_t i = 0; i < n_pts; i += wd) {
-                const int64_t cnt = n_pts - i < wd ? n_pts - i : wd;
-                const uint8_t *p = c.p;
-                c.skip((uint64_t)cnt * (uint64_t)rec);
-                row(p, cnt, rec, (int64_t)y_off + i / wd, x_off, fc | MST_HIC_ROW_DENSE);
+            const uint8_t type = c.get<uint8_t>();
+            const uint32_t fc = short_counts ? MST_HIC_ROW_SHORT_COUNTS : 0u;
+            if (type == 1) {
+                const int64_t rec = (short_x ? 2 : 4) + (short_counts ? 2 : 4);
+                const int32_t n_rows = short_y ? (int32_t)c.get<int16_t>() : c.get<int32_t>();
+                for (int32_t r = 0; r < n_rows; ++r) {
+                    const int32_t y = short_y ? (int32_t)c.get<int16_t>() : c.get<int32_t>();
+                    int32_t cols = short_x ? (int32_t)c.get<int16_t>() : c.get<int32_t>();
+                    if (cols < 0) cols = 0;                           // the decoder's loop runs zero times as well
+                    const uint8_t *p = c.p;
+                    c.skip((uint64_t)cols * (uint64_t)rec);
+                    if (cols > 0) row(p, (int64_t)cols, rec, (int64_t)y_off + y, x_off, fc | (short_x ? 0u : MST_HIC_ROW_INT_COLUMNS));
+                }
+            } else if (type == 2) {
+                const int32_t n_pts = c.get<int32_t>();
+                const int32_t wd = (int32_t)c.get<int16_t>();
+                if (wd <= 0) throw FormatError{"dense block of width 0"};
+                const int64_t rec = short_counts ? 2 : 4;
+                for (int64_t i = 0; i < n_pts; i += wd) {
+                    const int64_t cnt = n_pts - i < wd ? n_pts - i : wd;
+                    const uint8_t *p = c.p;
+                    c.skip((uint64_t)cnt * (uint64_t)rec);
+                    row(p, cnt, rec, (int64_t)y_off + i / wd, x_off, fc | MST_HIC_ROW_DENSE);
+                }
+            } else {
+                throw FormatError{"unknown block type"};
             }
-        } else {
-            throw FormatError{"unknown block type"};
         }
-    }
 
-    // One block.  The usual case: the zlib stream is inflated STRAIGHT INTO the worker's slab (no staging buffer, no copy) when
-    // the room left is at least `ratio` times the compressed size -- the largest expansion this worker has seen so far, with a
-    // margin -- and its rows are then listed where they lie (the block's 14-18 header bytes and 4-8 bytes per row travel along
-    // unused).  A block that does not fit what is left opens the next slab; one that does not fit an empty slab goes through the
-    // staging buffer and is cut at row boundaries.
-    void one_block(Worker &w, const BlockRef *b, std::vector<uint8_t> &buf, std::vector<uint8_t> &pad, double &ratio) {
-        const uint8_t *comp = h->map + b->pos;
-        const size_t comp_size = (size_t)b->size, past = h->size - (size_t)b->pos - comp_size;
-        if (!use_zlib() && past >= mst_inflate::kSlack) {
-            for (int attempt = 0; attempt < 2; ++attempt) {
-                if (w.cur < 0) w.next_slab();
-                const int64_t at = (w.pay + 15) / 16 * 16;
-                // the directory grows down from the slab's end: room for this block's rows is kept free (checked after the walk)
-                const int64_t room = slab_bytes - at - 16 * ((int64_t)w.rows + 1) - (int64_t)mst_inflate::kSlack;
-                if (room >= (int64_t)((double)comp_size * ratio) + 64) {
-                    size_t n_out = 0;
-                    const int rc = mst_inflate::inflate_zlib(comp, comp_size, w.m + at, (size_t)room, &n_out);
-                    if (rc == mst_inflate::kOk) {
-                        const double seen = (double)n_out / (double)(comp_size ? comp_size : 1) * 1.05;
-                        if (seen > ratio) ratio = seen;
-                        int64_t nrows = 0;
-                        walk_block(w.m + at, n_out, [&](const uint8_t *, int64_t, int64_t, int64_t, int32_t, uint32_t) { ++nrows; });
-                        if (at + (int64_t)n_out + 16 * ((int64_t)w.rows + nrows) <= slab_bytes) {
-                            walk_block(w.m + at, n_out, [&](const uint8_t *p, int64_t count, int64_t, int64_t y, int32_t x_off, uint32_t flags) {
-                                w.list_row((int64_t)(p - w.m), count, y, x_off, flags);
-                            });
-                            w.pay = at + (int64_t)n_out;
-                            w.pay += w.pay & 1;
-                            return;
+        // One block.  The usual case: the zlib stream is inflated STRAIGHT INTO the worker's slab (no staging buffer, no copy) when
+        // the room left is at least `ratio` times the compressed size and its rows are then listed where they lie (the block's
+        // 14-18 header bytes and 4-8 bytes per row travel along unused).  A block that does not fit what is left opens the next
+        // slab; one that does not fit an empty slab goes through the staging buffer and is cut at row boundaries.
+        void block(const BlockRef *b) {
+            const mst_hic *h = s->h;
+            const int64_t slab_bytes = s->slab_bytes;
+            const uint8_t *comp = h->map + b->pos;
+            const size_t comp_size = (size_t)b->size, past = h->size - (size_t)b->pos - comp_size;
+            if (!use_zlib() && past >= mst_inflate::kSlack) {
+                for (int attempt = 0; attempt < 2; ++attempt) {
+                    if (cur < 0) next_slab();
+                    const int64_t at = (pay + 15) / 16 * 16;
+                    // the directory grows down from the slab's end: room for this block's rows is kept free (checked after the walk)
+                    const int64_t room = slab_bytes - at - 16 * ((int64_t)rows + 1) - (int64_t)mst_inflate::kSlack;
+                    if (room >= (int64_t)((double)comp_size * ratio) + 64) {
+                        size_t n_out = 0;
+                        const int rc = mst_inflate::inflate_zlib(comp, comp_size, m + at, (size_t)room, &n_out);
+                        if (rc == mst_inflate::kOk) {
+                            const double seen = (double)n_out / (double)(comp_size ? comp_size : 1) * 1.05;
+                            if (seen > ratio) ratio = seen;
+                            int64_t nrows = 0;
+                            walk_block(m + at, n_out, [&](const uint8_t *, int64_t, int64_t, int64_t, int32_t, uint32_t) { ++nrows; });
+                            if (at + (int64_t)n_out + 16 * ((int64_t)rows + nrows) <= slab_bytes) {
+                                walk_block(m + at, n_out, [&](const uint8_t *p, int64_t count, int64_t, int64_t y, int32_t x_off, uint32_t flags) {
+                                    list_row((int64_t)(p - m), count, y, x_off, flags);
+                                });
+                                pay = at + (int64_t)n_out;
+                                pay += pay & 1;
+                                return;
+                            }
+                        } else if (rc != mst_inflate::kOutputFull) {
+                            throw FormatError{"zlib inflate failed"};
+                        } else if (ratio < 64.0) {
+                            ratio *= 2.0;                           // the estimate was too small: remember, and take a fresh slab
                         }
-                    } else if (rc != mst_inflate::kOutputFull) {
-                        throw FormatError{"zlib inflate failed"};
-                    } else if (ratio < 64.0) {
-                        ratio *= 2.0;                           // the estimate was too small: remember, and take a fresh slab
                     }
+                    if (rows == 0 && pay == 0) break;               // does not fit an EMPTY slab: staged below
+                    next_slab();
                 }
-                if (w.rows == 0 && w.pay == 0) break;           // does not fit an EMPTY slab: staged below
-                w.next_slab();
             }
+            const size_t n_out = inflate_block(h, b, buf, pad);
+            walk_block(buf.data(), n_out, [&](const uint8_t *p, int64_t count, int64_t rec, int64_t y, int32_t x_off, uint32_t flags) {
+                put_row(p, count, rec, y, x_off, flags);
+            });
         }
-        const size_t n_out = inflate_block(comp, comp_size, past, buf, pad);
-        walk_block(buf.data(), n_out, [&](const uint8_t *p, int64_t count, int64_t rec, int64_t y, int32_t x_off, uint32_t flags) {
-            w.put_row(p, count, rec, y, x_off, flags);
-        });
-    }
-
-    void work() {
-        std::vector<uint8_t> buf, pad;
-        Worker w{this};
-        double ratio = 2.0;
-        try {
-            for (;;) {
-                const size_t i = next.fetch_add(1);
-                if (i >= todo.size()) break;
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    if (failed || cancelled) break;
-                }
-                one_block(w, todo[i], buf, pad, ratio);
-            }
-            w.publish();
-        } catch (const Cancelled &) {
-        } catch (const FormatError &e) {
-            fail_with(e.what);
-        } catch (...) {
-            fail_with("out of memory");
-        }
-        std::lock_guard<std::mutex> lk(mu);
-        if (--active == 0) cv_ready.notify_all();
-    }
+    };
 };
+
+// What the two raw opens differ in; everything else of an open is rawstream_start.
+struct RawOpen {
+    const char *fn, *v6_hint;                 // the entry point's name and its advice for a version 6 file, for the messages
+    bool pair;                                // false: the intra matrix of chrom_a (chrom_b and transposed are null)
+    const char *chrom_a, *chrom_b;
+    int64_t max_dist_bins;
+    int32_t part, n_parts;
+    int32_t *transposed;                      // pair only
+};
+
+static int rawstream_start(const RawOpen &o, mst_hic *h, int32_t resolution, const char *norm, int32_t n_threads, void *slab_memory,
+                           int32_t n_slabs, int64_t slab_bytes, mst_hic_rawstream **out) {
+    if (!h || !o.chrom_a || (o.pair && (!o.chrom_b || !o.transposed)) || !out || resolution <= 0 || o.n_parts < 1 || o.part < 0 ||
+        o.part >= o.n_parts || !slab_memory || n_slabs < 2 || slab_bytes < 4096 || (slab_bytes & 15) ||
+        slab_bytes > ((int64_t)1 << 32) || (reinterpret_cast<uintptr_t>(slab_memory) & 15))
+        return fail(MST_IO_E_ARG, "%s: bad argument (slab_bytes: a multiple of 16 in [4096, 2^32]; slab_memory 16-byte aligned)", o.fn);
+    *out = nullptr;
+    if (h->version < 7) return fail(MST_IO_E_FORMAT, "%s: version %d blocks are plain records, not rows%s", o.fn, h->version, o.v6_hint);
+    return guarded([&]() -> int {
+        std::unique_ptr<mst_hic_rawstream> s(new mst_hic_rawstream());
+        s->h = h;
+        const int rc = open_matrix(h, o.chrom_a, o.chrom_b, resolution, norm, o.max_dist_bins, s->matrix, o.fn);
+        if (rc != MST_IO_OK) return rc;
+        s->blocks_total = (int32_t)s->matrix.todo.size();
+        split_todo(s->matrix.todo, o.part, o.n_parts);
+        if (o.transposed) *o.transposed = s->matrix.transposed;
+        s->base = static_cast<uint8_t *>(slab_memory);
+        s->n_slabs = n_slabs;
+        s->slab_bytes = slab_bytes;
+        s->pay_bytes.assign((size_t)n_slabs, 0);
+        s->row_count.assign((size_t)n_slabs, 0);
+        s->q.start(s.get(), n_threads, n_slabs);
+        *out = s.release();
+        return MST_IO_OK;
+    });
+}
 
 extern "C" int mst_hic_rawstream_open(mst_hic *h, const char *chrom, int32_t resolution, const char *norm, int64_t max_dist_bins,
                                       int32_t n_threads, int32_t part, int32_t n_parts, void *slab_memory, int32_t n_slabs,
                                       int64_t slab_bytes, mst_hic_rawstream **out) {
-    if (!h || !chrom || !out || resolution <= 0 || n_parts < 1 || part < 0 || part >= n_parts || !slab_memory || n_slabs < 2 ||
-        slab_bytes < 4096 || (slab_bytes & 15) || slab_bytes > ((int64_t)1 << 32) || (reinterpret_cast<uintptr_t>(slab_memory) & 15))
-        return fail(MST_IO_E_ARG, "mst_hic_rawstream_open: bad argument (slab_bytes: a multiple of 16 in [4096, 2^32]; "
-                                  "slab_memory 16-byte aligned)");
-    *out = nullptr;
-    if (h->version < 7)
-        return fail(MST_IO_E_FORMAT, "mst_hic_rawstream_open: version %d blocks are plain records, not rows: use mst_hic_stream_open",
-                    h->version);
-    mst_hic_rawstream *s = nullptr;
-    try {
-        s = new mst_hic_rawstream();
-        s->h = h;
-        std::vector<const BlockRef *> todo;
-        const int rc = intra_todo(h, chrom, resolution, norm, max_dist_bins, todo, s->zoom, s->norm_vec, &s->use_norm);
-        if (rc != MST_IO_OK) {
-            delete s;
-            return rc;
-        }
-        s->blocks_total = (int32_t)todo.size();
-        s->chrom_length = h->chroms[(size_t)find_chromosome(h, chrom)].length;
-        split_todo(todo, part, n_parts);
-        s->todo.swap(todo);
-        s->base = static_cast<uint8_t *>(slab_memory);
-        s->n_slabs = n_slabs;
-        s->slab_bytes = slab_bytes;
-        s->pay_bytes.assign((size_t)n_slabs, 0);
-        s->row_count.assign((size_t)n_slabs, 0);
-        for (int32_t i = 0; i < n_slabs; ++i) s->free_q.push_back(i);
-        int nt = n_threads > 0 ? n_threads : default_threads();
-        if (nt < 1) nt = 1;
-        if ((size_t)nt > s->todo.size()) nt = s->todo.empty() ? 1 : (int)s->todo.size();
-        if (nt > n_slabs - 1) nt = n_slabs - 1;                 // every worker holds a slab; one more keeps the consumer fed
-        s->active = nt;
-        for (int t = 0; t < nt; ++t) s->workers.emplace_back([s] { s->work(); });
-        *out = s;
-        return MST_IO_OK;
-    } catch (const FormatError &e) {
-        delete s;
-        return fail(MST_IO_E_FORMAT, "%s", e.what);
-    } catch (...) {
-        delete s;
-        return fail(MST_IO_E_FORMAT, "unreadable file (out of memory?)");
-    }
+    const RawOpen o{"mst_hic_rawstream_open", ": use mst_hic_stream_open", false, chrom, nullptr, max_dist_bins, part, n_parts, nullptr};
+    return rawstream_start(o, h, resolution, norm, n_threads, slab_memory, n_slabs, slab_bytes, out);
 }
 
-// ---- trans matrices: every block of the pair's matrix, rows delivered as for the intra stream ---------------------------------
-static int norm_vector_of(mst_hic *h, const char *norm, int ci, int32_t resolution, std::vector<double> &out) {
-    read_norm_index(h);
-    auto nit = h->norm_index.find(norm_key(norm, ci, "BP", resolution));
-    if (nit == h->norm_index.end())
-        return fail(MST_IO_E_NOTFOUND, "no %s normalisation vector for %s at %d bp", norm, h->chroms[(size_t)ci].name.c_str(),
-                    resolution);
-    out = read_norm_vector(h, nit->second);
-    return MST_IO_OK;
-}
-
+// every block of the pair's matrix (no distance limit, one part), rows delivered as for the intra stream
 extern "C" int mst_hic_rawstream_open_trans(mst_hic *h, const char *chrom_a, const char *chrom_b, int32_t resolution,
                                             const char *norm, int32_t n_threads, void *slab_memory, int32_t n_slabs,
                                             int64_t slab_bytes, int32_t *transposed, mst_hic_rawstream **out) {
-    if (!h || !chrom_a || !chrom_b || !out || !transposed || resolution <= 0 || !slab_memory || n_slabs < 2 || slab_bytes < 4096 ||
-        (slab_bytes & 15) || slab_bytes > ((int64_t)1 << 32) || (reinterpret_cast<uintptr_t>(slab_memory) & 15))
-        return fail(MST_IO_E_ARG, "mst_hic_rawstream_open_trans: bad argument (slab_bytes: a multiple of 16 in [4096, 2^32]; "
-                                  "slab_memory 16-byte aligned)");
-    *out = nullptr;
-    if (h->version < 7)
-        return fail(MST_IO_E_FORMAT, "mst_hic_rawstream_open_trans: version %d blocks are plain records, not rows (versions 7-9 "
-                                     "are read)", h->version);
-    mst_hic_rawstream *s = nullptr;
-    try {
-        const int ca = find_chromosome(h, chrom_a), cb = find_chromosome(h, chrom_b);
-        if (ca < 0) return fail(MST_IO_E_NOTFOUND, "chromosome %s is not in the file", chrom_a);
-        if (cb < 0) return fail(MST_IO_E_NOTFOUND, "chromosome %s is not in the file", chrom_b);
-        if (ca == cb) return fail(MST_IO_E_ARG, "mst_hic_rawstream_open_trans: %s and %s are one chromosome", chrom_a, chrom_b);
-        const int lo = ca < cb ? ca : cb, hi = ca < cb ? cb : ca;
-        auto it = h->matrices.find(std::to_string(lo) + "_" + std::to_string(hi));
-        if (it == h->matrices.end()) return fail(MST_IO_E_NOTFOUND, "no matrix for the pair %s, %s", chrom_a, chrom_b);
-        s = new mst_hic_rawstream();
-        s->h = h;
-        s->zoom = read_zoom(h, it->second.first, resolution);
-        if (!s->zoom.found) {
-            delete s;
-            return fail(MST_IO_E_NOTFOUND, "resolution %d is not in the file", resolution);
-        }
-        s->use_norm = norm && *norm && strcmp(norm, "NONE") != 0;
-        if (s->use_norm) {
-            int rc = norm_vector_of(h, norm, ca, resolution, s->norm_vec);
-            if (rc == MST_IO_OK) rc = norm_vector_of(h, norm, cb, resolution, s->norm_vec2);
-            if (rc != MST_IO_OK) {
-                delete s;
-                return rc;
-            }
-        }
-        for (const BlockRef &b : s->zoom.blocks) {
-            if (b.size <= 0) continue;
-            if (b.pos < 0 || (uint64_t)b.pos + (uint64_t)b.size > h->size) throw FormatError{"block outside the file"};
-            s->todo.push_back(&b);
-        }
-        s->blocks_total = (int32_t)s->todo.size();
-        s->chrom_length = h->chroms[(size_t)ca].length;
-        s->chrom_length2 = h->chroms[(size_t)cb].length;
-        *transposed = ca > cb ? 1 : 0;
-        s->base = static_cast<uint8_t *>(slab_memory);
-        s->n_slabs = n_slabs;
-        s->slab_bytes = slab_bytes;
-        s->pay_bytes.assign((size_t)n_slabs, 0);
-        s->row_count.assign((size_t)n_slabs, 0);
-        for (int32_t i = 0; i < n_slabs; ++i) s->free_q.push_back(i);
-        int nt = n_threads > 0 ? n_threads : default_threads();
-        if (nt < 1) nt = 1;
-        if ((size_t)nt > s->todo.size()) nt = s->todo.empty() ? 1 : (int)s->todo.size();
-        if (nt > n_slabs - 1) nt = n_slabs - 1;
-        s->active = nt;
-        for (int t = 0; t < nt; ++t) s->workers.emplace_back([s] { s->work(); });
-        *out = s;
-        return MST_IO_OK;
-    } catch (const FormatError &e) {
-        delete s;
-        return fail(MST_IO_E_FORMAT, "%s", e.what);
-    } catch (...) {
-        delete s;
-        return fail(MST_IO_E_FORMAT, "unreadable file (out of memory?)");
-    }
+    const RawOpen o{"mst_hic_rawstream_open_trans", " (versions 7-9 are read)", true, chrom_a, chrom_b, -1, 0, 1, transposed};
+    return rawstream_start(o, h, resolution, norm, n_threads, slab_memory, n_slabs, slab_bytes, out);
 }
 
 extern "C" int mst_hic_rawstream_info_trans(mst_hic_rawstream *s, const double **norm_a, int64_t *count_a, const double **norm_b,
                                             int64_t *count_b, int64_t *length_a_bp, int64_t *length_b_bp) {
     if (!s || !norm_a || !count_a || !norm_b || !count_b || !length_a_bp || !length_b_bp)
         return fail(MST_IO_E_ARG, "mst_hic_rawstream_info_trans: bad argument");
-    *norm_a = s->use_norm ? s->norm_vec.data() : nullptr;
-    *count_a = s->use_norm ? (int64_t)s->norm_vec.size() : -1;
-    *norm_b = s->use_norm ? s->norm_vec2.data() : nullptr;
-    *count_b = s->use_norm ? (int64_t)s->norm_vec2.size() : -1;
-    *length_a_bp = s->chrom_length;
-    *length_b_bp = s->chrom_length2;
+    const Matrix &m = s->matrix;
+    *norm_a = m.use_norm ? m.norm_vec.data() : nullptr;
+    *count_a = m.use_norm ? (int64_t)m.norm_vec.size() : -1;
+    *norm_b = m.use_norm ? m.norm_vec2.data() : nullptr;
+    *count_b = m.use_norm ? (int64_t)m.norm_vec2.size() : -1;
+    *length_a_bp = m.chrom_length;
+    *length_b_bp = m.chrom_length2;
     return MST_IO_OK;
 }
 
 extern "C" int mst_hic_rawstream_info(mst_hic_rawstream *s, const double **norm_values, int64_t *norm_count,
                                       int64_t *chrom_length_bp) {
     if (!s || !norm_values || !norm_count || !chrom_length_bp) return fail(MST_IO_E_ARG, "mst_hic_rawstream_info: bad argument");
-    *norm_values = s->use_norm ? s->norm_vec.data() : nullptr;
-    *norm_count = s->use_norm ? (int64_t)s->norm_vec.size() : -1;
-    *chrom_length_bp = s->chrom_length;
+    *norm_values = s->matrix.use_norm ? s->matrix.norm_vec.data() : nullptr;
+    *norm_count = s->matrix.use_norm ? (int64_t)s->matrix.norm_vec.size() : -1;
+    *chrom_length_bp = s->matrix.chrom_length;
     return MST_IO_OK;
 }
 
 extern "C" int mst_hic_rawstream_next(mst_hic_rawstream *s, int32_t timeout_ms, int32_t *slab, int64_t *payload_bytes,
                                       int32_t *rows) {
     if (!s || !slab || !payload_bytes || !rows) return fail(MST_IO_E_ARG, "mst_hic_rawstream_next: bad argument");
-    std::unique_lock<std::mutex> lk(s->mu);
-    auto ready = [&] { return !s->ready_q.empty() || s->failed || s->active == 0; };
-    if (timeout_ms < 0) s->cv_ready.wait(lk, ready);
-    else if (!s->cv_ready.wait_for(lk, std::chrono::milliseconds(timeout_ms), ready)) return 2;      // nothing yet
-    if (s->failed) return fail(MST_IO_E_ZLIB, "block decode failed: %s", s->error.c_str());
-    if (!s->ready_q.empty()) {
-        *slab = s->ready_q.front();
-        s->ready_q.pop_front();
-        *payload_bytes = s->pay_bytes[(size_t)*slab];
-        *rows = s->row_count[(size_t)*slab];
-        return 1;
-    }
-    return 0;                                                                                         // all delivered
+    return s->q.wait_ready(timeout_ms, [&](int32_t i) {
+        *slab = i;
+        *payload_bytes = s->pay_bytes[(size_t)i];
+        *rows = s->row_count[(size_t)i];
+    });
 }
 
 extern "C" int mst_hic_rawstream_release(mst_hic_rawstream *s, int32_t slab) {
     if (!s || slab < 0 || slab >= s->n_slabs) return fail(MST_IO_E_ARG, "mst_hic_rawstream_release: bad argument");
-    std::lock_guard<std::mutex> lk(s->mu);
-    s->free_q.push_back(slab);
-    s->cv_free.notify_one();
+    s->q.release(slab);
     return MST_IO_OK;
 }
 
 extern "C" int mst_hic_rawstream_close(mst_hic_rawstream *s, int64_t *rows_total, int64_t *bytes_total, int32_t *blocks_total,
                                        int32_t *blocks_mine) {
     if (!s) return MST_IO_OK;
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        s->cancelled = true;
-        s->cv_free.notify_all();
-    }
-    for (auto &t : s->workers) t.join();
-    int rc = MST_IO_OK;
-    if (s->failed) rc = fail(MST_IO_E_ZLIB, "block decode failed: %s", s->error.c_str());
+    s->q.cancel_and_join();
+    const int rc = s->q.failed ? decode_failed(s->q.error.c_str()) : MST_IO_OK;
     if (rows_total) *rows_total = s->rows_total;
     if (bytes_total) *bytes_total = s->bytes_total;
     if (blocks_total) *blocks_total = s->blocks_total;
-    if (blocks_mine) *blocks_mine = (int32_t)s->todo.size();
+    if (blocks_mine) *blocks_mine = (int32_t)s->matrix.todo.size();
     delete s;
     return rc;
 }

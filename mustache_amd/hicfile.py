@@ -163,91 +163,90 @@ class HicFile:
         return x, y, v
 
 
-class HicStream:
-    """mst_hic_stream_*: the packed records of one chromosome (or of share `part` of its blocks) delivered slab by slab into
-    caller-owned memory while later blocks are still being inflated.  `memory_ptr` points to n_slabs * slab_records *
-    (8 + dist_bytes) bytes (page-locked for GPU uploads); see include/mustache_io.h for the slab layout."""
+def _norm_copy(p, n):
+    """the float64 copy of a normalisation vector a stream handle lends out (n < 0: norm NONE -> None)"""
+    if n.value < 0:
+        return None
+    if n.value == 0:
+        return np.zeros(0, np.float64)
+    return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_double)), shape=(n.value,)).copy()
 
-    def __init__(self, hic, chrom, resolution, norm, max_dist_bins, chrom_size_bp, memory_ptr, n_slabs, slab_records,
-                 dist_bytes=2, threads=0, part=(0, 1)):
+
+class _SlabStream:
+    """What the three stream wrappers share: next / release / close of `<_PREFIX>_next`, `_release`, `_close`.  _NEXT: the
+    ctypes types `next` fills behind the slab index; _CLOSE: (attribute, ctypes type) of every counter `close` reports."""
+    _PREFIX = _NEXT = _CLOSE = None
+
+    def _open(self, hic, opener, *args):
         self._lib, self._hic = hic._lib, hic
         self._s = _P()
-        self.slab_records, self.dist_bytes, self.n_slabs = int(slab_records), int(dist_bytes), int(n_slabs)
-        _check(self._lib, self._lib.mst_hic_stream_open(hic._h, str(chrom).encode(), int(resolution), str(norm).encode(),
-                                                        int(max_dist_bins), int(chrom_size_bp), int(threads), int(part[0]),
-                                                        int(part[1]), _P(memory_ptr), int(n_slabs), int(slab_records),
-                                                        int(dist_bytes), ctypes.byref(self._s)))
-        self.n = self.total = self.blocks_total = self.blocks_mine = None
+        for name, _ in self._CLOSE:
+            setattr(self, name, None)
+        _check(self._lib, opener(hic._h, *args, ctypes.byref(self._s)))
+
+    def _fn(self, what):
+        return getattr(self._lib, self._PREFIX + what)
 
     def next(self, timeout_ms=-1):
-        """(slab index, record count) of a filled slab; None when nothing was ready within timeout_ms; False at the end."""
-        slab, count = ctypes.c_int32(), ctypes.c_int64()
-        rc = _check(self._lib, self._lib.mst_hic_stream_next(self._s, int(timeout_ms), ctypes.byref(slab), ctypes.byref(count)))
+        """(slab index, ...) of a filled slab; None when nothing was ready within timeout_ms; False at the end."""
+        out = [ctypes.c_int32()] + [t() for t in self._NEXT]
+        rc = _check(self._lib, self._fn("_next")(self._s, int(timeout_ms), *[ctypes.byref(o) for o in out]))
         if rc == 1:
-            return int(slab.value), int(count.value)
+            return tuple(int(o.value) for o in out)
         return None if rc == 2 else False
 
     def release(self, slab):
-        _check(self._lib, self._lib.mst_hic_stream_release(self._s, int(slab)))
+        _check(self._lib, self._fn("_release")(self._s, int(slab)))
 
     def close(self):
         if self._s:
-            n, tot, bt, bm = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+            out = [t() for _, t in self._CLOSE]
             s, self._s = self._s, _P()
-            _check(self._lib, self._lib.mst_hic_stream_close(s, ctypes.byref(n), ctypes.byref(tot), ctypes.byref(bt),
-                                                             ctypes.byref(bm)))
-            self.n, self.total, self.blocks_total, self.blocks_mine = int(n.value), int(tot.value), int(bt.value), int(bm.value)
+            _check(self._lib, self._fn("_close")(s, *[ctypes.byref(o) for o in out]))
+            for (name, _), o in zip(self._CLOSE, out):
+                setattr(self, name, int(o.value))
 
-    __del__ = close
+    def __del__(self):
+        if getattr(self, "_s", None):
+            self.close()
 
 
-class HicRawStream:
+class HicStream(_SlabStream):
+    """mst_hic_stream_*: the packed records of one chromosome (or of share `part` of its blocks) delivered slab by slab into
+    caller-owned memory while later blocks are still being inflated.  `memory_ptr` points to n_slabs * slab_records *
+    (8 + dist_bytes) bytes (page-locked for GPU uploads); see include/mustache_io.h for the slab layout.
+    next() -> (slab index, record count)."""
+    _PREFIX, _NEXT = "mst_hic_stream", (ctypes.c_int64,)
+    _CLOSE = (("n", ctypes.c_int64), ("total", ctypes.c_int64), ("blocks_total", ctypes.c_int32), ("blocks_mine", ctypes.c_int32))
+
+    def __init__(self, hic, chrom, resolution, norm, max_dist_bins, chrom_size_bp, memory_ptr, n_slabs, slab_records,
+                 dist_bytes=2, threads=0, part=(0, 1)):
+        self.slab_records, self.dist_bytes, self.n_slabs = int(slab_records), int(dist_bytes), int(n_slabs)
+        self._open(hic, hic._lib.mst_hic_stream_open, str(chrom).encode(), int(resolution), str(norm).encode(), int(max_dist_bins),
+                   int(chrom_size_bp), int(threads), int(part[0]), int(part[1]), _P(memory_ptr), int(n_slabs), int(slab_records),
+                   int(dist_bytes))
+
+
+class HicRawStream(_SlabStream):
     """mst_hic_rawstream_*: the RAW rows of one chromosome's near-diagonal blocks (or of share `part` of them) delivered slab by
     slab into caller-owned memory while later blocks are still being inflated -- record bytes as the file stores them plus one
     16-byte directory entry per row (include/mustache_hicrow.h); the rows are decoded on the GPU (mst_band_scatter_hic_rows).
-    `memory_ptr` points to n_slabs * slab_bytes bytes (page-locked).  Versions 7-9 only."""
+    `memory_ptr` points to n_slabs * slab_bytes bytes (page-locked).  Versions 7-9 only.
+    next() -> (slab index, payload bytes, rows)."""
+    _PREFIX, _NEXT = "mst_hic_rawstream", (ctypes.c_int64, ctypes.c_int32)
+    _CLOSE = (("rows_total", ctypes.c_int64), ("bytes_total", ctypes.c_int64), ("blocks_total", ctypes.c_int32),
+              ("blocks_mine", ctypes.c_int32))
 
     def __init__(self, hic, chrom, resolution, norm, max_dist_bins, memory_ptr, n_slabs, slab_bytes, threads=0, part=(0, 1)):
-        self._lib, self._hic = hic._lib, hic
-        self._s = _P()
         self.slab_bytes, self.n_slabs = int(slab_bytes), int(n_slabs)
-        _check(self._lib, self._lib.mst_hic_rawstream_open(hic._h, str(chrom).encode(), int(resolution), str(norm).encode(),
-                                                           int(max_dist_bins), int(threads), int(part[0]), int(part[1]),
-                                                           _P(memory_ptr), int(n_slabs), int(slab_bytes), ctypes.byref(self._s)))
-        self.rows_total = self.bytes_total = self.blocks_total = self.blocks_mine = None
+        self._open(hic, hic._lib.mst_hic_rawstream_open, str(chrom).encode(), int(resolution), str(norm).encode(),
+                   int(max_dist_bins), int(threads), int(part[0]), int(part[1]), _P(memory_ptr), int(n_slabs), int(slab_bytes))
 
     def info(self):
         """(the chromosome's normalisation vector as a float64 array (a copy) or None for norm NONE, its length in bp)"""
         v, n, length = _P(), ctypes.c_int64(), ctypes.c_int64()
         _check(self._lib, self._lib.mst_hic_rawstream_info(self._s, ctypes.byref(v), ctypes.byref(n), ctypes.byref(length)))
-        if n.value < 0:
-            return None, int(length.value)
-        if n.value == 0:
-            return np.zeros(0, np.float64), int(length.value)
-        return np.ctypeslib.as_array(ctypes.cast(v, ctypes.POINTER(ctypes.c_double)), shape=(n.value,)).copy(), int(length.value)
-
-    def next(self, timeout_ms=-1):
-        """(slab index, payload bytes, rows) of a filled slab; None when nothing was ready within timeout_ms; False at the end."""
-        slab, nbytes, rows = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32()
-        rc = _check(self._lib, self._lib.mst_hic_rawstream_next(self._s, int(timeout_ms), ctypes.byref(slab), ctypes.byref(nbytes),
-                                                                ctypes.byref(rows)))
-        if rc == 1:
-            return int(slab.value), int(nbytes.value), int(rows.value)
-        return None if rc == 2 else False
-
-    def release(self, slab):
-        _check(self._lib, self._lib.mst_hic_rawstream_release(self._s, int(slab)))
-
-    def close(self):
-        if self._s:
-            rt, bt_, bt, bm = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
-            s, self._s = self._s, _P()
-            _check(self._lib, self._lib.mst_hic_rawstream_close(s, ctypes.byref(rt), ctypes.byref(bt_), ctypes.byref(bt),
-                                                                ctypes.byref(bm)))
-            self.rows_total, self.bytes_total = int(rt.value), int(bt_.value)
-            self.blocks_total, self.blocks_mine = int(bt.value), int(bm.value)
-
-    __del__ = close
+        return _norm_copy(v, n), int(length.value)
 
 
 class HicTransRawStream(HicRawStream):
@@ -256,30 +255,18 @@ class HicTransRawStream(HicRawStream):
     rows are decoded on the GPU (mst_trans_decode_hic_rows).  Versions 7-9 only."""
 
     def __init__(self, hic, chrom_a, chrom_b, resolution, norm, memory_ptr, n_slabs, slab_bytes, threads=0):
-        self._lib, self._hic = hic._lib, hic
-        self._s = _P()
         self.slab_bytes, self.n_slabs = int(slab_bytes), int(n_slabs)
         tr = ctypes.c_int32()
-        _check(self._lib, self._lib.mst_hic_rawstream_open_trans(hic._h, str(chrom_a).encode(), str(chrom_b).encode(),
-                                                                 int(resolution), str(norm).encode(), int(threads), _P(memory_ptr),
-                                                                 int(n_slabs), int(slab_bytes), ctypes.byref(tr),
-                                                                 ctypes.byref(self._s)))
+        self._open(hic, hic._lib.mst_hic_rawstream_open_trans, str(chrom_a).encode(), str(chrom_b).encode(), int(resolution),
+                   str(norm).encode(), int(threads), _P(memory_ptr), int(n_slabs), int(slab_bytes), ctypes.byref(tr))
         self.transposed = bool(tr.value)
-        self.rows_total = self.bytes_total = self.blocks_total = self.blocks_mine = None
 
     def info(self):
         """(norm vector of chrom_a, of chrom_b -- float64 copies, or None for norm NONE --, length of chrom_a, of chrom_b in bp)"""
         va, na, vb, nb, la, lb = _P(), ctypes.c_int64(), _P(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         _check(self._lib, self._lib.mst_hic_rawstream_info_trans(self._s, ctypes.byref(va), ctypes.byref(na), ctypes.byref(vb),
                                                                  ctypes.byref(nb), ctypes.byref(la), ctypes.byref(lb)))
-
-        def vec(p, n):
-            if n.value < 0:
-                return None
-            if n.value == 0:
-                return np.zeros(0, np.float64)
-            return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_double)), shape=(n.value,)).copy()
-        return vec(va, na), vec(vb, nb), int(la.value), int(lb.value)
+        return _norm_copy(va, na), _norm_copy(vb, nb), int(la.value), int(lb.value)
 
 
 class PackedContacts:

@@ -92,6 +92,36 @@ def _slab_count(threads, slab_bytes):
     return max(8, min(256, 2 * threads + 8, max(threads + 2, cap // slab_bytes)))
 
 
+def _pump_slabs(side, pool_bytes, open_stream, upload, prepare=None):
+    """The loop of both streamed reads.  Under _SLAB_LOCK: st = open_stream(pool) on the page-locked pool of `pool_bytes` --
+    nothing but the stream's constructor, so that whatever fails later finds `st` set and closes it (its workers write into the
+    pool) before the lock goes to the next read --, state = prepare(st), then for every slab the stream delivers,
+    upload(pool, state, got) queues its copy (and whatever follows it) on the copy stream `side` and returns the event behind
+    the COPY; a slab goes back to the workers once that event has completed.  Returns (the closed stream, state)."""
+    pending = []
+    _SLAB_LOCK.acquire()
+    st = None
+    try:
+        pool = _slab_pool(pool_bytes)
+        st = open_stream(pool)
+        state = prepare(st) if prepare else None
+        while True:
+            got = st.next(2 if pending else -1)
+            while pending and pending[0][0].query():          # slabs whose copies have completed go back to the workers
+                st.release(pending.pop(0)[1])
+            if got is None:
+                continue
+            if got is False:
+                break
+            pending.append((upload(pool, state, got), got[0]))
+    finally:
+        side.synchronize()          # also on the error path: no copy out of the pool may be in flight when the next read fills it
+        if st is not None:
+            st.close()
+        _SLAB_LOCK.release()
+    return st, state
+
+
 def read_hic_stream_to_device(hic, chrom, res, norm, dpx, chrom_size_bp, device, part=(0, 1), threads=0,
                               slab_records=1 << 19, n_slabs=None, raw=None, keep_raw=False):
     """hicfile.HicFile -> hicfile.PackedContacts whose contacts already sit in DEVICE memory when this returns; the PCIe
@@ -125,45 +155,32 @@ def read_hic_stream_to_device(hic, chrom, res, norm, dpx, chrom_size_bp, device,
     from .engine import device_streams
     side = device_streams(torch.device(device))[2]          # the process's one copy stream of this device
     ddt = torch.uint16 if dist_bytes == 2 else torch.int32
-    _SLAB_LOCK.acquire()
-    st = None
-    parts, pending = [], []
-    try:
-        pool = _slab_pool(n_slabs * slab_bytes)
-        st = HicStream(hic, chrom, res, norm, int(dpx), int(chrom_size_bp), pool.data_ptr(), n_slabs, slab_records, dist_bytes,
-                       threads=threads, part=part)
-        while True:
-            got = st.next(2 if pending else -1)
-            # slabs whose copies have completed go back to the workers
-            while pending and pending[0][0].query():
-                st.release(pending.pop(0)[1])
-            if got is None:
-                continue
-            if got is False:
-                break
-            slab, cnt = got
-            base = slab * slab_bytes
-            full = cnt == slab_records
-            with torch.cuda.stream(side):
-                if full:
-                    # a full slab (all but each worker's last) goes over in ONE copy: its three arrays are contiguous
-                    dv = pool[base:base + slab_bytes].to(device, non_blocking=True)
-                    xd = dv[:4 * cnt].view(torch.int32)
-                    vd = dv[4 * slab_records:4 * slab_records + 4 * cnt].view(torch.float32)
-                    dd = dv[8 * slab_records:8 * slab_records + dist_bytes * cnt].view(ddt)
-                else:
-                    hx = pool[base:base + 4 * cnt].view(torch.int32)
-                    hv = pool[base + 4 * slab_records:base + 4 * slab_records + 4 * cnt].view(torch.float32)
-                    hd = pool[base + 8 * slab_records:base + 8 * slab_records + dist_bytes * cnt].view(ddt)
-                    xd, dd, vd = (t.to(device, non_blocking=True) for t in (hx, hd, hv))
-                ev = side.record_event()
-            parts.append((xd, dd, vd, cnt))
-            pending.append((ev, slab))
-    finally:
-        side.synchronize()          # also on the error path: no copy out of the pool may be in flight when the next read fills it
-        if st is not None:
-            st.close()
-        _SLAB_LOCK.release()
+    parts = []
+
+    def open_stream(pool):
+        return HicStream(hic, chrom, res, norm, int(dpx), int(chrom_size_bp), pool.data_ptr(), n_slabs, slab_records, dist_bytes,
+                         threads=threads, part=part)
+
+    def upload(pool, _, got):
+        slab, cnt = got
+        base = slab * slab_bytes
+        with torch.cuda.stream(side):
+            if cnt == slab_records:
+                # a full slab (all but each worker's last) goes over in ONE copy: its three arrays are contiguous
+                dv = pool[base:base + slab_bytes].to(device, non_blocking=True)
+                xd = dv[:4 * cnt].view(torch.int32)
+                vd = dv[4 * slab_records:4 * slab_records + 4 * cnt].view(torch.float32)
+                dd = dv[8 * slab_records:8 * slab_records + dist_bytes * cnt].view(ddt)
+            else:
+                hx = pool[base:base + 4 * cnt].view(torch.int32)
+                hv = pool[base + 4 * slab_records:base + 4 * slab_records + 4 * cnt].view(torch.float32)
+                hd = pool[base + 8 * slab_records:base + 8 * slab_records + dist_bytes * cnt].view(ddt)
+                xd, dd, vd = (t.to(device, non_blocking=True) for t in (hx, hd, hv))
+            ev = side.record_event()
+        parts.append((xd, dd, vd, cnt))
+        return ev
+
+    st, _ = _pump_slabs(side, n_slabs * slab_bytes, open_stream, upload)
     torch.cuda.current_stream(device).wait_stream(side)
     pc = PackedContacts(None, None, None, st.n, res, part=part[0], n_parts=part[1], blocks_total=st.blocks_total,
                         blocks_mine=st.blocks_mine, count=st.total)
@@ -196,12 +213,12 @@ def _read_hic_raw_to_band(hic, chrom, res, norm, dpx, chrom_size_bp, device, par
         n_slabs = _slab_count(threads, slab_bytes)
     side = device_streams(device)[2]                        # the process's one copy stream of this device
     keep = keep_raw or part[1] > 1 or bool(os.environ.get("MUSTACHE_CHECK_PACKED"))
-    parts, pending = [], []
-    _SLAB_LOCK.acquire()
-    st = None
-    try:
-        pool = _slab_pool(n_slabs * slab_bytes)
-        st = HicRawStream(hic, chrom, res, norm, int(dpx), pool.data_ptr(), n_slabs, slab_bytes, threads=threads, part=part)
+    parts = []
+
+    def open_stream(pool):
+        return HicRawStream(hic, chrom, res, norm, int(dpx), pool.data_ptr(), n_slabs, slab_bytes, threads=threads, part=part)
+
+    def prepare(st):
         normv, length = st.info()
         y_limit = -(-int(chrom_size_bp) // int(res)) if chrom_size_bp and chrom_size_bp > 0 else 0
         n_alloc = max(1, -(-int(length) // int(res)))
@@ -212,33 +229,25 @@ def _read_hic_raw_to_band(hic, chrom, res, norm, dpx, chrom_size_bp, device, par
             stats = torch.zeros(4, dtype=torch.int64, device=device)
             ctx = {"norm": None if normv is None else torch.from_numpy(normv).to(device), "n_norm": -1 if normv is None else len(normv),
                    "max_dist": int(dpx), "y_limit": y_limit, "n_alloc": n_alloc, "dpx": int(dpx)}
-        while True:
-            got = st.next(2 if pending else -1)
-            while pending and pending[0][0].query():          # slabs whose copies have completed go back to the workers
-                st.release(pending.pop(0)[1])
-            if got is None:
-                continue
-            if got is False:
-                break
-            slab, nbytes, rows = got
-            base = slab * slab_bytes
-            with torch.cuda.stream(side), torch.cuda.device(device):
-                if slab_bytes - nbytes - 16 * rows <= slab_bytes // 16:
-                    dv = pool[base:base + slab_bytes].to(device, non_blocking=True)       # a full slab goes over in ONE copy
-                    pay, dr = dv[:nbytes], dv[slab_bytes - 16 * rows:]
-                else:
-                    pay = pool[base:base + nbytes].to(device, non_blocking=True)
-                    dr = pool[base + slab_bytes - 16 * rows:base + slab_bytes].to(device, non_blocking=True)
-                ev = side.record_event()
-                _scatter_rows(lib, pay, dr, rows, ctx, band, stats, side.cuda_stream)
-            if keep:
-                parts.append((pay, dr, rows))
-            pending.append((ev, slab))
-    finally:
-        side.synchronize()          # also on the error path: no copy out of the pool may be in flight when the next read fills it
-        if st is not None:
-            st.close()
-        _SLAB_LOCK.release()
+        return band, stats, ctx, length
+
+    def upload(pool, state, got):
+        slab, nbytes, rows = got
+        base = slab * slab_bytes
+        with torch.cuda.stream(side), torch.cuda.device(device):
+            if slab_bytes - nbytes - 16 * rows <= slab_bytes // 16:
+                dv = pool[base:base + slab_bytes].to(device, non_blocking=True)       # a full slab goes over in ONE copy
+                pay, dr = dv[:nbytes], dv[slab_bytes - 16 * rows:]
+            else:
+                pay = pool[base:base + nbytes].to(device, non_blocking=True)
+                dr = pool[base + slab_bytes - 16 * rows:base + slab_bytes].to(device, non_blocking=True)
+            ev = side.record_event()
+            _scatter_rows(lib, pay, dr, rows, state[2], state[0], state[1], side.cuda_stream)
+        if keep:
+            parts.append((pay, dr, rows))
+        return ev
+
+    st, (band, stats, ctx, length) = _pump_slabs(side, n_slabs * slab_bytes, open_stream, upload, prepare)
     ymax1, kept, beyond, _ = (int(a) for a in stats.cpu().numpy())
     if beyond and part[1] == 1:
         import warnings

@@ -484,3 +484,278 @@ def test_own_inflate_accepts_the_incomplete_codes_zlib_accepts():
             z = None
         assert (z == b"") == ok, ("zlib itself", dist_len, z)
         assert (ours(comp) == 0) == ok and (ok or ours(comp) < 0), (dist_len, ours(comp))
+
+
+# ---- what the shared slab queue, prologue and thread rule of hic_reader.cpp promise ------------------------------------------
+# One small file: chr1 (300 bins, blocks of 16 bins: tens of blocks within the distance limit, fewer than 64), chr3 without a
+# matrix, and the pair (chr1, chr2); the smallest legal slabs (64 packed records, 4096 raw bytes) are exchanged dozens of times.
+_Q = dict(n=300, n2=250, res=1000, dpx=12, cap=64, raw_bytes=4096)
+_E_NOTFOUND, _E_ZLIB = -4, -5
+_KINDS = ("packed", "raw", "trans")
+
+
+def _matrix_blocks(data, key):
+    """[(number, position, size)] of the first zoom of matrix `key` ("c1_c2") of a version 8 file"""
+    import struct
+    at = struct.unpack_from("<q", data, 8)[0] + 4
+    n_entries = struct.unpack_from("<i", data, at)[0]
+    at += 4
+    where = None
+    for _ in range(n_entries):
+        end = data.index(b"\x00", at)
+        name, (pos, _size) = data[at:end].decode(), struct.unpack_from("<qi", data, end + 1)
+        at = end + 13
+        if name == key:
+            where = pos
+    at = data.index(b"\x00", where + 12) + 1 + 4 + 16                       # c1, c2, nZooms, "BP\0", zoom index, 4 floats
+    _res, _bbc, bcc, nb = struct.unpack_from("<iiii", data, at)
+    return bcc, [struct.unpack_from("<iqi", data, at + 16 + 16 * i) for i in range(nb)]
+
+
+def write_queue_files(directory):
+    """good.hic and bad.hic in `directory`: bad.hic is a copy with one block of "1_1" and one of "1_2" -- neither the first --
+    made undecodable.  Returns the two paths.  (scripts/reader_sanitize_main.cpp reads the same pair.)"""
+    from hic_trans_writer import write_hic_pairs
+    q = _Q
+    x, y, c = _contacts(q["n"], 20, 12000, 31, integer=False)
+    rng = np.random.default_rng(32)
+    key = np.unique(rng.integers(0, q["n"], 2500) * 1000003 + rng.integers(0, q["n2"], 2500))
+    norm1, norm2 = rng.uniform(0.5, 2.0, q["n"] + 1), rng.uniform(0.5, 2.0, q["n2"] + 1)
+    good, bad = os.path.join(str(directory), "good.hic"), os.path.join(str(directory), "bad.hic")
+    write_hic_pairs(good, [("All", 1000), ("chr1", q["n"] * q["res"]), ("chr2", q["n2"] * q["res"]), ("chr3", 50000)],
+                    {(1, 1): {q["res"]: (x, y, c)}, (1, 2): {q["res"]: (key // 1000003, key % 1000003, rng.integers(1, 50, len(key)))}},
+                    {("KR", 1, q["res"]): norm1, ("KR", 2, q["res"]): norm2}, version=8, block_bin_count=16)
+    with open(good, "rb") as fh:
+        data = bytearray(fh.read())
+    bcc, intra = _matrix_blocks(data, "1_1")
+    diagonal = [b for b in intra if b[0] // bcc == b[0] % bcc]            # inside any distance limit
+    for number, pos, size in (diagonal[len(diagonal) // 2], _matrix_blocks(data, "1_2")[1][40]):
+        assert size > 12 and pos > min(b[1] for b in intra)
+        data[pos + 2:pos + 8] = b"\xff" * 6                                # behind the zlib header: a reserved deflate block type
+    with open(bad, "wb") as fh:
+        fh.write(bytes(data))
+    return good, bad
+
+
+@pytest.fixture(scope="module")
+def queue_files(tmp_path_factory):
+    return write_queue_files(tmp_path_factory.mktemp("queue"))
+
+
+class _Drain:
+    """one stream of `kind` over memory of its own; take() -> the records of the next slab (copied out) or None / False"""
+
+    def __init__(self, kind, h, n_slabs, threads=0, part=(0, 1)):
+        from mustache_amd.hicfile import HicRawStream, HicStream, HicTransRawStream
+        q = _Q
+        self.kind, self.slab_bytes = kind, q["cap"] * 10 if kind == "packed" else q["raw_bytes"]
+        self.mem = np.zeros(n_slabs * self.slab_bytes + 16, np.uint8)
+        self.base0 = (-self.mem.ctypes.data) % 16
+        ptr = self.mem.ctypes.data + self.base0
+        if kind == "packed":
+            self.st = HicStream(h, "chr1", q["res"], "KR", q["dpx"], 0, ptr, n_slabs, q["cap"], 2, threads=threads, part=part)
+        elif kind == "raw":
+            self.st = HicRawStream(h, "chr1", q["res"], "KR", q["dpx"], ptr, n_slabs, self.slab_bytes, threads=threads, part=part)
+            self.norm = self.st.info()[0]
+        else:
+            self.st = HicTransRawStream(h, "chr1", "chr2", q["res"], "KR", ptr, n_slabs, self.slab_bytes, threads=threads)
+
+    def take(self, timeout_ms=-1):
+        """(slab, x, y, v) -- x, y, v None for a trans slab, whose rows only the device decodes"""
+        from hic_rows_numpy import decode_slab
+        r = self.st.next(timeout_ms)
+        if not r:
+            return r
+        base, cap = self.base0 + r[0] * self.slab_bytes, _Q["cap"]
+        if self.kind == "packed":
+            cnt = r[1]
+            assert 0 < cnt <= cap
+            x = self.mem[base:base + 4 * cnt].view(np.int32).astype(np.int64)
+            v = self.mem[base + 4 * cap:base + 4 * cap + 4 * cnt].view(np.float32).copy()
+            return r[0], x, x + self.mem[base + 8 * cap:base + 8 * cap + 2 * cnt].view(np.uint16), v
+        nbytes, rows = r[1:]
+        assert rows > 0 and nbytes + 16 * rows <= self.slab_bytes
+        if self.kind == "trans":
+            return r[0], None, None, None
+        return (r[0],) + tuple(decode_slab(self.mem[base:base + nbytes].copy(),
+                                           self.mem[base + self.slab_bytes - 16 * rows:base + self.slab_bytes].copy(), self.norm,
+                                           _Q["dpx"]))
+
+    def rest(self, got):
+        """drain to the end, every slab released at once; `got` collects the records"""
+        while True:
+            r = self.take(50)
+            if r is False:
+                return got
+            if r is not None:
+                got.append(r[1:])
+                self.st.release(r[0])
+
+
+def _one_shot(h, threads=0):
+    from mustache_amd.hicfile import read_intra_packed
+    pc = read_intra_packed(h, "chr1", _Q["res"], "KR", _Q["dpx"], 0, threads=threads)
+    x = pc.x.astype(np.int64)
+    return _sorted(x, x + pc.dist, pc.v), pc
+
+
+def _same_records(got, want):
+    x, y, v = (np.concatenate([g[i] for g in got]) for i in range(3))
+    x, y, v = _sorted(x, y, v.astype(np.float32))
+    return len(x) == len(want[0]) > 1000 and all(np.array_equal(a, b) for a, b in zip((x, y, v), want))
+
+
+@pytest.mark.parametrize("kind", _KINDS)
+def test_stream_closed_early_returns_its_counters(queue_files, kind):
+    """a consumer that takes one of two slabs, never gives it back and closes: the worker waiting for a slab is cancelled, close
+    returns OK with the counters, a second close does nothing.  (Closed on a helper thread so that a lost wake-up fails here
+    instead of hanging the suite.)"""
+    import threading
+    from mustache_amd.hicfile import HicFile
+    with HicFile(queue_files[0]) as h:
+        d = _Drain(kind, h, 2)
+        assert d.take(-1)
+        err = []
+
+        def close():
+            try:
+                d.st.close()
+            except Exception as e:                 # noqa: BLE001
+                err.append(e)
+        t = threading.Thread(target=close, daemon=True)
+        t.start()
+        t.join(60)
+        assert not t.is_alive() and not err
+        counters = ("n", "total") if kind == "packed" else ("rows_total", "bytes_total")
+        assert all(getattr(d.st, a) > 0 for a in counters + ("blocks_total", "blocks_mine"))
+        assert d.st.blocks_mine == d.st.blocks_total
+        before = [getattr(d.st, a) for a in counters]
+        d.st.close()
+        assert before == [getattr(d.st, a) for a in counters]
+
+
+@pytest.mark.parametrize("kind", ("packed", "raw"))
+def test_stream_back_pressure_and_the_three_answers_of_next(queue_files, kind):
+    """two slabs = one worker: with both slabs in the consumer's hands next(20) answers None; one slab given back, next(-1)
+    delivers again; at the end next answers False, and the records are those of the one-shot read"""
+    from mustache_amd.hicfile import HicFile
+    with HicFile(queue_files[0]) as h:
+        want, _ = _one_shot(h)
+        d = _Drain(kind, h, 2)
+        a, b = d.take(-1), d.take(-1)
+        assert a and b and a[0] != b[0]
+        assert d.take(20) is None
+        d.st.release(a[0])
+        c = d.take(-1)
+        assert c and c[0] == a[0]
+        d.st.release(b[0])
+        d.st.release(c[0])
+        got = d.rest([a[1:], b[1:], c[1:]])
+        assert d.take(0) is False
+        d.st.close()
+        assert _same_records(got, want)
+        # the two slabs went round many times (a raw slab of 4096 bytes holds some 600 records, a packed one 64)
+        assert len(got) > (24 if kind == "packed" else 4)
+
+
+@pytest.mark.parametrize("threads", (1, 4))
+def test_undecodable_block_in_the_middle_is_reported_by_every_path(queue_files, threads):
+    """a block that is not the first fails to inflate: every stream's next raises MST_IO_E_ZLIB "block decode failed" before or
+    at the end of the drain and its close reports the same; both one-shot reads return that code"""
+    from mustache_amd.hicfile import HicError, HicFile, read_intra_packed
+    with HicFile(queue_files[1]) as h:
+        for kind in _KINDS:
+            d = _Drain(kind, h, 5, threads=threads)
+            with pytest.raises(HicError) as e:
+                d.rest([])
+            assert e.value.code == _E_ZLIB and "block decode failed" in str(e.value)
+            with pytest.raises(HicError) as e2:
+                d.st.close()
+            assert e2.value.code == _E_ZLIB and str(e2.value) == str(e.value)
+        for read in (lambda: h.read_intra("chr1", _Q["res"], "KR", _Q["dpx"], threads=threads),
+                     lambda: read_intra_packed(h, "chr1", _Q["res"], "KR", _Q["dpx"], 0, threads=threads)):
+            with pytest.raises(HicError) as e:
+                read()
+            assert e.value.code == _E_ZLIB and "block decode failed" in str(e.value)
+
+
+def test_every_path_shares_one_prologue(queue_files):
+    """the block list, its split into parts and the four not-found errors (chromosome, matrix, resolution, normalisation
+    vector) are the same from the one-shot reads, the packed stream and the raw stream"""
+    from mustache_amd.hicfile import HicError, HicFile, HicRawStream, HicStream, read_intra_packed
+    q = _Q
+    mem = np.zeros(2 * q["raw_bytes"] + 16, np.uint8)
+    ptr = mem.ctypes.data + (-mem.ctypes.data) % 16
+    with HicFile(queue_files[0]) as h:
+        for part in ((0, 1), (1, 3), (7, 8)):
+            pc = read_intra_packed(h, "chr1", q["res"], "KR", q["dpx"], 0, part=part)
+            want = (pc.blocks_total, pc.blocks_mine)
+            assert 16 < want[0] < 64 and (want[1] == want[0] if part[1] == 1 else 0 < want[1] < want[0])
+            for st in (HicStream(h, "chr1", q["res"], "KR", q["dpx"], 0, ptr, 2, q["cap"], 2, part=part),
+                       HicRawStream(h, "chr1", q["res"], "KR", q["dpx"], ptr, 2, q["raw_bytes"], part=part)):
+                st.close()
+                assert (st.blocks_total, st.blocks_mine) == want
+        for chrom, res, norm, text in (("chr9", q["res"], "KR", "chromosome chr9 is not in the file"),
+                                       ("chr3", q["res"], "KR", "no intra-chromosomal matrix for chr3"),
+                                       ("chr1", 7777, "KR", "resolution 7777 is not in the file"),
+                                       ("chr1", q["res"], "VC", "no VC normalisation vector for chr1 at 1000 bp")):
+            seen = set()
+            for read in (lambda: h.read_intra(chrom, res, norm, q["dpx"]),
+                         lambda: read_intra_packed(h, chrom, res, norm, q["dpx"], 0),
+                         lambda: HicStream(h, chrom, res, norm, q["dpx"], 0, ptr, 2, q["cap"], 2),
+                         lambda: HicRawStream(h, chrom, res, norm, q["dpx"], ptr, 2, q["raw_bytes"])):
+                with pytest.raises(HicError) as e:
+                    read()
+                seen.add((e.value.code, str(e.value)))
+            assert seen == {(_E_NOTFOUND, "libmustache_io error -4: " + text)}
+
+
+def test_thread_and_slab_counts_do_not_change_the_records(queue_files):
+    """threads asked for: the default, 1, 3 and more than the file has blocks; slabs: 2 (one worker whatever was asked for) and
+    5 -- the same records from the one-shot read and from both streams"""
+    from mustache_amd.hicfile import HicFile
+    with HicFile(queue_files[0]) as h:
+        want, pc = _one_shot(h, 1)
+        assert pc.blocks_total < 64
+        for threads in (0, 1, 3, 64):
+            assert all(np.array_equal(a, b) for a, b in zip(_one_shot(h, threads)[0], want))
+            for n_slabs in (2, 5):
+                for kind in ("packed", "raw"):
+                    d = _Drain(kind, h, n_slabs, threads=threads)
+                    got = d.rest([])
+                    d.st.close()
+                    assert _same_records(got, want), (kind, threads, n_slabs)
+
+
+def test_pump_closes_the_stream_before_the_slab_lock_goes_on(queue_files, monkeypatch):
+    """normalize._pump_slabs owns the stream from the moment it exists: when the preparation behind the open fails (the band's
+    allocation, say), the workers are joined -- close has set the counters -- before the lock on the shared slab pool is
+    released, and the copy stream was synchronised first.  (No GPU: plain memory stands in for the page-locked pool.)"""
+    import threading
+    import torch
+    from mustache_amd import normalize
+    from mustache_amd.hicfile import HicFile, HicRawStream
+    monkeypatch.setattr(normalize, "_slab_pool", lambda nbytes: torch.zeros(nbytes + 16, dtype=torch.uint8))
+    seen, order = [], []
+
+    class Side:
+        def synchronize(self):
+            order.append(("synchronize", seen[0].rows_total))
+
+    def open_stream(pool):
+        ptr = pool.data_ptr() + (-pool.data_ptr()) % 16
+        seen.append(HicRawStream(h, "chr1", _Q["res"], "KR", _Q["dpx"], ptr, 4, _Q["raw_bytes"], threads=3))
+        return seen[0]
+
+    def prepare(st):
+        raise MemoryError("no room for the band")
+
+    with HicFile(queue_files[0]) as h:
+        with pytest.raises(MemoryError):
+            normalize._pump_slabs(Side(), 4 * _Q["raw_bytes"], open_stream, lambda *a: None, prepare)
+        assert order == [("synchronize", None)] and seen[0].rows_total is not None and seen[0].blocks_mine > 16
+        free = []
+        t = threading.Thread(target=lambda: free.append(normalize._SLAB_LOCK.acquire(timeout=10) and not normalize._SLAB_LOCK.release()))
+        t.start()
+        t.join(30)
+        assert free == [True]
