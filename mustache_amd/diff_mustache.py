@@ -329,6 +329,10 @@ def parse_args(args):
     p.add_argument("-v", "--verbose", dest="verbose", type=bool, default=True, required=False)
     p.add_argument("--balance", dest="balance", default=None, metavar="ICE", required=False,
                    help="OPTIONAL: balance each raw contact map on the GPU (ICE) instead of -b1/-b2 / -norm")
+    p.add_argument("--trans-all", dest="trans_all", action="store_true",
+                   help="OPTIONAL: call differential inter-chromosomal loops for every unordered pair of the -ch list (without "
+                        "-ch: of every chromosome of the first .hic / .cool / .mcool file) in shared launches; no "
+                        "intra-chromosomal rows.")
     return p.parse_args(args)
 
 
@@ -354,6 +358,79 @@ HEADER = "BIN1_CHR\tBIN1_START\tBIN1_END\tBIN2_CHROMOSOME\tBIN2_START\tBIN2_END\
 SUFFIX = {1: ".loop1", 2: ".diffloop1", 3: ".loop2", 4: ".diffloop2"}
 
 
+def write_tagged(outdir, chromosome, chromosome2, res, rows, first):
+    """rows [x, y, fdr, sigma, tag] of one chromosome pair into outdir + SUFFIX[tag] (`first`: the four headers before them);
+    returns the rows per tag"""
+    if first:
+        for suf in SUFFIX.values():
+            with open(outdir + suf, 'w') as fh:
+                fh.write(HEADER)
+    counts = {1: 0, 2: 0, 3: 0, 4: 0}
+    files = {t: open(outdir + suf, 'a') for t, suf in SUFFIX.items()}
+    try:
+        from .mustache import _scalar_text           # the reference's str() of NumPy scalars, same text (mustache.write_loops)
+        c1, c2, rs = str(chromosome), str(chromosome2), int(res)
+        for r in rows:
+            counts[r[4]] += 1
+            x, y = int(r[0]), int(r[1])
+            files[r[4]].write("%s\t%d\t%d\t%s\t%d\t%d\t%s\t%s\n" % (c1, x * rs, (x + 1) * rs, c2, y * rs, (y + 1) * rs,
+                                                                   _scalar_text(r[2]), _scalar_text(r[3])))
+    finally:
+        for fh in files.values():
+            fh.close()
+    return counts
+
+
+def print_found(counts, chromosome, chromosome2, pt, pt2, seconds):
+    where = chromosome if chromosome == chromosome2 else "%s,%s" % (chromosome, chromosome2)
+    print(f"({counts[1]},{counts[3]}) loops and ({counts[2]},{counts[4]}) differential-loops found in "
+          f"chrmosome={where} for detection-fdr<{pt} and difference-fdr<{pt2} in {seconds:.2f}sec")
+
+
+def trans_all_request(f1, f2, res, ch, ch2, balance, world_size):
+    """--trans-all -> the pairs (mustache.trans_all_pairs on the first file, in its order), or the `Error:` line of a run that
+    cannot go ahead; decided before the GPU is touched, and before a file is read."""
+    from .mustache import trans_all_pairs, trans_all_refusal
+    why = trans_all_refusal(f1, ch2) or trans_all_refusal(f2, ch2)
+    if why:
+        return why
+    if balance is not None:
+        return "Error: --balance does not apply to inter-chromosomal pairs"
+    if world_size > 1:
+        return "Error: inter-chromosomal pairs run on one GPU only (this run has %d ranks)" % world_size
+    return trans_all_pairs(f1, res, ch, ch2)
+
+
+def run_trans_all(f1, f2, args, res, pairs, device=None):
+    """The --trans-all run: the next pair's two samples are read on a reader thread while the current pair joins the batch
+    (mustache.run_trans_pairs, diff_trans_genome.DiffTransGenomeCaller); rows are written in pair order, the headers with the
+    first pair's."""
+    from .diff_trans_genome import DiffTransGenomeCaller
+    from .mustache import run_trans_pairs
+    from .trans import read_trans_contacts
+    state = {"t0": time.time()}
+
+    def fetch(k):
+        recs, res_seen = [], None
+        for f in (f1, f2):
+            got = read_trans_contacts(f, args.norm_method, pairs[k][0], pairs[k][1], res, device=device)
+            if got is not None:
+                if res_seen is not None and got[3] != res_seen:
+                    raise ValueError('Both contact maps should have the same resolution.')
+                res_seen = got[3]
+            recs.append(None if got is None else got[:3])
+        return recs
+
+    def emit(k, o):
+        counts = write_tagged(args.outdir, pairs[k][0], pairs[k][1], res, o, first=(k == 0))
+        print_found(counts, pairs[k][0], pairs[k][1], args.pt, args.pt2, time.time() - state["t0"])
+        state["t0"] = time.time()
+
+    caller = DiffTransGenomeCaller([args.s_z * (2 ** i) for i in range(args.octaves)], args.st, args.pt, args.pt2, emit,
+                                   verbose=args.verbose)
+    run_trans_pairs(pairs, fetch, lambda k, recs, label: caller.add(k, recs[0], recs[1], label), caller.flush, args.verbose)
+
+
 def main(argv=None):
     t0 = time.time()
     args = parse_args(sys.argv[1:] if argv is None else argv)
@@ -369,6 +446,14 @@ def main(argv=None):
     if not res:
         print("Error: Invalid resolution")
         return
+    if args.trans_all:
+        from .sharding import init_from_env
+        pairs = trans_all_request(f1, f2, res, args.chromosome, args.chromosome2, args.balance, init_from_env()[1])
+        if isinstance(pairs, str):
+            print(pairs)
+            return
+        import torch
+        return run_trans_all(f1, f2, args, res, pairs, device=torch.device("cuda", torch.cuda.current_device()))
     pairs = chromosome_pairs(f1, res, args.chromosome, args.chromosome2)
     if isinstance(pairs, str):
         print(pairs)
@@ -409,25 +494,7 @@ def main(argv=None):
     mine = owned_chromosomes(f1, res, pairs, rank, world_size) if world_size > 1 else list(range(n_cis))
 
     def write(i, o):
-        chromosome, chromosome2 = pairs[i]
-        if i == 0:
-            for suf in SUFFIX.values():
-                with open(args.outdir + suf, 'w') as fh:
-                    fh.write(HEADER)
-        counts = {1: 0, 2: 0, 3: 0, 4: 0}
-        files = {t: open(args.outdir + suf, 'a') for t, suf in SUFFIX.items()}
-        try:
-            from .mustache import _scalar_text           # the reference's str() of NumPy scalars, same text (mustache.write_loops)
-            c1, c2, rs = str(chromosome), str(chromosome2), int(res)
-            for r in o:
-                counts[r[4]] += 1
-                x, y = int(r[0]), int(r[1])
-                files[r[4]].write("%s\t%d\t%d\t%s\t%d\t%d\t%s\t%s\n" % (c1, x * rs, (x + 1) * rs, c2, y * rs, (y + 1) * rs,
-                                                                       _scalar_text(r[2]), _scalar_text(r[3])))
-        finally:
-            for fh in files.values():
-                fh.close()
-        return counts
+        return write_tagged(args.outdir, pairs[i][0], pairs[i][1], res, o, first=(i == 0))
 
     results = {}
 
@@ -439,9 +506,7 @@ def main(argv=None):
             counts = {t: sum(1 for r in o if r[4] == t) for t in (1, 2, 3, 4)}
         else:
             counts = write(i, o)
-        where = chromosome if chromosome == pairs[i][1] else "%s,%s" % pairs[i]
-        print(f"({counts[1]},{counts[3]}) loops and ({counts[2]},{counts[4]}) differential-loops found in "
-              f"chrmosome={where} for detection-fdr<{args.pt} and difference-fdr<{args.pt2} in {time.time() - t0:.2f}sec")
+        print_found(counts, chromosome, pairs[i][1], args.pt, args.pt2, time.time() - t0)
         t0 = time.time()
 
     # Several chromosomes on this rank (the whole-genome run of BASELINE config 5): both samples' normalised bands are

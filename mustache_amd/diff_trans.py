@@ -31,13 +31,47 @@ from ._lib import ptr as _ptr, stream as _stream
 from .trans import TRANS_CHUNK, TransCaller, TransError, owned_rows, prepared_tiles, read_trans_contacts, trans_tiling
 
 
+def pair_tile_loops(eng, dev, B, C, fill, st, pt, pt2):
+    """Rule 4 on the B tile PAIRS of one launch: `fill(s, half)` scatters sample s's records into its half of one buffer of
+    2 B tiles (sample 1 in [0, B), sample 2 in [B, 2 B)), then one prologue, one fused scale-space launch over both samples'
+    tiles with the pair p-values (mst_diff_dog_tiles) and one batched tail.  Per tile pair its (loops1, diff_loops1, loops2,
+    diff_loops2), rows [x, y, fdr, sigma] in TILE coordinates."""
+    import torch
+    from .diff_mustache import _pair_tails
+
+    def both(c):
+        fill(0, c[:B])
+        fill(1, c[B:])
+    c, nz, nzc = prepared_tiles(eng, dev, 2 * B, C, both)
+    with torch.cuda.device(dev):
+        batch = eng.run_filled_pairs(c, nz, nzc, tiles=True)
+    return _pair_tails(batch, [(k, B + k, 0) for k in range(B)], pt, pt2, st, False)
+
+
+def tagged_owned_rows(res4, tiling, i, j):
+    """the map rows [x, y, fdr, sigma, tag] of tile pair (i, j)'s four lists that the tile owns (rule 3), tag 1..4"""
+    return [row + [tag] for tag, loops in enumerate(res4, start=1) for row in owned_rows(loops, tiling, i, j)]
+
+
+def row_order(r):
+    """rule 5's order of a pair's rows: (tag, x, y)"""
+    return (r[4], int(r[0]), int(r[1]))
+
+
+def tile_pair_bytes(C, n_octaves=2):
+    """HBM of one tile pair of C x C in a launch, before the record buffers: two tiles (float64), two masks (bytes) and D_2 of
+    the difference image per octave (float64) -- 34 C^2 at two octaves, 136 MB at C = 2000"""
+    return (2 * 8 + 2 * 1 + 8 * int(n_octaves)) * int(C) * int(C)
+
+
 class DiffTransCaller(TransCaller):
     """Rules 2-5 on the GPU for the records of two samples.  `tiles_per_launch` tile PAIRS go through two scatters, one
-    prologue and one fused scale-space launch over both samples' tiles, one mst_diff_dog_tiles and one batched tail."""
+    prologue and one fused scale-space launch over both samples' tiles, one mst_diff_dog_tiles and one batched tail
+    (pair_tile_loops)."""
 
     # tile PAIRS per launch when the caller names none.  A pair of 2000 x 2000 tiles at two octaves holds 2 x 32 MB of tiles,
-    # 2 x 4 MB of masks and 2 x 32 MB of D_2 in HBM, 136 MB before the record buffers: 32 pairs = the 64 tiles of the one-sample
-    # caller's launch, ~4.4 GB.
+    # 2 x 4 MB of masks and 2 x 32 MB of D_2 in HBM, 136 MB before the record buffers (tile_pair_bytes): 32 pairs = the 64 tiles
+    # of the one-sample caller's launch, ~4.4 GB.
     PAIRS_PER_LAUNCH = 32
 
     def __init__(self, octave_values=(1.6, 3.2), device=None, tiles_per_launch=None, chunk=TRANS_CHUNK):
@@ -47,9 +81,7 @@ class DiffTransCaller(TransCaller):
         """rules 3-5 on two samples' normalised device records s = (x, y, vz): rows [x, y, fdr, sigma, tag]"""
         import torch
         from . import _lib
-        from .diff_mustache import _pair_tails
-        eng, dev = self.eng, self.device
-        lib = eng.lib
+        dev, lib = self.device, self.eng.lib
         tiling = trans_tiling(n1, n2, self.chunk)
         C, (rs, _), (cs, _) = tiling
         tiles = [(i, j) for i in range(len(rs)) for j in range(len(cs))]
@@ -60,19 +92,13 @@ class DiffTransCaller(TransCaller):
             row0 = torch.tensor([rs[i] for i, _ in group], dtype=torch.int64, device=dev)
             col0 = torch.tensor([cs[j] for _, j in group], dtype=torch.int64, device=dev)
 
-            def fill(c):                                                         # sample 1 in [0, P), sample 2 in [P, 2P)
-                for (x, y, vz), half in ((s1, c[:P]), (s2, c[P:])):
-                    _lib.check(lib.mst_trans_scatter_tiles(_ptr(x), _ptr(y), _ptr(vz), int(vz.numel()), _ptr(row0), _ptr(col0),
-                                                           P, C, _ptr(half), _stream()))
-            c, nz, nzc = prepared_tiles(eng, dev, 2 * P, C, fill)
-            with torch.cuda.device(dev):
-                batch = eng.run_filled_pairs(c, nz, nzc, tiles=True)
-            tails = _pair_tails(batch, [(p, P + p, 0) for p in range(P)], pt, pt2, st, False)
-            for (i, j), res4 in zip(group, tails):
-                for tag, loops in enumerate(res4, start=1):
-                    out += [row + [tag] for row in owned_rows(loops, tiling, i, j)]
-            del batch, c, nz
-        out.sort(key=lambda r: (r[4], int(r[0]), int(r[1])))
+            def fill(s, half):
+                x, y, vz = (s1, s2)[s]
+                _lib.check(lib.mst_trans_scatter_tiles(_ptr(x), _ptr(y), _ptr(vz), int(vz.numel()), _ptr(row0), _ptr(col0),
+                                                       P, C, _ptr(half), _stream()))
+            for (i, j), res4 in zip(group, pair_tile_loops(self.eng, dev, P, C, fill, st, pt, pt2)):
+                out += tagged_owned_rows(res4, tiling, i, j)
+        out.sort(key=row_order)
         return out
 
     def run(self, rec1, rec2, st, pt, pt2, verbose=False, label=""):

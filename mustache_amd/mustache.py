@@ -538,13 +538,21 @@ def chromosome_pairs(f, res, ch, ch2):
     return list(zip(ch, ch2))
 
 
+def trans_all_refusal(f, ch2):
+    """the Error: line of a --trans-all run that `f` or -ch2 rules out, or None; reads nothing"""
+    if isinstance(ch2, list):
+        return "Error: --trans-all pairs the -ch list with itself; give -ch2 without it"
+    if not str(f).endswith((".cool", ".mcool", ".hic")):
+        return "Error: Interchromosomal analysis is only supported for .hic and .cool input formats."
+    return None
+
+
 def trans_all_pairs(f, res, ch, ch2):
     """--trans-all -> every unordered pair (A, B) of the -ch list in list order (without -ch: of list_chromosomes(f, res)), or
     the Error: line to print."""
-    if isinstance(ch2, list):
-        return "Error: --trans-all pairs the -ch list with itself; give -ch2 without it"
-    if not f.endswith((".cool", ".mcool", ".hic")):
-        return "Error: Interchromosomal analysis is only supported for .hic and .cool input formats."
+    why = trans_all_refusal(f, ch2)
+    if why:
+        return why
     if not ch or ch == 'n':
         from .readers import list_chromosomes
         ch = list_chromosomes(f, res)
@@ -552,19 +560,48 @@ def trans_all_pairs(f, res, ch, ch2):
     return [(ch[i], ch[j]) for i in range(len(ch)) for j in range(i + 1, len(ch))]
 
 
+def read_ahead(count, fetch):
+    """(k, fetch(k)) for k = 0 .. count - 1 in order, fetch(k + 1) running on a reader thread while the caller works on k; what
+    fetch raises is re-raised here, at its item's turn"""
+    from concurrent.futures import ThreadPoolExecutor
+
+    def guarded(k):
+        try:
+            return fetch(k)
+        except BaseException as e:
+            return e
+
+    with ThreadPoolExecutor(max_workers=1) as pool:
+        ahead = pool.submit(guarded, 0) if count else None
+        for k in range(count):
+            got = ahead.result()
+            ahead = pool.submit(guarded, k + 1) if k + 1 < count else None
+            if isinstance(got, BaseException):
+                raise got
+            yield k, got
+
+
+def run_trans_pairs(pairs, fetch, add, flush, verbose):
+    """The body of a --trans-all run, one sample or two: pair k's records, read ahead (read_ahead), join the batch through
+    `add(k, records, label)`; `flush()` at the end."""
+    for k, records in read_ahead(len(pairs), fetch):
+        if verbose:
+            print("Reading contact map (pair %s,%s)..." % pairs[k])
+        add(k, records, "%s,%s" % pairs[k])
+        del records
+    flush()
+
+
 def run_trans_all(f, args, res, pairs, device=None):
     """The --trans-all run: the next pair is read on a reader thread while the current one joins the batch
     (trans_genome.TransGenomeCaller); rows are written in pair order, the header with the first pair's."""
-    from concurrent.futures import ThreadPoolExecutor
     from .trans import read_trans_contacts
     from .trans_genome import TransGenomeCaller
     state = {"first": True, "t0": time.time()}
 
     def fetch(k):
-        try:
-            return read_trans_contacts(f, args.norm_method, pairs[k][0], pairs[k][1], res, device=device)
-        except BaseException as e:          # re-raised in the main thread, at this pair's turn
-            return e
+        contacts = read_trans_contacts(f, args.norm_method, pairs[k][0], pairs[k][1], res, device=device)
+        return None if contacts is None else contacts[:3]
 
     def emit(k, o):
         chromosome, chromosome2 = pairs[k]
@@ -576,18 +613,7 @@ def run_trans_all(f, args, res, pairs, device=None):
         state["t0"] = time.time()
 
     caller = TransGenomeCaller([args.s_z * (2 ** i) for i in range(args.octaves)], args.st, args.pt, emit, verbose=args.verbose)
-    with ThreadPoolExecutor(max_workers=1) as pool:
-        ahead = pool.submit(fetch, 0) if pairs else None
-        for k in range(len(pairs)):
-            contacts = ahead.result()
-            ahead = pool.submit(fetch, k + 1) if k + 1 < len(pairs) else None
-            if isinstance(contacts, BaseException):
-                raise contacts
-            if args.verbose:
-                print("Reading contact map (pair %s,%s)..." % pairs[k])
-            caller.add(k, None if contacts is None else contacts[:3], "%s,%s" % pairs[k])
-            del contacts
-        caller.flush()
+    run_trans_pairs(pairs, fetch, caller.add, caller.flush, args.verbose)
 
 
 def owned_chromosomes(f, res, pairs, rank, world):

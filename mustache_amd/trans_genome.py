@@ -16,6 +16,9 @@ call_trans_coo returns for that pair alone.  What changes is how the work reache
   group's pairs are a contiguous range, so its records are one range of the batch; mst_trans_scatter_worklist writes them into
   the group's tiles, finding the windows that hold a record from its coordinates.  Everything after the scatter is the code
   TransCaller.run_tiles runs too: trans.tile_loops (mst_trans_prologue, the sigma loop, the batched tail) and trans.owned_rows.
+The batch body (PairBatcher, SampleBatch) is written for S samples per pair: TransGenomeCaller is its one-sample form,
+diff_trans_genome.DiffTransGenomeCaller its two-sample form (a pair's dimensions are the maxima over the samples' extents, a tile
+is kept when every sample's count reaches the threshold, every sample is scattered into its own tiles of the launch).
 """
 import numpy as np
 
@@ -82,25 +85,119 @@ def launch_groups(table, counts, tiles_per_launch, threshold=TRANS_MIN_TESTED):
     return [tuple(g) for g in groups]
 
 
-def default_budget(device, chunk, tiles_per_launch):
+def default_budget(device, chunk, tiles_per_launch, bytes_per_pixel=9):
     """Bytes of records (RECORD_BYTES each) a run may hold before it flushes them as one batch: what
-    pipeline.genome_batch_budget allows, less the tile buffers of one launch (9 bytes per pixel: c and nz)."""
+    pipeline.genome_batch_budget allows, less the tile buffers of one launch (`bytes_per_pixel` of each of its
+    `tiles_per_launch` tiles; one sample: 9, c and nz)."""
     from .pipeline import genome_batch_budget
-    tile_bytes = 9 * int(tiles_per_launch) * int(chunk) * int(chunk)
+    tile_bytes = int(bytes_per_pixel) * int(tiles_per_launch) * int(chunk) * int(chunk)
     return max(0, genome_batch_budget(device) - tile_bytes)
 
 
-class TransGenomeCaller:
-    """add(index, records, label) pair by pair, flush() at the end; `emit(index, loops)` receives every pair's loops in the
-    order the pairs were added.  `budget_bytes` bounds the records held (RECORD_BYTES each); the partition into batches
-    changes no bit of the output, since every pair is normalised by its own statistics."""
+def joint_dims(per_sample):
+    """dims of pair_table from the samples' own: per_sample[s][p] = (n1, n2) of pair p in sample s, or None where rule 2 leaves
+    the sample nothing to tile (no record, std = 0, a non-finite mean or std).  Rule 3: a pair is tiled over the maxima of its
+    samples' dimensions -- and not at all when one of them is None."""
+    dims = []
+    for of_pair in zip(*per_sample):
+        if any(d is None for d in of_pair):
+            dims.append(None)
+        else:
+            dims.append((max(int(d[0]) for d in of_pair), max(int(d[1]) for d in of_pair)))
+    return dims
 
-    def __init__(self, octave_values, st, pt, emit, chunk=TRANS_CHUNK, tiles_per_launch=None, budget_bytes=None, stats=None,
+
+def joint_counts(counts):
+    """the count the skip rule tests per tile: the smallest of the samples' counts (a tile pair is kept only when EVERY
+    sample holds TRANS_MIN_TESTED records with v' != 0 in its window)"""
+    out = np.asarray(counts[0])
+    for c in counts[1:]:
+        out = np.minimum(out, np.asarray(c))
+    return out
+
+
+class SampleBatch:
+    """One sample's records of the P pairs of a batch: concatenated (x, y, v [N], seg [P + 1]), normalised in place pair by
+    pair (mst_trans_zscore_segmented), with every pair's {mean, std, n, flags} (`stats` [P, 4]) and {max x, max y} (`extent`
+    [P, 2]) on the host after ONE copy.  `recs[p]` = device (x, y, v) or None, at least one not None; the list is emptied as the
+    records are copied."""
+
+    def __init__(self, lib, dev, recs):
+        import torch
+        from . import _lib
+        self.lib, self.dev = lib, dev
+        P = self.P = len(recs)
+        self.lens = [0 if r is None else int(r[2].numel()) for r in recs]
+        seg = self.seg = np.zeros(P + 1, np.int64)
+        np.cumsum(self.lens, out=seg[1:])
+        N = self.N = int(seg[-1])
+        x = self.x = torch.empty(N, dtype=torch.int32, device=dev)
+        y = self.y = torch.empty(N, dtype=torch.int32, device=dev)
+        v = self.v = torch.empty(N, dtype=torch.float64, device=dev)
+        for p in range(P):                                         # the batch owns its copy; the held tensors go one by one
+            if self.lens[p]:
+                x[seg[p]:seg[p + 1]].copy_(recs[p][0])
+                y[seg[p]:seg[p + 1]].copy_(recs[p][1])
+                v[seg[p]:seg[p + 1]].copy_(recs[p][2])
+            recs[p] = None
+        self.seg_d = torch.from_numpy(seg).to(dev)
+        # stats f64 [4 P] and extent int32 [2 P] in ONE buffer: one copy brings every pair's mean, std, n1 and n2 to the host
+        both = torch.empty(40 * P, dtype=torch.uint8, device=dev)
+        stats_d, extent_d = both[:32 * P].view(torch.float64), both[32 * P:].view(torch.int32)
+        ws_bytes = int(lib.mst_trans_zscore_segmented_workspace_bytes(P))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mst_trans_zscore_segmented(_ptr(x), _ptr(y), _ptr(v), N, _ptr(self.seg_d), P, _ptr(v), _ptr(stats_d),
+                                                      _ptr(extent_d), _ptr(ws), ws_bytes, _stream()))
+        host = both.cpu().numpy()
+        self.stats = host[:32 * P].view(np.float64).reshape(P, 4)
+        self.extent = host[32 * P:].view(np.int32).reshape(P, 2)
+
+    def dims(self):
+        """per pair (n1, n2) = (max x + 1, max y + 1), or None (rule 2: no record, a non-finite mean or std, std = 0)"""
+        out = []
+        for p in range(self.P):
+            mean, std = float(self.stats[p, 0]), float(self.stats[p, 1])
+            if self.lens[p] == 0 or not (np.isfinite(mean) and np.isfinite(std)) or std == 0:
+                out.append(None)
+            else:
+                out.append((int(self.extent[p, 0]) + 1, int(self.extent[p, 1]) + 1))
+        return out
+
+    def count_tiles(self, table_d, T):
+        """per tile of the batch's pair table, this sample's records with v' != 0 inside its window (host, uint32 [T])"""
+        import torch
+        from . import _lib
+        counts_d = torch.empty(T, dtype=torch.int32, device=self.dev)
+        with torch.cuda.device(self.dev):
+            _lib.check(self.lib.mst_trans_count_tiles(_ptr(self.x), _ptr(self.y), _ptr(self.v), self.N, _ptr(self.seg_d),
+                                                      _ptr(table_d), self.P, T, _ptr(counts_d), _stream()))
+        return counts_d.cpu().numpy().view(np.uint32)
+
+    def scatter(self, table_d, p0, p1, T, slot, B, C, c):
+        """this sample's records of the pairs p0 .. p1 into the B tiles `c` of one launch, chosen by slot[t]"""
+        from . import _lib
+        seg = self.seg
+        _lib.check(self.lib.mst_trans_scatter_worklist(_ptr(self.x), _ptr(self.y), _ptr(self.v), _ptr(self.seg_d), _ptr(table_d),
+                                                       p0, p1 + 1, int(seg[p1 + 1] - seg[p0]), T, _ptr(slot), B, C, _ptr(c),
+                                                       _stream()))
+
+
+class PairBatcher:
+    """What the all-pairs callers of one sample (TransGenomeCaller) and of two (diff_trans_genome.DiffTransGenomeCaller) share:
+    pairs held on the device under a byte budget, the flush, batches of one; per batch the samples' segmented z-scores, the
+    joint pair table, the counts and the skip rule, the launch groups and the slot table of the work-list scatter.  A
+    subclass says how a launch turns B filled tiles (per sample) into rows: tile_rows, owned and the order of a pair's rows."""
+
+    SAMPLES = 1
+    UNIT = "tiles"                 # what `stats` and the verbose line count
+
+    def __init__(self, octave_values, emit, chunk=TRANS_CHUNK, tiles_per_launch=None, budget_bytes=None, stats=None,
                  verbose=False):
         from .mustache import _engine
         self.eng = _engine(octave_values)
         self.device = self.eng.device
-        self.st, self.pt, self.emit, self.chunk, self.verbose = st, pt, emit, int(chunk), verbose
+        self.emit, self.chunk, self.verbose = emit, int(chunk), verbose
         self.tiles_per_launch = tiles_per_launch_of(tiles_per_launch)
         self.budget = budget_bytes
         self.stats = stats if stats is not None else {}
@@ -108,24 +205,42 @@ class TransGenomeCaller:
             self.stats[k] = 0
         self.held, self.held_records = [], 0
 
-    def add(self, index, records, label=None):
-        """records: (x, y, v) host arrays or device tensors, or None / empty for a pair without a record"""
+    # ---- what a subclass says ---------------------------------------------------------------------------------------------
+    def default_budget(self):
+        return default_budget(self.device, self.chunk, self.tiles_per_launch)
+
+    def no_contact(self, label):
+        raise NotImplementedError
+
+    def tile_rows(self, B, C, fill):
+        """per tile of a launch what `owned` takes; fill(s, c) scatters sample s's records into the B tiles c"""
+        raise NotImplementedError
+
+    def owned(self, got, tiling, i, j):
+        raise NotImplementedError
+
+    def row_order(self, r):
+        raise NotImplementedError
+
+    # ---- holding ----------------------------------------------------------------------------------------------------------
+    def hold(self, index, records, label=None):
+        """records: per sample (x, y, v) host arrays or device tensors, or None / empty for a sample without a record"""
         import torch
-        n = 0 if records is None else len(records[2])
-        if n:
-            dev = self.device
-            x = torch.as_tensor(records[0]).to(dev, dtype=torch.int32)
-            y = torch.as_tensor(records[1]).to(dev, dtype=torch.int32)
-            v = torch.as_tensor(records[2]).to(dev, dtype=torch.float64)
-            item = (index, x, y, v, label)
-        else:
-            item = (index, None, None, None, label)
+        dev = self.device
+        recs, n = [], 0
+        for rec in records:
+            k = 0 if rec is None else len(rec[2])
+            if k:
+                rec = (torch.as_tensor(rec[0]).to(dev, dtype=torch.int32), torch.as_tensor(rec[1]).to(dev, dtype=torch.int32),
+                       torch.as_tensor(rec[2]).to(dev, dtype=torch.float64))
+            recs.append(rec if k else None)
+            n += k
         if self.budget is None:
-            self.budget = default_budget(self.device, self.chunk, self.tiles_per_launch)
+            self.budget = self.default_budget()
         over = (self.held_records + n) * RECORD_BYTES > self.budget or self.held_records + n > MAX_BATCH_RECORDS
         if self.held_records and over:
             self.flush()
-        self.held.append(item)
+        self.held.append((index, recs, label))
         self.held_records += n
         if self.held_records * RECORD_BYTES > self.budget:       # over the budget by itself: a batch of one
             self.flush()
@@ -135,102 +250,99 @@ class TransGenomeCaller:
         if held:
             self._run_batch(held)
 
-    def _no_contact(self, label):
-        if label is not None:
-            print("There is no contact in the chromosome pair %s to work on." % label)
-
+    # ---- one batch --------------------------------------------------------------------------------------------------------
     def _run_batch(self, items):
         import torch
-        from . import _lib
         lib, dev = self.eng.lib, self.device
         P = len(items)
-        lens = [0 if it[1] is None else int(it[3].numel()) for it in items]
-        seg = np.zeros(P + 1, np.int64)
-        np.cumsum(lens, out=seg[1:])
-        N = int(seg[-1])
         out = [[] for _ in range(P)]
         self.stats["batches"] += 1
-        if N == 0:
+        # a sample that holds no record of the whole batch leaves no pair to tile: decided before anything is concatenated
+        if any(all(it[1][s] is None for it in items) for s in range(self.SAMPLES)):
             for p, it in enumerate(items):
-                self._no_contact(it[4])
+                self.no_contact(it[2])
                 self.emit(it[0], out[p])
             return
-        x = torch.empty(N, dtype=torch.int32, device=dev)
-        y = torch.empty(N, dtype=torch.int32, device=dev)
-        v = torch.empty(N, dtype=torch.float64, device=dev)
-        for p in range(P):                                         # the batch owns its copy; the held tensors go one by one
-            if lens[p]:
-                x[seg[p]:seg[p + 1]].copy_(items[p][1])
-                y[seg[p]:seg[p + 1]].copy_(items[p][2])
-                v[seg[p]:seg[p + 1]].copy_(items[p][3])
-                items[p] = (items[p][0], None, None, None, items[p][4])
-        seg_d = torch.from_numpy(seg).to(dev)
-        # stats f64 [4 P] and extent int32 [2 P] in ONE buffer: one copy brings every pair's mean, std, n1 and n2 to the host
-        both = torch.empty(40 * P, dtype=torch.uint8, device=dev)
-        stats_d, extent_d = both[:32 * P].view(torch.float64), both[32 * P:].view(torch.int32)
-        ws_bytes = int(lib.mst_trans_zscore_segmented_workspace_bytes(P))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.mst_trans_zscore_segmented(_ptr(x), _ptr(y), _ptr(v), N, _ptr(seg_d), P, _ptr(v), _ptr(stats_d),
-                                                      _ptr(extent_d), _ptr(ws), ws_bytes, _stream()))
-        host = both.cpu().numpy()
-        stats = host[:32 * P].view(np.float64).reshape(P, 4)
-        extent = host[32 * P:].view(np.int32).reshape(P, 2)
-        dims = []
-        for p in range(P):
-            mean, std = float(stats[p, 0]), float(stats[p, 1])
-            if lens[p] == 0 or not (np.isfinite(mean) and np.isfinite(std)) or std == 0:
-                self._no_contact(items[p][4])
-                dims.append(None)
-            else:
-                dims.append((int(extent[p, 0]) + 1, int(extent[p, 1]) + 1))
+        samples = []
+        for s in range(self.SAMPLES):
+            recs = [it[1][s] for it in items]
+            for it in items:
+                it[1][s] = None
+            samples.append(SampleBatch(lib, dev, recs))
+        dims = joint_dims([s.dims() for s in samples])
+        for p, d in enumerate(dims):
+            if d is None:
+                self.no_contact(items[p][2])
         table, T = pair_table(dims, self.chunk)
         groups = []
         if T:
             table_d = torch.from_numpy(table.view(np.uint8)).to(dev)
-            counts_d = torch.empty(T, dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.mst_trans_count_tiles(_ptr(x), _ptr(y), _ptr(v), N, _ptr(seg_d), _ptr(table_d), P, T,
-                                                     _ptr(counts_d), _stream()))
-            counts = counts_d.cpu().numpy().view(np.uint32)
+            counts = joint_counts([s.count_tiles(table_d, T) for s in samples])
             groups = launch_groups(table, counts, self.tiles_per_launch)
             kept = sum(len(g[0]) for g in groups)
             self.stats["tiles_total"] += T
             self.stats["tiles_skipped"] += T - kept
             if self.verbose:
-                print("Loop calling (trans batch: %d pairs, %d records, %d of %d tiles in %d launches)..." % (
-                    P, N, kept, T, len(groups)))
+                print("Loop calling (trans batch: %d pairs, %d records, %d of %d %s in %d launches)..." % (
+                    P, sum(s.N for s in samples), kept, T, self.UNIT, len(groups)))
         if groups:
             slot = torch.full((T,), -1, dtype=torch.int32, device=dev)
             tile_pair = np.repeat(np.arange(P), table["K1"].astype(np.int64) * table["K2"])
             tilings = {}
             for tiles, C, p0, p1 in groups:
-                self._run_group(x, y, v, seg, seg_d, table, table_d, T, slot, tiles, C, p0, p1, tile_pair, tilings, dims, out)
+                self._run_group(samples, table, table_d, T, slot, tiles, C, p0, p1, tile_pair, tilings, dims, out)
                 self.stats["launches"] += 1
         for p, it in enumerate(items):
-            out[p].sort(key=lambda r: (int(r[0]), int(r[1])))
+            out[p].sort(key=self.row_order)
             self.emit(it[0], out[p])
 
-    def _run_group(self, x, y, v, seg, seg_d, table, table_d, T, slot, tiles, C, p0, p1, tile_pair, tilings, dims, out):
-        """one launch: the tiles of a group through trans.tile_loops, scattered from the work list"""
+    def _run_group(self, samples, table, table_d, T, slot, tiles, C, p0, p1, tile_pair, tilings, dims, out):
+        """one launch: the tiles of a group, scattered from the work list sample by sample, through tile_rows"""
         import torch
-        from . import _lib
-        dev, lib = self.device, self.eng.lib
+        dev = self.device
         B = len(tiles)
         idx = torch.as_tensor(np.asarray(tiles, np.int64)).to(dev)
         slot[idx] = torch.arange(B, dtype=torch.int32, device=dev)
 
-        def fill(c):
-            _lib.check(lib.mst_trans_scatter_worklist(_ptr(x), _ptr(y), _ptr(v), _ptr(seg_d), _ptr(table_d), p0, p1 + 1,
-                                                      int(seg[p1 + 1] - seg[p0]), T, _ptr(slot), B, C, _ptr(c), _stream()))
-        loops = tile_loops(self.eng, dev, B, C, fill, self.st, self.pt)
+        def fill(s, c):
+            samples[s].scatter(table_d, p0, p1, T, slot, B, C, c)
+        got = self.tile_rows(B, C, fill)
         slot[idx] = -1
-        for t, lp in zip(tiles, loops):
+        for t, g in zip(tiles, got):
             p = int(tile_pair[t])
             if p not in tilings:
                 tilings[p] = trans_tiling(dims[p][0], dims[p][1], self.chunk)
             i, j = divmod(t - int(table[p]["tile_base"]), int(table[p]["K2"]))
-            out[p] += owned_rows(lp, tilings[p], i, j)
+            out[p] += self.owned(g, tilings[p], i, j)
+
+
+class TransGenomeCaller(PairBatcher):
+    """add(index, records, label) pair by pair, flush() at the end; `emit(index, loops)` receives every pair's loops in the
+    order the pairs were added.  `budget_bytes` bounds the records held (RECORD_BYTES each); the partition into batches
+    changes no bit of the output, since every pair is normalised by its own statistics."""
+
+    def __init__(self, octave_values, st, pt, emit, chunk=TRANS_CHUNK, tiles_per_launch=None, budget_bytes=None, stats=None,
+                 verbose=False):
+        super().__init__(octave_values, emit, chunk, tiles_per_launch, budget_bytes, stats, verbose)
+        self.st, self.pt = st, pt
+
+    def add(self, index, records, label=None):
+        """records: (x, y, v) host arrays or device tensors, or None / empty for a pair without a record"""
+        self.hold(index, [records], label)
+
+    def no_contact(self, label):
+        if label is not None:
+            print("There is no contact in the chromosome pair %s to work on." % label)
+
+    def tile_rows(self, B, C, fill):
+        """trans.tile_loops on the B tiles of one launch"""
+        return tile_loops(self.eng, self.device, B, C, lambda c: fill(0, c), self.st, self.pt)
+
+    def owned(self, loops, tiling, i, j):
+        return owned_rows(loops, tiling, i, j)
+
+    def row_order(self, r):
+        return (int(r[0]), int(r[1]))
 
 
 def call_trans_genome(pairs, octave_values, st, pt, chunk=TRANS_CHUNK, tiles_per_launch=None, budget_bytes=None, stats=None,
