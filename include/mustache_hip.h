@@ -29,6 +29,11 @@ extern "C" {
 #endif
 
 #define MST_ABI_VERSION 3
+/* Counts the entry points added since MST_ABI_VERSION last changed (additions leave every existing signature as it is, so the
+ * version stays).  A binding compares both numbers before it looks any symbol up: a library older than the binding then fails
+ * with the version message, not with a missing symbol.  1: mst_abi_revision itself, mst_balance_newton,
+ * mst_balance_newton_workspace_bytes. */
+#define MST_ABI_REVISION 1
 
 /* Stability of the entry points (annotations only: both expand to nothing and every symbol is exported).
  *   MST_STABLE   : the boundary SURVEY section 8(b) asks for -- scatter / prologue / blur / scale space / found records, their
@@ -88,6 +93,7 @@ typedef struct mst_found {
 } mst_found;
 
 MST_STABLE int mst_abi_version(void);
+MST_STABLE int mst_abi_revision(void);
 MST_STABLE const char *mst_last_error(void);
 
 /* mustache.py:919-924 (regulator's COO -> dense block scatter) for B blocks at once.
@@ -430,7 +436,7 @@ MST_STABLE int mst_pair_gather(const mst_found *found, uint32_t found_cap, const
                     const uint32_t *sel_index, const uint32_t *sel_pixel, const uint32_t *sel_count, uint32_t out_cap,
                     uint32_t max_selected, double *out_pair, double *out_value, double *out_other, void *stream);
 
-/* ---- ICE balancing (mustache_amd/balance.py; the algorithm is stated there) -------------------------------------------------
+/* ---- balancing, ICE and Newton (mustache_amd/balance.py; the algorithms are stated there) -------------------------------------------------
  * The matrix is the full symmetric CSR of one chromosome's kept pixels: row_ptr dev [n + 1] int64, col dev [nnz] int32,
  * val dev [nnz] float64, sorted by (row, column); an off-diagonal pixel appears in both rows.  Each row is cut into chunks of
  * 1024 entries counted from its first entry: chunk_ptr dev [n + 1] int64 (the chunks of row r are [chunk_ptr[r],
@@ -460,6 +466,39 @@ MST_STABLE int mst_balance_marginals(const int64_t *row_ptr, const int32_t *col,
 MST_STABLE int mst_balance_iterate(const int64_t *row_ptr, const int32_t *col, const double *val, const int32_t *chunk_row,
                         const int64_t *chunk_ptr, int64_t n, int64_t n_chunks, double *w, int32_t steps, int32_t max_iter,
                         double tol, mst_balance_state *state, void *workspace, uint64_t workspace_bytes, void *stream);
+/* Newton balancing (Knight & Ruiz: inexact Newton on x_i (A x)_i = 1, conjugate gradients preconditioned by v = x * (A x);
+ * mustache_amd/balance.py states the iteration).  The whole control flow lives in this record: one enqueued step is one mat-vec
+ * plus its vector stages, a CG step or an outer update, whichever `phase` says. */
+typedef struct mst_newton_state {
+    double rho, rho_prev;     /* r.z of the current and of the previous CG step */
+    double rout, rold;        /* r.r after the last and after the last-but-one outer update */
+    double eta, innertol;     /* forcing term; the inner iteration runs while rho > innertol */
+    double alpha, gamma;      /* CG step length; the fraction of it a capped step takes */
+    double variance;          /* population variance of v over the active set, last outer update */
+    int32_t phase;            /* next step: 0 start (v, r, the active set from x = 1), 1 CG step, 2 outer update */
+    int32_t k;                /* CG steps taken since the last outer update */
+    int32_t matvecs;          /* mat-vecs counted (the start step's is not) */
+    int32_t iterations;       /* outer updates */
+    int32_t capped_steps;     /* CG steps cut short at y = 0.1 or y = 3 */
+    int32_t capped_upper;     /* ... of which at y = 3 */
+    int32_t isolated;         /* unmasked bins whose partners are all masked: they keep x = 1 */
+    int32_t active;           /* unmasked bins that take part */
+    int32_t cg_step;          /* the step being run is a CG step (set by its scalar stage) */
+    int32_t capped;           /* the CG step being run: 0 full, 1 capped below, 2 capped above */
+    int32_t converged;        /* 1 once rout <= tol^2 */
+    int32_t done;             /* 1 once converged, matvecs >= max_matvecs, or p.w was not positive and finite: later steps are no-ops */
+} mst_newton_state;
+
+MST_STABLE uint64_t mst_balance_newton_workspace_bytes(int64_t n, int64_t n_chunks);
+/* `steps` steps on w (dev [n] f64; in: 1 on unmasked bins, 0 on masked; updated in place to x on the active set, 1 on isolated
+ * bins, 0 on masked ones).  state: dev, zeroed by the caller before the first call; a step enqueued after state->done is set
+ * does nothing.  trace: dev [trace_cap] f64, sqrt(rout) after every outer update (updates past trace_cap are not recorded).
+ * workspace: dev, at least mst_balance_newton_workspace_bytes(n, n_chunks) bytes, kept by the caller from the first step to the
+ * last; mst_balance_bias may then run in the same workspace. */
+MST_STABLE int mst_balance_newton(const int64_t *row_ptr, const int32_t *col, const double *val, const int32_t *chunk_row,
+                       const int64_t *chunk_ptr, int64_t n, int64_t n_chunks, double *w, int32_t steps, int32_t max_matvecs,
+                       double tol, mst_newton_state *state, double *trace, int32_t trace_cap, void *workspace,
+                       uint64_t workspace_bytes, void *stream);
 /* kappa = sqrt(sum_{i <= j} A_ij w_i w_j / sum_{i <= j} A_ij) (the balanced total equals the raw total), bias[i] = kappa / w[i]
  * where w[i] != 0, NaN elsewhere.  bias: dev [n] f64; kappa: dev f64 [1] or NULL. */
 MST_STABLE int mst_balance_bias(const int64_t *row_ptr, const int32_t *col, const double *val, const int32_t *chunk_row,

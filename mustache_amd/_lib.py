@@ -7,6 +7,7 @@ MST_MAX_LEVELS = 64
 MST_MAX_RADIUS = 32
 MST_MAX_TESTED = 48
 MST_ABI_VERSION = 3
+MST_ABI_REVISION = 1         # include/mustache_hip.h: entry points added since the version last changed
 
 MST_OK, MST_E_ARG, MST_E_HIP, MST_E_OVERFLOW, MST_E_NONFINITE = 0, -1, -2, -3, -4
 
@@ -48,6 +49,7 @@ _u64 = ctypes.c_uint64
 
 _SIGNATURES = {
     "mst_abi_version": (ctypes.c_int, []),
+    "mst_abi_revision": (ctypes.c_int, []),
     "mst_last_error": (ctypes.c_char_p, []),
     "mst_scatter_blocks": (ctypes.c_int, [_p, _p, _p, _i64, ctypes.POINTER(_i64), _i32, _i32, _p, _p]),
     "mst_block_prologue": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
@@ -104,6 +106,9 @@ _SIGNATURES = {
     "mst_balance_workspace_bytes": (_u64, [_i64, _i64]),
     "mst_balance_marginals": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _u64, _p]),
     "mst_balance_iterate": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _i32, _i32, ctypes.c_double, _p, _p, _u64, _p]),
+    "mst_balance_newton_workspace_bytes": (_u64, [_i64, _i64]),
+    "mst_balance_newton": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _i32, _i32, ctypes.c_double, _p, _p, _i32, _p, _u64,
+                                          _p]),
     "mst_balance_bias": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _u64, _p]),
     "mst_balance_apply_packed": (ctypes.c_int, [_p, _p, _p, _i64, _p, _i64, _p, _p]),
     "mst_trans_decode_hic_rows": (ctypes.c_int, [_p, _p, _i32, _p, _i64, _p, _i64, _i32, _p, _p, _p, _i64, _p, _p]),
@@ -142,6 +147,13 @@ def load():
     # allocations).  Opening ours first would pull in /opt/rocm's copy and leave two runtimes fighting over the GPU.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
+    # the version first: a stale library names itself before any symbol it lacks is looked up (a library from before
+    # mst_abi_revision existed is revision 0)
+    lib.mst_abi_version.restype = ctypes.c_int
+    have = (lib.mst_abi_version(), lib.mst_abi_revision() if hasattr(lib, "mst_abi_revision") else 0)
+    if have != (MST_ABI_VERSION, MST_ABI_REVISION):
+        raise ImportError("mustache_amd: ABI version mismatch (library %d.%d, binding %d.%d): rebuild %s"
+                          % (have + (MST_ABI_VERSION, MST_ABI_REVISION, LIB_PATH)))
     missing = []
     for name, (res, args) in _SIGNATURES.items():
         try:
@@ -153,9 +165,6 @@ def load():
         fn.argtypes = args
     if missing:
         raise ImportError("mustache_amd: %s lacks symbols %s (stale build?)" % (LIB_PATH, missing))
-    if lib.mst_abi_version() != MST_ABI_VERSION:
-        raise ImportError("mustache_amd: ABI version mismatch (library %d, binding %d)"
-                          % (lib.mst_abi_version(), MST_ABI_VERSION))
     _lib = lib
     return lib
 

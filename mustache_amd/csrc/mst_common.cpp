@@ -240,6 +240,7 @@ void dump_notes() {
 }  // namespace mst
 
 extern "C" int mst_abi_version(void) { return MST_ABI_VERSION; }
+extern "C" int mst_abi_revision(void) { return MST_ABI_REVISION; }
 extern "C" const char *mst_last_error(void) { return mst::error_buffer(); }
 
 #ifdef MST_PROFILE

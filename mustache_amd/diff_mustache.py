@@ -254,8 +254,8 @@ def _pairs_from_filled(eng, pipe, dbands, n, dpx, starts, CH, dense=False, pt=No
 def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2, chromosome, chromosome2, verbose=True,
               balance=None):
     """The reading half of regulator() (diff_mustache.py:591-626): -> (coo1, coo2, res) or None when a sample is empty.
-    balance="ICE": each sample's raw map is balanced on its own on the GPU (mustache_amd.balance), as mustache.read_contacts
-    does for one sample; bias1 / bias2 and a stored normalisation are then not used."""
+    balance="ICE" or "NEWTON": each sample's raw map is balanced on its own on the GPU (mustache_amd.balance), as
+    mustache.read_contacts does for one sample; bias1 / bias2 and a stored normalisation are then not used."""
     if not chromosome2 or chromosome2 == 'n':
         chromosome2 = chromosome
     if chromosome != chromosome2:
@@ -285,7 +285,8 @@ def regulator(f1, f2, norm_method, CHRM_SIZE, outdir, bed1="", bed2="", res=5000
               chromosome='n', chromosome2=None, balance=None):
     """Two-sample loop calling for one chromosome (diff_mustache.py:572-690); returns [x, y, fdr, sigma, tag] rows.
     chromosome2 = B != chromosome: the inter-chromosomal pair (A, B), which the reference cannot run (diff_trans.py).
-    `balance="ICE"` (not in the reference): balance each sample's raw map on the GPU instead of applying bias1 / bias2."""
+    `balance="ICE"` or `"NEWTON"` (not in the reference): balance each sample's raw map on the GPU instead of applying
+    bias1 / bias2."""
     octave_values = [sigma0 * (2 ** i) for i in range(octaves)]
     if chromosome2 and chromosome2 != 'n' and chromosome != chromosome2:      # the trans pair (A, B): mustache_amd/diff_trans.py
         from .diff_trans import regulate
@@ -327,8 +328,8 @@ def parse_args(args):
     p.add_argument("-ch", "--chromosome", dest="chromosome", nargs='+', default='n', required=False)
     p.add_argument("-ch2", "--chromosome2", dest="chromosome2", nargs='+', default='n', required=False)
     p.add_argument("-v", "--verbose", dest="verbose", type=bool, default=True, required=False)
-    p.add_argument("--balance", dest="balance", default=None, metavar="ICE", required=False,
-                   help="OPTIONAL: balance each raw contact map on the GPU (ICE) instead of -b1/-b2 / -norm")
+    p.add_argument("--balance", dest="balance", default=None, metavar="ICE|NEWTON", required=False,
+                   help="OPTIONAL: balance each raw contact map on the GPU (ICE or NEWTON) instead of -b1/-b2 / -norm")
     p.add_argument("--trans-all", dest="trans_all", action="store_true",
                    help="OPTIONAL: call differential inter-chromosomal loops for every unordered pair of the -ch list (without "
                         "-ch: of every chromosome of the first .hic / .cool / .mcool file) in shared launches; no "

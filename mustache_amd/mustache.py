@@ -227,16 +227,17 @@ def _text_records(f, sep, chromosome):
     return (np.asarray(df[a], np.float64), np.asarray(df[b], np.float64), np.asarray(df[cnt], np.float64))
 
 
-def read_pd_balanced(f, distance_in_bp, chromosome, res, device=None, **ice_args):
-    """read_pd under `--balance ICE`: every record of the chromosome, before the distance filter, is balanced on the GPU
-    (balance.ice); the bias is then applied as read_pd applies a -b vector.  Returns read_pd's triple, or None."""
+def read_pd_balanced(f, distance_in_bp, chromosome, res, device=None, method="ICE", **solver_args):
+    """read_pd under `--balance`: every record of the chromosome, before the distance filter, is balanced on the GPU
+    (balance.solve with `method`); the bias is then applied as read_pd applies a -b vector.  Returns read_pd's triple, or
+    None."""
     from .balance import balance_text, bias_lookup, report
     recs = _text_records(f, get_sep(f), chromosome)
     if recs is None:
         print('Could\'t read any interaction for this chromosome!')
         return
     p1, p2, cnt = recs
-    bias, info = balance_text(p1, p2, cnt, res, device=device, **ice_args)
+    bias, info = balance_text(p1, p2, cnt, res, method=method, device=device, **solver_args)
     if len(bias):
         report(info, "chromosome %s" % chromosome)
     return _finish_text(p1, p2, cnt, distance_in_bp, bias_lookup(bias), res)
@@ -326,7 +327,7 @@ def read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromos
     chromosome while the GPU works on the current one.  Returns (x, y, v, res) or None when nothing was read.
     packed=True: a `.hic` file read by the native reader comes back as hicfile.PackedContacts (12 bytes per record, what
     the GPU loader takes) instead of the int64 / float64 triple.
-    balance="ICE": the map's raw counts are balanced on the GPU (mustache_amd.balance) instead of using a bias file or a
+    balance="ICE" or "NEWTON": the map's raw counts are balanced on the GPU (mustache_amd.balance) instead of using a bias file or a
     stored normalisation; the result is always the int64 / float64 triple."""
     chromosome2 = _check_pair(f, chromosome, chromosome2)
     distance_in_bp = distance_filter
@@ -355,14 +356,14 @@ def read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome
     (x, y, v, res) host arrays (res: the file's own for `.cool`), possibly empty; hicfile.PackedContacts for a `.hic` file
     when `packed` and the native reader serves it (a rank's share of `part` may be empty and is still returned: every
     rank takes part in the exchange); None when a text reader finds no record of the chromosome.
-    balance="ICE": the raw counts balanced on the GPU (`.hic` through the native reader whatever MUSTACHE_HIC_BACKEND says,
+    balance="ICE" or "NEWTON": the raw counts balanced on the GPU by that method (`.hic` through the native reader whatever MUSTACHE_HIC_BACKEND says,
     text otherwise); the caller has already checked the request (balance.check_request)."""
     if balance:
-        from .balance import read_hic_balanced
+        from .balance import method_of, read_hic_balanced
         if f.endswith(".hic"):
-            r = read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res, device=device)
+            r = read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res, device=device, method=method_of(balance))
         else:
-            r = read_pd_balanced(f, distance_in_bp, chromosome, res, device=device)
+            r = read_pd_balanced(f, distance_in_bp, chromosome, res, device=device, method=method_of(balance))
     elif f.endswith(".hic"):
         from .readers import hic_backend, read_hic_file, read_hic_packed
         if packed and hic_backend() == "native":
@@ -389,7 +390,8 @@ def regulator(f, norm_method, CHRM_SIZE, outdir, bed="", res=5000, sigma0=1.6, s
     reference (s = 10 is hard-wired at :711); `nprocesses` is ignored: all blocks run as one GPU batch.
     `contacts` (not in the reference): what read_contacts() returned for this chromosome, when the caller read ahead;
     `shard_blocks=False`: in a multi-GPU job this rank runs the whole chromosome alone (whole-genome sharding by chromosome).
-    `balance="ICE"` (not in the reference): balance the raw map on the GPU instead of applying `bias` (read_contacts)."""
+    `balance="ICE"` or `"NEWTON"` (not in the reference): balance the raw map on the GPU instead of applying `bias`
+    (read_contacts)."""
     chromosome2 = _check_pair(f, chromosome, chromosome2)
     octave_values = [sigma0 * (2 ** i) for i in range(octaves)]
     if chromosome != chromosome2:          # chromosome2 = B: the trans pair (A, B), mustache_amd/trans.py
@@ -455,8 +457,9 @@ def parse_args(args):
                         "chromosomes is called inter-chromosomally on the GPU (.hic / .cool / .mcool input, one GPU, no "
                         "--balance); a pair of one chromosome runs the intra-chromosomal path.")
     p.add_argument("-v", "--verbose", dest="verbose", type=bool, default=True, help="OPTIONAL: verbosity")
-    p.add_argument("--balance", dest="balance", default=None, metavar="ICE",
-                   help="OPTIONAL: balance the raw contact map on the GPU (ICE) instead of -b / -norm; text and .hic input")
+    p.add_argument("--balance", dest="balance", default=None, metavar="ICE|NEWTON",
+                   help="OPTIONAL: balance the raw contact map on the GPU (ICE: iterative correction; NEWTON: Knight-Ruiz, "
+                        "far fewer passes over the map) instead of -b / -norm; text and .hic input")
     p.add_argument("--trans-all", dest="trans_all", action="store_true",
                    help="OPTIONAL: call inter-chromosomal loops for every unordered pair of the -ch list (without -ch: of "
                         "every chromosome of a .hic / .cool / .mcool file) in shared launches; no intra-chromosomal rows.")

@@ -556,7 +556,8 @@ def parse_args(args):
                    help="chromosomes to use (default: those of the cis rows, in order of first appearance)")
     p.add_argument("-b", "--biases", dest="biasfile", default=None, help="bias vector of a text map")
     p.add_argument("-norm", "--normalization", dest="norm_method", default=False, help=".hic normalisation (KR, VC, NONE)")
-    p.add_argument("--balance", dest="balance", default=None, metavar="ICE", help="balance the raw map on the GPU (ICE)")
+    p.add_argument("--balance", dest="balance", default=None, metavar="ICE|NEWTON",
+                   help="balance the raw map on the GPU (ICE or NEWTON)")
     p.add_argument("-w", "--window", dest="w", type=int, default=10, help="window half-width in bins (default 10, at most 64)")
     p.add_argument("-q", "--corner", dest="q", type=int, default=6, help="corner size in bins (default 6)")
     p.add_argument("-n", "--min-distance", dest="n_min", type=int, default=None,
