@@ -531,7 +531,9 @@ MST_STABLE uint64_t mst_trans_zscore_workspace_bytes(void);
 MST_STABLE int mst_trans_zscore(const double *v, int64_t n, double *out, double *stats, void *workspace, uint64_t workspace_bytes,
                      void *stream);
 /* Records -> B tiles: c dev [B][CH][CH] f64, zeroed, then c[b][x - row0[b]][y - col0[b]] = v for every record inside tile b's
- * window (a record lands in every tile that holds it).  row0, col0: dev int64 [B], 1 <= B <= 4096.  Pixels are unique. */
+ * window (a record lands in every tile that holds it).  row0, col0: dev int64 [B], 1 <= B <= 4096.  Pixels are unique.
+ * The package itself scatters every pair, a pair alone too, through mst_trans_scatter_worklist; this is the independent
+ * single-pair form its bytes are pinned against and the tests' pair-alone path runs (tests/trans_pair_alone.py). */
 MST_STABLE int mst_trans_scatter_tiles(const int32_t *x, const int32_t *y, const double *v, int64_t n, const int64_t *row0,
                             const int64_t *col0, int32_t B, int32_t CH, double *c, void *stream);
 /* The trans prologue: nz[b] = c[b] != 0 over the whole tile, no fills; nz_count dev [B] uint32, overwritten. */

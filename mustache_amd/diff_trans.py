@@ -1,4 +1,6 @@
-"""Two-sample (differential) loop calling for one inter-chromosomal pair (A, B) on the GPU.
+"""Two-sample (differential) loop calling for one inter-chromosomal pair (A, B) on the GPU: the rules and what one launch of
+tile pairs runs.  The host path from records to rows is diff_trans_genome.py's (trans_genome.PairBatcher), for one pair
+(call_diff_trans_coo: a batch of one) as for many.
 
 The reference's two-sample caller is dead on a trans pair (diff_mustache.py:687-690 only prints), so the semantics are fixed
 here, from trans.py's rules for one sample and diff_mustache.py:260-569 for what two samples add;
@@ -12,7 +14,11 @@ tests/diff_trans_reference.py restates them in NumPy / SciPy.
    tiling of both samples; ownership as in trans.py rule 3.
 4. Per tile pair:
    - nz_s = c_s != 0 over the whole tile (no triangle masks, no fills); nz = nz_1 & nz_2; cd = c_1 - c_2 on nz, 0 elsewhere;
-   - either sample with fewer than 50, or fewer than 10 000, tested pixels: the pair's four lists are empty;
+   - either sample with fewer than 50, or fewer than 10 000, tested pixels: the pair's four lists are empty.  The skip rule:
+     a sample's tested pixels are its distinct pixels with v' != 0, never more than its records with v' != 0, so a tile
+     pair of which either sample holds fewer than 10 000 such records in its window (mst_trans_count_tiles) has four empty
+     lists and is dropped before it is scattered; the rule never drops a tile pair that could report a row, and one it
+     keeps still meets the thresholds in the tail;
    - per sample the sigma loop on nz_s, BH over its found set, q < pt, the sparsity filter (x != 0, the cis windows), no
      diagonal-mean filter; a sample without a surviving candidate empties all four lists (diff_mustache.py:507); clustering
      as in trans.py rule 5;
@@ -25,10 +31,7 @@ tests/diff_trans_reference.py restates them in NumPy / SciPy.
 5. Output rows [x, y, fdr, sigma, tag], tag 1..4 = loops1, diffloops1, loops2, diffloops2, sorted by (tag, x, y) within the
    pair; the command line writes them to .loop1 / .diffloop1 / .loop2 / .diffloop2 with A in column 1 and B in column 4.
 """
-import numpy as np
-
-from ._lib import ptr as _ptr, stream as _stream
-from .trans import TRANS_CHUNK, TransCaller, TransError, owned_rows, prepared_tiles, read_trans_contacts, trans_tiling
+from .trans import TRANS_CHUNK, TransError, owned_rows, prepared_tiles, read_trans_contacts
 
 
 def pair_tile_loops(eng, dev, B, C, fill, st, pt, pt2):
@@ -64,70 +67,15 @@ def tile_pair_bytes(C, n_octaves=2):
     return (2 * 8 + 2 * 1 + 8 * int(n_octaves)) * int(C) * int(C)
 
 
-class DiffTransCaller(TransCaller):
-    """Rules 2-5 on the GPU for the records of two samples.  `tiles_per_launch` tile PAIRS go through two scatters, one
-    prologue and one fused scale-space launch over both samples' tiles, one mst_diff_dog_tiles and one batched tail
-    (pair_tile_loops)."""
-
-    # tile PAIRS per launch when the caller names none.  A pair of 2000 x 2000 tiles at two octaves holds 2 x 32 MB of tiles,
-    # 2 x 4 MB of masks and 2 x 32 MB of D_2 in HBM, 136 MB before the record buffers (tile_pair_bytes): 32 pairs = the 64 tiles
-    # of the one-sample caller's launch, ~4.4 GB.
-    PAIRS_PER_LAUNCH = 32
-
-    def __init__(self, octave_values=(1.6, 3.2), device=None, tiles_per_launch=None, chunk=TRANS_CHUNK):
-        super().__init__(octave_values, device=device, tiles_per_launch=tiles_per_launch or self.PAIRS_PER_LAUNCH, chunk=chunk)
-
-    def run_tiles(self, s1, s2, n1, n2, st, pt, pt2):
-        """rules 3-5 on two samples' normalised device records s = (x, y, vz): rows [x, y, fdr, sigma, tag]"""
-        import torch
-        from . import _lib
-        dev, lib = self.device, self.eng.lib
-        tiling = trans_tiling(n1, n2, self.chunk)
-        C, (rs, _), (cs, _) = tiling
-        tiles = [(i, j) for i in range(len(rs)) for j in range(len(cs))]
-        out = []
-        for g0 in range(0, len(tiles), self.tiles_per_launch):
-            group = tiles[g0:g0 + self.tiles_per_launch]
-            P = len(group)
-            row0 = torch.tensor([rs[i] for i, _ in group], dtype=torch.int64, device=dev)
-            col0 = torch.tensor([cs[j] for _, j in group], dtype=torch.int64, device=dev)
-
-            def fill(s, half):
-                x, y, vz = (s1, s2)[s]
-                _lib.check(lib.mst_trans_scatter_tiles(_ptr(x), _ptr(y), _ptr(vz), int(vz.numel()), _ptr(row0), _ptr(col0),
-                                                       P, C, _ptr(half), _stream()))
-            for (i, j), res4 in zip(group, pair_tile_loops(self.eng, dev, P, C, fill, st, pt, pt2)):
-                out += tagged_owned_rows(res4, tiling, i, j)
-        out.sort(key=row_order)
-        return out
-
-    def run(self, rec1, rec2, st, pt, pt2, verbose=False, label=""):
-        """rules 2-5 on two samples' records rec = (x, y, v) (host arrays or device tensors)"""
-        import torch
-        samples = []
-        for x, y, v in (rec1, rec2):
-            ok = len(v) > 0
-            if ok:
-                x, y, vz, (mean, std, _) = self.normalize(x, y, v)
-                ok = bool(np.isfinite(mean) and np.isfinite(std)) and std != 0
-            if not ok:
-                print("There is no contact in the chromosome pair %s of one of the samples to work on." % label)
-                return []
-            samples.append((x, y, vz))
-        n1 = max(int(torch.max(s[0]).item()) for s in samples) + 1
-        n2 = max(int(torch.max(s[1]).item()) for s in samples) + 1
-        if verbose:
-            C, (rs, _), (cs, _) = trans_tiling(n1, n2, self.chunk)
-            print("Loop calling (trans %s: %d x %d bins, %d tile pairs of %d)..." % (label, n1, n2, len(rs) * len(cs), C))
-        return self.run_tiles(samples[0], samples[1], n1, n2, st, pt, pt2)
-
-
 def call_diff_trans_coo(rec1, rec2, octave_values, st, pt, pt2, chunk=TRANS_CHUNK, tiles_per_launch=None, verbose=False,
                         label=""):
     """Differential loops of one chromosome pair from the two samples' records rec = (x, y, v) (x = bins of A, y = bins of B,
-    v > 0): rules 2-5 of this module.  Returns [[x, y, fdr, sigma, tag], ...] sorted by (tag, x, y)."""
-    return DiffTransCaller(octave_values, tiles_per_launch=tiles_per_launch, chunk=chunk).run(rec1, rec2, st, pt, pt2,
-                                                                                             verbose=verbose, label=label)
+    v > 0; host arrays or device tensors, which are not written): rules 2-5 of this module, as a batch of one pair
+    (trans_genome.PairBatcher.run_pair).  Returns [[x, y, fdr, sigma, tag], ...] sorted by (tag, x, y)."""
+    from .diff_trans_genome import DiffTransGenomeCaller
+    caller = DiffTransGenomeCaller(octave_values, st, pt, pt2, None, chunk=chunk, tiles_per_launch=tiles_per_launch,
+                                   verbose=verbose)
+    return caller.run_pair([rec1, rec2], label)
 
 
 def refusal(files, balance, world_size, chromosomes_given=True):

@@ -1,7 +1,8 @@
 """Two-sample (differential) loop calling for MANY inter-chromosomal pairs in shared launches.
 
-The rules are those of mustache_amd/diff_trans.py, pair by pair; every row this module returns for a pair equals the row
-call_diff_trans_coo returns for that pair alone.  What changes is how the work reaches the GPU, and it is what
+The rules are those of mustache_amd/diff_trans.py, pair by pair, and this module is the one host path they run on: a pair
+alone (diff_trans.call_diff_trans_coo, `-ch A -ch2 B`) is a batch of one pair.  Every row of a pair is the row of that pair
+run alone (tests/trans_pair_alone.py keeps the independent single-pair form).  How the work reaches the GPU is what
 mustache_amd/trans_genome.py does for one sample (trans_genome.PairBatcher is the one body of both), with two samples per pair:
 
 * A held pair costs RECORD_BYTES per record of BOTH samples against the budget.  At a flush each sample's held records are
@@ -18,9 +19,9 @@ mustache_amd/trans_genome.py does for one sample (trans_genome.PairBatcher is th
 * The kept tile pairs are cut into launch groups (trans_genome.launch_groups: runs of up to `tiles_per_launch` tile pairs of
   equal C).  A group of B tile pairs is one buffer of 2 B tiles, sample 1 in [0, B), sample 2 in [B, 2 B): one
   mst_trans_scatter_worklist per sample writes into its half (the table and the slot array are shared), and everything after
-  the scatter is diff_trans.pair_tile_loops, the code DiffTransCaller.run_tiles runs too.
+  the scatter is diff_trans.pair_tile_loops.
 """
-from .diff_trans import DiffTransCaller, pair_tile_loops, row_order, tagged_owned_rows, tile_pair_bytes
+from .diff_trans import pair_tile_loops, row_order, tagged_owned_rows, tile_pair_bytes
 from .trans import TRANS_CHUNK
 from .trans_genome import PairBatcher, default_budget
 
@@ -28,14 +29,19 @@ from .trans_genome import PairBatcher, default_budget
 class DiffTransGenomeCaller(PairBatcher):
     """add(index, rec1, rec2, label) pair by pair, flush() at the end; `emit(index, rows)` receives every pair's rows
     [x, y, fdr, sigma, tag] in the order the pairs were added.  `budget_bytes` bounds the records held (RECORD_BYTES each, both
-    samples); the partition into batches changes no bit of the output.  `stats` counts tile PAIRS."""
+    samples); the partition into batches changes no bit of the output.  `stats` counts tile PAIRS.
+    run_pair([rec1, rec2], label): one pair alone (`emit` may be None)."""
 
     SAMPLES = 2
     UNIT = "tile pairs"
+    # tile PAIRS per launch when the caller names none.  A pair of 2000 x 2000 tiles at two octaves holds 2 x 32 MB of tiles,
+    # 2 x 4 MB of masks and 2 x 32 MB of D_2 in HBM, 136 MB before the record buffers (tile_pair_bytes): 32 pairs = the 64 tiles
+    # of the one-sample caller's launch, ~4.4 GB.
+    PAIRS_PER_LAUNCH = 32
 
     def __init__(self, octave_values, st, pt, pt2, emit, chunk=TRANS_CHUNK, tiles_per_launch=None, budget_bytes=None,
                  stats=None, verbose=False):
-        super().__init__(octave_values, emit, chunk, tiles_per_launch or DiffTransCaller.PAIRS_PER_LAUNCH, budget_bytes, stats,
+        super().__init__(octave_values, emit, chunk, tiles_per_launch or self.PAIRS_PER_LAUNCH, budget_bytes, stats,
                          verbose)
         self.st, self.pt, self.pt2 = st, pt, pt2
         self.n_octaves = len(octave_values)
@@ -66,7 +72,7 @@ def call_diff_trans_genome(pairs, octave_values, st, pt, pt2, chunk=TRANS_CHUNK,
                            stats=None, verbose=False, labels=None):
     """Differential loops of every chromosome pair of `pairs` (pairs[p] = (rec1, rec2), rec = (x, y, v) as host arrays or
     device tensors, None or empty for a sample without records): a list with, per pair, [[x, y, fdr, sigma, tag], ...] sorted
-    by (tag, x, y) -- the rows call_diff_trans_coo returns for that pair alone.  A pair of which a sample has no record, a
+    by (tag, x, y) -- the rows of that pair alone.  A pair of which a sample has no record, a
     non-finite mean / std or std = 0 yields [] (and, when `labels` names the pairs, the "There is no contact ..." line).
     `stats`, a dict, receives tiles_total, tiles_skipped (tile pairs), launches and batches."""
     pairs = list(pairs)

@@ -1,4 +1,6 @@
-"""Inter-chromosomal (trans) loop calling for one chromosome pair (A, B) on the GPU (and what the other trans callers share).
+"""Inter-chromosomal (trans) loop calling for one chromosome pair (A, B) on the GPU: the rules, the reader, and what one
+launch of tiles runs.  The host path from records to rows is trans_genome.py's, for one pair (call_trans_coo: a batch of one)
+as for many.
 
 The reference's trans branch is dead code (mustache.py:939-942 calls inter_normalize_map with the wrong arguments and never
 tiles), so the semantics are fixed here; tests/trans_reference.py restates them in NumPy / SciPy.
@@ -12,6 +14,9 @@ tiles), so the semantics are fixed here; tests/trans_reference.py restates them 
 4. Per tile: nz = c != 0 over the whole tile (mst_trans_prologue: no triangle masks, no fills); the reference's sigma loop on
    nz (mst_scale_space, dense source); BH over the tile's found set, q < pt; fewer than 50 or 10 000 tested pixels: no loops;
    the cis sparsity filter (x != 0, the same window arithmetic); no diagonal-mean filter.
+   The skip rule: a tile's tested pixels are its distinct pixels with v' != 0, never more than its records with v' != 0, so a
+   tile whose window holds fewer than 10 000 such records (mst_trans_count_tiles) yields no loops and is dropped before it is
+   scattered.  The rule never drops a tile that could report a loop; a tile it keeps still meets the thresholds in the tail.
 5. Clustering: 8-connected components of the selected pixels each dilated by its 3 x 3 neighbourhood, clipped at the tile
    edges; the representative is the component's lowest q (o = q at found pixels, >= 1 elsewhere), ties to the first pixel in
    row-major order (mst_cluster_representatives does exactly this for any tile; its halo never wraps).  A representative
@@ -188,69 +193,10 @@ def owned_rows(loops, tiling, i, j):
     return out
 
 
-class TransCaller:
-    """Rules 2-6 on the GPU for one pair's records.  `tiles_per_launch` tiles go through one scatter, one prologue and one
-    fused scale-space launch (mst_scale_space over dense tiles) and one batched tail (tile_loops)."""
-
-    def __init__(self, octave_values=(1.6, 3.2), device=None, tiles_per_launch=None, chunk=TRANS_CHUNK):
-        from .mustache import _engine
-        self.chunk = int(chunk)            # rule 3's 2000; smaller values only to exercise many tiles on small maps
-        self.eng = _engine(octave_values)
-        self.device = self.eng.device if device is None else device
-        self.tiles_per_launch = tiles_per_launch_of(tiles_per_launch)
-
-    def normalize(self, x, y, v):
-        """device (x int32, y int32, v' float64) and (mean, std, n) of rule 2"""
-        import torch
-        dev = self.device
-        x = torch.as_tensor(x).to(dev, dtype=torch.int32).contiguous()
-        y = torch.as_tensor(y).to(dev, dtype=torch.int32).contiguous()
-        vz, mean, std, n = zscore_device(v, dev)
-        return x, y, vz, (mean, std, n)
-
-    def run_tiles(self, x, y, vz, n1, n2, st, pt):
-        """rules 3-6 on normalised device records: loops [x, y, fdr, sigma] sorted by (x, y)"""
-        import torch
-        from . import _lib
-        dev, lib = self.device, self.eng.lib
-        tiling = trans_tiling(n1, n2, self.chunk)
-        C, (rs, _), (cs, _) = tiling
-        tiles = [(i, j) for i in range(len(rs)) for j in range(len(cs))]
-        out = []
-        for g0 in range(0, len(tiles), self.tiles_per_launch):
-            group = tiles[g0:g0 + self.tiles_per_launch]
-            B = len(group)
-            row0 = torch.tensor([rs[i] for i, _ in group], dtype=torch.int64, device=dev)
-            col0 = torch.tensor([cs[j] for _, j in group], dtype=torch.int64, device=dev)
-
-            def fill(c):
-                _lib.check(lib.mst_trans_scatter_tiles(_ptr(x), _ptr(y), _ptr(vz), int(vz.numel()), _ptr(row0), _ptr(col0), B, C,
-                                                       _ptr(c), _stream()))
-            for (i, j), lp in zip(group, tile_loops(self.eng, dev, B, C, fill, st, pt)):
-                out += owned_rows(lp, tiling, i, j)
-        out.sort(key=lambda r: (int(r[0]), int(r[1])))
-        return out
-
-    def run(self, x, y, v, st, pt, verbose=False, label=""):
-        """rules 2-6 on a pair's records (host arrays or device tensors)"""
-        import torch
-        if len(v) == 0:
-            print("There is no contact in the chromosome pair %s to work on." % label)
-            return []
-        x, y, vz, (mean, std, n) = self.normalize(x, y, v)
-        if not (np.isfinite(mean) and np.isfinite(std)) or std == 0:
-            print("There is no contact in the chromosome pair %s to work on." % label)
-            return []
-        n1 = int(torch.max(x).item()) + 1
-        n2 = int(torch.max(y).item()) + 1
-        if verbose:
-            C, (rs, _), (cs, _) = trans_tiling(n1, n2, self.chunk)
-            print("Loop calling (trans %s: %d x %d bins, %d tiles of %d)..." % (label, n1, n2, len(rs) * len(cs), C))
-        return self.run_tiles(x, y, vz, n1, n2, st, pt)
-
-
 def call_trans_coo(x, y, v, octave_values, st, pt, verbose=False, label="", tiles_per_launch=None, chunk=TRANS_CHUNK):
-    """Loops of one chromosome pair from its records (x = bins of A, y = bins of B, v > 0): rules 2-6 of this module.
+    """Loops of one chromosome pair from its records (x = bins of A, y = bins of B, v > 0; host arrays or device tensors, which
+    are not written): rules 2-6 of this module, as a batch of one pair (trans_genome.PairBatcher.run_pair).
     Returns [[x, y, fdr, sigma], ...] sorted by (x, y)."""
-    return TransCaller(octave_values, tiles_per_launch=tiles_per_launch, chunk=chunk).run(x, y, v, st, pt, verbose=verbose,
-                                                                                          label=label)
+    from .trans_genome import TransGenomeCaller
+    caller = TransGenomeCaller(octave_values, st, pt, None, chunk=chunk, tiles_per_launch=tiles_per_launch, verbose=verbose)
+    return caller.run_pair([(x, y, v)], label)

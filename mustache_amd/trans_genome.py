@@ -1,7 +1,9 @@
 """Inter-chromosomal (trans) loop calling for MANY chromosome pairs in shared launches.
 
-The rules are those of mustache_amd/trans.py, pair by pair; every row this module returns for a pair equals the row
-call_trans_coo returns for that pair alone.  What changes is how the work reaches the GPU:
+The rules are those of mustache_amd/trans.py, pair by pair, and this module is the one host path they run on: a pair alone
+(trans.call_trans_coo, `-ch A -ch2 B`) is a batch of one pair (PairBatcher.run_pair).  Every row of a pair is the row of that
+pair run alone -- tests/trans_pair_alone.py keeps the independent single-pair form (mst_trans_zscore, mst_trans_scatter_tiles,
+no skip rule) the tests compare with.  How the work reaches the GPU:
 
 * Pairs are held on the device until their records reach a budget, then go through as one batch: their records are
   concatenated, ONE segmented z-score (mst_trans_zscore_segmented) normalises every pair by its own mean and std -- bit for bit
@@ -14,8 +16,8 @@ call_trans_coo returns for that pair alone.  What changes is how the work reache
   could report a loop; a tile it keeps still meets rule 4 in the tail.
 * The kept tiles, in pair-major order, are cut into launch groups: runs of up to `tiles_per_launch` tiles of equal C.  A
   group's pairs are a contiguous range, so its records are one range of the batch; mst_trans_scatter_worklist writes them into
-  the group's tiles, finding the windows that hold a record from its coordinates.  Everything after the scatter is the code
-  TransCaller.run_tiles runs too: trans.tile_loops (mst_trans_prologue, the sigma loop, the batched tail) and trans.owned_rows.
+  the group's tiles, finding the windows that hold a record from its coordinates.  Behind the scatter: trans.tile_loops
+  (mst_trans_prologue, the sigma loop, the batched tail) and trans.owned_rows.
 The batch body (PairBatcher, SampleBatch) is written for S samples per pair: TransGenomeCaller is its one-sample form,
 diff_trans_genome.DiffTransGenomeCaller its two-sample form (a pair's dimensions are the maxima over the samples' extents, a tile
 is kept when every sample's count reaches the threshold, every sample is scattered into its own tiles of the launch).
@@ -119,8 +121,9 @@ def joint_counts(counts):
 class SampleBatch:
     """One sample's records of the P pairs of a batch: concatenated (x, y, v [N], seg [P + 1]), normalised in place pair by
     pair (mst_trans_zscore_segmented), with every pair's {mean, std, n, flags} (`stats` [P, 4]) and {max x, max y} (`extent`
-    [P, 2]) on the host after ONE copy.  `recs[p]` = device (x, y, v) or None, at least one not None; the list is emptied as the
-    records are copied."""
+    [P, 2]) on the host after ONE copy.  `recs[p]` = device (x int32, y int32, v float64) or None, at least one not None; the
+    list is emptied as the records are copied.  The batch owns its `v`, which the z-score overwrites; x and y are only read,
+    so a batch of one pair adopts them instead of holding the pair's coordinates twice."""
 
     def __init__(self, lib, dev, recs):
         import torch
@@ -131,13 +134,17 @@ class SampleBatch:
         seg = self.seg = np.zeros(P + 1, np.int64)
         np.cumsum(self.lens, out=seg[1:])
         N = self.N = int(seg[-1])
-        x = self.x = torch.empty(N, dtype=torch.int32, device=dev)
-        y = self.y = torch.empty(N, dtype=torch.int32, device=dev)
         v = self.v = torch.empty(N, dtype=torch.float64, device=dev)
+        if P == 1:
+            x, y = self.x, self.y = recs[0][0].contiguous(), recs[0][1].contiguous()
+        else:
+            x = self.x = torch.empty(N, dtype=torch.int32, device=dev)
+            y = self.y = torch.empty(N, dtype=torch.int32, device=dev)
         for p in range(P):                                         # the batch owns its copy; the held tensors go one by one
             if self.lens[p]:
-                x[seg[p]:seg[p + 1]].copy_(recs[p][0])
-                y[seg[p]:seg[p + 1]].copy_(recs[p][1])
+                if P > 1:
+                    x[seg[p]:seg[p + 1]].copy_(recs[p][0])
+                    y[seg[p]:seg[p + 1]].copy_(recs[p][1])
                 v[seg[p]:seg[p + 1]].copy_(recs[p][2])
             recs[p] = None
         self.seg_d = torch.from_numpy(seg).to(dev)
@@ -185,9 +192,10 @@ class SampleBatch:
 
 class PairBatcher:
     """What the all-pairs callers of one sample (TransGenomeCaller) and of two (diff_trans_genome.DiffTransGenomeCaller) share:
-    pairs held on the device under a byte budget, the flush, batches of one; per batch the samples' segmented z-scores, the
-    joint pair table, the counts and the skip rule, the launch groups and the slot table of the work-list scatter.  A
-    subclass says how a launch turns B filled tiles (per sample) into rows: tile_rows, owned and the order of a pair's rows."""
+    pairs held on the device under a byte budget, the flush, batches of one (run_pair: a pair alone, without the budget); per
+    batch the samples' segmented z-scores, the joint pair table, the counts and the skip rule, the launch groups and the slot
+    table of the work-list scatter.  A subclass says how a launch turns B filled tiles (per sample) into rows: tile_rows,
+    owned and the order of a pair's rows."""
 
     SAMPLES = 1
     UNIT = "tiles"                 # what `stats` and the verbose line count
@@ -223,8 +231,9 @@ class PairBatcher:
         raise NotImplementedError
 
     # ---- holding ----------------------------------------------------------------------------------------------------------
-    def hold(self, index, records, label=None):
-        """records: per sample (x, y, v) host arrays or device tensors, or None / empty for a sample without a record"""
+    def on_device(self, records):
+        """(recs, n): per sample device (x int32, y int32, v float64) -- the caller's own tensors where they already are that
+        -- or None for a sample without a record, and the records of all samples"""
         import torch
         dev = self.device
         recs, n = [], 0
@@ -235,6 +244,16 @@ class PairBatcher:
                        torch.as_tensor(rec[2]).to(dev, dtype=torch.float64))
             recs.append(rec if k else None)
             n += k
+        return recs, n
+
+    def run_pair(self, records, label=""):
+        """One pair alone (records as hold() takes them), now, as a batch of one: its rows.  Nothing is held, so no budget is
+        asked for (default_budget queries the device's free memory); `label` is printed as given, "" too."""
+        return self._run_batch([(0, self.on_device(records)[0], label)], alone=True)[0]
+
+    def hold(self, index, records, label=None):
+        """records: per sample (x, y, v) host arrays or device tensors, or None / empty for a sample without a record"""
+        recs, n = self.on_device(records)
         if self.budget is None:
             self.budget = self.default_budget()
         over = (self.held_records + n) * RECORD_BYTES > self.budget or self.held_records + n > MAX_BATCH_RECORDS
@@ -248,10 +267,12 @@ class PairBatcher:
     def flush(self):
         held, self.held, self.held_records = self.held, [], 0
         if held:
-            self._run_batch(held)
+            for it, rows in zip(held, self._run_batch(held)):
+                self.emit(it[0], rows)
 
     # ---- one batch --------------------------------------------------------------------------------------------------------
-    def _run_batch(self, items):
+    def _run_batch(self, items, alone=False):
+        """the rows of every pair of `items` = [(index, recs, label)], in their order; `alone`: the verbose line of a pair"""
         import torch
         lib, dev = self.eng.lib, self.device
         P = len(items)
@@ -259,10 +280,9 @@ class PairBatcher:
         self.stats["batches"] += 1
         # a sample that holds no record of the whole batch leaves no pair to tile: decided before anything is concatenated
         if any(all(it[1][s] is None for it in items) for s in range(self.SAMPLES)):
-            for p, it in enumerate(items):
+            for it in items:
                 self.no_contact(it[2])
-                self.emit(it[0], out[p])
-            return
+            return out
         samples = []
         for s in range(self.SAMPLES):
             recs = [it[1][s] for it in items]
@@ -282,32 +302,33 @@ class PairBatcher:
             kept = sum(len(g[0]) for g in groups)
             self.stats["tiles_total"] += T
             self.stats["tiles_skipped"] += T - kept
-            if self.verbose:
+            if self.verbose and alone:
+                print("Loop calling (trans %s: %d x %d bins, %d %s of %d)..." % (items[0][2], dims[0][0], dims[0][1], T, self.UNIT,
+                                                                                 int(table[0]["C"])))
+            elif self.verbose:
                 print("Loop calling (trans batch: %d pairs, %d records, %d of %d %s in %d launches)..." % (
                     P, sum(s.N for s in samples), kept, T, self.UNIT, len(groups)))
         if groups:
-            slot = torch.full((T,), -1, dtype=torch.int32, device=dev)
             tile_pair = np.repeat(np.arange(P), table["K1"].astype(np.int64) * table["K2"])
             tilings = {}
             for tiles, C, p0, p1 in groups:
-                self._run_group(samples, table, table_d, T, slot, tiles, C, p0, p1, tile_pair, tilings, dims, out)
+                self._run_group(samples, table, table_d, T, tiles, C, p0, p1, tile_pair, tilings, dims, out)
                 self.stats["launches"] += 1
-        for p, it in enumerate(items):
-            out[p].sort(key=self.row_order)
-            self.emit(it[0], out[p])
+        for rows in out:
+            rows.sort(key=self.row_order)
+        return out
 
-    def _run_group(self, samples, table, table_d, T, slot, tiles, C, p0, p1, tile_pair, tilings, dims, out):
+    def _run_group(self, samples, table, table_d, T, tiles, C, p0, p1, tile_pair, tilings, dims, out):
         """one launch: the tiles of a group, scattered from the work list sample by sample, through tile_rows"""
         import torch
-        dev = self.device
         B = len(tiles)
-        idx = torch.as_tensor(np.asarray(tiles, np.int64)).to(dev)
-        slot[idx] = torch.arange(B, dtype=torch.int32, device=dev)
+        slot = np.full(T, -1, np.int32)                            # the work list: tile t of the batch -> its place in the launch
+        slot[tiles] = np.arange(B, dtype=np.int32)
+        slot = torch.from_numpy(slot).to(self.device)
 
         def fill(s, c):
             samples[s].scatter(table_d, p0, p1, T, slot, B, C, c)
         got = self.tile_rows(B, C, fill)
-        slot[idx] = -1
         for t, g in zip(tiles, got):
             p = int(tile_pair[t])
             if p not in tilings:
@@ -319,7 +340,8 @@ class PairBatcher:
 class TransGenomeCaller(PairBatcher):
     """add(index, records, label) pair by pair, flush() at the end; `emit(index, loops)` receives every pair's loops in the
     order the pairs were added.  `budget_bytes` bounds the records held (RECORD_BYTES each); the partition into batches
-    changes no bit of the output, since every pair is normalised by its own statistics."""
+    changes no bit of the output, since every pair is normalised by its own statistics.  run_pair([(x, y, v)], label): one
+    pair alone (`emit` may be None)."""
 
     def __init__(self, octave_values, st, pt, emit, chunk=TRANS_CHUNK, tiles_per_launch=None, budget_bytes=None, stats=None,
                  verbose=False):
@@ -348,8 +370,8 @@ class TransGenomeCaller(PairBatcher):
 def call_trans_genome(pairs, octave_values, st, pt, chunk=TRANS_CHUNK, tiles_per_launch=None, budget_bytes=None, stats=None,
                       verbose=False, labels=None):
     """Loops of every chromosome pair of `pairs` (pairs[p] = (x, y, v) as host arrays or device tensors, None or empty for a
-    pair without records): a list with, per pair, [[x, y, fdr, sigma], ...] sorted by (x, y) -- the rows call_trans_coo
-    returns for that pair alone.  A pair with no record, a non-finite mean / std or std = 0 yields [] (and, when `labels`
+    pair without records): a list with, per pair, [[x, y, fdr, sigma], ...] sorted by (x, y) -- the rows of that pair
+    alone.  A pair with no record, a non-finite mean / std or std = 0 yields [] (and, when `labels`
     names the pairs, the "There is no contact ..." line).  `stats`, a dict, receives tiles_total, tiles_skipped, launches and
     batches."""
     pairs = list(pairs)

@@ -121,17 +121,16 @@ def main():
 
     if not args.no_call:
         import diff_trans_reference as dr
-        from mustache_amd.diff_trans import DiffTransCaller
+        from mustache_amd.diff_trans import call_diff_trans_coo
         from mustache_amd.trans import trans_tiling
         case = dr.CASES["production_2x2"]
         rec1, rec2 = dr.case_records("production_2x2")
         Cc, (rs, _), (cs, _) = trans_tiling(case["n1"], case["n2"], case["chunk"])
-        caller = DiffTransCaller(case["oct"], chunk=case["chunk"])
         call_t, rows = [], None
         for i in range(args.warmup + args.reps):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            rows = caller.run(rec1, rec2, dr.ST, dr.PT, dr.PT2)
+            rows = call_diff_trans_coo(rec1, rec2, case["oct"], dr.ST, dr.PT, dr.PT2, chunk=case["chunk"])
             torch.cuda.synchronize()
             if i >= args.warmup:
                 call_t.append(time.perf_counter() - t0)

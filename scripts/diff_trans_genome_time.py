@@ -3,7 +3,9 @@
 
   genome  call_diff_trans_genome: one batch -- a segmented z-score and a tile count per sample, the kept tile pairs in shared
           launches
-  pairs   a loop of call_diff_trans_coo over the same pairs: per pair two z-scores, four extent round trips and its own launches
+  pairs   a loop of call_diff_trans_coo over the same pairs: 12 batches of one pair, each with its own two segmented z-scores,
+          statistics copies, tile counts and launches (the same kernels and the same skip rule; what is compared is the
+          batching)
 
 The genome: 6 chromosomes of 6000, 5200, 4400, 3600, 3000 and 2400 bins, the first 12 of their pairs in pair order, drawn on the
 device: sample 1 holds a log-normal background on a share of the pixels that falls geometrically from 0.2 (6000 x 5200:

@@ -2,7 +2,8 @@
 """All trans pairs of a synthetic genome, two ways on the same device-resident records:
 
   genome  call_trans_genome: one batch -- a segmented z-score, the tile counts, the kept tiles in shared launches
-  pairs   a loop of call_trans_coo over the same pairs: a z-score, two extent round trips and the launches of each pair
+  pairs   a loop of call_trans_coo over the same pairs: 28 batches of one pair, each with its own segmented z-score, statistics
+          copy, tile count and launches (the same kernels and the same skip rule; what is compared is the batching)
 
 The genome: 8 chromosomes of 5200, 4100, 3300, 2600, 2100, 1500, 900 and 600 bins, 28 pairs from tests/trans_reference.py's
 synth_trans with densities from 0.0005 to 0.05 (geometric steps in pair order), so most tiles hold fewer than 10 000 records,

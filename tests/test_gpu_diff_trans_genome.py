@@ -1,5 +1,6 @@
 """Differential trans loops of many chromosome pairs in shared launches (mustache_amd/diff_trans_genome.py) on the MI355X:
-every pair's rows equal call_diff_trans_coo's rows for that pair alone -- under every launch grouping and batch partition,
+every pair's rows equal the rows of that pair alone (tests/trans_pair_alone.py: the single-pair kernels, every tile pair, no
+skip rule) -- under every launch grouping and batch partition,
 over the joint extents of two samples, with tile pairs and whole pairs skipped below 10 000 tested records in either sample,
 beside degenerate pairs, and through `diff_mustache --trans-all`.
 
@@ -31,11 +32,11 @@ def _per_tag(rows):
 
 
 def _alone(pairs, chunk):
-    from mustache_amd.diff_trans import call_diff_trans_coo
+    from trans_pair_alone import diff_pair_alone
     out = []
     for rec1, rec2 in pairs:
-        out.append(_rows(call_diff_trans_coo(NONE if rec1 is None else rec1, NONE if rec2 is None else rec2, OCT, ST, PT, PT2,
-                                             chunk=chunk)))
+        out.append(_rows(diff_pair_alone(NONE if rec1 is None else rec1, NONE if rec2 is None else rec2, OCT, ST, PT, PT2,
+                                         chunk=chunk)))
     return out
 
 

@@ -1,6 +1,7 @@
 """Trans loops of many chromosome pairs in shared launches (mustache_amd/trans_genome.py) on the MI355X: every pair's rows equal
-call_trans_coo's rows for that pair alone -- under every launch grouping and batch partition, with tiles and whole pairs
-skipped below 10 000 tested records, at the production tile size, beside degenerate pairs, and through `--trans-all`.
+the rows of that pair alone (tests/trans_pair_alone.py: the single-pair kernels, every tile, no skip rule) -- under every
+launch grouping and batch partition, with tiles and whole pairs skipped below 10 000 tested records, at the production tile
+size, beside degenerate pairs, and through `--trans-all`.
 
 The loop counts stated below are those of the NumPy restatement (tests/trans_reference.py on zscore_exact's values, st 0.88,
 pt 0.2, octaves [1.6, 3.2]) run once on the CPU."""
@@ -36,8 +37,8 @@ def _genome_pairs(bins, densities):
 
 
 def _alone(pairs, chunk):
-    from mustache_amd.trans import call_trans_coo
-    return [_rows(call_trans_coo(x, y, v, OCT, ST, PT, chunk=chunk)) for x, y, v in pairs]
+    from trans_pair_alone import pair_alone
+    return [_rows(pair_alone(x, y, v, OCT, ST, PT, chunk=chunk)) for x, y, v in pairs]
 
 
 @pytest.fixture(scope="module")

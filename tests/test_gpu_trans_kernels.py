@@ -170,7 +170,7 @@ def test_zscore_of_thousands_of_short_sums():
 
 @pytest.mark.parametrize("bad", [[np.nan], [np.inf], [-np.inf], [np.nan, np.inf, -np.inf], [np.inf, -np.inf]])
 def test_zscore_with_non_finite_records_is_the_no_contact_case(bad, capsys):
-    from mustache_amd.trans import TransCaller
+    from mustache_amd.trans import call_trans_coo
     rng = np.random.default_rng(9)
     v = np.exp(rng.normal(0.0, 1.0, 70000))
     at = rng.choice(v.size, len(bad), replace=False)
@@ -183,7 +183,7 @@ def test_zscore_with_non_finite_records_is_the_no_contact_case(bad, capsys):
     x = rng.integers(0, 300, v.size)
     y = rng.integers(0, 300, v.size)
     capsys.readouterr()
-    assert TransCaller([1.6, 3.2]).run(x, y, v, 0.88, 0.2, label="1-2") == []
+    assert call_trans_coo(x, y, v, [1.6, 3.2], 0.88, 0.2, label="1-2") == []
     assert "There is no contact in the chromosome pair 1-2 to work on." in capsys.readouterr().out
     with np.errstate(invalid="ignore"):
         assert tr.trans_loops(x, y, v, 0.88, 0.2, [1.6, 3.2]) == []
@@ -191,7 +191,8 @@ def test_zscore_with_non_finite_records_is_the_no_contact_case(bad, capsys):
 
 # ---- B. scatter and prologue ---------------------------------------------------------------------------------------------
 def _scatter_device(x, y, v, row0, col0, C, expect_rc=0):
-    """(c, nz, nz_count) of mst_trans_scatter_tiles + mst_trans_prologue called the way TransCaller.run_tiles calls them"""
+    """(c, nz, nz_count) of mst_trans_scatter_tiles + mst_trans_prologue called the way trans_pair_alone.pair_alone calls
+    them"""
     import torch
     from mustache_amd import _lib
     from mustache_amd.engine import require_gpu
@@ -273,7 +274,7 @@ def test_scatter_and_prologue_match_numpy_on_the_tiling(n1, n2, chunk):
     ref = _check_scatter(x, y, v, [t[0] for t in tiles], [t[1] for t in tiles], C)
     for b, (r, q) in enumerate(tiles):                        # padding outside the map stays zero
         assert not ref[b, max(0, n1 - r):, :].any() and not ref[b, :, max(0, n2 - q):].any()
-    # the groups TransCaller would launch with tiles_per_launch = 1 and 4
+    # the groups trans_pair_alone.pair_alone would launch with tiles_per_launch = 1 and 4
     for g in (1, 4):
         for g0 in range(0, len(tiles), g):
             grp = tiles[g0:g0 + g]
