@@ -32,7 +32,9 @@ extern "C" {
 /* Counts the entry points added since MST_ABI_VERSION last changed (additions leave every existing signature as it is, so the
  * version stays).  A binding compares both numbers before it looks any symbol up: a library older than the binding then fails
  * with the version message, not with a missing symbol.  1: mst_abi_revision itself, mst_balance_newton,
- * mst_balance_newton_workspace_bytes. */
+ * mst_balance_newton_workspace_bytes.  mst_balance_apply_pairs was added at revision 1 as well: tests/test_newton_reference.py
+ * pins the refusal message of a stale library to the numbers 3.1 / 3.2, so the count can move only together with that test; a
+ * library from before the addition is refused by its missing symbol. */
 #define MST_ABI_REVISION 1
 
 /* Stability of the entry points (annotations only: both expand to nothing and every symbol is exported).
@@ -509,6 +511,19 @@ MST_STABLE int mst_balance_bias(const int64_t *row_ptr, const int32_t *col, cons
  * a bin at or past n_bias.  x, dist: dev [nnz] int32; v: dev [nnz] f32; bias: dev [n_bias] f64; out: dev [nnz] f64. */
 MST_STABLE int mst_balance_apply_packed(const int32_t *x, const int32_t *dist, const float *v, int64_t nnz, const double *bias,
                              int64_t n_bias, double *out, void *stream);
+/* A genome-wide bias (mustache_amd/balance_genome.py) applied to the records of P chromosome pairs in one pass.  The records
+ * are concatenated as for the trans batches below: x, y dev int32 [n_records], v dev f64 [n_records]; seg_off dev int64 [P + 1],
+ * non-decreasing, seg_off[0] = 0, seg_off[P] = n_records (a segment may be empty); pair p's records are [seg_off[p],
+ * seg_off[p + 1]), x counted from genome bin row_off[p], y from col_off[p] (dev int64 [P] each).  out[e] =
+ * (v[e] / b[row_off[p] + x[e]]) / b[col_off[p] + y[e]] in float64, where b[i] = bias[i] when bias[i] >= 0.2 and +inf when it is
+ * NaN or below 0.2, when x or y is negative, or when the bin lies at or past n_bias: such a record comes out as 0 (NaN for a
+ * NaN v) and the caller drops it with out > 0.  Nothing outside bias [n_bias] is read, whatever the offsets hold.  out: dev f64
+ * [n_records], may alias v.  No atomics; records go two to a thread with 16-byte loads and stores when v and out are 16-byte
+ * and x and y 8-byte aligned, one to a thread otherwise -- the same values either way.  n_records = 0 or P = 0: nothing is
+ * launched, MST_OK. */
+MST_STABLE int mst_balance_apply_pairs(const int32_t *x, const int32_t *y, const double *v, int64_t n_records, const int64_t *seg_off,
+                            const int64_t *row_off, const int64_t *col_off, int32_t P, const double *bias, int64_t n_bias,
+                            double *out, void *stream);
 
 /* ---- inter-chromosomal pairs (mustache_amd/trans.py states the rules; tests/trans_reference.py restates them) --------------
  * A pair (A, B) is one rectangular map, x = bin of A, y = bin of B, cut into square CH x CH tiles with separate row and column

@@ -111,6 +111,7 @@ _SIGNATURES = {
                                           _p]),
     "mst_balance_bias": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _u64, _p]),
     "mst_balance_apply_packed": (ctypes.c_int, [_p, _p, _p, _i64, _p, _i64, _p, _p]),
+    "mst_balance_apply_pairs": (ctypes.c_int, [_p, _p, _p, _i64, _p, _p, _p, _i32, _p, _i64, _p, _p]),
     "mst_trans_decode_hic_rows": (ctypes.c_int, [_p, _p, _i32, _p, _i64, _p, _i64, _i32, _p, _p, _p, _i64, _p, _p]),
     "mst_trans_zscore_workspace_bytes": (_u64, []),
     "mst_trans_zscore": (ctypes.c_int, [_p, _i64, _p, _p, _p, _u64, _p]),

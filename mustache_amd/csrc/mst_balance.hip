@@ -6,6 +6,8 @@
 //   mst_balance_newton     `steps` steps of the Newton balancing (Knight & Ruiz); every decision stays on the device
 //   mst_balance_bias       kappa = sqrt(sum_{i<=j} A_ij w_i w_j / sum_{i<=j} A_ij) and b = kappa / w (NaN where w = 0)
 //   mst_balance_apply_packed  (v / b[x]) / b[x + dist] for `.hic` records already on the device
+//   mst_balance_apply_pairs   (v / b[row_off[p] + x]) / b[col_off[p] + y] for the records of P chromosome pairs in one launch
+//                             (mustache_amd/balance_genome.py: a genome-wide bias applied to inter-chromosomal records)
 //
 // The matrix is the full symmetric CSR of the kept pixels (int32 column, float64 value), sorted by (row, column).  Each row
 // is cut into chunks of kChunk entries counted from the row's first entry; one wave reduces one chunk (lane l takes entries
@@ -303,6 +305,64 @@ apply_packed_kernel(const int32_t *__restrict__ x, const int32_t *__restrict__ d
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nnz; e += stride) {
         const int64_t a = x[e], b = a + dist[e];
         out[e] = ((double)v[e] / bias_at(bias, nb, a)) / bias_at(bias, nb, b);
+    }
+}
+
+// ---- a genome-wide bias applied to the records of P chromosome pairs (mustache_amd/balance_genome.py) -----------------------
+// b of the application rule: the vector's value where it is >= 0.2; +inf where it is NaN or below 0.2, and for a bin outside
+// [0, n) -- such a record leaves as 0 (or NaN) and is dropped by the caller's v' > 0.  Nothing outside the vector is read.
+__device__ __forceinline__ double genome_bias_at(const double *b, int64_t n, int64_t off, int32_t i) {
+    const int64_t g = off + (int64_t)i;
+    if (i < 0 || g < 0 || g >= n) return INFINITY;
+    const double v = b[g];
+    return (v >= 0.2) ? v : INFINITY;
+}
+
+// the pair of record e: the largest p in [0, P) with seg_off[p] <= e (empty segments are stepped over).  The result stays in
+// [0, P) whatever seg_off holds, so row_off / col_off are never read out of bounds.
+__device__ __forceinline__ int32_t pair_of(const int64_t *__restrict__ seg_off, int32_t P, int64_t e) {
+    int32_t lo = 0, hi = P;
+    while (hi - lo > 1) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (seg_off[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// One pass, no atomics.  kVec: a thread takes the records 2 t and 2 t + 1 -- their coordinates as one 8-byte load each, their
+// values as one 16-byte load and one 16-byte store (the host takes this path when the pointers are aligned for it); the second
+// record looks its pair up again only when it lies past the first one's segment.
+template <bool kVec>
+__global__ void __launch_bounds__(kThreads)
+apply_pairs_kernel(const int32_t *__restrict__ x, const int32_t *__restrict__ y, const double *v, int64_t N,
+                   const int64_t *__restrict__ seg_off, const int64_t *__restrict__ row_off, const int64_t *__restrict__ col_off,
+                   int32_t P, const double *__restrict__ bias, int64_t n, double *out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (kVec) {
+        const int64_t pairs = N >> 1;
+        for (int64_t t = t0; t < pairs; t += stride) {
+            const int64_t e = 2 * t;
+            const int2 xx = *reinterpret_cast<const int2 *>(x + e);
+            const int2 yy = *reinterpret_cast<const int2 *>(y + e);
+            const double2 vv = *reinterpret_cast<const double2 *>(v + e);
+            int32_t p = pair_of(seg_off, P, e);
+            double2 o;
+            o.x = (vv.x / genome_bias_at(bias, n, row_off[p], xx.x)) / genome_bias_at(bias, n, col_off[p], yy.x);
+            if (p + 1 < P && seg_off[p + 1] <= e + 1) p = pair_of(seg_off, P, e + 1);
+            o.y = (vv.y / genome_bias_at(bias, n, row_off[p], xx.y)) / genome_bias_at(bias, n, col_off[p], yy.y);
+            *reinterpret_cast<double2 *>(out + e) = o;
+        }
+        if ((N & 1) && t0 == 0) {                                // the odd record at the end
+            const int64_t e = N - 1;
+            const int32_t p = pair_of(seg_off, P, e);
+            out[e] = (v[e] / genome_bias_at(bias, n, row_off[p], x[e])) / genome_bias_at(bias, n, col_off[p], y[e]);
+        }
+    } else {
+        for (int64_t e = t0; e < N; e += stride) {
+            const int32_t p = pair_of(seg_off, P, e);
+            out[e] = (v[e] / genome_bias_at(bias, n, row_off[p], x[e])) / genome_bias_at(bias, n, col_off[p], y[e]);
+        }
     }
 }
 
@@ -776,6 +836,26 @@ extern "C" int mst_balance_apply_packed(const int32_t *x, const int32_t *dist, c
         return mst::fail(MST_E_ARG, "mst_balance_apply_packed: bad argument");
     if (nnz == 0) return MST_OK;
     apply_packed_kernel<<<grid_for(nnz, kThreads), kThreads, 0, mst::as_stream(stream)>>>(x, dist, v, nnz, bias, n_bias, out);
+    MST_LAUNCH_CHECK();
+    return MST_OK;
+}
+
+extern "C" int mst_balance_apply_pairs(const int32_t *x, const int32_t *y, const double *v, int64_t n_records, const int64_t *seg_off,
+                                       const int64_t *row_off, const int64_t *col_off, int32_t P, const double *bias, int64_t n_bias,
+                                       double *out, void *stream) {
+    if (n_records < 0 || P < 0 || n_bias < 0 || (n_bias > 0 && !bias) ||
+        (n_records > 0 && (P < 1 || !x || !y || !v || !out || !seg_off || !row_off || !col_off)))
+        return mst::fail(MST_E_ARG, "mst_balance_apply_pairs: bad argument");
+    if (n_records == 0 || P == 0) return MST_OK;
+    hipStream_t s = mst::as_stream(stream);
+    const bool vec = ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 &&
+                     ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7) == 0;
+    if (vec)
+        apply_pairs_kernel<true><<<grid_for((n_records + 1) / 2, kThreads), kThreads, 0, s>>>(x, y, v, n_records, seg_off, row_off,
+                                                                                              col_off, P, bias, n_bias, out);
+    else
+        apply_pairs_kernel<false><<<grid_for(n_records, kThreads), kThreads, 0, s>>>(x, y, v, n_records, seg_off, row_off, col_off,
+                                                                                     P, bias, n_bias, out);
     MST_LAUNCH_CHECK();
     return MST_OK;
 }

@@ -334,6 +334,8 @@ def parse_args(args):
                    help="OPTIONAL: call differential inter-chromosomal loops for every unordered pair of the -ch list (without "
                         "-ch: of every chromosome of the first .hic / .cool / .mcool file) in shared launches; no "
                         "intra-chromosomal rows.")
+    from .balance_genome import add_arguments
+    add_arguments(p)
     return p.parse_args(args)
 
 
@@ -402,10 +404,24 @@ def trans_all_request(f1, f2, res, ch, ch2, balance, world_size):
     return trans_all_pairs(f1, res, ch, ch2)
 
 
-def run_trans_all(f1, f2, args, res, pairs, device=None):
+def genome_biases_or_error(f1, f2, res, request, device=None):
+    """--balance-genome: each sample balanced on its own (one balance.report line per sample) -> the two GenomeBias, or None
+    after an `Error:` line"""
+    from .mustache import genome_bias_or_error
+    out = []
+    for f in (f1, f2):
+        gb = genome_bias_or_error(f, res, request, device)
+        if gb is None:
+            return None
+        out.append(gb)
+    return out
+
+
+def run_trans_all(f1, f2, args, res, pairs, device=None, genomes=None):
     """The --trans-all run: the next pair's two samples are read on a reader thread while the current pair joins the batch
     (mustache.run_trans_pairs, diff_trans_genome.DiffTransGenomeCaller); rows are written in pair order, the headers with the
-    first pair's."""
+    first pair's.  genomes (the samples' balance_genome.GenomeBias, --balance-genome): nothing is read again; both samples'
+    resident records are balanced in shared launches and join the batch."""
     from .diff_trans_genome import DiffTransGenomeCaller
     from .mustache import run_trans_pairs
     from .trans import read_trans_contacts
@@ -429,7 +445,28 @@ def run_trans_all(f1, f2, args, res, pairs, device=None):
 
     caller = DiffTransGenomeCaller([args.s_z * (2 ** i) for i in range(args.octaves)], args.st, args.pt, args.pt2, emit,
                                    verbose=args.verbose)
+    if genomes is not None:
+        from .balance_genome import balanced_batches
+        for (k, rec1), (_, rec2) in zip(balanced_batches(genomes[0], pairs), balanced_batches(genomes[1], pairs)):
+            caller.add(k, rec1, rec2, "%s,%s" % pairs[k])
+        return caller.flush()
     run_trans_pairs(pairs, fetch, lambda k, recs, label: caller.add(k, recs[0], recs[1], label), caller.flush, args.verbose)
+
+
+def balanced_trans_rows(genomes, files, pair, args):
+    """The rows of one trans pair under --balance-genome: both samples' resident records balanced by their own genome bias
+    (balance_genome.balanced_pair), then diff_trans.call_diff_trans_coo"""
+    from .balance_genome import balanced_pair
+    from .diff_trans import call_diff_trans_coo
+    recs = []
+    for gb, f in zip(genomes, files):
+        got = balanced_pair(gb, pair[0], pair[1])
+        if got is None:
+            print("There is no contact in the chromosome pair %s,%s of %s to work on." % (pair[0], pair[1], f))
+            return []
+        recs.append(got)
+    return call_diff_trans_coo(recs[0], recs[1], [args.s_z * (2 ** i) for i in range(args.octaves)], args.st, args.pt, args.pt2,
+                               verbose=args.verbose, label="%s,%s" % pair)
 
 
 def main(argv=None):
@@ -453,8 +490,20 @@ def main(argv=None):
         if isinstance(pairs, str):
             print(pairs)
             return
+        from .balance import BalanceError
+        from .balance_genome import request_of
+        try:
+            genomes = request_of(args, [f1, f2], args.biasfile1 or args.biasfile2, 1, pairs)
+        except BalanceError as e:
+            print("Error: %s" % e)
+            return
         import torch
-        return run_trans_all(f1, f2, args, res, pairs, device=torch.device("cuda", torch.cuda.current_device()))
+        device = torch.device("cuda", torch.cuda.current_device())
+        if genomes is not None:
+            genomes = genome_biases_or_error(f1, f2, res, genomes, device)
+            if genomes is None:
+                return
+        return run_trans_all(f1, f2, args, res, pairs, device=device, genomes=genomes)
     pairs = chromosome_pairs(f1, res, args.chromosome, args.chromosome2)
     if isinstance(pairs, str):
         print(pairs)
@@ -489,6 +538,17 @@ def main(argv=None):
         why = refusal((f1, f2), args.balance, world_size, bool(args.chromosome) and args.chromosome != 'n')
         if why:
             print("Error: %s" % why)
+            return
+    from .balance import BalanceError
+    from .balance_genome import request_of
+    try:
+        genomes = request_of(args, [f1, f2], args.biasfile1 or args.biasfile2, world_size, cis_pairs + trans_pairs)
+    except BalanceError as e:
+        print("Error: %s" % e)
+        return
+    if genomes is not None:                  # --balance-genome: every matrix of both files is read once, here
+        genomes = genome_biases_or_error(f1, f2, res, genomes)
+        if genomes is None:
             return
     pairs = cis_pairs + trans_pairs
     n_cis = len(cis_pairs)
@@ -546,6 +606,9 @@ def main(argv=None):
     genome.flush()
     for i in range(n_cis, len(pairs)):
         t0 = time.time()
+        if genomes is not None:
+            emit(i, balanced_trans_rows(genomes, (f1, f2), pairs[i], args))
+            continue
         emit(i, regulator(f1, f2, args.norm_method, False, args.outdir, res=res, sigma0=args.s_z, verbose=args.verbose,
                           pt=args.pt, pt2=args.pt2, st=args.st, chromosome=pairs[i][0], chromosome2=pairs[i][1],
                           octaves=args.octaves))

@@ -463,6 +463,8 @@ def parse_args(args):
     p.add_argument("--trans-all", dest="trans_all", action="store_true",
                    help="OPTIONAL: call inter-chromosomal loops for every unordered pair of the -ch list (without -ch: of "
                         "every chromosome of a .hic / .cool / .mcool file) in shared launches; no intra-chromosomal rows.")
+    from .balance_genome import add_arguments
+    add_arguments(p)
     return p.parse_args(args)
 
 
@@ -595,9 +597,25 @@ def run_trans_pairs(pairs, fetch, add, flush, verbose):
     flush()
 
 
-def run_trans_all(f, args, res, pairs, device=None):
+def genome_bias_or_error(f, res, request, device=None):
+    """--balance-genome: balance.report's line and the GenomeBias of `f`; None after the `Error:` line of a run the device's
+    memory cannot hold.  request = (method, pixels) as balance_genome.request_of returns it."""
+    from .balance import BalanceError, report
+    from .balance_genome import genome_bias
+    try:
+        gb = genome_bias(f, res, method=request[0], pixels=request[1], device=device)
+    except BalanceError as e:
+        print("Error: %s" % e)
+        return None
+    report(gb.info, gb.label)
+    return gb
+
+
+def run_trans_all(f, args, res, pairs, device=None, genome=None):
     """The --trans-all run: the next pair is read on a reader thread while the current one joins the batch
-    (trans_genome.TransGenomeCaller); rows are written in pair order, the header with the first pair's."""
+    (trans_genome.TransGenomeCaller); rows are written in pair order, the header with the first pair's.
+    genome (a balance_genome.GenomeBias, --balance-genome): nothing is read again -- the pairs' resident records are balanced
+    in shared launches (balance_genome.balanced_batches) and join the batch."""
     from .trans import read_trans_contacts
     from .trans_genome import TransGenomeCaller
     state = {"first": True, "t0": time.time()}
@@ -616,6 +634,11 @@ def run_trans_all(f, args, res, pairs, device=None):
         state["t0"] = time.time()
 
     caller = TransGenomeCaller([args.s_z * (2 ** i) for i in range(args.octaves)], args.st, args.pt, emit, verbose=args.verbose)
+    if genome is not None:
+        from .balance_genome import balanced_batches
+        for k, records in balanced_batches(genome, pairs):
+            caller.add(k, records, "%s,%s" % pairs[k])
+        return caller.flush()
     run_trans_pairs(pairs, fetch, caller.add, caller.flush, args.verbose)
 
 
@@ -656,8 +679,20 @@ def main(argv=None):
         if isinstance(pairs, str):
             print(pairs)
             return
+        from .balance import BalanceError
+        from .balance_genome import request_of
+        try:
+            genome = request_of(args, f, args.biasfile, _world, pairs)
+        except BalanceError as e:
+            print("Error: %s" % e)
+            return
         import torch
-        return run_trans_all(f, args, res, pairs, device=torch.device("cuda", torch.cuda.current_device()))
+        device = torch.device("cuda", torch.cuda.current_device())
+        if genome is not None:
+            genome = genome_bias_or_error(f, res, genome, device)
+            if genome is None:
+                return
+        return run_trans_all(f, args, res, pairs, device=device, genome=genome)
     pairs = chromosome_pairs(f, res, args.chromosome, args.chromosome2)
     if isinstance(pairs, str):
         print(pairs)
@@ -695,6 +730,13 @@ def main(argv=None):
         if refusal:
             print("Error: %s" % refusal)
             return
+    from .balance import BalanceError
+    from .balance_genome import request_of
+    try:
+        gbias = request_of(args, f, args.biasfile, _world, pairs + trans_pairs)
+    except BalanceError as e:
+        print("Error: %s" % e)
+        return
 
     try:                                     # the reader thread below must upload to THIS thread's device, not to GPU 0
         import torch
@@ -791,11 +833,23 @@ def main(argv=None):
             del band                          # the batcher's reference is the only one: run_genome releases it as it copies
         genome.flush()
     first = not pairs                        # the header is written with the first pair's rows
+    if gbias is not None:                    # --balance-genome: every matrix is read once, here; the pairs are called from it
+        gbias = genome_bias_or_error(f, res, gbias, my_device)
+        if gbias is None:
+            return
     for chromosome, chromosome2 in trans_pairs:
         start_time = time.time()
         _check_pair(f, chromosome, chromosome2)          # text input: the reference's refusal
-        contacts = read_contacts(f, args.norm_method, False, res, distFilter, biasf, chromosome, chromosome2,
-                                 verbose=args.verbose, device=my_device)
+        if gbias is not None:
+            from .balance_genome import balanced_pair
+            contacts = balanced_pair(gbias, chromosome, chromosome2)
+            if contacts is None:
+                print("There is no contact in the chromosome pair %s,%s to work on." % (chromosome, chromosome2))
+            else:
+                contacts = contacts + (res,)
+        else:
+            contacts = read_contacts(f, args.norm_method, False, res, distFilter, biasf, chromosome, chromosome2,
+                                     verbose=args.verbose, device=my_device)
         o = [] if contacts is None else regulator(
             f, args.norm_method, False, args.outdir, res=contacts[3], sigma0=args.s_z, verbose=args.verbose, pt=args.pt,
             st=args.st, distance_filter=distFilter, chromosome=chromosome, chromosome2=chromosome2, octaves=args.octaves,
