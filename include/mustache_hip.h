@@ -628,6 +628,28 @@ MST_STABLE int mst_pileup_trans_windows(const int32_t *x, const int32_t *y, cons
                                         uint8_t *valid_cols, double *expected, double *obs, double *oe, double *loop_stats,
                                         void *workspace, uint64_t workspace_bytes, void *stream);
 
+/* ---- read pairs -> pixels (rules: mustache_amd/pairs.py; tests/pairs_reference.py restates them).  Added without a change
+ * of MST_ABI_REVISION, as mst_balance_apply_pairs was: a library from before the addition is refused by its missing symbols. */
+/* One pass over the rows (pos1, pos2: dev int32 [n_rows]) of one chromosome.  A row is dropped when a position is < 1 or
+ * > limit (zero_based != 0: < 0 or >= limit; limit = 2^31 when there is none) or when its larger bin is >= n; otherwise
+ * bin = (pos - 1) / res (zero_based: pos / res) and its pixel is (x, y) = (min, max) of the two bins.  A pixel with
+ * y - x < dense_diags adds to dense[(y - x) * n + x] (dev uint32 [dense_diags][n], diagonal-major, ACCUMULATED: the caller
+ * zeroes it); any other pixel appends (far_key = x * n + y, far_mult) to the far list (dev int64 / uint32 [far_cap]), one entry
+ * per run of adjacent rows of a wave that share the pixel, so a pixel may appear in several entries, in no fixed order.
+ * counters (dev uint64 [2], ACCUMULATED, the caller zeroes them): [0] far entries, [1] dropped rows.  counters[0] > far_cap
+ * means entries were lost (nothing is written past far_cap): far_cap = n_rows always suffices.  dense_diags = 0 is legal (dense
+ * may be NULL); dense_diags <= n.  All sums are integer sums: the results do not depend on the order of the rows. */
+MST_STABLE int mst_pairs_bin(const int32_t *pos1, const int32_t *pos2, int64_t n_rows, int32_t res, int32_t zero_based, int64_t limit,
+                             int64_t n, int32_t dense_diags, uint32_t *dense, int64_t *far_key, uint32_t *far_mult, int64_t far_cap,
+                             uint64_t *counters, void *stream);
+/* The non-zero counters of dense [dense_diags][n] -> records (out_x, out_dist: dev int32 [cap]; out_count: dev uint32 [cap]) in
+ * position order (by diagonal, then by x); *n_out (dev int64) = their number, which may exceed cap: nothing is written past
+ * cap.  Two passes and a scan, no atomics.  workspace: dev, mst_pairs_compact_workspace_bytes(dense_diags, n) bytes. */
+MST_STABLE uint64_t mst_pairs_compact_workspace_bytes(int32_t dense_diags, int64_t n);
+MST_STABLE int mst_pairs_compact(const uint32_t *dense, int32_t dense_diags, int64_t n, int32_t *out_x, int32_t *out_dist,
+                                 uint32_t *out_count, int64_t cap, int64_t *n_out, void *workspace, uint64_t workspace_bytes,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -394,11 +394,10 @@ def read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res, device=None
     """`.hic` under --balance: every raw record of the chromosome (norm NONE, no distance limit), `method` on the device, the
     bias applied on the device, then the reader's distance rule -> (x, y, v) host arrays, None when nothing is left."""
     import torch
-    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    from ._lib import require_gpu
     from .hicfile import read_intra_packed
     from .readers import _HIC_LOCK, _hic_handle
-    from . import _lib
-    lib = require_gpu()
+    require_gpu()
     with _HIC_LOCK:
         h = _hic_handle(f)
         if not CHRM_SIZE:
@@ -417,14 +416,35 @@ def read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res, device=None
         xd = torch.from_numpy(pc.x[:pc.count]).to(dev)
         dd = torch.from_numpy(pc.dist[:pc.count]).to(dev)
         vd = torch.from_numpy(pc.v[:pc.count]).to(dev)
+    return balance_records_device(xd, dd, vd, distance_in_bp, chromosome, res, dev, method=method, **kw)
+
+
+def balance_records_device(xd, dd, vd, distance_in_bp, chromosome, res, dev, method="ICE", **kw):
+    """The half of a --balance read that follows the pixel set, shared by `.hic` input (read_hic_balanced) and read pairs
+    (pairs.read_pairs_balanced): device records (xd = bin, dd = distance: int32; vd = raw counts, float32 as a `.hic` file
+    stores them or float64) -> n = max bin + 1, `method` on the device, the bias applied on the device as
+    v' = (v / b[x]) / b[y] (NaN or < 0.2 count as +inf), then v' > 0 and the reader's distance rule -> (x, y, v) host arrays,
+    None when nothing is left."""
+    import torch
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    from . import _lib
+    lib = require_gpu()
+    count = int(vd.numel())
+    with torch.cuda.device(dev):
         yd = xd.to(torch.int64) + dd.to(torch.int64)
         n = int(yd.max().item()) + 1
         bias, info = solve(method, xd, yd, vd.to(torch.float64), n, device=dev, **kw)
         report(info, "chromosome %s" % chromosome)
         bd = torch.from_numpy(bias).to(dev)
-        out = torch.empty(pc.count, dtype=torch.float64, device=dev)
-        _lib.check(lib.mst_balance_apply_packed(_ptr(xd), _ptr(dd), _ptr(vd), int(pc.count), _ptr(bd), int(n), _ptr(out),
-                                                _stream()))
+        out = torch.empty(count, dtype=torch.float64, device=dev)
+        if vd.dtype == torch.float32:
+            _lib.check(lib.mst_balance_apply_packed(_ptr(xd), _ptr(dd), _ptr(vd), count, _ptr(bd), int(n), _ptr(out), _stream()))
+        else:                                   # float64 counts: the pair form with one segment that starts at bin 0
+            seg = torch.tensor([0, count], dtype=torch.int64, device=dev)
+            zero = torch.zeros(1, dtype=torch.int64, device=dev)
+            y32 = yd.to(torch.int32)
+            _lib.check(lib.mst_balance_apply_pairs(_ptr(xd), _ptr(y32), _ptr(vd), count, _ptr(seg), _ptr(zero), _ptr(zero), 1,
+                                                   _ptr(bd), int(n), _ptr(out), _stream()))
         keep = (out > 0) & (dd <= int(distance_in_bp // res))
         x, y, v = xd[keep].to(torch.int64).cpu().numpy(), yd[keep].cpu().numpy(), out[keep].cpu().numpy()
     if len(v) == 0:

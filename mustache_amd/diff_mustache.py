@@ -252,7 +252,7 @@ def _pairs_from_filled(eng, pipe, dbands, n, dpx, starts, CH, dense=False, pt=No
 
 
 def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2, chromosome, chromosome2, verbose=True,
-              balance=None):
+              balance=None, pairs_zero_based=False):
     """The reading half of regulator() (diff_mustache.py:591-626): -> (coo1, coo2, res) or None when a sample is empty.
     balance="ICE" or "NEWTON": each sample's raw map is balanced on its own on the GPU (mustache_amd.balance), as
     mustache.read_contacts does for one sample; bias1 / bias2 and a stored normalisation are then not used."""
@@ -268,7 +268,8 @@ def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2,
     from .hicfile import PackedContacts
     coos = []
     for f, bias in ((f1, bias1), (f2, bias2)):
-        coo = read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome, balance=balance)
+        coo = read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome, balance=balance,
+                          pairs_zero_based=pairs_zero_based, verbose=verbose)
         if coo is not None and not isinstance(coo, PackedContacts):
             if coos and coo[3] != res:                # only a `.cool` file brings a resolution of its own
                 raise ValueError('Both contact maps should have the same resolution.')
@@ -282,18 +283,18 @@ def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2,
 
 def regulator(f1, f2, norm_method, CHRM_SIZE, outdir, bed1="", bed2="", res=5000, sigma0=1.6, s=10, pt=0.1, pt2=0.1,
               st=0.88, octaves=2, verbose=True, nprocesses=4, distance_filter=2000000, bias1=False, bias2=False,
-              chromosome='n', chromosome2=None, balance=None):
+              chromosome='n', chromosome2=None, balance=None, pairs_zero_based=False):
     """Two-sample loop calling for one chromosome (diff_mustache.py:572-690); returns [x, y, fdr, sigma, tag] rows.
     chromosome2 = B != chromosome: the inter-chromosomal pair (A, B), which the reference cannot run (diff_trans.py).
     `balance="ICE"` or `"NEWTON"` (not in the reference): balance each sample's raw map on the GPU instead of applying
-    bias1 / bias2."""
+    bias1 / bias2; `pairs_zero_based`: the position convention of `.pairs` input (mustache_amd/pairs.py)."""
     octave_values = [sigma0 * (2 ** i) for i in range(octaves)]
     if chromosome2 and chromosome2 != 'n' and chromosome != chromosome2:      # the trans pair (A, B): mustache_amd/diff_trans.py
         from .diff_trans import regulate
         return regulate(f1, f2, norm_method, res, octave_values, st, pt, pt2, chromosome, chromosome2, verbose=verbose,
                         balance=balance)
     got = read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_filter, bias1, bias2, chromosome, chromosome2, verbose,
-                    balance=balance)
+                    balance=balance, pairs_zero_based=pairs_zero_based)
     if got is None:
         return []
     coo1, coo2, res = got
@@ -334,6 +335,8 @@ def parse_args(args):
                    help="OPTIONAL: call differential inter-chromosomal loops for every unordered pair of the -ch list (without "
                         "-ch: of every chromosome of the first .hic / .cool / .mcool file) in shared launches; no "
                         "intra-chromosomal rows.")
+    p.add_argument("--pairs-zero-based", dest="pairs_zero_based", action="store_true",
+                   help="OPTIONAL: .pairs / .pairs.gz input only: positions are 0-based (bin = pos // res)")
     from .balance_genome import add_arguments
     add_arguments(p)
     return p.parse_args(args)
@@ -484,6 +487,12 @@ def main(argv=None):
     if not res:
         print("Error: Invalid resolution")
         return
+    from .pairs import refusal as pairs_refusal
+    why = pairs_refusal([f1, f2], args.balance, args.biasfile1 or args.biasfile2, args.norm_method, args.chromosome,
+                        args.chromosome2, args.trans_all, args.balance_genome, args.pairs_zero_based, bias_flag="-b1/-b2")
+    if why:                                  # (a multi-rank run is refused by --balance's own check below)
+        print("Error: %s" % why)
+        return
     if args.trans_all:
         from .sharding import init_from_env
         pairs = trans_all_request(f1, f2, res, args.chromosome, args.chromosome2, args.balance, init_from_env()[1])
@@ -504,7 +513,7 @@ def main(argv=None):
             if genomes is None:
                 return
         return run_trans_all(f1, f2, args, res, pairs, device=device, genomes=genomes)
-    pairs = chromosome_pairs(f1, res, args.chromosome, args.chromosome2)
+    pairs = chromosome_pairs(f1, res, args.chromosome, args.chromosome2, args.pairs_zero_based)
     if isinstance(pairs, str):
         print(pairs)
         return
@@ -585,10 +594,11 @@ def main(argv=None):
             emit(i, regulator(f1, f2, args.norm_method, False, args.outdir, bed1=args.bed1, bed2=args.bed2, res=res,
                               sigma0=args.s_z, s=args.s, verbose=args.verbose, pt=args.pt, pt2=args.pt2, st=args.st,
                               distance_filter=distFilter, nprocesses=args.nprocesses, bias1=biasf1, bias2=biasf2,
-                              chromosome=chromosome, chromosome2=chromosome2, octaves=args.octaves, balance=args.balance))
+                              chromosome=chromosome, chromosome2=chromosome2, octaves=args.octaves, balance=args.balance,
+                              pairs_zero_based=args.pairs_zero_based))
             continue
         got = read_pair(f1, f2, args.norm_method, False, res, distFilter, biasf1, biasf2, chromosome, chromosome2,
-                        args.verbose, balance=args.balance)
+                        args.verbose, balance=args.balance, pairs_zero_based=args.pairs_zero_based)
         if got is None:
             genome.skip(i)
             continue

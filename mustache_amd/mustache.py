@@ -322,13 +322,14 @@ def call_trans_coo(x, y, v, octave_values, st, pt, verbose=True, label=""):
 
 
 def read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromosome, chromosome2, verbose=True,
-                  packed=False, part=(0, 1), device=None, balance=None):
+                  packed=False, part=(0, 1), device=None, balance=None, pairs_zero_based=False):
     """The reading half of regulator() (reference mustache.py:866-889): host I/O only, so main() can fetch the next
     chromosome while the GPU works on the current one.  Returns (x, y, v, res) or None when nothing was read.
     packed=True: a `.hic` file read by the native reader comes back as hicfile.PackedContacts (12 bytes per record, what
     the GPU loader takes) instead of the int64 / float64 triple.
     balance="ICE" or "NEWTON": the map's raw counts are balanced on the GPU (mustache_amd.balance) instead of using a bias file or a
-    stored normalisation; the result is always the int64 / float64 triple."""
+    stored normalisation; the result is always the int64 / float64 triple.
+    pairs_zero_based: the position convention of a `.pairs` / `.pairs.gz` file (mustache_amd/pairs.py), which needs `balance`."""
     chromosome2 = _check_pair(f, chromosome, chromosome2)
     distance_in_bp = distance_filter
     if verbose:
@@ -344,21 +345,30 @@ def read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromos
         from .balance import check_request
         check_request(balance, f, bias, norm_method, world=part[1])
     r = read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome, packed=packed, part=part,
-                    device=device, balance=balance)
+                    device=device, balance=balance, pairs_zero_based=pairs_zero_based, verbose=verbose)
     if isinstance(r, tuple) and len(r[2]) == 0:
         return None
     return r
 
 
 def read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome, packed=True, part=(0, 1), device=None,
-                balance=None):
+                balance=None, pairs_zero_based=False, verbose=True):
     """One sample's intra-chromosomal records by file type, for read_contacts and diff_mustache.read_pair.  Returns
     (x, y, v, res) host arrays (res: the file's own for `.cool`), possibly empty; hicfile.PackedContacts for a `.hic` file
     when `packed` and the native reader serves it (a rank's share of `part` may be empty and is still returned: every
     rank takes part in the exchange); None when a text reader finds no record of the chromosome.
     balance="ICE" or "NEWTON": the raw counts balanced on the GPU by that method (`.hic` through the native reader whatever MUSTACHE_HIC_BACKEND says,
-    text otherwise); the caller has already checked the request (balance.check_request)."""
-    if balance:
+    text otherwise); the caller has already checked the request (balance.check_request).
+    A `.pairs` / `.pairs.gz` file (raw read pairs, mustache_amd/pairs.py) is binned on the GPU and needs `balance`."""
+    from .pairs import is_pairs
+    if is_pairs(f):
+        from .pairs import PairsError, read_pairs_balanced
+        if not balance:
+            raise PairsError("%s holds raw read pairs: give --balance ICE|NEWTON" % f)
+        from .balance import method_of
+        r = read_pairs_balanced(f, distance_in_bp, chromosome, res, device=device, method=method_of(balance),
+                                zero_based=pairs_zero_based, verbose=verbose)
+    elif balance:
         from .balance import method_of, read_hic_balanced
         if f.endswith(".hic"):
             r = read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res, device=device, method=method_of(balance))
@@ -385,26 +395,26 @@ def read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome
 
 def regulator(f, norm_method, CHRM_SIZE, outdir, bed="", res=5000, sigma0=1.6, s=10, pt=0.1, st=0.88, octaves=2,
               verbose=True, nprocesses=4, distance_filter=2000000, bias=False, chromosome='n', chromosome2=None,
-              contacts=None, shard_blocks=True, balance=None):
+              contacts=None, shard_blocks=True, balance=None, pairs_zero_based=False):
     """Loop calling for one chromosome (reference mustache.py:853-942).  `s` is accepted and ignored like in the
     reference (s = 10 is hard-wired at :711); `nprocesses` is ignored: all blocks run as one GPU batch.
     `contacts` (not in the reference): what read_contacts() returned for this chromosome, when the caller read ahead;
     `shard_blocks=False`: in a multi-GPU job this rank runs the whole chromosome alone (whole-genome sharding by chromosome).
     `balance="ICE"` or `"NEWTON"` (not in the reference): balance the raw map on the GPU instead of applying `bias`
-    (read_contacts)."""
+    (read_contacts); `pairs_zero_based`: the position convention of `.pairs` input (read_contacts)."""
     chromosome2 = _check_pair(f, chromosome, chromosome2)
     octave_values = [sigma0 * (2 ** i) for i in range(octaves)]
     if chromosome != chromosome2:          # chromosome2 = B: the trans pair (A, B), mustache_amd/trans.py
         if contacts is None:
             contacts = read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromosome, chromosome2, verbose,
-                                     balance=balance)
+                                     balance=balance, pairs_zero_based=pairs_zero_based)
             if contacts is None:
                 return []
         x, y, v, _res = contacts
         return call_trans_coo(x, y, v, octave_values, st, pt, verbose=verbose, label="%s,%s" % (chromosome, chromosome2))
     if contacts is None:
         contacts = read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromosome, chromosome2, verbose,
-                                 balance=balance)
+                                 balance=balance, pairs_zero_based=pairs_zero_based)
         if contacts is None:
             return []
     from .hicfile import PackedContacts
@@ -463,6 +473,9 @@ def parse_args(args):
     p.add_argument("--trans-all", dest="trans_all", action="store_true",
                    help="OPTIONAL: call inter-chromosomal loops for every unordered pair of the -ch list (without -ch: of "
                         "every chromosome of a .hic / .cool / .mcool file) in shared launches; no intra-chromosomal rows.")
+    p.add_argument("--pairs-zero-based", dest="pairs_zero_based", action="store_true",
+                   help="OPTIONAL: .pairs / .pairs.gz input only: positions are 0-based (bin = pos // res) instead of the "
+                        "format's 1-based ones (bin = (pos - 1) // res)")
     from .balance_genome import add_arguments
     add_arguments(p)
     return p.parse_args(args)
@@ -529,14 +542,24 @@ def _scalar_text(v):
     return repr(float(v)) if isinstance(v, (float, np.float64)) else str(v)      # str(np.float32) is NOT repr(float(v)): left to str()
 
 
-def chromosome_pairs(f, res, ch, ch2):
-    """-ch / -ch2 -> [(chromosome, chromosome2)] (without -ch: every chromosome of a `.hic` / `.cool` / `.mcool` file), or the
-    Error: line to print when they cannot be paired (reference mustache.py:1019-1045, diff_mustache.py:781-800)."""
+def chromosome_pairs(f, res, ch, ch2, pairs_zero_based=False):
+    """-ch / -ch2 -> [(chromosome, chromosome2)] (without -ch: every chromosome of a `.hic` / `.cool` / `.mcool` file, or of a
+    `.pairs` / `.pairs.gz` file's table in table order), or the Error: line to print when they cannot be paired (reference
+    mustache.py:1019-1045, diff_mustache.py:781-800)."""
     if not ch or ch == 'n':
-        if not f.endswith((".cool", ".mcool", ".hic")):
+        from .pairs import is_pairs
+        if is_pairs(f):                   # the one parse of the run: the handle stays cached for the reads that follow
+            from .hicfile import HicError
+            from .pairs import list_chromosomes as pairs_chromosomes
+            try:
+                ch = pairs_chromosomes(f, pairs_zero_based)
+            except HicError as e:
+                return "Error: %s" % e
+        elif not f.endswith((".cool", ".mcool", ".hic")):
             return "Error: Please enter the chromosome name."
-        from .readers import list_chromosomes
-        ch = list_chromosomes(f, res)
+        else:
+            from .readers import list_chromosomes
+            ch = list_chromosomes(f, res)
     ch2 = ch2 if isinstance(ch2, list) else ch
     if len(ch) != len(ch2):
         return "Error: the same number of chromosome1 and chromosome2 should be provided."
@@ -669,6 +692,12 @@ def main(argv=None):
     if not res:
         print("Error: Invalid resolution")
         return
+    from .pairs import refusal as pairs_refusal
+    why = pairs_refusal(f, args.balance, args.biasfile, args.norm_method, args.chromosome, args.chromosome2, args.trans_all,
+                        args.balance_genome, args.pairs_zero_based, _world)
+    if why:
+        print("Error: %s" % why)
+        return
     if args.trans_all:
         pairs = trans_all_pairs(f, res, args.chromosome, args.chromosome2)
         if not isinstance(pairs, str):
@@ -693,7 +722,7 @@ def main(argv=None):
             if genome is None:
                 return
         return run_trans_all(f, args, res, pairs, device=device, genome=genome)
-    pairs = chromosome_pairs(f, res, args.chromosome, args.chromosome2)
+    pairs = chromosome_pairs(f, res, args.chromosome, args.chromosome2, args.pairs_zero_based)
     if isinstance(pairs, str):
         print(pairs)
         return
@@ -752,7 +781,7 @@ def main(argv=None):
             with stage("read %s" % chromosome):
                 return read_contacts(f, args.norm_method, CHRM_SIZE, res, distFilter, biasf, chromosome, chromosome2,
                                      verbose=args.verbose, packed=True, part=(0, 1) if by_chromosome else (rank, _world),
-                                     device=my_device, balance=args.balance)
+                                     device=my_device, balance=args.balance, pairs_zero_based=args.pairs_zero_based)
         except BaseException as e:          # re-raised in the main thread, at this chromosome's turn
             return e
 
