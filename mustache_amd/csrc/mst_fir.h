@@ -31,8 +31,8 @@
 #endif
 
 #ifndef MST_KC8_BELOW
-#define MST_KC8_BELOW 11      // radii below this use one 8-output window per item, wider ones two 4-output windows
-#endif
+#define MST_KC8_BELOW 10      // radii below this use one 8-output window per item, wider ones two 4-output windows
+#endif                        // (10, 11, 12, 14 re-timed with all window loads at full rate: LABBOOK, "16-byte window loads at odd radii")
 
 namespace {
 
@@ -82,6 +82,9 @@ constexpr int pitch_for(int need) {
     // (mod 32) doubles -- pitch/2 odd -- makes 32 consecutive rows land on 32 distinct slots, and keeps the loads
     // 16-byte aligned.  (The V pass's 4-row leftover pieces cannot meet the rule for radii below 9: their half-waves
     // mix up to 8 row groups with < 18 columns, at most 14 + 2r distinct slots -- they run at half LDS rate.)
+    // That every window load IS a ds_read_b128 is not a property of the pitch alone: fir_chunk has to keep the compiler
+    // from re-cutting a window whose end elements are unused (see there); tests/test_window_load_kinds.py reads the
+    // built library and fails on a ds_read2_b64 in any pass.
     int p = need;
     while (p % 32 != 2 && p % 32 != 30) ++p;
     return p;
@@ -161,6 +164,15 @@ struct Chunk {
 // The window is streamed: 16-byte pairs are loaded (ds_read_b128) in the order the taps first touch them -- the centre
 // run, then alternately from the left end inwards and from the right end inwards -- so only ~2*KC samples plus the
 // loads in flight are live at a time instead of all KC + 2R, and the LDS latency hides under the FP64 work.
+// OFF = 1 (the axis-0 pass at odd RMAX - R): the taps never touch x[0] and x[2 NP - 1], the outer halves of the window's first
+// and last pair.  Left alone, LLVM splits the double2 loads into scalars, drops the two dead ones and re-vectorises the chain
+// from p[1], which is only 8-byte aligned: every pair then straddles a 16-byte boundary and is emitted as ds_read2_b64 -- two
+// passes of 4 x 16 lanes, half the LDS rate, banks modulo 32 instead of 64 (2-way conflicted at the 62-double pitch), and in the
+// pieces an address VGPR per load, because the 8-bit read2 offsets cannot reach a piece's column.  So fir_chunk returns both
+// elements and an OFF = 1 caller names them as used (keep_window_ends), which keeps all NP pairs the aligned loads the source
+// writes.  The caller does that behind its LAST chunk, not in here: a volatile asm counts as a memory access, and between the
+// two 4-output chunks of an item it would stop the compiler from sharing the pairs both chunks read.  Both elements lie inside
+// the staged tile (row RMAX - R - 1 >= 0; the last one at most CTR - 1, since an odd RMAX - R means R <= RMAX - 1).
 // For each tap the KC adds / muls / accumulates are adjacent in program order: KC independent chains keep the FP64
 // pipe issuing (a sample-major order is one serial add->mul->add chain).
 #if defined(MST_INJECT)
@@ -170,8 +182,14 @@ struct Chunk {
 #define MST_FIR_INJ_TPARAM
 #define MST_FIR_INJ_PARAM
 #endif
+struct WindowEnds {
+    double lo, hi;                      // first and last element of the pairs a chunk loaded
+};
+// An empty statement that uses both values: no instruction is emitted.
+__device__ __forceinline__ void keep_window_ends(const WindowEnds &e) { asm volatile("" ::"v"(e.lo), "v"(e.hi)); }
+
 template <int KC, int R, int OFF, bool FMA MST_FIR_INJ_TPARAM>
-__device__ __forceinline__ void fir_chunk(const double *__restrict__ p, const double (&w)[R + 1], double (&t)[KC] MST_FIR_INJ_PARAM) {
+__device__ __forceinline__ WindowEnds fir_chunk(const double *__restrict__ p, const double (&w)[R + 1], double (&t)[KC] MST_FIR_INJ_PARAM) {
     constexpr int NP = (KC + 2 * R + OFF + 1) / 2;                       // 16-byte pairs spanned by the window
     constexpr int QC0 = (R + OFF) >> 1, QC1 = (R + KC - 1 + OFF) >> 1;   // pairs holding the centre run
     const double2 *p2 = reinterpret_cast<const double2 *>(p);
@@ -239,6 +257,7 @@ __device__ __forceinline__ void fir_chunk(const double *__restrict__ p, const do
 #endif
     }
 #undef MST_LD
+    return WindowEnds{x[0], x[2 * NP - 1]};
 }
 
 // Axis-0 pass for radius R over the (RGR rows) x (RGC + 2R columns) strip the axis-1 pass will need.  The c tile is
@@ -265,16 +284,21 @@ __device__ __forceinline__ void vpass(const double *__restrict__ ct, double *__r
         // per tile; the radius only adds a compile-time constant that folds into the ds_read offset field
         const double *p = vsrc + (T::RMAX - R) * T::CTP + (T::RMAX - R - OFF);
         double *q = vdst;
+        WindowEnds ends[K / KC];
 #pragma unroll
         for (int h = 0; h < K / KC; ++h) {
             double t[KC];
 #if defined(MST_INJECT) && (MST_INJECT == 3 || MST_INJECT == 4)
-            if (h == 0) fir_chunk<KC, R, OFF, T::FMA, MST_INJECT>(p + h * KC, w, t, &inj);
+            if (h == 0) ends[h] = fir_chunk<KC, R, OFF, T::FMA, MST_INJECT>(p + h * KC, w, t, &inj);
             else
 #endif
-            fir_chunk<KC, R, OFF, T::FMA>(p + h * KC, w, t);
+            ends[h] = fir_chunk<KC, R, OFF, T::FMA>(p + h * KC, w, t);
 #pragma unroll
             for (int k = 0; k < KC; ++k) q[(h * KC + k) * T::VP] = t[k];
+        }
+        if constexpr (OFF == 1) {
+#pragma unroll
+            for (int h = 0; h < K / KC; ++h) keep_window_ends(ends[h]);
         }
 #if defined(MST_INJECT) && MST_INJECT == 1
         inject_work<>(inj);
@@ -291,10 +315,11 @@ __device__ __forceinline__ void vpass(const double *__restrict__ ct, double *__r
             const int row0 = rgp * PR;
             const double *p = ct + ((T::RMAX - R) + col) * T::CTP + (row0 + T::RMAX - R - OFF);
             double t[PR];
-            fir_chunk<PR, R, OFF, T::FMA>(p, w, t);
+            const WindowEnds ends = fir_chunk<PR, R, OFF, T::FMA>(p, w, t);
             double *q = vb + row0 * T::VP + col;
 #pragma unroll
             for (int k = 0; k < PR; ++k) q[k * T::VP] = t[k];
+            if constexpr (OFF == 1) keep_window_ends(ends);
         }
     }
 }

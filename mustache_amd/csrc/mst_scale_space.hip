@@ -15,7 +15,11 @@
 // of HBM/L2 reads), then walks all 24 levels out of LDS:
 //   V pass  (axis 0): a thread produces 8 vertically consecutive samples of one column from a register window of
 //                     8+2r samples (c tile stored transposed -> the window is contiguous, read as ds_read_b128;
-//                     lanes run along columns with a pitch of 30 mod 32 doubles -> conflict-free), result -> LDS vb
+//                     lanes run along columns with a pitch of 30 mod 32 doubles -> the main items' loads are
+//                     conflict-free; the 4-row pieces of the halo columns are not, see pitch_for in mst_fir.h).
+//                     At odd RMAX - r the window starts on an odd row: fir_chunk then loads the aligned pairs
+//                     around it and keeps the compiler from re-cutting them into ds_read2_b64 (mst_fir.h);
+//                     result -> LDS vb
 //   H pass  (axis 1): a thread produces 8 horizontally consecutive samples of one row (same access pattern on vb),
 //                     result stays in registers
 //   DoG in registers; zero-padded 3x3 max = horizontal 3-max in registers (2 edge samples through a 4 KB LDS strip)

@@ -11,7 +11,15 @@ the default tile (Tile<32,64,14,8,1,false,false>, BAND = true) is cut into basic
 radius switch: [axis-0 main items] -> [axis-0 leftover pieces, executed by the first 16 r threads only] -> s_barrier ->
 [axis-1 pass]; the radius of a case follows from its multiplies (8 (r + 1) in the main block).  Everything else in the loop is
 common to all radii: tap fetch, dispatch, DoG, edge strip, second barrier, 3 x 3 maximum, sieve, statistics, state moves.
-Blocks of the branchy sieve form that only run when some lane passes a test are counted as executed (an upper bound)."""
+Blocks of the branchy sieve form that only run when some lane passes a test are counted as executed (an upper bound).
+
+    python scripts/isa_census.py --window-loads [library.so] > profiles/<tag>_window_loads.txt
+
+The second form reads a BUILT library (llvm-objdump, default mustache_amd/libmustache_hip.so) and prints, for every kernel that
+includes mst_fir.h -- the fused kernel at every tile and source, the difference kernel -- and per radius case and pass (axis-0
+main items, axis-0 leftover pieces, axis-1), the count of each LDS read opcode and the VALU that is not tap arithmetic.  A
+window load that is not a ds_read_b128 runs at half the LDS rate (mst_fir.h, fir_chunk); tests/test_window_load_kinds.py
+asserts through window_loads() that no pass holds a ds_read2_b64."""
 import collections
 import os
 import re
@@ -33,7 +41,7 @@ VALU = CATS[:8]
 def category(op, text):
     if "dpp" in op or " row_" in text or " wave_sh" in text or "row_bcast" in text:
         return "DPP move"
-    if op.startswith(("v_add_f64", "v_mul_f64", "v_fma_f64")):
+    if op.startswith(("v_add_f64", "v_mul_f64", "v_fma_f64", "v_fmac_f64")):
         return "fp64 add/mul"
     if op.startswith(("v_max_f64", "v_min_f64")):
         return "fp64 max/min"
@@ -101,7 +109,128 @@ def count(ins):
     return c
 
 
+# ---- window loads per radius case and pass, from a BUILT library (llvm-objdump; tests/test_window_load_kinds.py) ----------
+# Every blur kernel that includes mst_fir.h: the fused kernel (every tile, band and dense source) and the difference kernel.
+OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+LIB = os.path.join(ROOT, "mustache_amd", "libmustache_hip.so")
+BLUR_KERNEL = re.compile(r"^[0-9a-f]+ <(_ZN\S*?(scale_space_kernel|diff_dog_kernel)I\S*)>:$")
+TILE = re.compile(r"4TileILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELb([01])EEE?(.*)$")
+INSN = re.compile(r"^\s+(\S+)\s*(.*?)\s*// ([0-9A-F]+):(?: [0-9A-F]{8})+(?: <[^>+]+\+0x([0-9a-f]+)>)?\s*$")
+PASSES = ("axis-0 main", "axis-0 pieces", "axis-1")
+PIECE_ROWS = 4      # vpass: rows per leftover piece
+
+
+def kernel_title(name):
+    """'scale_space_kernel Tile<32,64,14,8,1,0,0> band' from the mangled name"""
+    m = TILE.search(name)
+    base = "scale_space_kernel" if "scale_space_kernel" in name else "diff_dog_kernel"
+    if base == "scale_space_kernel":
+        src = "band" if m.group(8).startswith("Lb1E") else "dense"
+    else:
+        src = "band" if "BandSource" in m.group(8) else "dense"
+    return "%s Tile<%s> %s source" % (base, ",".join(m.group(i) for i in range(1, 8)), src)
+
+
+def disassemble(lib=LIB):
+    """{mangled kernel name: [(address, op, text, branch target or None)]} of the blur kernels in a built library"""
+    sys.path.append(os.path.dirname(os.path.abspath(__file__)))      # kernel_resources.py lies next to this file
+    import kernel_resources
+    out = {}
+    for co in kernel_resources.code_objects(lib):
+        txt = subprocess.run([OBJDUMP, "-d", co], check=True, capture_output=True, text=True).stdout
+        cur = base = None
+        for l in txt.split("\n"):
+            if l and not l[0].isspace():
+                m = BLUR_KERNEL.match(l)
+                cur = out.setdefault(m.group(1), []) if m else None
+                base = int(l.split()[0], 16) if m else None
+                continue
+            m = INSN.match(l) if cur is not None else None
+            if m:
+                cur.append((int(m.group(3), 16), m.group(1), m.group(1) + " " + m.group(2),
+                            base + int(m.group(4), 16) if m.group(4) and m.group(1).startswith(("s_cbranch", "s_branch")) else None))
+    return out
+
+
+def disasm_blocks(ins):
+    """basic blocks [[(op, text)]] in layout order: cut behind every branch, s_barrier, s_endpgm and in front of every branch target"""
+    targets = {t for _, _, _, t in ins if t is not None}
+    out, cur = [], []
+    for addr, op, text, _ in ins:
+        if addr in targets and cur:
+            out.append(cur)
+            cur = []
+        cur.append((op, text))
+        if op.startswith(("s_cbranch", "s_branch", "s_setpc", "s_swappc", "s_endpgm")) or op == "s_barrier":
+            out.append(cur)
+            cur = []
+    if cur:
+        out.append(cur)
+    return out
+
+
+def pass_blocks(ins, K):
+    """{radius: (axis-0 main, axis-0 pieces, axis-1)}, each the block's [(op, text)].  A block that holds tap products belongs to a
+    pass; a radius case is three such blocks in a row with K (r + 1), 4 (r + 1) and K (r + 1) products (multiplies, or multiply +
+    fused multiply-adds in the FMA tiles)."""
+    taps = lambda b: sum(1 for op, _ in b if op.startswith(("v_mul_f64", "v_fma_f64", "v_fmac_f64")))
+    bl = [(b, taps(b)) for b in disasm_blocks(ins)]
+    bl = [(b, n) for b, n in bl if n]
+    cases, k = {}, 0
+    while k + 2 < len(bl):
+        n = bl[k][1]
+        r = n // K - 1
+        if n % K == 0 and r >= 1 and bl[k + 1][1] == PIECE_ROWS * (r + 1) and bl[k + 2][1] == n and r not in cases:
+            cases[r] = (bl[k][0], bl[k + 1][0], bl[k + 2][0])
+            k += 3
+        else:
+            k += 1
+    return cases
+
+
+def lds_reads(block):
+    """Counter of the LDS read opcodes of a block"""
+    return collections.Counter(op for op, _ in block if category(op, "") == "LDS read")
+
+
+def other_valu(block):
+    """VALU instructions of a pass block that are not tap arithmetic: address arithmetic and moves"""
+    c = count(block)
+    return sum(c[x] for x in VALU) - c["fp64 add/mul"]
+
+
+def window_loads(lib=LIB):
+    """[(title, RMAX, {radius: ((LDS read Counter, other VALU) per pass)})] for every blur kernel of the library"""
+    res = []
+    for name, ins in sorted(disassemble(lib).items(), key=lambda kv: kernel_title(kv[0])):
+        m = TILE.search(name)
+        cases = pass_blocks(ins, int(m.group(4)))
+        res.append((kernel_title(name), int(m.group(3)), {r: tuple((lds_reads(b), other_valu(b)) for b in ps) for r, ps in cases.items()}))
+    return res
+
+
+def window_loads_report(lib):
+    print("LDS reads and address arithmetic of the blur passes, per radius case, from %s" % os.path.relpath(lib, ROOT))
+    print("per pass: count of each LDS read opcode; VALU that is not tap arithmetic (addresses, moves)")
+    for title, rmax, cases in window_loads(lib):
+        ops = sorted({op for ps in cases.values() for c, _ in ps for op in c})
+        tot = collections.Counter()
+        print()
+        print("%s: radius cases found %d of %d" % (title, len(cases), rmax))
+        print("   r  " + "".join("| %-*s" % (11 * len(ops) + 7, p) for p in PASSES))
+        print("      " + "".join("| " + "".join("%-11s" % op[3:] for op in ops) + " VALU  " for _ in PASSES))
+        for r in sorted(cases):
+            print("  %2d  " % r + "".join("| " + "".join("%-11d" % c[op] for op in ops) + " %-6d" % v for c, v in cases[r]))
+            for c, _ in cases[r]:
+                tot.update(c)
+        print("  all passes: " + ", ".join("%d %s" % (tot[op], op) for op in ops))
+
+
 def main():
+    if "--window-loads" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--window-loads"]
+        window_loads_report(os.path.abspath(rest[0]) if rest else LIB)
+        return
     defines = [a for a in sys.argv[1:] if a.startswith("-D")]
     srcs = [a for a in sys.argv[1:] if not a.startswith("-")]         # another revision of the file (git show REV:... > /tmp/x.hip)
     bl = blocks(kernel_text(defines, srcs[0] if srcs else SRC))
