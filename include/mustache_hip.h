@@ -650,6 +650,38 @@ MST_STABLE int mst_pairs_compact(const uint32_t *dense, int32_t dense_diags, int
                                  uint32_t *out_count, int64_t cap, int64_t *n_out, void *workspace, uint64_t workspace_bytes,
                                  void *stream);
 
+/* ---- trans read pairs -> per-pair pixels, every chromosome pair of the genome in one pass (rules: mustache_amd/pairs.py;
+ * tests/pairs_trans_reference.py restates them).  Added without a change of MST_ABI_REVISION, as mst_pairs_bin was. */
+/* The rows (posA, posB: dev int32 [n_rows]) are pair-major: pair p owns rows [seg_off[p], seg_off[p + 1]) (seg_off: dev int64
+ * [n_pairs + 1], seg_off[0] = 0, seg_off[n_pairs] = n_rows), posA on the pair's first chromosome and posB on its second.  Per
+ * pair (dev int64 [n_pairs] each): limA / limB the chromosomes' lengths in bp (2^31 when there is none), nA / nB their bin
+ * counts, cell_off the running sum of nA * nB over the pairs before it.  A row is dropped when its position on a side is < 1
+ * or > that side's limit (zero_based != 0: < 0 or >= the limit), or when a bin is >= its n; otherwise x = (posA - 1) / res,
+ * y = (posB - 1) / res (zero_based: pos / res) and its key is cell_off[p] + x * nB[p] + y -- no min / max: the pair is oriented.
+ * A key < dense_cells adds to dense[key] (dev uint32 [dense_cells], ACCUMULATED: the caller zeroes it); any other key appends
+ * (far_key, far_mult) to the far list (dev int64 / uint32 [far_cap]), one entry per run of adjacent rows of a wave that share
+ * the key, in no fixed order.  *n_far (dev uint64, ACCUMULATED, zeroed by the caller): the far entries; *n_far > far_cap means
+ * entries were lost (nothing is written past far_cap): far_cap = n_rows always suffices.  dropped (dev uint64 [n_pairs],
+ * ACCUMULATED, zeroed by the caller): the dropped rows of each pair.  dense_cells = 0 is legal (dense may be NULL), and so is any
+ * other value, one inside a pair included.  n_rows = 0 or n_pairs = 0 launches nothing.  All sums are integer sums: the results
+ * do not depend on the order of the rows within their pairs. */
+MST_STABLE int mst_pairs_bin_trans(const int32_t *posA, const int32_t *posB, int64_t n_rows, const int64_t *seg_off, int32_t n_pairs,
+                                   const int64_t *limA, const int64_t *limB, const int64_t *nA, const int64_t *nB,
+                                   const int64_t *cell_off, int32_t res, int32_t zero_based, int64_t dense_cells, uint32_t *dense,
+                                   int64_t *far_key, uint32_t *far_mult, int64_t far_cap, uint64_t *n_far, uint64_t *dropped,
+                                   void *stream);
+/* The non-zero counters of dense [dense_cells] -> (out_key: dev int64 [cap] = the counter's index, out_count: dev uint32 [cap])
+ * in ascending key order; *n_out (dev int64) = their number, which may exceed cap: nothing is written past cap.  Two passes and
+ * a scan, no atomics.  workspace: dev, mst_pairs_trans_compact_workspace_bytes(dense_cells) bytes. */
+MST_STABLE uint64_t mst_pairs_trans_compact_workspace_bytes(int64_t dense_cells);
+MST_STABLE int mst_pairs_trans_compact(const uint32_t *dense, int64_t dense_cells, int64_t *out_key, uint32_t *out_count, int64_t cap,
+                                       int64_t *n_out, void *workspace, uint64_t workspace_bytes, void *stream);
+/* keys (dev int64 [n], each within the cells of a pair) and counts (dev int64 [n]) -> out_x, out_y (dev int32 [n]) and out_v
+ * (dev float64 [n]): the pair p is the last one with cell_off[p] <= key, x = (key - cell_off[p]) / nB[p], y = the remainder,
+ * v = the count, carried to float64 without passing through float32. */
+MST_STABLE int mst_pairs_trans_decode(const int64_t *keys, const int64_t *counts, int64_t n, const int64_t *cell_off, const int64_t *nB,
+                                      int32_t n_pairs, int32_t *out_x, int32_t *out_y, double *out_v, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

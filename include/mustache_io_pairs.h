@@ -51,6 +51,29 @@ int64_t mst_pairs_rows(const mst_pairs *h, int32_t index, const int32_t **pos1, 
  * chromosome.  rows read = the sum of the other four. */
 int mst_pairs_counters(const mst_pairs *h, int64_t counters[5]);
 
+/* ---- trans rows, on request (inter-chromosomal calls from a pairs file: --pairs-trans) -------------------------------------
+ * mst_pairs_open_ex is mst_pairs_open_chunked with keep_trans.  keep_trans == 0: exactly mst_pairs_open_chunked -- no trans
+ * row is stored.  keep_trans != 0: a trans row whose two chromosomes are both in the `#chromsize` table is stored as well,
+ * 8 bytes of host memory per such row.  For the pair (a, b) of table indices a < b the position on a goes into the first array
+ * and the position on b into the second, whichever way round the row named them; rows keep file order within their pair for
+ * any n_threads and chunk_bytes; a position that does not fit int32 is stored as INT32_MIN.  Every counter, array and entry
+ * point above keeps its meaning.  A file without `#chromsize` lines fails the open with MST_IO_E_FORMAT and a message that
+ * names `#chromsize`: the pairs are those of the table, and the genome layout needs the lengths. */
+int mst_pairs_open_ex(const char *path, int32_t zero_based, int32_t n_threads, int64_t chunk_bytes, int32_t keep_trans,
+                      mst_pairs **out);
+
+/* The stored trans rows of the whole file, in one pair of int32 arrays in pair-major order: (0,1), (0,2), ..., (1,2), ... --
+ * every pair of the table, empty ones included.  *n_pairs = P = C (C - 1) / 2; *seg_off: int64 [P + 1], pair p's rows are
+ * [seg_off[p], seg_off[p + 1]); *posA / *posB: int32 [seg_off[P]] (NULL when there is no row); *out_of_range: int64 [P], how
+ * many of the pair's rows are out of range -- the position on a outside a's range or the position on b outside b's, by the
+ * rule of the cis rows.  All borrowed, valid until close.  MST_IO_E_ARG on a handle opened without keep_trans. */
+int mst_pairs_trans_rows(const mst_pairs *h, int64_t *n_pairs, const int64_t **seg_off, const int32_t **posA, const int32_t **posB,
+                         const int64_t **out_of_range);
+
+/* counters[0 .. 2]: trans rows stored; how many of those are out of range; trans rows naming a chromosome the table lacks (not
+ * stored).  [0] + [2] = counters[2] of mst_pairs_counters.  MST_IO_E_ARG on a handle opened without keep_trans. */
+int mst_pairs_trans_counters(const mst_pairs *h, int64_t counters[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,10 @@ _SIGNATURES = {
     "mst_pairs_bin": (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i64, _i64, _i32, _p, _p, _p, _i64, _p, _p]),
     "mst_pairs_compact_workspace_bytes": (_u64, [_i32, _i64]),
     "mst_pairs_compact": (ctypes.c_int, [_p, _i32, _i64, _p, _p, _p, _i64, _p, _p, _u64, _p]),
+    "mst_pairs_bin_trans": (ctypes.c_int, [_p, _p, _i64, _p, _i32, _p, _p, _p, _p, _p, _i32, _i32, _i64, _p, _p, _p, _i64, _p, _p, _p]),
+    "mst_pairs_trans_compact_workspace_bytes": (_u64, [_i64]),
+    "mst_pairs_trans_compact": (ctypes.c_int, [_p, _i64, _p, _p, _i64, _p, _p, _u64, _p]),
+    "mst_pairs_trans_decode": (ctypes.c_int, [_p, _p, _i64, _p, _p, _i32, _p, _p, _p, _p]),
 }
 
 _lib = None

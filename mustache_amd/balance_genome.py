@@ -1,5 +1,5 @@
 """Balancing of the WHOLE GENOME's contact matrix on the GPU, for inter-chromosomal (trans) calling on `.hic` files that carry no
-usable normalisation vector: `--balance-genome ICE|NEWTON` (with `--balance-pixels all|inter`) on the command lines,
+usable normalisation vector, and on `.pairs` / `.pairs.gz` files, which carry none at all (`--pairs-trans`): `--balance-genome ICE|NEWTON` (with `--balance-pixels all|inter`) on the command lines,
 genome_bias() / balanced_pair() / balanced_pairs() in Python.  `--balance` balances one chromosome's own map and so says nothing
 about a trans pair; the bias a trans pair needs has seen the trans pixels (what Juicer's GW_* / INTER_* vectors are).
 
@@ -31,6 +31,15 @@ what the records read so far will need (estimate_bytes) against torch.cuda.mem_g
 (BalanceCSR's sort makes the result independent of the record order, so the bias has the same bits whichever way round a pair
 is stored and whichever `.hic` version holds it); the application is one launch of mst_balance_apply_pairs
 (csrc/mst_balance.hip) for any number of pairs.
+
+A pairs file is the second source of the same assembly (mustache_amd/pairs.py states its rules).  The chromosomes and their
+lengths are the `#chromsize` table's, in table order; the file is parsed once with its trans rows kept (8 bytes of host memory
+each).  The trans rows of the whole genome are uploaded and binned in one pass (pairs.bin_trans_device, csrc/mst_pairs_trans.hip)
+into the same resident (x, y, v) records a `.hic` pair gives; under `all` each chromosome's cis rows are binned by
+pairs.bin_pairs_device with every diagonal and lose their pixels below IGNORE_DIAGS; under `inter` no cis row is uploaded.
+Unlike a `.hic` matrix the rows' count is known before the upload, so the memory check comes first: pairs_upload_bytes against
+torch.cuda.mem_get_info.  Integer counts reach float64 unrounded, so a pairs file and a `.hic` file of the same contacts give
+the same bias to the bit.
 """
 import numpy as np
 
@@ -64,11 +73,12 @@ def genome_layout(lengths, res):
     return bins, offsets, int(sum(bins))
 
 
-def check_genome_request(method, pixels, files, bias, norm_method, balance, world, trans):
+def check_genome_request(method, pixels, files, bias, norm_method, balance, world, trans, pairs_trans=False):
     """Raise BalanceError with the text of the `Error:` line when `--balance-genome method --balance-pixels pixels` cannot be
     honoured; return (method in upper case, pixels).  files: the input path(s); bias: a -b / -b1 / -b2 file or None; balance:
     what --balance was given; world: the ranks of the run; trans: "all" when every pair of the run is inter-chromosomal,
-    "some" when only some are, "none" when none is (True / False: "all" / "none")."""
+    "some" when only some are, "none" when none is (True / False: "all" / "none"); pairs_trans: --pairs-trans, with which a
+    `.pairs` / `.pairs.gz` file is an input like a `.hic` file (its trans rows are kept and binned: mustache_amd/pairs.py)."""
     trans = {True: "all", False: "none"}.get(trans, trans)
     if balance is not None and trans != "none":
         raise BalanceError("--balance does not apply to inter-chromosomal pairs")
@@ -84,7 +94,8 @@ def check_genome_request(method, pixels, files, bias, norm_method, balance, worl
     if trans != "all":
         raise BalanceError("--balance-genome is for inter-chromosomal calls; use --balance")
     files = [files] if isinstance(files, str) else list(files or [])
-    if not all(str(p).endswith((".hic", ".cool", ".mcool")) for p in files):
+    from .pairs import is_pairs
+    if not all(str(p).endswith((".hic", ".cool", ".mcool")) or (pairs_trans and is_pairs(p)) for p in files):
         raise BalanceError("Interchromosomal analysis is only supported for .hic and .cool input formats.")
     if bias:
         raise BalanceError("--balance-genome %s and a bias file (-b / -b1 / -b2): give either a bias file or --balance-genome, "
@@ -115,6 +126,9 @@ def add_arguments(parser):
                              "genome's raw matrix on the GPU and call from the balanced records, instead of -norm")
     parser.add_argument("--balance-pixels", dest="balance_pixels", default="all", metavar="all|inter", action=_Given,
                         help="OPTIONAL: the pixels --balance-genome balances on: all (cis and trans, default) or inter (trans only)")
+    parser.add_argument("--pairs-trans", dest="pairs_trans", action="store_true",
+                        help="OPTIONAL: .pairs / .pairs.gz input only: keep the file's inter-chromosomal rows (8 bytes of host "
+                             "memory each) so that -ch A -ch2 B and --trans-all run from it; needs --balance-genome")
     parser.set_defaults(balance_pixels_given=False)
 
 
@@ -125,7 +139,8 @@ def request_of(args, files, bias, world, pairs):
         return None
     n_trans = sum(1 for a, b in pairs if a != b)
     trans = "none" if n_trans == 0 else ("all" if n_trans == len(pairs) else "some")
-    return check_genome_request(args.balance_genome, args.balance_pixels, files, bias, args.norm_method, args.balance, world, trans)
+    return check_genome_request(args.balance_genome, args.balance_pixels, files, bias, args.norm_method, args.balance, world, trans,
+                                pairs_trans=getattr(args, "pairs_trans", False))
 
 
 class GenomeBias:
@@ -193,42 +208,152 @@ def _check_memory(records, resident):
                            "%d resident ones, %d bytes are free" % (records, need, resident, free))
 
 
-def genome_bias(f, res, method="NEWTON", pixels="all", device=None, keep_records=True, **solver_args):
-    """Balance the whole genome of the `.hic` file f at resolution res -> GenomeBias.  Every matrix is read once; the trans
-    pairs' raw records stay on the device when keep_records.  Raises BalanceError for an unknown method or pixels value and
-    when the records do not fit the device's free memory."""
+def _hic_source(f, res, dev, pixels, verbose):
+    """The `.hic` source of genome_bias: (names, lengths, cis, trans).  cis() yields (c, x, d, v) int64 / float64 device tensors
+    of chromosome c's raw matrix through hicfile.read_intra_packed; trans() yields ((i, j), (x, y, v)) through
+    trans.read_hic_trans.  Every matrix is read once."""
     import torch
     from . import readers
-    from .balance import solve
     from .hicfile import HicError, read_intra_packed
-    from ._lib import require_gpu
     from .trans import read_hic_trans
-    method, pixels = check_genome_request(method, pixels, [f], None, None, None, 1, True)
-    require_gpu()
-    res = int(res)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     names = list(readers.list_chromosomes(f, res))
     with readers._HIC_LOCK:
         lengths_of = dict(readers._hic_handle(f).chromosomes())
-    bins, offsets, n = genome_layout([lengths_of[c] for c in names], res)
-    los, his, vs = [], [], []
-    records, total, resident = {}, 0, 0
-    with torch.cuda.device(dev):
-        if pixels == "all":
-            for c, name in enumerate(names):
-                with readers._HIC_LOCK:
-                    try:
-                        pc = read_intra_packed(readers._hic_handle(f), name, res, "NONE", -1, int(lengths_of[name]))
-                    except HicError as e:
-                        if not _no_matrix(e):
-                            raise
-                        continue
-                if len(pc) == 0:
+
+    def cis():
+        for c, name in enumerate(names):
+            with readers._HIC_LOCK:
+                try:
+                    pc = read_intra_packed(readers._hic_handle(f), name, res, "NONE", -1, int(lengths_of[name]))
+                except HicError as e:
+                    if not _no_matrix(e):
+                        raise
                     continue
-                x = torch.from_numpy(pc.x[:pc.count]).to(dev).to(torch.int64)
-                d = torch.from_numpy(pc.dist[:pc.count]).to(dev).to(torch.int64)
-                v = torch.from_numpy(pc.v[:pc.count]).to(dev).to(torch.float64)
-                del pc
+            if len(pc) == 0:
+                continue
+            x = torch.from_numpy(pc.x[:pc.count]).to(dev).to(torch.int64)
+            d = torch.from_numpy(pc.dist[:pc.count]).to(dev).to(torch.int64)
+            v = torch.from_numpy(pc.v[:pc.count]).to(dev).to(torch.float64)
+            del pc
+            yield c, x, d, v
+
+    def trans():
+        for i in range(len(names)):
+            for j in range(i + 1, len(names)):
+                try:
+                    rec = read_hic_trans(f, "NONE", names[i], names[j], res, device=dev)
+                except HicError as e:
+                    if not _no_matrix(e):
+                        raise
+                    continue
+                yield (i, j), rec
+
+    return names, [lengths_of[c] for c in names], cis, trans
+
+
+def pairs_upload_bytes(rows, cells, budget):
+    """Device bytes the binning of `rows` stored trans rows asks for before a record exists: the rows (8 bytes each), the far
+    list (12 bytes each: one entry per row always suffices) and the counter array (4 bytes per cell of the genome's trans
+    matrices when that fits `budget`, pairs.dense_budget(); none otherwise)"""
+    return int(rows) * (8 + 12) + (4 * int(cells) if 4 * int(cells) <= int(budget) else 0)
+
+
+def pairs_open(f, zero_based):
+    """the parsed pairs file with its trans rows (the cached handle; the one parse of a run); a file the reader refuses -- one
+    without `#chromsize` lines above all -- is a BalanceError with the reader's text.  Touches no GPU."""
+    from . import pairs as pr
+    from .hicfile import HicError
+    with pr._LOCK:
+        try:
+            return pr.pairs_handle(f, zero_based, keep_trans=True)
+        except HicError as e:
+            raise BalanceError(str(e))
+
+
+def _pairs_source(h, f, res, dev, pixels, verbose, zero_based):
+    """The pairs source of genome_bias (mustache_amd/pairs.py): chromosomes and lengths are the `#chromsize` table's, in table
+    order; cis() bins each chromosome's cis rows (pairs.bin_pairs_device, every diagonal); trans() bins the stored trans rows of
+    the whole file in one pass (pairs.bin_trans_device).  The file is parsed once, with its trans rows kept."""
+    import os
+    import torch
+    from . import pairs as pr
+    with pr._LOCK:
+        table = h.chromosomes()
+        totals, tcount = h.counters(), h.trans_counters()
+    names, lengths = [n for n, _ in table], [length for _, length in table]
+    bins = genome_layout(lengths, res)[0]
+    stats = {}
+
+    def check_upload(rows):
+        need = pairs_upload_bytes(rows, pr.trans_tables(lengths, bins)[1], pr.dense_budget(dev))
+        free = int(torch.cuda.mem_get_info()[0])
+        if need > free:
+            raise BalanceError("--balance-genome: binning the %d trans rows of %s needs about %d bytes of device memory, "
+                               "%d bytes are free" % (rows, os.path.basename(str(f)), need, free))
+
+    check_upload(tcount["stored"])           # known since the parse: a run that cannot hold them ends before any upload
+
+    def cis():
+        for c, name in enumerate(names):
+            with pr._LOCK:
+                p1, p2, out_of_range = h.rows(c)
+                if len(p1) == 0:
+                    continue
+                d1, d2 = torch.from_numpy(p1).to(dev), torch.from_numpy(p2).to(dev)
+            px = pr.bin_pairs_device(d1, d2, res, zero_based=zero_based, length=lengths[c], distance_bins=None, device=dev)
+            del d1, d2
+            if px.dropped != out_of_range:
+                raise RuntimeError("pairs: the device dropped %d rows of %s as out of range, the host reader counted %d"
+                                   % (px.dropped, name, out_of_range))
+            if len(px):
+                yield c, px.x.to(torch.int64), px.dist.to(torch.int64), px.count.to(torch.float64)
+
+    def trans():
+        with pr._LOCK:
+            pa, pb, seg_off, out_of_range = h.trans_rows()
+            check_upload(len(pa))
+            da, db = torch.from_numpy(pa).to(dev), torch.from_numpy(pb).to(dev)
+        got = pr.bin_trans_device(da, db, seg_off, lengths, res, zero_based=zero_based, bins=bins, out_of_range=out_of_range,
+                                  device=dev, names=names, stats=stats)
+        del da, db
+        if verbose:
+            print("pairs %s: %d rows read, %d trans rows (%d stored, %d naming a chromosome the table lacks, %d out of range), "
+                  "%d trans pixels, %d pairs with records"
+                  % (os.path.basename(str(f)), totals["rows"], totals["trans"], tcount["stored"], tcount["unknown"],
+                     tcount["out_of_range"], stats["pixels"], stats["pairs"]))
+        for key in sorted(got):
+            yield key, got.pop(key)
+
+    return names, lengths, cis, trans
+
+
+def genome_bias(f, res, method="NEWTON", pixels="all", device=None, keep_records=True, pairs_zero_based=False, verbose=False,
+                **solver_args):
+    """Balance the whole genome of f at resolution res -> GenomeBias.  f is a `.hic` file, or a `.pairs` / `.pairs.gz` file with
+    `#chromsize` lines (pairs_zero_based: its position convention).  Every matrix is read once -- a pairs file is parsed once
+    and its rows are binned on the device; the trans pairs' raw records stay on the device when keep_records.  Both sources
+    feed one assembly: per-chromosome cis pixels (`all` only), per-pair trans records, then solve(..., ignore_diags=0).
+    Raises BalanceError for an unknown method or pixels value and when the records do not fit the device's free memory."""
+    import torch
+    from . import pairs as pairs_mod
+    from .balance import solve
+    from ._lib import require_gpu
+    from_pairs = pairs_mod.is_pairs(f)
+    method, pixels = check_genome_request(method, pixels, [f], None, None, None, 1, True, pairs_trans=from_pairs)
+    handle = pairs_open(f, pairs_zero_based) if from_pairs else None
+    require_gpu()
+    res = int(res)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    with torch.cuda.device(dev):
+        if from_pairs:
+            names, lengths, cis, trans = _pairs_source(handle, f, res, dev, pixels, verbose, pairs_zero_based)
+        else:
+            names, lengths, cis, trans = _hic_source(f, res, dev, pixels, verbose)
+        bins, offsets, n = genome_layout(lengths, res)
+        los, his, vs = [], [], []
+        records, total, resident = {}, 0, 0
+        if pixels == "all":
+            for c, x, d, v in cis():
                 keep = (d >= IGNORE_DIAGS) & (x >= 0) & (x + d < bins[c])
                 x, d, v = x[keep], d[keep], v[keep]
                 los.append(x + offsets[c])
@@ -236,25 +361,18 @@ def genome_bias(f, res, method="NEWTON", pixels="all", device=None, keep_records
                 vs.append(v)
                 total += int(v.numel())
                 _check_memory(total, resident)
-        for i in range(len(names)):
-            for j in range(i + 1, len(names)):
-                try:
-                    x, y, v = read_hic_trans(f, "NONE", names[i], names[j], res, device=dev)
-                except HicError as e:
-                    if not _no_matrix(e):
-                        raise
-                    continue
-                if v.numel() == 0:
-                    continue
-                if keep_records:
-                    records[(i, j)] = (x, y, v)
-                    resident += RESIDENT_BYTES * int(v.numel())
-                inside = (x >= 0) & (x < bins[i]) & (y >= 0) & (y < bins[j])
-                los.append(x[inside].to(torch.int64) + offsets[i])
-                his.append(y[inside].to(torch.int64) + offsets[j])
-                vs.append(v[inside])
-                total += int(vs[-1].numel())
-                _check_memory(total, resident)
+        for (i, j), (x, y, v) in trans():
+            if v.numel() == 0:
+                continue
+            if keep_records:
+                records[(i, j)] = (x, y, v)
+                resident += RESIDENT_BYTES * int(v.numel())
+            inside = (x >= 0) & (x < bins[i]) & (y >= 0) & (y < bins[j])
+            los.append(x[inside].to(torch.int64) + offsets[i])
+            his.append(y[inside].to(torch.int64) + offsets[j])
+            vs.append(v[inside])
+            total += int(vs[-1].numel())
+            _check_memory(total, resident)
         if vs:
             lo, hi, v = torch.cat(los), torch.cat(his), torch.cat(vs)
         else:

@@ -3,7 +3,9 @@
 // One pass over the file.  A plain file is memory-mapped and cut into byte ranges at line ends; a `.gz` file is inflated by one
 // producer thread (gzread: concatenated members, so bgzf too) that cuts its buffer at line ends.  Either way the chunks are
 // parsed by a pool of threads into per-chunk, per-chromosome position vectors, which are then laid end to end in chunk order:
-// rows keep file order within a chromosome whatever the thread count and the chunk size are.
+// rows keep file order within a chromosome whatever the thread count and the chunk size are.  With keep_trans the trans rows
+// whose two chromosomes are in the table are kept as well: per chunk as (pair, position on a, position on b) triples, laid in
+// pair-major order, chunk after chunk, by the same merge.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -88,7 +90,9 @@ struct ChunkOut {
     Table local;                                 // the names of this chunk in order of first appearance (header-less files)
     std::vector<std::vector<int32_t>> p1, p2;    // per chromosome id (global when the table is fixed, local otherwise)
     std::vector<int64_t> out_of_range;
-    int64_t rows = 0, trans = 0, unknown = 0;
+    std::vector<int64_t> tp;                     // keep_trans: the pair index of each stored trans row, file order
+    std::vector<int32_t> ta, tb;                 // its position on the pair's first / second chromosome (table order)
+    int64_t rows = 0, trans = 0, unknown = 0, trans_unknown = 0;
     bool bad = false;
     int64_t bad_line = 0;                        // 0-based, counted from the chunk's first line
     std::string what;
@@ -100,7 +104,17 @@ struct Job {
     int64_t first_line = 0;                      // 1-based number of the chunk's first line
 };
 
-void parse_chunk(const char *p, const char *end, const Columns &col, const Table &table, bool zero_based, ChunkOut &out) {
+// the index of the pair (a, b), a < b, of a table of C chromosomes in pair-major order: (0,1), (0,2), ..., (1,2), ...
+inline int64_t pair_index(int64_t a, int64_t b, int64_t C) { return a * (2 * C - a - 1) / 2 + (b - a - 1); }
+
+inline bool out_of_range(int32_t pos, int64_t len, bool zero_based) {
+    if (pos < (zero_based ? 0 : 1)) return true;
+    return len >= 0 && (zero_based ? pos >= len : pos > len);
+}
+
+void parse_chunk(const char *p, const char *end, const Columns &col, const Table &table, bool zero_based, bool keep_trans,
+                 ChunkOut &out) {
+    const int64_t C = (int64_t)table.names.size();
     const int want = col.last() + 1;
     std::vector<const char *> f0(want), f1(want);
     if (table.fixed) {
@@ -164,6 +178,15 @@ void parse_chunk(const char *p, const char *end, const Columns &col, const Table
             if (!table.fixed) {                  // both names still take their place in the order of first appearance
                 lookup(f0[col.chr1], f1[col.chr1]);
                 lookup(f0[col.chr2], f1[col.chr2]);
+            } else if (keep_trans) {             // oriented by the table: the lower index is the pair's first chromosome
+                const int i1 = lookup(f0[col.chr1], f1[col.chr1]), i2 = lookup(f0[col.chr2], f1[col.chr2]);
+                if (i1 < 0 || i2 < 0 || i1 == i2) {          // (two spellings of one table entry cannot happen: exact compare)
+                    ++out.trans_unknown;
+                } else {
+                    out.tp.push_back(i1 < i2 ? pair_index(i1, i2, C) : pair_index(i2, i1, C));
+                    out.ta.push_back(i1 < i2 ? a : b);
+                    out.tb.push_back(i1 < i2 ? b : a);
+                }
             }
             continue;
         }
@@ -239,13 +262,61 @@ struct mst_pairs {
     std::vector<int32_t *> p1, p2;
     std::vector<int64_t> rows, out_of_range;
     int64_t counters[5] = {0, 0, 0, 0, 0};
+    bool keep_trans = false;
+    bool zero_based = false;
+    std::vector<int64_t> seg_off, trans_oor;     // keep_trans: [P + 1] and [P], P = C (C - 1) / 2
+    int32_t *ta = nullptr, *tb = nullptr;        // the stored trans rows, pair-major
+    int64_t trans_counters[3] = {0, 0, 0};       // stored; of those out of range; naming a chromosome the table lacks
     ~mst_pairs() {
         for (int32_t *p : p1) free(p);
         for (int32_t *p : p2) free(p);
+        free(ta);
+        free(tb);
     }
 };
 
 namespace {
+
+// keep_trans: a counting sort of the chunks' trans rows by pair, chunk after chunk -- file order within a pair
+bool merge_trans(std::deque<ChunkOut> &parts, mst_pairs &h) {
+    const int64_t C = (int64_t)h.table.names.size(), P = C * (C - 1) / 2;
+    h.seg_off.assign((size_t)P + 1, 0);
+    h.trans_oor.assign((size_t)P, 0);
+    for (const ChunkOut &part : parts) {
+        h.trans_counters[2] += part.trans_unknown;
+        for (int64_t p : part.tp) ++h.seg_off[(size_t)p + 1];
+    }
+    for (int64_t p = 0; p < P; ++p) h.seg_off[(size_t)p + 1] += h.seg_off[(size_t)p];
+    const int64_t total = h.seg_off[(size_t)P];
+    h.trans_counters[0] = total;
+    if (total) {
+        h.ta = (int32_t *)malloc((size_t)total * sizeof(int32_t));
+        h.tb = (int32_t *)malloc((size_t)total * sizeof(int32_t));
+        if (!h.ta || !h.tb) return false;
+    }
+    std::vector<int32_t> first((size_t)P), second((size_t)P);     // pair -> its two chromosomes
+    for (int64_t a = 0, p = 0; a < C; ++a)
+        for (int64_t b = a + 1; b < C; ++b, ++p) {
+            first[(size_t)p] = (int32_t)a;
+            second[(size_t)p] = (int32_t)b;
+        }
+    std::vector<int64_t> fill(h.seg_off.begin(), h.seg_off.end() - 1);
+    for (ChunkOut &part : parts) {
+        for (size_t k = 0; k < part.tp.size(); ++k) {
+            const size_t p = (size_t)part.tp[k];
+            const int32_t a = part.ta[k], b = part.tb[k];
+            h.ta[fill[p]] = a;
+            h.tb[fill[p]++] = b;
+            h.trans_oor[p] += out_of_range(a, h.table.length[(size_t)first[p]], h.zero_based) ||
+                              out_of_range(b, h.table.length[(size_t)second[p]], h.zero_based);
+        }
+        std::vector<int64_t>().swap(part.tp);
+        std::vector<int32_t>().swap(part.ta);
+        std::vector<int32_t>().swap(part.tb);
+    }
+    for (int64_t v : h.trans_oor) h.trans_counters[1] += v;
+    return true;
+}
 
 // lay the chunks' vectors end to end, in chunk order
 bool merge(std::deque<ChunkOut> &parts, mst_pairs &h) {
@@ -291,7 +362,7 @@ bool merge(std::deque<ChunkOut> &parts, mst_pairs &h) {
         std::vector<std::vector<int32_t>>().swap(parts[c].p1);
         std::vector<std::vector<int32_t>>().swap(parts[c].p2);
     }
-    return true;
+    return !h.keep_trans || merge_trans(parts, h);
 }
 
 int64_t count_lines(const char *p, const char *end) {
@@ -311,6 +382,11 @@ int report_bad(const char *path, std::deque<ChunkOut> &parts, const std::vector<
             return mst_io::fail(MST_IO_E_FORMAT, "%s: line %lld: %s", path, (long long)(first_line[c] + parts[c].bad_line),
                                 parts[c].what.c_str());
     return MST_IO_OK;
+}
+
+int no_table(const char *path) {
+    return mst_io::fail(MST_IO_E_FORMAT, "%s has no #chromsize lines: trans rows are kept by the table's chromosome pairs, and the "
+                                         "genome layout needs the lengths", path);
 }
 
 int open_plain(const char *path, bool zero_based, int nt, size_t chunk_bytes, mst_pairs &h) {
@@ -338,6 +414,8 @@ int open_plain(const char *path, bool zero_based, int nt, size_t chunk_bytes, ms
         const char *data = read_header(base, end, true, h.table, col, &header_lines, &why, &bad);
         if (bad) {
             rc = mst_io::fail(MST_IO_E_FORMAT, "%s: line %lld: %s", path, (long long)(header_lines + 1), why.c_str());
+        } else if (h.keep_trans && !h.table.fixed) {
+            rc = no_table(path);
         } else {
             const size_t left = (size_t)(end - data);
             size_t nchunks = left / chunk_bytes + 1;
@@ -359,7 +437,7 @@ int open_plain(const char *path, bool zero_based, int nt, size_t chunk_bytes, ms
                     const size_t i = next.fetch_add(1);
                     if (i >= nchunks || stop.load()) return;
                     try {
-                        parse_chunk(cut[i], cut[i + 1], col, h.table, zero_based, parts[i]);
+                        parse_chunk(cut[i], cut[i + 1], col, h.table, zero_based, h.keep_trans, parts[i]);
                         if (parts[i].bad) stop.store(1);
                     } catch (...) {
                         stop.store(2);
@@ -419,7 +497,7 @@ int open_gz(const char *path, bool zero_based, int nt, size_t chunk_bytes, mst_p
             }
             if (stop.load()) continue;           // drain: the producer may be waiting for room
             try {
-                parse_chunk(item.second->p, item.second->end, col, h.table, zero_based, *out);
+                parse_chunk(item.second->p, item.second->end, col, h.table, zero_based, h.keep_trans, *out);
                 if (out->bad) stop.store(1);
             } catch (...) {
                 stop.store(2);
@@ -481,6 +559,10 @@ int open_gz(const char *path, bool zero_based, int nt, size_t chunk_bytes, mst_p
                     col = Columns();
                     continue;
                 }
+                if (h.keep_trans && !h.table.fixed) {
+                    rc = no_table(path);
+                    break;
+                }
                 line += lines;
                 start = (size_t)(data - buf.data());
                 in_header = false;
@@ -526,7 +608,8 @@ bool ends_with(const char *s, const char *tail) {
 
 }  // namespace
 
-extern "C" int mst_pairs_open_chunked(const char *path, int32_t zero_based, int32_t n_threads, int64_t chunk_bytes, mst_pairs **out) {
+extern "C" int mst_pairs_open_ex(const char *path, int32_t zero_based, int32_t n_threads, int64_t chunk_bytes, int32_t keep_trans,
+                                 mst_pairs **out) {
     if (!path || !out) return mst_io::fail(MST_IO_E_ARG, "mst_pairs_open: bad argument");
     *out = nullptr;
     int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
@@ -535,6 +618,8 @@ extern "C" int mst_pairs_open_chunked(const char *path, int32_t zero_based, int3
     const size_t chunk = chunk_bytes > 0 ? (size_t)chunk_bytes : (size_t)4 << 20;
     try {
         std::unique_ptr<mst_pairs> h(new mst_pairs());
+        h->keep_trans = keep_trans != 0;
+        h->zero_based = zero_based != 0;
         const int rc = ends_with(path, ".gz") ? open_gz(path, zero_based != 0, nt, chunk, *h) : open_plain(path, zero_based != 0, nt, chunk, *h);
         if (rc != MST_IO_OK) return rc;
         if (h->rows.size() < h->table.names.size()) {           // an empty file body: no chunk was merged
@@ -544,11 +629,23 @@ extern "C" int mst_pairs_open_chunked(const char *path, int32_t zero_based, int3
             h->p1.resize(nc, nullptr);
             h->p2.resize(nc, nullptr);
         }
+        if (h->keep_trans) {
+            if (!h->table.fixed) return no_table(path);         // an empty file
+            const size_t C = h->table.names.size(), P = C * (C - 1) / 2;
+            if (h->seg_off.size() != P + 1) {                   // an empty file body
+                h->seg_off.assign(P + 1, 0);
+                h->trans_oor.assign(P, 0);
+            }
+        }
         *out = h.release();
         return MST_IO_OK;
     } catch (...) {
         return mst_io::fail(MST_IO_E_FILE, "out of memory while reading %s", path);
     }
+}
+
+extern "C" int mst_pairs_open_chunked(const char *path, int32_t zero_based, int32_t n_threads, int64_t chunk_bytes, mst_pairs **out) {
+    return mst_pairs_open_ex(path, zero_based, n_threads, chunk_bytes, 0, out);
 }
 
 extern "C" int mst_pairs_open(const char *path, int32_t zero_based, int32_t n_threads, mst_pairs **out) {
@@ -579,5 +676,23 @@ extern "C" int64_t mst_pairs_rows(const mst_pairs *h, int32_t index, const int32
 extern "C" int mst_pairs_counters(const mst_pairs *h, int64_t counters[5]) {
     if (!h || !counters) return mst_io::fail(MST_IO_E_ARG, "mst_pairs_counters: bad argument");
     memcpy(counters, h->counters, sizeof(h->counters));
+    return MST_IO_OK;
+}
+
+extern "C" int mst_pairs_trans_rows(const mst_pairs *h, int64_t *n_pairs, const int64_t **seg_off, const int32_t **posA,
+                                    const int32_t **posB, const int64_t **out_of_range) {
+    if (!h || !h->keep_trans) return mst_io::fail(MST_IO_E_ARG, "mst_pairs_trans_rows: the handle was opened without keep_trans");
+    if (n_pairs) *n_pairs = (int64_t)h->trans_oor.size();
+    if (seg_off) *seg_off = h->seg_off.data();
+    if (posA) *posA = h->ta;
+    if (posB) *posB = h->tb;
+    if (out_of_range) *out_of_range = h->trans_oor.data();
+    return MST_IO_OK;
+}
+
+extern "C" int mst_pairs_trans_counters(const mst_pairs *h, int64_t counters[3]) {
+    if (!h || !counters || !h->keep_trans)
+        return mst_io::fail(MST_IO_E_ARG, "mst_pairs_trans_counters: the handle was opened without keep_trans");
+    memcpy(counters, h->trans_counters, sizeof(h->trans_counters));
     return MST_IO_OK;
 }

@@ -393,27 +393,27 @@ def print_found(counts, chromosome, chromosome2, pt, pt2, seconds):
           f"chrmosome={where} for detection-fdr<{pt} and difference-fdr<{pt2} in {seconds:.2f}sec")
 
 
-def trans_all_request(f1, f2, res, ch, ch2, balance, world_size):
+def trans_all_request(f1, f2, res, ch, ch2, balance, world_size, pairs_trans=False, pairs_zero_based=False):
     """--trans-all -> the pairs (mustache.trans_all_pairs on the first file, in its order), or the `Error:` line of a run that
     cannot go ahead; decided before the GPU is touched, and before a file is read."""
     from .mustache import trans_all_pairs, trans_all_refusal
-    why = trans_all_refusal(f1, ch2) or trans_all_refusal(f2, ch2)
+    why = trans_all_refusal(f1, ch2, pairs_trans) or trans_all_refusal(f2, ch2, pairs_trans)
     if why:
         return why
     if balance is not None:
         return "Error: --balance does not apply to inter-chromosomal pairs"
     if world_size > 1:
         return "Error: inter-chromosomal pairs run on one GPU only (this run has %d ranks)" % world_size
-    return trans_all_pairs(f1, res, ch, ch2)
+    return trans_all_pairs(f1, res, ch, ch2, pairs_trans, pairs_zero_based)
 
 
-def genome_biases_or_error(f1, f2, res, request, device=None):
+def genome_biases_or_error(f1, f2, res, request, device=None, pairs_zero_based=False, verbose=True):
     """--balance-genome: each sample balanced on its own (one balance.report line per sample) -> the two GenomeBias, or None
-    after an `Error:` line"""
+    after an `Error:` line.  Either sample may be a `.hic` or, under --pairs-trans, a pairs file."""
     from .mustache import genome_bias_or_error
     out = []
     for f in (f1, f2):
-        gb = genome_bias_or_error(f, res, request, device)
+        gb = genome_bias_or_error(f, res, request, device, pairs_zero_based, verbose)
         if gb is None:
             return None
         out.append(gb)
@@ -472,6 +472,11 @@ def balanced_trans_rows(genomes, files, pair, args):
                                verbose=args.verbose, label="%s,%s" % pair)
 
 
+def _ranks():
+    """the ranks of the run as torchrun's environment states them: known before a process group (and a GPU) is touched"""
+    return int(os.environ.get("WORLD_SIZE", "1"))
+
+
 def main(argv=None):
     t0 = time.time()
     args = parse_args(sys.argv[1:] if argv is None else argv)
@@ -489,13 +494,28 @@ def main(argv=None):
         return
     from .pairs import refusal as pairs_refusal
     why = pairs_refusal([f1, f2], args.balance, args.biasfile1 or args.biasfile2, args.norm_method, args.chromosome,
-                        args.chromosome2, args.trans_all, args.balance_genome, args.pairs_zero_based, bias_flag="-b1/-b2")
+                        args.chromosome2, args.trans_all, args.balance_genome, args.pairs_zero_based, bias_flag="-b1/-b2",
+                        pairs_trans=args.pairs_trans, world=_ranks() if args.pairs_trans else 1)
     if why:                                  # (a multi-rank run is refused by --balance's own check below)
         print("Error: %s" % why)
         return
+    from .pairs import is_pairs
+    if args.pairs_trans:                     # each pairs file's one parse keeps the trans rows
+        from .balance import BalanceError
+        from .balance_genome import pairs_open
+        from .pairs import want_trans
+        for f in (f1, f2):
+            if is_pairs(f):
+                want_trans(f)
+                try:                         # parsed here, before the GPU is touched: a file without `#chromsize` lines ends the run
+                    pairs_open(f, args.pairs_zero_based)
+                except BalanceError as e:
+                    print("Error: %s" % e)
+                    return
     if args.trans_all:
         from .sharding import init_from_env
-        pairs = trans_all_request(f1, f2, res, args.chromosome, args.chromosome2, args.balance, init_from_env()[1])
+        pairs = trans_all_request(f1, f2, res, args.chromosome, args.chromosome2, args.balance, init_from_env()[1],
+                                  args.pairs_trans, args.pairs_zero_based)
         if isinstance(pairs, str):
             print(pairs)
             return
@@ -509,7 +529,7 @@ def main(argv=None):
         import torch
         device = torch.device("cuda", torch.cuda.current_device())
         if genomes is not None:
-            genomes = genome_biases_or_error(f1, f2, res, genomes, device)
+            genomes = genome_biases_or_error(f1, f2, res, genomes, device, args.pairs_zero_based, args.verbose)
             if genomes is None:
                 return
         return run_trans_all(f1, f2, args, res, pairs, device=device, genomes=genomes)
@@ -544,7 +564,8 @@ def main(argv=None):
     trans_pairs = [p for p in pairs if p[0] != p[1]]
     if trans_pairs:
         from .diff_trans import refusal
-        why = refusal((f1, f2), args.balance, world_size, bool(args.chromosome) and args.chromosome != 'n')
+        why = refusal([f for f in (f1, f2) if not (args.pairs_trans and is_pairs(f))], args.balance, world_size,
+                      bool(args.chromosome) and args.chromosome != 'n')
         if why:
             print("Error: %s" % why)
             return
@@ -556,7 +577,7 @@ def main(argv=None):
         print("Error: %s" % e)
         return
     if genomes is not None:                  # --balance-genome: every matrix of both files is read once, here
-        genomes = genome_biases_or_error(f1, f2, res, genomes)
+        genomes = genome_biases_or_error(f1, f2, res, genomes, None, args.pairs_zero_based, args.verbose)
         if genomes is None:
             return
     pairs = cis_pairs + trans_pairs

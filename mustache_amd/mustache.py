@@ -402,7 +402,10 @@ def regulator(f, norm_method, CHRM_SIZE, outdir, bed="", res=5000, sigma0=1.6, s
     `shard_blocks=False`: in a multi-GPU job this rank runs the whole chromosome alone (whole-genome sharding by chromosome).
     `balance="ICE"` or `"NEWTON"` (not in the reference): balance the raw map on the GPU instead of applying `bias`
     (read_contacts); `pairs_zero_based`: the position convention of `.pairs` input (read_contacts)."""
-    chromosome2 = _check_pair(f, chromosome, chromosome2)
+    if contacts is None:
+        chromosome2 = _check_pair(f, chromosome, chromosome2)
+    elif not chromosome2 or chromosome2 == 'n':            # read already (a pairs file's trans records among them): nothing to refuse
+        chromosome2 = chromosome
     octave_values = [sigma0 * (2 ** i) for i in range(octaves)]
     if chromosome != chromosome2:          # chromosome2 = B: the trans pair (A, B), mustache_amd/trans.py
         if contacts is None:
@@ -566,22 +569,32 @@ def chromosome_pairs(f, res, ch, ch2, pairs_zero_based=False):
     return list(zip(ch, ch2))
 
 
-def trans_all_refusal(f, ch2):
-    """the Error: line of a --trans-all run that `f` or -ch2 rules out, or None; reads nothing"""
+def trans_all_refusal(f, ch2, pairs_trans=False):
+    """the Error: line of a --trans-all run that `f` or -ch2 rules out, or None; reads nothing.  pairs_trans: --pairs-trans,
+    with which a `.pairs` / `.pairs.gz` file is an input too"""
+    from .pairs import is_pairs
     if isinstance(ch2, list):
         return "Error: --trans-all pairs the -ch list with itself; give -ch2 without it"
-    if not str(f).endswith((".cool", ".mcool", ".hic")):
+    if not str(f).endswith((".cool", ".mcool", ".hic")) and not (pairs_trans and is_pairs(f)):
         return "Error: Interchromosomal analysis is only supported for .hic and .cool input formats."
     return None
 
 
-def trans_all_pairs(f, res, ch, ch2):
-    """--trans-all -> every unordered pair (A, B) of the -ch list in list order (without -ch: of list_chromosomes(f, res)), or
-    the Error: line to print."""
-    why = trans_all_refusal(f, ch2)
+def trans_all_pairs(f, res, ch, ch2, pairs_trans=False, pairs_zero_based=False):
+    """--trans-all -> every unordered pair (A, B) of the -ch list in list order (without -ch: of list_chromosomes(f, res); of a
+    pairs file's table, in table order), or the Error: line to print."""
+    from .pairs import is_pairs
+    why = trans_all_refusal(f, ch2, pairs_trans)
     if why:
         return why
-    if not ch or ch == 'n':
+    if (not ch or ch == 'n') and is_pairs(f):
+        from .hicfile import HicError
+        from .pairs import list_chromosomes as pairs_chromosomes
+        try:                              # the one parse of the run (pairs.want_trans: it keeps the trans rows)
+            ch = pairs_chromosomes(f, pairs_zero_based)
+        except HicError as e:
+            return "Error: %s" % e
+    elif not ch or ch == 'n':
         from .readers import list_chromosomes
         ch = list_chromosomes(f, res)
     ch = list(ch)
@@ -620,13 +633,15 @@ def run_trans_pairs(pairs, fetch, add, flush, verbose):
     flush()
 
 
-def genome_bias_or_error(f, res, request, device=None):
+def genome_bias_or_error(f, res, request, device=None, pairs_zero_based=False, verbose=True):
     """--balance-genome: balance.report's line and the GenomeBias of `f`; None after the `Error:` line of a run the device's
-    memory cannot hold.  request = (method, pixels) as balance_genome.request_of returns it."""
+    memory cannot hold (or of a pairs file without `#chromsize` lines).  request = (method, pixels) as
+    balance_genome.request_of returns it."""
     from .balance import BalanceError, report
     from .balance_genome import genome_bias
     try:
-        gb = genome_bias(f, res, method=request[0], pixels=request[1], device=device)
+        gb = genome_bias(f, res, method=request[0], pixels=request[1], device=device, pairs_zero_based=pairs_zero_based,
+                         verbose=verbose)
     except BalanceError as e:
         print("Error: %s" % e)
         return None
@@ -694,12 +709,22 @@ def main(argv=None):
         return
     from .pairs import refusal as pairs_refusal
     why = pairs_refusal(f, args.balance, args.biasfile, args.norm_method, args.chromosome, args.chromosome2, args.trans_all,
-                        args.balance_genome, args.pairs_zero_based, _world)
+                        args.balance_genome, args.pairs_zero_based, _world, pairs_trans=args.pairs_trans)
     if why:
         print("Error: %s" % why)
         return
+    if args.pairs_trans:                     # the file's one parse keeps the trans rows, whoever asks for the handle first
+        from .balance import BalanceError
+        from .balance_genome import pairs_open
+        from .pairs import want_trans
+        want_trans(f)
+        try:                                 # parsed here, before the GPU is touched: a file without `#chromsize` lines ends the run
+            pairs_open(f, args.pairs_zero_based)
+        except BalanceError as e:
+            print("Error: %s" % e)
+            return
     if args.trans_all:
-        pairs = trans_all_pairs(f, res, args.chromosome, args.chromosome2)
+        pairs = trans_all_pairs(f, res, args.chromosome, args.chromosome2, args.pairs_trans, args.pairs_zero_based)
         if not isinstance(pairs, str):
             if _world > 1:
                 pairs = "Error: inter-chromosomal pairs run on one GPU only (this run has %d ranks)" % _world
@@ -718,7 +743,7 @@ def main(argv=None):
         import torch
         device = torch.device("cuda", torch.cuda.current_device())
         if genome is not None:
-            genome = genome_bias_or_error(f, res, genome, device)
+            genome = genome_bias_or_error(f, res, genome, device, args.pairs_zero_based, args.verbose)
             if genome is None:
                 return
         return run_trans_all(f, args, res, pairs, device=device, genome=genome)
@@ -863,12 +888,13 @@ def main(argv=None):
         genome.flush()
     first = not pairs                        # the header is written with the first pair's rows
     if gbias is not None:                    # --balance-genome: every matrix is read once, here; the pairs are called from it
-        gbias = genome_bias_or_error(f, res, gbias, my_device)
+        gbias = genome_bias_or_error(f, res, gbias, my_device, args.pairs_zero_based, args.verbose)
         if gbias is None:
             return
     for chromosome, chromosome2 in trans_pairs:
         start_time = time.time()
-        _check_pair(f, chromosome, chromosome2)          # text input: the reference's refusal
+        if gbias is None:
+            _check_pair(f, chromosome, chromosome2)      # text input: the reference's refusal
         if gbias is not None:
             from .balance_genome import balanced_pair
             contacts = balanced_pair(gbias, chromosome, chromosome2)

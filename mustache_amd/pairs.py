@@ -44,6 +44,13 @@ and under any order of the rows; its record order is unspecified (BalanceCSR sor
 
 Host memory is 8 bytes per cis pair for the length of a run: the file is parsed once, whatever -ch says, and the handle is
 cached per path (PairsFile.OPENS counts the parses).
+
+Trans rows on request (`--pairs-trans`, PairsFile(..., keep_trans=True); the file must have `#chromsize` lines): a trans row
+whose two chromosomes are both in the table is stored as well, 8 bytes of host memory each, pair-major -- (0,1), (0,2), ...,
+(1,2), ... in table order -- with the position on the lower table index first, whichever way round the row named them, and in
+file order within the pair.  The rule of their binning stands above bin_trans_device; what follows it is
+balance_genome.genome_bias (`--balance-genome`), whose second source a pairs file is.  tests/pairs_trans_reference.py restates
+this half.
 """
 import atexit
 import ctypes
@@ -76,6 +83,11 @@ _SIGNATURES = {
     "mst_pairs_chromosome": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64)]),
     "mst_pairs_rows": (ctypes.c_int64, [_P, ctypes.c_int32, ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
     "mst_pairs_counters": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64)]),
+    "mst_pairs_open_ex": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                         ctypes.POINTER(_P)]),
+    "mst_pairs_trans_rows": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_P), ctypes.POINTER(_P),
+                                            ctypes.POINTER(_P), ctypes.POINTER(_P)]),
+    "mst_pairs_trans_counters": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64)]),
 }
 _bound = None
 
@@ -102,16 +114,17 @@ def load():
 
 class PairsFile:
     """One parsed pairs file: the chromosome table, each chromosome's rows (borrowed int32 arrays, valid until close) and the
-    counters.  OPENS counts the files parsed by this process."""
+    counters.  OPENS counts the files parsed by this process.  keep_trans: the trans rows between chromosomes of the table
+    are stored as well (trans_rows, trans_counters; 8 bytes of host memory each); the file must have `#chromsize` lines."""
     OPENS = 0
 
-    def __init__(self, path, zero_based=False, threads=0, chunk_bytes=0):
+    def __init__(self, path, zero_based=False, threads=0, chunk_bytes=0, keep_trans=False):
         from .hicfile import _check
         self._lib, self._h = load(), _P()
-        _check(self._lib, self._lib.mst_pairs_open_chunked(os.fsencode(path), int(bool(zero_based)), int(threads), int(chunk_bytes),
-                                                           ctypes.byref(self._h)))
+        _check(self._lib, self._lib.mst_pairs_open_ex(os.fsencode(path), int(bool(zero_based)), int(threads), int(chunk_bytes),
+                                                      int(bool(keep_trans)), ctypes.byref(self._h)))
         PairsFile.OPENS += 1
-        self.path, self.zero_based = path, bool(zero_based)
+        self.path, self.zero_based, self.keep_trans = path, bool(zero_based), bool(keep_trans)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -162,20 +175,59 @@ class PairsFile:
         _check(self._lib, self._lib.mst_pairs_counters(self._h, c))
         return dict(zip(("rows", "kept", "trans", "out_of_range", "unknown"), (int(v) for v in c)))
 
+    def trans_rows(self):
+        """(posA, posB, seg_off, out_of_range) of a handle opened with keep_trans: the stored trans rows of the whole file as
+        int32 views (valid until close) in pair-major order -- pair p = (a, b), a < b in table order, owns
+        [seg_off[p], seg_off[p + 1]), posA on a and posB on b -- with seg_off int64 [P + 1] and the pairs' out-of-range counts
+        int64 [P] as copies."""
+        from .hicfile import _check
+        P, seg, a, b, oor = ctypes.c_int64(), _P(), _P(), _P(), _P()
+        _check(self._lib, self._lib.mst_pairs_trans_rows(self._h, ctypes.byref(P), ctypes.byref(seg), ctypes.byref(a), ctypes.byref(b),
+                                                         ctypes.byref(oor)))
+        P = int(P.value)
+        seg_off = np.ctypeslib.as_array(ctypes.cast(seg, ctypes.POINTER(ctypes.c_int64)), shape=(P + 1,)).copy()
+        out_of_range = np.ctypeslib.as_array(ctypes.cast(oor, ctypes.POINTER(ctypes.c_int64)), shape=(P,)).copy() if P \
+            else np.zeros(0, np.int64)
+        n = int(seg_off[-1])
+        if n == 0:
+            return np.zeros(0, np.int32), np.zeros(0, np.int32), seg_off, out_of_range
+        pa = np.ctypeslib.as_array(ctypes.cast(a, ctypes.POINTER(ctypes.c_int32)), shape=(n,))
+        pb = np.ctypeslib.as_array(ctypes.cast(b, ctypes.POINTER(ctypes.c_int32)), shape=(n,))
+        return pa, pb, seg_off, out_of_range
+
+    def trans_counters(self):
+        """{"stored", "out_of_range", "unknown"} of the trans rows of a handle opened with keep_trans: stored + unknown =
+        counters()["trans"]"""
+        from .hicfile import _check
+        c = (ctypes.c_int64 * 3)()
+        _check(self._lib, self._lib.mst_pairs_trans_counters(self._h, c))
+        return dict(zip(("stored", "out_of_range", "unknown"), (int(v) for v in c)))
+
 
 _LOCK = threading.RLock()
 _HANDLES = {}                            # absolute path -> PairsFile: a run parses each file once
 
 
-def pairs_handle(path, zero_based=False):
-    """The cached PairsFile of `path` (parsed on first use; parsed again only when the position convention changes)."""
+WANT_TRANS = set()                       # absolute paths whose first parse keeps the trans rows (--pairs-trans)
+
+
+def want_trans(path):
+    """The command lines' --pairs-trans: the next parse of `path` keeps the trans rows, whoever asks for the handle first."""
+    WANT_TRANS.add(os.path.abspath(str(path)))
+
+
+def pairs_handle(path, zero_based=False, keep_trans=False):
+    """The cached PairsFile of `path` (parsed on first use; parsed again only when the position convention changes, or when
+    trans rows are wanted of a handle that holds none -- a handle that holds them serves cis requests too)."""
     key = os.path.abspath(str(path))
     with _LOCK:
         h = _HANDLES.get(key)
-        if h is None or h.zero_based != bool(zero_based):
+        if h is None or h.zero_based != bool(zero_based) or (keep_trans and not h.keep_trans):
+            keep = bool(keep_trans) or key in WANT_TRANS or (h is not None and h.keep_trans)
             if h is not None:
                 h.close()
-            h = _HANDLES[key] = PairsFile(key, zero_based)
+                del _HANDLES[key]
+            h = _HANDLES[key] = PairsFile(key, zero_based, keep_trans=keep)
         return h
 
 
@@ -198,21 +250,39 @@ def list_chromosomes(path, zero_based=False):
 # ----------------------------------------------------------------------------------------------------------------------
 # what the command lines refuse
 # ----------------------------------------------------------------------------------------------------------------------
-def refusal(files, balance, bias, norm_method, ch, ch2, trans_all, balance_genome, zero_based, world=1, bias_flag="-b"):
-    """The text behind `Error:` of a run that its pairs input (or --pairs-zero-based without one) rules out, or None.  Reads
-    nothing and touches no GPU.  files: the input path(s); ch / ch2: the -ch / -ch2 lists ('n' when absent)."""
+def refusal(files, balance, bias, norm_method, ch, ch2, trans_all, balance_genome, zero_based, world=1, bias_flag="-b",
+            pairs_trans=False):
+    """The text behind `Error:` of a run that its pairs input (or --pairs-zero-based / --pairs-trans without one) rules out, or
+    None.  Reads nothing and touches no GPU.  files: the input path(s); ch / ch2: the -ch / -ch2 lists ('n' when absent);
+    pairs_trans: --pairs-trans, which keeps the trans rows of the pairs input for --balance-genome (balance_genome.py)."""
     files = [files] if isinstance(files, str) else list(files)
     mine = [f for f in files if is_pairs(f)]
     if not mine:
+        if pairs_trans:
+            return "--pairs-trans is for .pairs / .pairs.gz input (%s is none)" % ", ".join(str(f) for f in files)
         if zero_based:
             return "--pairs-zero-based is for .pairs / .pairs.gz input (%s is none)" % ", ".join(str(f) for f in files)
         return None
+    other = isinstance(ch2, list) and (not isinstance(ch, list) or len(ch) != len(ch2) or any(a != b for a, b in zip(ch, ch2)))
+    if pairs_trans:
+        if not trans_all and not other:
+            return "--pairs-trans on a run with no inter-chromosomal pair: give --trans-all, or -ch A -ch2 B"
+        if balance is not None or bias or (norm_method and str(norm_method).upper() != "NONE"):
+            return "--pairs-trans with --balance, %s or -norm: the trans rows of %s are raw read pairs and are balanced with " \
+                   "the whole genome; give --balance-genome ICE|NEWTON alone" % (bias_flag, mine[0])
+        if balance_genome is None:
+            return "--pairs-trans without --balance-genome: %s holds raw read pairs; give --balance-genome ICE|NEWTON" % mine[0]
+        if world > 1:
+            return "--pairs-trans in a multi-rank run (world size %d): the genome is balanced on one GPU; start a single " \
+                   "process" % world
+        return None
+    without = "without --pairs-trans only intra-chromosomal loops are called from a pairs file"
     if trans_all:
-        return "--trans-all and %s: only intra-chromosomal loops are called from a pairs file" % mine[0]
+        return "--trans-all and %s: %s" % (mine[0], without)
     if balance_genome is not None:
-        return "--balance-genome and %s: only intra-chromosomal loops are called from a pairs file; use --balance" % mine[0]
-    if isinstance(ch2, list) and (not isinstance(ch, list) or len(ch) != len(ch2) or any(a != b for a, b in zip(ch, ch2))):
-        return "-ch2 with another chromosome and %s: only intra-chromosomal loops are called from a pairs file" % mine[0]
+        return "--balance-genome and %s: %s; use --balance" % (mine[0], without)
+    if other:
+        return "-ch2 with another chromosome and %s: %s" % (mine[0], without)
     if balance is None:
         return "%s holds raw read pairs: give --balance ICE|NEWTON" % mine[0]
     from .balance import BalanceError, check_request
@@ -343,6 +413,158 @@ def bin_pairs_device(pos1, pos2, res, zero_based=False, length=None, distance_bi
         x, d, c = (torch.cat(xs), torch.cat(ds), torch.cat(cs)) if len(xs) > 1 else (xs[0], ds[0], cs[0])
         top = int((x + d).max().item()) + 1 if x.numel() else 0
         return Pixels(x, d, c, top, dropped, K, far_entries, n)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the device binning of trans rows: every chromosome pair of the genome in one pass (csrc/mst_pairs_trans.hip)
+#
+# The rule.  The stored trans rows are pair-major (PairsFile.trans_rows): pair p = (a, b), a < b in table order, with the position
+# on a first.  Each side is judged by its own chromosome's range, as a cis position is; x = bin on a, y = bin on b -- no min / max,
+# the pair is oriented -- and a row whose bin is >= its chromosome's bin count is dropped as well.  Pair p's pixels live at the
+# keys cell_off[p] + x * n_b + y, cell_off = the running sum of n_a * n_b over the pairs before p: keys are unique across pairs
+# and ascending keys are pair-major.  A key below dense_cells is counted in a uint32 array, any other goes through the far list;
+# counts are exact integers and reach float64 without passing through float32.
+# ----------------------------------------------------------------------------------------------------------------------
+def pair_list(n_chromosomes):
+    """[(a, b)] of the table's pairs in pair-major order: (0,1), (0,2), ..., (1,2), ..."""
+    return [(a, b) for a in range(int(n_chromosomes)) for b in range(a + 1, int(n_chromosomes))]
+
+
+def trans_tables(lengths, bins):
+    """int64 host arrays [5][P] -- limA, limB, nA, nB, cell_off -- and the cell total, for chromosome lengths (negative: no
+    upper limit) and bin counts in table order"""
+    pairs = pair_list(len(bins))
+    t = np.zeros((5, len(pairs)), np.int64)
+    total = 0
+    for p, (a, b) in enumerate(pairs):
+        la, lb = int(lengths[a]), int(lengths[b])
+        t[:, p] = (NO_LIMIT if la < 0 else la, NO_LIMIT if lb < 0 else lb, int(bins[a]), int(bins[b]), total)
+        total += int(bins[a]) * int(bins[b])
+    return t, total
+
+
+def bin_trans_keys(posA, posB, seg_off, tables, res, zero_based=False, dense_cells=0, far_capacity=None, device=None):
+    """mst_pairs_bin_trans, mst_pairs_trans_compact and the far list's sort and sum: pair-major rows (posA, posB: int32 host
+    arrays or device tensors; seg_off: int64 [P + 1]) and the per-pair tables (int64 [5][P]: limA, limB, nA, nB, cell_off) ->
+    (keys int64 ascending and unique, counts int64, dropped int64 host array [P], far entries before they were summed).
+    dense_cells: keys below it are counted in a uint32 array of that many counters.  far_capacity: room of the far list
+    (None: one entry per row, which always suffices)."""
+    import torch
+    from . import _lib
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    lib = require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    res = int(res)
+    if res < 1:
+        raise ValueError("bin_trans_keys: res must be >= 1")
+    tables = np.ascontiguousarray(tables, dtype=np.int64)
+    P = int(tables.shape[1])
+    seg_off = np.ascontiguousarray(seg_off, dtype=np.int64)
+    if tables.shape[0] != 5 or seg_off.shape != (P + 1,):
+        raise ValueError("bin_trans_keys: tables of [5][P] and seg_off of P + 1 entries")
+    with torch.cuda.device(dev):
+        as_dev = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))).to(
+            device=dev, dtype=torch.int32).contiguous()
+        pa, pb = as_dev(posA), as_dev(posB)
+        rows = int(pa.numel())
+        if int(pb.numel()) != rows or (P and (int(seg_off[0]) != 0 or int(seg_off[-1]) != rows or np.any(np.diff(seg_off) < 0))):
+            raise ValueError("bin_trans_keys: posA and posB of seg_off[P] rows, seg_off ascending from 0")
+        i64 = lambda k: torch.empty(k, dtype=torch.int64, device=dev)
+        dropped = torch.zeros(P + 1, dtype=torch.int64, device=dev)              # [P] dropped rows, then the far entries
+        if rows == 0 or P == 0:
+            return i64(0), i64(0), np.zeros(P, np.int64), 0
+        dense_cells = max(0, int(dense_cells))
+        cap = rows if far_capacity is None else int(far_capacity)
+        table_d = torch.from_numpy(np.concatenate([tables.reshape(-1), seg_off])).to(dev)
+        lim_a, lim_b, n_a, n_b, cell_off = (table_d[k * P:(k + 1) * P] for k in range(5))
+        dense = torch.zeros(dense_cells, dtype=torch.int32, device=dev)           # uint32 counters
+        far_key = i64(cap)
+        far_mult = torch.empty(cap, dtype=torch.int32, device=dev)                # uint32, at most 64
+        _lib.check(lib.mst_pairs_bin_trans(_ptr(pa), _ptr(pb), rows, _ptr(table_d[5 * P:]), P, _ptr(lim_a), _ptr(lim_b), _ptr(n_a),
+                                           _ptr(n_b), _ptr(cell_off), res, int(bool(zero_based)), dense_cells,
+                                           _ptr(dense) if dense_cells else None, _ptr(far_key) if cap else None,
+                                           _ptr(far_mult) if cap else None, cap, _ptr(dropped[P:]), _ptr(dropped), _stream()))
+        counted = dropped.cpu().numpy()
+        far_entries = int(counted[P])
+        if far_entries > cap:
+            raise _lib.MstOverflow(_lib.MST_E_OVERFLOW, "bin_trans_keys: the far list holds %d entries, %d were needed"
+                                   % (cap, far_entries))
+        ks, cs = [], []
+        if dense_cells:
+            room = min(rows, dense_cells)
+            k, c = i64(room), torch.empty(room, dtype=torch.int32, device=dev)
+            found = torch.zeros(1, dtype=torch.int64, device=dev)
+            ws = torch.empty(int(lib.mst_pairs_trans_compact_workspace_bytes(dense_cells)), dtype=torch.uint8, device=dev)
+            _lib.check(lib.mst_pairs_trans_compact(_ptr(dense), dense_cells, _ptr(k), _ptr(c), room, _ptr(found), _ptr(ws), ws.numel(),
+                                                   _stream()))
+            m = int(found.item())
+            if m > room:
+                raise RuntimeError("bin_trans_keys: %d non-zero counters from %d rows" % (m, rows))
+            ks.append(k[:m])
+            cs.append(c[:m].to(torch.int64) & 0xFFFFFFFF)
+            del dense, ws
+        if far_entries:                              # every far key is >= dense_cells: behind the dense part, already ascending
+            keys, counts = sum_far_list(far_key[:far_entries], far_mult[:far_entries])
+            ks.append(keys)
+            cs.append(counts)
+        del far_key, far_mult
+        if not ks:
+            return i64(0), i64(0), counted[:P].copy(), far_entries
+        keys, counts = (torch.cat(ks), torch.cat(cs)) if len(ks) > 1 else (ks[0], cs[0])
+        return keys, counts, counted[:P].copy(), far_entries
+
+
+def decode_trans_keys(keys, counts, tables):
+    """mst_pairs_trans_decode: ascending unique keys and int64 counts (device tensors) -> {p: (x int32, y int32, v float64)}
+    device tensors in key order for every pair p of `tables` that has a record"""
+    import torch
+    from . import _lib
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    lib = require_gpu()
+    tables = np.ascontiguousarray(tables, dtype=np.int64)
+    P, n, dev = int(tables.shape[1]), int(keys.numel()), keys.device
+    if n == 0 or P == 0:
+        return {}
+    with torch.cuda.device(dev):
+        keys, counts = keys.contiguous(), counts.to(torch.int64).contiguous()
+        table_d = torch.from_numpy(np.concatenate([tables[4], tables[3]])).to(dev)
+        x, y = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        v = torch.empty(n, dtype=torch.float64, device=dev)
+        _lib.check(lib.mst_pairs_trans_decode(_ptr(keys), _ptr(counts), n, _ptr(table_d[:P]), _ptr(table_d[P:]), P, _ptr(x), _ptr(y),
+                                              _ptr(v), _stream()))
+        cuts = torch.searchsorted(keys, table_d[:P]).cpu().tolist() + [n]
+    return {p: (x[cuts[p]:cuts[p + 1]], y[cuts[p]:cuts[p + 1]], v[cuts[p]:cuts[p + 1]]) for p in range(P) if cuts[p + 1] > cuts[p]}
+
+
+def bin_trans_device(posA, posB, seg_off, lengths, res, zero_based=False, bins=None, out_of_range=None, dense_bytes=None,
+                     dense_cells=None, far_capacity=None, device=None, names=None, stats=None):
+    """The stored trans rows of a genome (PairsFile.trans_rows: posA, posB, seg_off) -> {(i, j): (x, y, v)}, i < j table indices,
+    x = bins of i (int32), y = bins of j (int32), v = counts (float64) as device tensors in key order; pairs without a record
+    are absent.  lengths: the table's chromosome lengths in bp; bins: the bin count of each chromosome (None: length // res + 1,
+    balance_genome.genome_layout's).  dense_cells: None = every cell when 4 bytes per cell fit dense_bytes (None:
+    dense_budget()), else 0.  out_of_range: the reader's per-pair counts; a pair whose device-dropped count differs raises.
+    stats (a dict) receives "pixels", "pairs", "dropped", "dense_cells" and "far_entries"."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    bins = [int(length) // int(res) + 1 for length in lengths] if bins is None else [int(b) for b in bins]
+    tables, cells = trans_tables(lengths, bins)
+    pairs = pair_list(len(bins))
+    if dense_cells is None:
+        budget = dense_budget(dev) if dense_bytes is None else int(dense_bytes)
+        dense_cells = cells if 4 * cells <= budget else 0
+    dense_cells = max(0, min(int(dense_cells), cells))
+    keys, counts, dropped, far_entries = bin_trans_keys(posA, posB, seg_off, tables, res, zero_based, dense_cells, far_capacity, dev)
+    if out_of_range is not None:
+        for p in np.flatnonzero(dropped != np.asarray(out_of_range, np.int64)):
+            a, b = pairs[int(p)]
+            label = "%s,%s" % (names[a], names[b]) if names else "(%d, %d)" % (a, b)
+            raise RuntimeError("pairs: the device dropped %d trans rows of the pair %s as out of range, the host reader counted %d"
+                               % (dropped[p], label, out_of_range[p]))
+    got = decode_trans_keys(keys, counts, tables)
+    if stats is not None:
+        stats.update(pixels=int(keys.numel()), pairs=len(got), dropped=int(dropped.sum()), dense_cells=dense_cells,
+                     far_entries=far_entries)
+    return {pairs[p]: rec for p, rec in got.items()}
 
 
 # ----------------------------------------------------------------------------------------------------------------------
