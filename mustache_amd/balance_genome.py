@@ -79,9 +79,10 @@ def check_genome_request(method, pixels, files, bias, norm_method, balance, worl
     what --balance was given; world: the ranks of the run; trans: "all" when every pair of the run is inter-chromosomal,
     "some" when only some are, "none" when none is (True / False: "all" / "none"); pairs_trans: --pairs-trans, with which a
     `.pairs` / `.pairs.gz` file is an input like a `.hic` file (its trans rows are kept and binned: mustache_amd/pairs.py)."""
+    from .request import balance_on_trans, trans_input
     trans = {True: "all", False: "none"}.get(trans, trans)
-    if balance is not None and trans != "none":
-        raise BalanceError("--balance does not apply to inter-chromosomal pairs")
+    if trans != "none" and balance_on_trans(balance):
+        raise BalanceError(balance_on_trans(balance))
     if method is None:
         raise BalanceError("--balance-pixels %s without --balance-genome: it chooses the pixels --balance-genome balances on"
                            % pixels)
@@ -94,9 +95,8 @@ def check_genome_request(method, pixels, files, bias, norm_method, balance, worl
     if trans != "all":
         raise BalanceError("--balance-genome is for inter-chromosomal calls; use --balance")
     files = [files] if isinstance(files, str) else list(files or [])
-    from .pairs import is_pairs
-    if not all(str(p).endswith((".hic", ".cool", ".mcool")) or (pairs_trans and is_pairs(p)) for p in files):
-        raise BalanceError("Interchromosomal analysis is only supported for .hic and .cool input formats.")
+    if trans_input(files, pairs_trans):
+        raise BalanceError(trans_input(files, pairs_trans))
     if bias:
         raise BalanceError("--balance-genome %s and a bias file (-b / -b1 / -b2): give either a bias file or --balance-genome, "
                            "not both" % m)
@@ -130,17 +130,6 @@ def add_arguments(parser):
                         help="OPTIONAL: .pairs / .pairs.gz input only: keep the file's inter-chromosomal rows (8 bytes of host "
                              "memory each) so that -ch A -ch2 B and --trans-all run from it; needs --balance-genome")
     parser.set_defaults(balance_pixels_given=False)
-
-
-def request_of(args, files, bias, world, pairs):
-    """The command lines' use of check_genome_request: None when neither option was given, else (method, pixels); raises
-    BalanceError.  pairs: the run's (chromosome, chromosome2) list."""
-    if args.balance_genome is None and not args.balance_pixels_given:
-        return None
-    n_trans = sum(1 for a, b in pairs if a != b)
-    trans = "none" if n_trans == 0 else ("all" if n_trans == len(pairs) else "some")
-    return check_genome_request(args.balance_genome, args.balance_pixels, files, bias, args.norm_method, args.balance, world, trans,
-                                pairs_trans=getattr(args, "pairs_trans", False))
 
 
 class GenomeBias:

@@ -24,8 +24,8 @@ import time
 
 import numpy as np
 
-from .mustache import (_engine, block_tiling, block_mask_size, chromosome_pairs, owned_chromosomes, parseBP,
-                       read_sample)
+from .mustache import (_engine, block_tiling, block_mask_size, genome_biases_or_error, octave_values, owned_chromosomes,
+                       parseBP, read_sample, run_trans_all)
 from .tail import (fdr_candidates_multi, diag_mean_filter_multi, cluster_representatives, loops_from_reps,
                    _features_multi)
 
@@ -393,67 +393,26 @@ def print_found(counts, chromosome, chromosome2, pt, pt2, seconds):
           f"chrmosome={where} for detection-fdr<{pt} and difference-fdr<{pt2} in {seconds:.2f}sec")
 
 
-def trans_all_request(f1, f2, res, ch, ch2, balance, world_size, pairs_trans=False, pairs_zero_based=False):
-    """--trans-all -> the pairs (mustache.trans_all_pairs on the first file, in its order), or the `Error:` line of a run that
-    cannot go ahead; decided before the GPU is touched, and before a file is read."""
-    from .mustache import trans_all_pairs, trans_all_refusal
-    why = trans_all_refusal(f1, ch2, pairs_trans) or trans_all_refusal(f2, ch2, pairs_trans)
-    if why:
-        return why
-    if balance is not None:
-        return "Error: --balance does not apply to inter-chromosomal pairs"
-    if world_size > 1:
-        return "Error: inter-chromosomal pairs run on one GPU only (this run has %d ranks)" % world_size
-    return trans_all_pairs(f1, res, ch, ch2, pairs_trans, pairs_zero_based)
-
-
-def genome_biases_or_error(f1, f2, res, request, device=None, pairs_zero_based=False, verbose=True):
-    """--balance-genome: each sample balanced on its own (one balance.report line per sample) -> the two GenomeBias, or None
-    after an `Error:` line.  Either sample may be a `.hic` or, under --pairs-trans, a pairs file."""
-    from .mustache import genome_bias_or_error
-    out = []
-    for f in (f1, f2):
-        gb = genome_bias_or_error(f, res, request, device, pairs_zero_based, verbose)
-        if gb is None:
-            return None
-        out.append(gb)
-    return out
-
-
-def run_trans_all(f1, f2, args, res, pairs, device=None, genomes=None):
-    """The --trans-all run: the next pair's two samples are read on a reader thread while the current pair joins the batch
-    (mustache.run_trans_pairs, diff_trans_genome.DiffTransGenomeCaller); rows are written in pair order, the headers with the
-    first pair's.  genomes (the samples' balance_genome.GenomeBias, --balance-genome): nothing is read again; both samples'
-    resident records are balanced in shared launches and join the batch."""
+def call_trans_all(files, args, res, run):
+    """diff_mustache's --trans-all run (mustache.run_trans_all on both samples' files, diff_trans_genome.DiffTransGenomeCaller):
+    rows are written in pair order, the four headers with the first pair's"""
+    import torch
     from .diff_trans_genome import DiffTransGenomeCaller
-    from .mustache import run_trans_pairs
-    from .trans import read_trans_contacts
-    state = {"t0": time.time()}
-
-    def fetch(k):
-        recs, res_seen = [], None
-        for f in (f1, f2):
-            got = read_trans_contacts(f, args.norm_method, pairs[k][0], pairs[k][1], res, device=device)
-            if got is not None:
-                if res_seen is not None and got[3] != res_seen:
-                    raise ValueError('Both contact maps should have the same resolution.')
-                res_seen = got[3]
-            recs.append(None if got is None else got[:3])
-        return recs
+    device = torch.device("cuda", torch.cuda.current_device())
+    genomes = None
+    if run.genome is not None:
+        genomes = genome_biases_or_error(files, res, run.genome, device, args.pairs_zero_based, args.verbose)
+        if genomes is None:
+            return
+    pairs, state = run.trans, {"t0": time.time()}
 
     def emit(k, o):
         counts = write_tagged(args.outdir, pairs[k][0], pairs[k][1], res, o, first=(k == 0))
         print_found(counts, pairs[k][0], pairs[k][1], args.pt, args.pt2, time.time() - state["t0"])
         state["t0"] = time.time()
 
-    caller = DiffTransGenomeCaller([args.s_z * (2 ** i) for i in range(args.octaves)], args.st, args.pt, args.pt2, emit,
-                                   verbose=args.verbose)
-    if genomes is not None:
-        from .balance_genome import balanced_batches
-        for (k, rec1), (_, rec2) in zip(balanced_batches(genomes[0], pairs), balanced_batches(genomes[1], pairs)):
-            caller.add(k, rec1, rec2, "%s,%s" % pairs[k])
-        return caller.flush()
-    run_trans_pairs(pairs, fetch, lambda k, recs, label: caller.add(k, recs[0], recs[1], label), caller.flush, args.verbose)
+    caller = DiffTransGenomeCaller(octave_values(args), args.st, args.pt, args.pt2, emit, verbose=args.verbose)
+    run_trans_all(files, args, res, pairs, caller, device, genomes)
 
 
 def balanced_trans_rows(genomes, files, pair, args):
@@ -468,120 +427,45 @@ def balanced_trans_rows(genomes, files, pair, args):
             print("There is no contact in the chromosome pair %s,%s of %s to work on." % (pair[0], pair[1], f))
             return []
         recs.append(got)
-    return call_diff_trans_coo(recs[0], recs[1], [args.s_z * (2 ** i) for i in range(args.octaves)], args.st, args.pt, args.pt2,
-                               verbose=args.verbose, label="%s,%s" % pair)
-
-
-def _ranks():
-    """the ranks of the run as torchrun's environment states them: known before a process group (and a GPU) is touched"""
-    return int(os.environ.get("WORLD_SIZE", "1"))
+    return call_diff_trans_coo(recs[0], recs[1], octave_values(args), args.st, args.pt, args.pt2, verbose=args.verbose,
+                               label="%s,%s" % pair)
 
 
 def main(argv=None):
     t0 = time.time()
     args = parse_args(sys.argv[1:] if argv is None else argv)
-    f1, f2 = args.f_path1, args.f_path2
-    if args.bed1 and args.mat1:
-        f1 = args.mat1
-    if args.bed2 and args.mat2:
-        f2 = args.mat2
-    if not f1 or not f2 or not os.path.exists(f1) or not os.path.exists(f2):
-        print("Error: Couldn't find the specified contact files")
-        return
+    from .request import plan, refuse, request_of
+    from .sharding import gather_chromosome_rows, init_from_env
+    f1 = args.mat1 if args.bed1 and args.mat1 else args.f_path1
+    f2 = args.mat2 if args.bed2 and args.mat2 else args.f_path2
     res = parseBP(args.resolution)
-    if not res:
-        print("Error: Invalid resolution")
-        return
-    from .pairs import refusal as pairs_refusal
-    why = pairs_refusal([f1, f2], args.balance, args.biasfile1 or args.biasfile2, args.norm_method, args.chromosome,
-                        args.chromosome2, args.trans_all, args.balance_genome, args.pairs_zero_based, bias_flag="-b1/-b2",
-                        pairs_trans=args.pairs_trans, world=_ranks() if args.pairs_trans else 1)
-    if why:                                  # (a multi-rank run is refused by --balance's own check below)
-        print("Error: %s" % why)
-        return
-    from .pairs import is_pairs
-    if args.pairs_trans:                     # each pairs file's one parse keeps the trans rows
-        from .balance import BalanceError
-        from .balance_genome import pairs_open
-        from .pairs import want_trans
-        for f in (f1, f2):
-            if is_pairs(f):
-                want_trans(f)
-                try:                         # parsed here, before the GPU is touched: a file without `#chromsize` lines ends the run
-                    pairs_open(f, args.pairs_zero_based)
-                except BalanceError as e:
-                    print("Error: %s" % e)
-                    return
-    if args.trans_all:
-        from .sharding import init_from_env
-        pairs = trans_all_request(f1, f2, res, args.chromosome, args.chromosome2, args.balance, init_from_env()[1],
-                                  args.pairs_trans, args.pairs_zero_based)
-        if isinstance(pairs, str):
-            print(pairs)
-            return
-        from .balance import BalanceError
-        from .balance_genome import request_of
-        try:
-            genomes = request_of(args, [f1, f2], args.biasfile1 or args.biasfile2, 1, pairs)
-        except BalanceError as e:
-            print("Error: %s" % e)
-            return
-        import torch
-        device = torch.device("cuda", torch.cuda.current_device())
-        if genomes is not None:
-            genomes = genome_biases_or_error(f1, f2, res, genomes, device, args.pairs_zero_based, args.verbose)
-            if genomes is None:
-                return
-        return run_trans_all(f1, f2, args, res, pairs, device=device, genomes=genomes)
-    pairs = chromosome_pairs(f1, res, args.chromosome, args.chromosome2, args.pairs_zero_based)
-    if isinstance(pairs, str):
-        print(pairs)
-        return
+    # the ranks are torchrun's WORLD_SIZE: known before the process group is joined, so a run that is refused joins none and
+    # touches no GPU.  The group, once joined, has the last word (a launcher whose environment does not state its ranks).
+    rq = request_of(args, [f1, f2], [(args.biasfile1, "Couldn't find the specified bias file1"),
+                                     (args.biasfile2, "Couldn't find the specified bias file2")], "-b1/-b2",
+                    int(os.environ.get("WORLD_SIZE", "1")))
+    run = plan(rq, res)
+    if not isinstance(run, str):
+        rank, world_size = init_from_env()
+        if world_size != rq.ranks:
+            run = plan(rq._replace(ranks=world_size), res)
+    if isinstance(run, str):
+        return refuse(run)
+    if run.trans_all:
+        return call_trans_all([f1, f2], args, res, run)
     distFilter = resolve_distance_filter(args.distFilter, res)
-    if args.biasfile1 and not os.path.exists(args.biasfile1):
-        print("Error: Couldn't find the specified bias file1")
-        return
-    if args.biasfile2 and not os.path.exists(args.biasfile2):
-        print("Error: Couldn't find the specified bias file2")
-        return
     biasf1 = False            # reference quirk (:824-827): -b1 is checked for existence but never passed on
     biasf2 = args.biasfile2 if args.biasfile2 else False
-
-    # multi-GPU (`torchrun -m mustache_amd.diff_mustache ...`): chromosomes are dealt to the ranks largest first, each rank
-    # reads and runs its own, ONE gather of (chromosome, x, y, fdr, sigma, list tag) records, rank 0 writes the four files
-    from .sharding import gather_chromosome_rows, init_from_env
-    rank, world_size = init_from_env()
-    if args.balance is not None:
-        from .balance import BalanceError, check_request
-        try:
-            args.balance = check_request(args.balance, [f1, f2], args.biasfile1 or args.biasfile2, args.norm_method,
-                                         world_size, bias_flag="-b1/-b2")
-        except BalanceError as e:
-            print("Error: %s" % e)
-            return
-    # inter-chromosomal pairs (mustache_amd/diff_trans.py) run after every intra-chromosomal pair, in pair order
-    cis_pairs = [p for p in pairs if p[0] == p[1]]
-    trans_pairs = [p for p in pairs if p[0] != p[1]]
-    if trans_pairs:
-        from .diff_trans import refusal
-        why = refusal([f for f in (f1, f2) if not (args.pairs_trans and is_pairs(f))], args.balance, world_size,
-                      bool(args.chromosome) and args.chromosome != 'n')
-        if why:
-            print("Error: %s" % why)
-            return
-    from .balance import BalanceError
-    from .balance_genome import request_of
-    try:
-        genomes = request_of(args, [f1, f2], args.biasfile1 or args.biasfile2, world_size, cis_pairs + trans_pairs)
-    except BalanceError as e:
-        print("Error: %s" % e)
-        return
-    if genomes is not None:                  # --balance-genome: every matrix of both files is read once, here
-        genomes = genome_biases_or_error(f1, f2, res, genomes, None, args.pairs_zero_based, args.verbose)
+    genomes = None
+    if run.genome is not None:               # --balance-genome: every matrix of both files is read once, here
+        genomes = genome_biases_or_error([f1, f2], res, run.genome, None, args.pairs_zero_based, args.verbose)
         if genomes is None:
             return
-    pairs = cis_pairs + trans_pairs
-    n_cis = len(cis_pairs)
+    # multi-GPU (`torchrun -m mustache_amd.diff_mustache ...`): chromosomes are dealt to the ranks largest first, each rank
+    # reads and runs its own, ONE gather of (chromosome, x, y, fdr, sigma, list tag) records, rank 0 writes the four files.
+    # inter-chromosomal pairs (mustache_amd/diff_trans.py) run after every intra-chromosomal pair, in pair order
+    pairs = run.cis + run.trans
+    n_cis = len(run.cis)
     mine = owned_chromosomes(f1, res, pairs, rank, world_size) if world_size > 1 else list(range(n_cis))
 
     def write(i, o):
@@ -615,17 +499,17 @@ def main(argv=None):
             emit(i, regulator(f1, f2, args.norm_method, False, args.outdir, bed1=args.bed1, bed2=args.bed2, res=res,
                               sigma0=args.s_z, s=args.s, verbose=args.verbose, pt=args.pt, pt2=args.pt2, st=args.st,
                               distance_filter=distFilter, nprocesses=args.nprocesses, bias1=biasf1, bias2=biasf2,
-                              chromosome=chromosome, chromosome2=chromosome2, octaves=args.octaves, balance=args.balance,
+                              chromosome=chromosome, chromosome2=chromosome2, octaves=args.octaves, balance=run.balance,
                               pairs_zero_based=args.pairs_zero_based))
             continue
         got = read_pair(f1, f2, args.norm_method, False, res, distFilter, biasf1, biasf2, chromosome, chromosome2,
-                        args.verbose, balance=args.balance, pairs_zero_based=args.pairs_zero_based)
+                        args.verbose, balance=run.balance, pairs_zero_based=args.pairs_zero_based)
         if got is None:
             genome.skip(i)
             continue
         if pipe is None:
             from .pipeline import ChromosomePipeline
-            pipe = ChromosomePipeline([args.s_z * (2 ** o_) for o_ in range(args.octaves)])
+            pipe = ChromosomePipeline(octave_values(args))
             from .engine import settle_gc
             settle_gc()                           # the command-line process only; the library leaves the collector alone
         coo1, coo2, res_c = got

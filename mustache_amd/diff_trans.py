@@ -78,24 +78,13 @@ def call_diff_trans_coo(rec1, rec2, octave_values, st, pt, pt2, chunk=TRANS_CHUN
     return caller.run_pair([rec1, rec2], label)
 
 
-def refusal(files, balance, world_size, chromosomes_given=True):
-    """Why a two-sample run with an inter-chromosomal pair cannot go ahead (the text of its `Error:` line), or None."""
-    if not chromosomes_given:
-        return "inter-chromosomal pairs need -ch and -ch2 (all-pairs runs are not supported)"
-    if not all(str(f).endswith((".hic", ".cool", ".mcool")) for f in files):
-        return "Interchromosomal analysis is only supported for .hic and .cool input formats."
-    if balance:
-        return "--balance does not apply to inter-chromosomal pairs"
-    if world_size > 1:
-        return "inter-chromosomal pairs run on one GPU only (this run has %d ranks)" % world_size
-    return None
-
-
 def regulate(f1, f2, norm_method, res, octave_values, st, pt, pt2, chromosome, chromosome2, verbose=True, balance=None):
     """diff_mustache.regulator()'s body for a trans pair: read both samples (rule 1), call.  Rows [x, y, fdr, sigma, tag].
-    Refuses text input and `balance` (TransError).  It runs on the current device alone and knows nothing of ranks: a
-    multi-rank caller (and -ch2 without -ch) is the command line's to refuse, before it gets here (diff_mustache.main)."""
-    why = refusal((f1, f2), balance, 1)
+    Refuses text input and `balance` (TransError, the rules of request.py).  It runs on the current device alone and knows
+    nothing of ranks: a multi-rank caller (and -ch2 without -ch) is the command line's to refuse, before it gets here
+    (request.plan)."""
+    from .request import balance_on_trans, trans_input
+    why = trans_input((f1, f2)) or balance_on_trans(balance or None)
     if why:
         raise TransError(why)
     if verbose:

@@ -305,11 +305,12 @@ def call_loops_coo(x, y, v, res, distance_in_px, octave_values, st, pt, chromoso
 
 
 def _check_pair(f, chromosome, chromosome2):
+    """chromosome2, defaulted; a trans pair on text input ends as in the reference (mustache.py:869-871): request.Raises"""
+    from .request import Raises, refuse, trans_input
     if not chromosome2 or chromosome2 == 'n':
         chromosome2 = chromosome
-    if (chromosome != chromosome2) and not (('.hic' in f) or ('.cool' in f) or ('.mcool' in f)):
-        print("Interchromosomal analysis is only supported for .hic and .cool input formats.")
-        raise FileNotFoundError
+    if chromosome != chromosome2 and trans_input([f]):
+        refuse(Raises(trans_input([f])))
     return chromosome2
 
 
@@ -335,11 +336,11 @@ def read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromos
     if verbose:
         print("Reading contact map...")
     if chromosome != chromosome2:          # a trans pair: every record of the matrix, no distance limit (trans.py rule 1)
+        from .request import balance_on_trans, trans_ranks
         from .trans import TransError, read_trans_contacts
-        if balance:
-            raise TransError("--balance does not apply to inter-chromosomal pairs")
-        if part[1] > 1:
-            raise TransError("inter-chromosomal pairs run on one GPU only")
+        why = balance_on_trans(balance or None) or trans_ranks(part[1], count=False)
+        if why:
+            raise TransError(why)
         return read_trans_contacts(f, norm_method, chromosome, chromosome2, res, device=device)
     if balance:
         from .balance import check_request
@@ -364,7 +365,8 @@ def read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome
     if is_pairs(f):
         from .pairs import PairsError, read_pairs_balanced
         if not balance:
-            raise PairsError("%s holds raw read pairs: give --balance ICE|NEWTON" % f)
+            from .request import RAW_PAIRS
+            raise PairsError(RAW_PAIRS % f)
         from .balance import method_of
         r = read_pairs_balanced(f, distance_in_bp, chromosome, res, device=device, method=method_of(balance),
                                 zero_based=pairs_zero_based, verbose=verbose)
@@ -545,62 +547,6 @@ def _scalar_text(v):
     return repr(float(v)) if isinstance(v, (float, np.float64)) else str(v)      # str(np.float32) is NOT repr(float(v)): left to str()
 
 
-def chromosome_pairs(f, res, ch, ch2, pairs_zero_based=False):
-    """-ch / -ch2 -> [(chromosome, chromosome2)] (without -ch: every chromosome of a `.hic` / `.cool` / `.mcool` file, or of a
-    `.pairs` / `.pairs.gz` file's table in table order), or the Error: line to print when they cannot be paired (reference
-    mustache.py:1019-1045, diff_mustache.py:781-800)."""
-    if not ch or ch == 'n':
-        from .pairs import is_pairs
-        if is_pairs(f):                   # the one parse of the run: the handle stays cached for the reads that follow
-            from .hicfile import HicError
-            from .pairs import list_chromosomes as pairs_chromosomes
-            try:
-                ch = pairs_chromosomes(f, pairs_zero_based)
-            except HicError as e:
-                return "Error: %s" % e
-        elif not f.endswith((".cool", ".mcool", ".hic")):
-            return "Error: Please enter the chromosome name."
-        else:
-            from .readers import list_chromosomes
-            ch = list_chromosomes(f, res)
-    ch2 = ch2 if isinstance(ch2, list) else ch
-    if len(ch) != len(ch2):
-        return "Error: the same number of chromosome1 and chromosome2 should be provided."
-    return list(zip(ch, ch2))
-
-
-def trans_all_refusal(f, ch2, pairs_trans=False):
-    """the Error: line of a --trans-all run that `f` or -ch2 rules out, or None; reads nothing.  pairs_trans: --pairs-trans,
-    with which a `.pairs` / `.pairs.gz` file is an input too"""
-    from .pairs import is_pairs
-    if isinstance(ch2, list):
-        return "Error: --trans-all pairs the -ch list with itself; give -ch2 without it"
-    if not str(f).endswith((".cool", ".mcool", ".hic")) and not (pairs_trans and is_pairs(f)):
-        return "Error: Interchromosomal analysis is only supported for .hic and .cool input formats."
-    return None
-
-
-def trans_all_pairs(f, res, ch, ch2, pairs_trans=False, pairs_zero_based=False):
-    """--trans-all -> every unordered pair (A, B) of the -ch list in list order (without -ch: of list_chromosomes(f, res); of a
-    pairs file's table, in table order), or the Error: line to print."""
-    from .pairs import is_pairs
-    why = trans_all_refusal(f, ch2, pairs_trans)
-    if why:
-        return why
-    if (not ch or ch == 'n') and is_pairs(f):
-        from .hicfile import HicError
-        from .pairs import list_chromosomes as pairs_chromosomes
-        try:                              # the one parse of the run (pairs.want_trans: it keeps the trans rows)
-            ch = pairs_chromosomes(f, pairs_zero_based)
-        except HicError as e:
-            return "Error: %s" % e
-    elif not ch or ch == 'n':
-        from .readers import list_chromosomes
-        ch = list_chromosomes(f, res)
-    ch = list(ch)
-    return [(ch[i], ch[j]) for i in range(len(ch)) for j in range(i + 1, len(ch))]
-
-
 def read_ahead(count, fetch):
     """(k, fetch(k)) for k = 0 .. count - 1 in order, fetch(k + 1) running on a reader thread while the caller works on k; what
     fetch raises is re-raised here, at its item's turn"""
@@ -622,62 +568,55 @@ def read_ahead(count, fetch):
             yield k, got
 
 
-def run_trans_pairs(pairs, fetch, add, flush, verbose):
-    """The body of a --trans-all run, one sample or two: pair k's records, read ahead (read_ahead), join the batch through
-    `add(k, records, label)`; `flush()` at the end."""
-    for k, records in read_ahead(len(pairs), fetch):
-        if verbose:
-            print("Reading contact map (pair %s,%s)..." % pairs[k])
-        add(k, records, "%s,%s" % pairs[k])
-        del records
-    flush()
+def octave_values(args):
+    """-sz / -oc of either command line -> the first sigma of each octave"""
+    return [args.s_z * (2 ** i) for i in range(args.octaves)]
 
 
-def genome_bias_or_error(f, res, request, device=None, pairs_zero_based=False, verbose=True):
-    """--balance-genome: balance.report's line and the GenomeBias of `f`; None after the `Error:` line of a run the device's
-    memory cannot hold (or of a pairs file without `#chromsize` lines).  request = (method, pixels) as
-    balance_genome.request_of returns it."""
+def genome_biases_or_error(files, res, request, device=None, pairs_zero_based=False, verbose=True):
+    """--balance-genome: each sample's file balanced on its own (`.hic` or, under --pairs-trans, a pairs file), one
+    balance.report line each -> their GenomeBias in order; None after the `Error:` line of a run the device's memory cannot hold
+    (or of a pairs file without `#chromsize` lines).  request = (method, pixels): request.Plan.genome."""
     from .balance import BalanceError, report
     from .balance_genome import genome_bias
-    try:
-        gb = genome_bias(f, res, method=request[0], pixels=request[1], device=device, pairs_zero_based=pairs_zero_based,
-                         verbose=verbose)
-    except BalanceError as e:
-        print("Error: %s" % e)
-        return None
-    report(gb.info, gb.label)
-    return gb
+    out = []
+    for f in files:
+        try:
+            gb = genome_bias(f, res, method=request[0], pixels=request[1], device=device, pairs_zero_based=pairs_zero_based,
+                             verbose=verbose)
+        except BalanceError as e:
+            print("Error: %s" % e)
+            return None
+        report(gb.info, gb.label)
+        out.append(gb)
+    return out
 
 
-def run_trans_all(f, args, res, pairs, device=None, genome=None):
-    """The --trans-all run: the next pair is read on a reader thread while the current one joins the batch
-    (trans_genome.TransGenomeCaller); rows are written in pair order, the header with the first pair's.
-    genome (a balance_genome.GenomeBias, --balance-genome): nothing is read again -- the pairs' resident records are balanced
-    in shared launches (balance_genome.balanced_batches) and join the batch."""
+def run_trans_all(files, args, res, pairs, caller, device=None, genomes=None):
+    """The --trans-all run of one sample or two: pair k's records of every file of `files`, read on a reader thread while pair
+    k - 1 joins the batch (read_ahead), are held by `caller` (a trans_genome.PairBatcher over len(files) samples), which emits
+    the pairs' rows in pair order.  genomes (the files' balance_genome.GenomeBias, --balance-genome): nothing is read again --
+    the pairs' resident records are balanced in shared launches (balance_genome.balanced_batches) and join the batch."""
     from .trans import read_trans_contacts
-    from .trans_genome import TransGenomeCaller
-    state = {"first": True, "t0": time.time()}
+    if genomes is not None:
+        from .balance_genome import balanced_batches
+        for per_sample in zip(*(balanced_batches(gb, pairs) for gb in genomes)):
+            k = per_sample[0][0]
+            caller.hold(k, [records for _, records in per_sample], "%s,%s" % pairs[k])
+        return caller.flush()
 
     def fetch(k):
-        contacts = read_trans_contacts(f, args.norm_method, pairs[k][0], pairs[k][1], res, device=device)
-        return None if contacts is None else contacts[:3]
+        got = [read_trans_contacts(f, args.norm_method, pairs[k][0], pairs[k][1], res, device=device) for f in files]
+        if len({g[3] for g in got if g is not None}) > 1:
+            raise ValueError('Both contact maps should have the same resolution.')
+        return [None if g is None else g[:3] for g in got]
 
-    def emit(k, o):
-        chromosome, chromosome2 = pairs[k]
-        print("{0} loops found for chrmosome pair={1},{2}, fdr<{3} in {4}sec".format(
-            len(o), chromosome, chromosome2, args.pt, "%.2f" % (time.time() - state["t0"])))
-        if state["first"] or o:
-            write_loops(args.outdir, chromosome, chromosome2, res, o, first=state["first"])
-            state["first"] = False
-        state["t0"] = time.time()
-
-    caller = TransGenomeCaller([args.s_z * (2 ** i) for i in range(args.octaves)], args.st, args.pt, emit, verbose=args.verbose)
-    if genome is not None:
-        from .balance_genome import balanced_batches
-        for k, records in balanced_batches(genome, pairs):
-            caller.add(k, records, "%s,%s" % pairs[k])
-        return caller.flush()
-    run_trans_pairs(pairs, fetch, caller.add, caller.flush, args.verbose)
+    for k, records in read_ahead(len(pairs), fetch):
+        if args.verbose:
+            print("Reading contact map (pair %s,%s)..." % pairs[k])
+        caller.hold(k, records, "%s,%s" % pairs[k])
+        del records
+    caller.flush()
 
 
 def owned_chromosomes(f, res, pairs, rank, world):
@@ -691,134 +630,56 @@ def owned_chromosomes(f, res, pairs, rank, world):
     return [i for i in range(len(pairs)) if owner[i] == rank]
 
 
-def main(argv=None):
-    start_time = time.time()
-    args = parse_args(sys.argv[1:] if argv is None else argv)
-    from .sharding import init_from_env
-    rank, _world = init_from_env()      # multi-GPU: blocks of each chromosome are sharded, rank 0 writes the TSV
-    print("\n")
-    f = args.f_path
-    if args.bed and args.mat:
-        f = args.mat
-    if not f or not os.path.exists(f):
-        print("Error: Couldn't find the specified contact files")
-        return
-    res = parseBP(args.resolution)
-    if not res:
-        print("Error: Invalid resolution")
-        return
-    from .pairs import refusal as pairs_refusal
-    why = pairs_refusal(f, args.balance, args.biasfile, args.norm_method, args.chromosome, args.chromosome2, args.trans_all,
-                        args.balance_genome, args.pairs_zero_based, _world, pairs_trans=args.pairs_trans)
-    if why:
-        print("Error: %s" % why)
-        return
-    if args.pairs_trans:                     # the file's one parse keeps the trans rows, whoever asks for the handle first
-        from .balance import BalanceError
-        from .balance_genome import pairs_open
-        from .pairs import want_trans
-        want_trans(f)
-        try:                                 # parsed here, before the GPU is touched: a file without `#chromsize` lines ends the run
-            pairs_open(f, args.pairs_zero_based)
-        except BalanceError as e:
-            print("Error: %s" % e)
+def call_trans_all(f, args, res, run):
+    """mustache's --trans-all run (run_trans_all): rows are written in pair order, the header with the first pair's"""
+    import torch
+    from .trans_genome import TransGenomeCaller
+    device = torch.device("cuda", torch.cuda.current_device())
+    genomes = None
+    if run.genome is not None:
+        genomes = genome_biases_or_error([f], res, run.genome, device, args.pairs_zero_based, args.verbose)
+        if genomes is None:
             return
-    if args.trans_all:
-        pairs = trans_all_pairs(f, res, args.chromosome, args.chromosome2, args.pairs_trans, args.pairs_zero_based)
-        if not isinstance(pairs, str):
-            if _world > 1:
-                pairs = "Error: inter-chromosomal pairs run on one GPU only (this run has %d ranks)" % _world
-            elif args.balance is not None:
-                pairs = "Error: --balance does not apply to inter-chromosomal pairs"
-        if isinstance(pairs, str):
-            print(pairs)
-            return
-        from .balance import BalanceError
-        from .balance_genome import request_of
-        try:
-            genome = request_of(args, f, args.biasfile, _world, pairs)
-        except BalanceError as e:
-            print("Error: %s" % e)
-            return
-        import torch
-        device = torch.device("cuda", torch.cuda.current_device())
-        if genome is not None:
-            genome = genome_bias_or_error(f, res, genome, device, args.pairs_zero_based, args.verbose)
-            if genome is None:
-                return
-        return run_trans_all(f, args, res, pairs, device=device, genome=genome)
-    pairs = chromosome_pairs(f, res, args.chromosome, args.chromosome2, args.pairs_zero_based)
-    if isinstance(pairs, str):
-        print(pairs)
-        return
-    distFilter = resolve_distance_filter(args.distFilter, res)
+    state = {"first": True, "t0": time.time()}
 
+    def emit(k, o):
+        chromosome, chromosome2 = run.trans[k]
+        print("{0} loops found for chrmosome pair={1},{2}, fdr<{3} in {4}sec".format(
+            len(o), chromosome, chromosome2, args.pt, "%.2f" % (time.time() - state["t0"])))
+        if state["first"] or o:
+            write_loops(args.outdir, chromosome, chromosome2, res, o, first=state["first"])
+            state["first"] = False
+        state["t0"] = time.time()
+
+    caller = TransGenomeCaller(octave_values(args), args.st, args.pt, emit, verbose=args.verbose)
+    run_trans_all([f], args, res, run.trans, caller, device, genomes)
+
+
+def call_cis_pairs(f, args, res, pairs, balance, distFilter, rank, world, device, start_time, new_pipeline):
+    """The intra-chromosomal pairs of a mustache run.  Returns None when the rows are written (by rank 0, chromosome by
+    chromosome), and {pair index: rows} of this rank's chromosomes when a multi-GPU run is sharded by chromosome (main gathers).
+    new_pipeline(): the ChromosomePipeline of a run that batches several chromosomes, made when the first one is at hand."""
     chrSize_in_bp = False
     if args.chrSize_file:
         import pandas as pd
         csz = pd.read_csv(args.chrSize_file, header=None, sep='\t')
         chrSize_in_bp = {"chr" + str(csz.iloc[i, 0]).replace('chr', ''): csz.iloc[i, 1] for i in range(csz.shape[0])}
-
-    if args.biasfile and not os.path.exists(args.biasfile):
-        print("Error: Couldn't find specified bias file")
-        return
     biasf = args.biasfile if args.biasfile else False
-    if args.balance is not None:
-        from .balance import BalanceError, check_request
-        try:
-            args.balance = check_request(args.balance, f, args.biasfile, args.norm_method, _world)
-        except BalanceError as e:
-            print("Error: %s" % e)
-            return
-    # inter-chromosomal pairs (mustache_amd/trans.py) run after every intra-chromosomal pair, in pair order
-    trans_pairs = [p for p in pairs if p[0] != p[1]]
-    pairs = [p for p in pairs if p[0] == p[1]]
-    if trans_pairs:
-        refusal = None
-        if not args.chromosome or args.chromosome == 'n':
-            refusal = "inter-chromosomal pairs need -ch and -ch2 (all-pairs runs are not supported)"
-        elif _world > 1:
-            refusal = "inter-chromosomal pairs run on one GPU only (this run has %d ranks)" % _world
-        elif args.balance is not None:
-            refusal = "--balance does not apply to inter-chromosomal pairs"
-        if refusal:
-            print("Error: %s" % refusal)
-            return
-    from .balance import BalanceError
-    from .balance_genome import request_of
-    try:
-        gbias = request_of(args, f, args.biasfile, _world, pairs + trans_pairs)
-    except BalanceError as e:
-        print("Error: %s" % e)
-        return
-
-    try:                                     # the reader thread below must upload to THIS thread's device, not to GPU 0
-        import torch
-        my_device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
-    except ImportError:
-        my_device = None
-
-    def fetch(i):
-        chromosome, chromosome2 = pairs[i]
-        CHRM_SIZE = chrSize_in_bp["chr" + str(chromosome).replace('chr', '')] if chrSize_in_bp else False
-        try:
-            from ._lib import stage
-            with stage("read %s" % chromosome):
-                return read_contacts(f, args.norm_method, CHRM_SIZE, res, distFilter, biasf, chromosome, chromosome2,
-                                     verbose=args.verbose, packed=True, part=(0, 1) if by_chromosome else (rank, _world),
-                                     device=my_device, balance=args.balance, pairs_zero_based=args.pairs_zero_based)
-        except BaseException as e:          # re-raised in the main thread, at this chromosome's turn
-            return e
-
     # Multi-GPU: a single chromosome (or fewer chromosomes than GPUs) is sharded by BLOCKS, every rank reading the same
     # input; a whole-genome run is sharded by CHROMOSOME (largest first, sharding.assign_chromosomes), each rank reading and
     # running only its own -- small chromosomes would otherwise be cut into launches of a few blocks per GPU.
-    by_chromosome = _world > 1 and len(pairs) >= _world
-    mine = owned_chromosomes(f, res, pairs, rank, _world) if by_chromosome else list(range(len(pairs)))
+    by_chromosome = world > 1 and len(pairs) >= world
+    mine = owned_chromosomes(f, res, pairs, rank, world) if by_chromosome else list(range(len(pairs)))
 
-    # the next chromosome is read (host I/O; the native .hic reader and pandas release the GIL) while the GPU works on
-    # the current one -- the reference reads and computes strictly in turn (mustache.py:1057-1080)
-    from concurrent.futures import ThreadPoolExecutor
+    def fetch(k):                            # on the reader thread: it must upload to THIS thread's device, not to GPU 0
+        chromosome, chromosome2 = pairs[mine[k]]
+        CHRM_SIZE = chrSize_in_bp["chr" + str(chromosome).replace('chr', '')] if chrSize_in_bp else False
+        from ._lib import stage
+        with stage("read %s" % chromosome):
+            return read_contacts(f, args.norm_method, CHRM_SIZE, res, distFilter, biasf, chromosome, chromosome2,
+                                 verbose=args.verbose, packed=True, part=(0, 1) if by_chromosome else (rank, world),
+                                 device=device, balance=balance, pairs_zero_based=args.pairs_zero_based)
+
     results = {}
 
     def emit(i, o):
@@ -842,69 +703,68 @@ def main(argv=None):
     # Several chromosomes on this rank (a whole-genome run): their normalised bands are collected in HBM and ALL their
     # blocks go through one sequence of launches (pipeline.run_genome) -- same loops as chromosome by chromosome, without
     # the launch-bound tail of 5-31 blocks per chromosome.  pipeline.GenomeBatcher bounds the bands held at once.
-    batched = len(mine) > 1 and (_world == 1 or by_chromosome)
+    batched = len(mine) > 1 and (world == 1 or by_chromosome)
     from .pipeline import GenomeBatcher
     pipe = None
     genome = GenomeBatcher(lambda: pipe.device, lambda bands, ns, dpx: pipe.run_genome(bands, ns, dpx, args.st, args.pt),
                            lambda band, n, dpx: pipe.run_band(band, n, dpx, args.st, args.pt, distributed=False), emit)
 
-    with ThreadPoolExecutor(max_workers=1) as pool:
-        ahead = pool.submit(fetch, mine[0]) if mine else None
-        for k, i in enumerate(mine):
-            chromosome, chromosome2 = pairs[i]
-            contacts = ahead.result()
-            ahead = pool.submit(fetch, mine[k + 1]) if k + 1 < len(mine) else None
-            if isinstance(contacts, BaseException):
-                raise contacts
-            if not batched:
-                emit(i, [] if contacts is None else regulator(
-                    f, args.norm_method, False, args.outdir, bed=args.bed, res=getattr(contacts, "res", None) or contacts[3],
-                    sigma0=args.s_z, s=args.s, verbose=args.verbose, pt=args.pt, st=args.st, distance_filter=distFilter,
-                    nprocesses=args.nprocesses, bias=biasf, chromosome=chromosome, chromosome2=chromosome2,
-                    octaves=args.octaves, contacts=contacts, shard_blocks=not by_chromosome))
-                continue
-            if contacts is None:
-                genome.skip(i)
-                continue
-            if pipe is None:
-                from .pipeline import ChromosomePipeline
-                pipe = ChromosomePipeline([args.s_z * (2 ** o_) for o_ in range(args.octaves)])
-                from .engine import settle_gc
-                settle_gc()                   # the command-line process only; the library leaves the collector alone
-            _check_pair(f, chromosome, chromosome2)
-            from .hicfile import PackedContacts
-            is_packed = isinstance(contacts, PackedContacts)
-            res_c = contacts.res if is_packed else contacts[3]
-            dpx = int(math.ceil(distFilter // res_c))
-            if args.verbose:
-                print("Normalizing contact map...")
-            if is_packed:
-                band, n = pipe.normalized_band_packed(contacts, dpx)
-            else:
-                band, n = pipe.normalized_band(contacts[0], contacts[1], contacts[2], res_c, dpx)
-            del contacts
-            genome.add(i, band, n, dpx, band.numel() * 8)
-            del band                          # the batcher's reference is the only one: run_genome releases it as it copies
-        genome.flush()
-    first = not pairs                        # the header is written with the first pair's rows
-    if gbias is not None:                    # --balance-genome: every matrix is read once, here; the pairs are called from it
-        gbias = genome_bias_or_error(f, res, gbias, my_device, args.pairs_zero_based, args.verbose)
+    # the next chromosome is read (host I/O; the native .hic reader and pandas release the GIL) while the GPU works on
+    # the current one -- the reference reads and computes strictly in turn (mustache.py:1057-1080)
+    for k, contacts in read_ahead(len(mine), fetch):
+        i = mine[k]
+        chromosome, chromosome2 = pairs[i]
+        if not batched:
+            emit(i, [] if contacts is None else regulator(
+                f, args.norm_method, False, args.outdir, bed=args.bed, res=getattr(contacts, "res", None) or contacts[3],
+                sigma0=args.s_z, s=args.s, verbose=args.verbose, pt=args.pt, st=args.st, distance_filter=distFilter,
+                nprocesses=args.nprocesses, bias=biasf, chromosome=chromosome, chromosome2=chromosome2,
+                octaves=args.octaves, contacts=contacts, shard_blocks=not by_chromosome))
+            continue
+        if contacts is None:
+            genome.skip(i)
+            continue
+        if pipe is None:
+            pipe = new_pipeline()
+        from .hicfile import PackedContacts
+        is_packed = isinstance(contacts, PackedContacts)
+        res_c = contacts.res if is_packed else contacts[3]
+        dpx = int(math.ceil(distFilter // res_c))
+        if args.verbose:
+            print("Normalizing contact map...")
+        if is_packed:
+            band, n = pipe.normalized_band_packed(contacts, dpx)
+        else:
+            band, n = pipe.normalized_band(contacts[0], contacts[1], contacts[2], res_c, dpx)
+        del contacts
+        genome.add(i, band, n, dpx, band.numel() * 8)
+        del band                          # the batcher's reference is the only one: run_genome releases it as it copies
+    genome.flush()
+    return results if by_chromosome else None
+
+
+def call_trans_pairs(f, args, res, run, distFilter, device):
+    """The inter-chromosomal pairs of a mustache run (mustache_amd/trans.py), one by one in pair order after every
+    intra-chromosomal pair; the header is written with the run's first pair's rows."""
+    biasf = args.biasfile if args.biasfile else False
+    first = not run.cis
+    gbias = None
+    if run.genome is not None:               # --balance-genome: every matrix is read once, here; the pairs are called from it
+        from .balance_genome import balanced_pair
+        gbias = genome_biases_or_error([f], res, run.genome, device, args.pairs_zero_based, args.verbose)
         if gbias is None:
             return
-    for chromosome, chromosome2 in trans_pairs:
+    for chromosome, chromosome2 in run.trans:
         start_time = time.time()
-        if gbias is None:
-            _check_pair(f, chromosome, chromosome2)      # text input: the reference's refusal
         if gbias is not None:
-            from .balance_genome import balanced_pair
-            contacts = balanced_pair(gbias, chromosome, chromosome2)
+            contacts = balanced_pair(gbias[0], chromosome, chromosome2)
             if contacts is None:
                 print("There is no contact in the chromosome pair %s,%s to work on." % (chromosome, chromosome2))
             else:
                 contacts = contacts + (res,)
         else:
             contacts = read_contacts(f, args.norm_method, False, res, distFilter, biasf, chromosome, chromosome2,
-                                     verbose=args.verbose, device=my_device)
+                                     verbose=args.verbose, device=device)
         o = [] if contacts is None else regulator(
             f, args.norm_method, False, args.outdir, res=contacts[3], sigma0=args.s_z, verbose=args.verbose, pt=args.pt,
             st=args.st, distance_filter=distFilter, chromosome=chromosome, chromosome2=chromosome2, octaves=args.octaves,
@@ -914,14 +774,47 @@ def main(argv=None):
         if first or o:
             write_loops(args.outdir, chromosome, chromosome2, res, o, first=first)
             first = False
-    if by_chromosome:
+
+
+def main(argv=None):
+    start_time = time.time()
+    args = parse_args(sys.argv[1:] if argv is None else argv)
+    from .request import plan, refuse, request_of
+    from .sharding import init_from_env
+    rank, world = init_from_env()       # multi-GPU: blocks of each chromosome are sharded, rank 0 writes the TSV
+    print("\n")
+    f = args.mat if args.bed and args.mat else args.f_path
+    res = parseBP(args.resolution)
+    run = plan(request_of(args, [f], [(args.biasfile, "Couldn't find specified bias file")], "-b", world, text_pair_raises=True),
+               res)
+    if isinstance(run, str):
+        return refuse(run)
+    if run.trans_all:
+        return call_trans_all(f, args, res, run)
+    distFilter = resolve_distance_filter(args.distFilter, res)
+    try:
+        import torch
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+    except ImportError:
+        device = None
+    def new_pipeline():
+        from .engine import settle_gc
+        from .pipeline import ChromosomePipeline
+        pipe = ChromosomePipeline(octave_values(args))
+        settle_gc()                       # the command-line process only; the library leaves the collector alone
+        return pipe
+
+    results = call_cis_pairs(f, args, res, run.cis, run.balance, distFilter, rank, world, device, start_time, new_pipeline)
+    call_trans_pairs(f, args, res, run, distFilter, device)
+    if results is not None:
         # one gather of (chromosome index, x, y, fdr, sigma) records; rank 0 writes the chromosomes in their order
         from .sharding import gather_chromosome_rows
-        per_chromosome = gather_chromosome_rows(results, len(pairs), 4)
+        per_chromosome = gather_chromosome_rows(results, len(run.cis), 4)
         for i, rows in enumerate(per_chromosome or []):
             o = [[np.int64(a), np.int64(b), np.float64(q), np.float64(sg)] for a, b, q, sg in rows]
             if i == 0 or o:
-                write_loops(args.outdir, pairs[i][0], pairs[i][1], res, o, first=(i == 0))
+                write_loops(args.outdir, run.cis[i][0], run.cis[i][1], res, o, first=(i == 0))
+
 
 
 if __name__ == '__main__':

@@ -248,52 +248,6 @@ def list_chromosomes(path, zero_based=False):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# what the command lines refuse
-# ----------------------------------------------------------------------------------------------------------------------
-def refusal(files, balance, bias, norm_method, ch, ch2, trans_all, balance_genome, zero_based, world=1, bias_flag="-b",
-            pairs_trans=False):
-    """The text behind `Error:` of a run that its pairs input (or --pairs-zero-based / --pairs-trans without one) rules out, or
-    None.  Reads nothing and touches no GPU.  files: the input path(s); ch / ch2: the -ch / -ch2 lists ('n' when absent);
-    pairs_trans: --pairs-trans, which keeps the trans rows of the pairs input for --balance-genome (balance_genome.py)."""
-    files = [files] if isinstance(files, str) else list(files)
-    mine = [f for f in files if is_pairs(f)]
-    if not mine:
-        if pairs_trans:
-            return "--pairs-trans is for .pairs / .pairs.gz input (%s is none)" % ", ".join(str(f) for f in files)
-        if zero_based:
-            return "--pairs-zero-based is for .pairs / .pairs.gz input (%s is none)" % ", ".join(str(f) for f in files)
-        return None
-    other = isinstance(ch2, list) and (not isinstance(ch, list) or len(ch) != len(ch2) or any(a != b for a, b in zip(ch, ch2)))
-    if pairs_trans:
-        if not trans_all and not other:
-            return "--pairs-trans on a run with no inter-chromosomal pair: give --trans-all, or -ch A -ch2 B"
-        if balance is not None or bias or (norm_method and str(norm_method).upper() != "NONE"):
-            return "--pairs-trans with --balance, %s or -norm: the trans rows of %s are raw read pairs and are balanced with " \
-                   "the whole genome; give --balance-genome ICE|NEWTON alone" % (bias_flag, mine[0])
-        if balance_genome is None:
-            return "--pairs-trans without --balance-genome: %s holds raw read pairs; give --balance-genome ICE|NEWTON" % mine[0]
-        if world > 1:
-            return "--pairs-trans in a multi-rank run (world size %d): the genome is balanced on one GPU; start a single " \
-                   "process" % world
-        return None
-    without = "without --pairs-trans only intra-chromosomal loops are called from a pairs file"
-    if trans_all:
-        return "--trans-all and %s: %s" % (mine[0], without)
-    if balance_genome is not None:
-        return "--balance-genome and %s: %s; use --balance" % (mine[0], without)
-    if other:
-        return "-ch2 with another chromosome and %s: %s" % (mine[0], without)
-    if balance is None:
-        return "%s holds raw read pairs: give --balance ICE|NEWTON" % mine[0]
-    from .balance import BalanceError, check_request
-    try:
-        check_request(balance, files, bias, norm_method, world, bias_flag=bias_flag)
-    except BalanceError as e:
-        return str(e)
-    return None
-
-
-# ----------------------------------------------------------------------------------------------------------------------
 # the device binning
 # ----------------------------------------------------------------------------------------------------------------------
 class Pixels:

@@ -423,8 +423,8 @@ def _read_pair(f, norm, A, B, res, device):
 def _pileup_trans(f, table, res, chromosomes, norm, bias, balance, w, q, n_min, x_max, device, verbose):
     """pileup() in trans mode: one pile-up per chromosome pair."""
     import torch
-    from .diff_trans import refusal
-    why = refusal((f,), balance, 1)
+    from .request import balance_on_trans, trans_input
+    why = trans_input((f,)) or balance_on_trans(balance or None)
     if why is None and bias:
         why = "-b does not apply to inter-chromosomal pairs"
     if why:

@@ -143,7 +143,8 @@ def read_trans_contacts(f, norm_method, chr_a, chr_b, res, device=None):
         from .readers import read_cooler_trans
         x, y, v, res = read_cooler_trans(f, chr_a, chr_b, res, norm_method)
     else:
-        raise TransError("Interchromosomal analysis is only supported for .hic and .cool input formats.")
+        from .request import TEXT_ON_TRANS
+        raise TransError(TEXT_ON_TRANS)
     if len(v) == 0:
         return None
     return x, y, v, res

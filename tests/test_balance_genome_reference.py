@@ -200,13 +200,20 @@ def test_check_genome_request():
         assert text in str(e.value)
 
 
-def test_positional_signatures_are_kept():
-    from mustache_amd.diff_mustache import trans_all_request
-    from mustache_amd.diff_trans import refusal
-    assert trans_all_request("a.hic", "b.hic", 10000, ["1", "2"], 'n', None, 1) == [("1", "2")]
-    assert trans_all_request("a.hic", "b.hic", 10000, ["1", "2"], 'n', "ICE", 1) == OLD_LINE
-    assert refusal(("a.hic", "b.hic"), None, 1) is None
-    assert refusal(("a.hic", "b.hic"), "ICE", 1, True) == OLD_LINE[len("Error: "):]
+def test_positional_signatures_are_kept(tmp_path):
+    """what diff_mustache.trans_all_request and diff_trans.refusal answered before the rules moved, through request.plan()"""
+    from mustache_amd.request import Request, plan
+
+    def ask(files, ch, ch2, balance, ranks, trans_all):
+        for f in files:
+            (tmp_path / f).write_bytes(b"")
+        run = plan(Request([str(tmp_path / f) for f in files], [(None, ""), (None, "")], "-b1/-b2", False, balance, None, "all",
+                           False, False, False, trans_all, ch, ch2, ranks, False), 10000)
+        return run if isinstance(run, str) else run.trans
+    assert ask(("a.hic", "b.hic"), ["1", "2"], 'n', None, 1, True) == [("1", "2")]
+    assert ask(("a.hic", "b.hic"), ["1", "2"], 'n', "ICE", 1, True) == OLD_LINE
+    assert ask(("a.hic", "b.hic"), ["1"], ["2"], None, 1, False) == [("1", "2")]
+    assert ask(("a.hic", "b.hic"), ["1"], ["2"], "ICE", 1, False) == OLD_LINE
 
 
 # ---- 5. defaults ------------------------------------------------------------------------------------------------------------

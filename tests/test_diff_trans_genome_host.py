@@ -44,10 +44,20 @@ def test_refusals_print_their_line_and_write_no_file(monkeypatch, tmp_path, caps
     assert not any((tmp_path / ("o" + suf)).exists() for suf in SUFFIXES)
 
 
-def test_the_request_names_the_pairs_of_the_first_file_in_order(monkeypatch):
+def test_the_request_names_the_pairs_of_the_first_file_in_order(monkeypatch, tmp_path):
     from mustache_amd import readers
-    from mustache_amd.diff_mustache import trans_all_request
-    monkeypatch.setattr(readers, "list_chromosomes", lambda f, res: ["1", "2", "X"] if f == "a.hic" else ["9"])
+    from mustache_amd.request import Request, plan
+    for name in ("a.hic", "b.hic", "b.mcool", "b.txt"):
+        (tmp_path / name).write_bytes(b"")
+
+    def trans_all_request(f1, f2, res, ch, ch2, balance, world_size):
+        """the two-sample --trans-all request through request.plan(): the pairs, or the Error: line"""
+        run = plan(Request(files=[str(tmp_path / f1), str(tmp_path / f2)], bias=[(None, ""), (None, "")], bias_flag="-b1/-b2",
+                           norm_method=False, balance=balance, balance_genome=None, balance_pixels="all",
+                           balance_pixels_given=False, pairs_trans=False, pairs_zero_based=False, trans_all=True, ch=ch, ch2=ch2,
+                           ranks=world_size, text_pair_raises=False), res)
+        return run if isinstance(run, str) else run.trans
+    monkeypatch.setattr(readers, "list_chromosomes", lambda f, res: ["1", "2", "X"] if f.endswith("a.hic") else ["9"])
     assert trans_all_request("a.hic", "b.mcool", 10000, 'n', 'n', None, 1) == [("1", "2"), ("1", "X"), ("2", "X")]
     assert trans_all_request("a.hic", "b.hic", 10000, ["3", "1", "2"], 'n', None, 1) == [("3", "1"), ("3", "2"), ("1", "2")]
     assert trans_all_request("a.hic", "b.hic", 10000, ["7"], 'n', None, 1) == []

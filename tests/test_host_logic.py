@@ -621,7 +621,7 @@ def test_genome_batcher_hands_run_many_the_only_references(monkeypatch):
 
 def test_chromosome_pairs(monkeypatch):
     import mustache_amd.readers as rd
-    from mustache_amd.mustache import chromosome_pairs
+    from mustache_amd.request import chromosome_pairs
     assert chromosome_pairs("m.txt", 5000, ["1", "2"], "n") == [("1", "1"), ("2", "2")]
     assert chromosome_pairs("m.hic", 5000, ["1", "2"], ["3", "2"]) == [("1", "3"), ("2", "2")]
     assert chromosome_pairs("m.txt", 5000, "n", "n") == "Error: Please enter the chromosome name."

@@ -219,7 +219,7 @@ def test_dense_diagonals_and_the_far_list_sum():
 
 def test_the_handle_is_cached_per_path(tmp_path):
     from mustache_amd import pairs
-    from mustache_amd.mustache import chromosome_pairs
+    from mustache_amd.request import chromosome_pairs
     p = tmp_path / "c.pairs"
     p.write_text(FILES["header"])
     q = tmp_path / "d.pairs"

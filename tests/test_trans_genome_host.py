@@ -66,7 +66,8 @@ def test_launch_groups_are_runs_of_equal_tile_size_over_contiguous_pairs():
 
 def test_trans_all_pairs_and_refusals(monkeypatch, tmp_path, capsys):
     from mustache_amd import readers
-    from mustache_amd.mustache import main, parse_args, trans_all_pairs
+    from mustache_amd.mustache import main, parse_args
+    from mustache_amd.request import trans_all_pairs
     monkeypatch.setattr(readers, "list_chromosomes", lambda f, res: ["1", "2", "X"])
     assert trans_all_pairs("g.hic", 10000, 'n', 'n') == [("1", "2"), ("1", "X"), ("2", "X")]
     assert trans_all_pairs("g.mcool", 10000, None, 'n') == [("1", "2"), ("1", "X"), ("2", "X")]
