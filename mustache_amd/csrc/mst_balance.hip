@@ -318,17 +318,6 @@ __device__ __forceinline__ double genome_bias_at(const double *b, int64_t n, int
     return (v >= 0.2) ? v : INFINITY;
 }
 
-// the pair of record e: the largest p in [0, P) with seg_off[p] <= e (empty segments are stepped over).  The result stays in
-// [0, P) whatever seg_off holds, so row_off / col_off are never read out of bounds.
-__device__ __forceinline__ int32_t pair_of(const int64_t *__restrict__ seg_off, int32_t P, int64_t e) {
-    int32_t lo = 0, hi = P;
-    while (hi - lo > 1) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (seg_off[mid] <= e) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // One pass, no atomics.  kVec: a thread takes the records 2 t and 2 t + 1 -- their coordinates as one 8-byte load each, their
 // values as one 16-byte load and one 16-byte store (the host takes this path when the pointers are aligned for it); the second
 // record looks its pair up again only when it lies past the first one's segment.
@@ -346,21 +335,21 @@ apply_pairs_kernel(const int32_t *__restrict__ x, const int32_t *__restrict__ y,
             const int2 xx = *reinterpret_cast<const int2 *>(x + e);
             const int2 yy = *reinterpret_cast<const int2 *>(y + e);
             const double2 vv = *reinterpret_cast<const double2 *>(v + e);
-            int32_t p = pair_of(seg_off, P, e);
+            int32_t p = mst::segment_of(seg_off, 0, P, e);
             double2 o;
             o.x = (vv.x / genome_bias_at(bias, n, row_off[p], xx.x)) / genome_bias_at(bias, n, col_off[p], yy.x);
-            if (p + 1 < P && seg_off[p + 1] <= e + 1) p = pair_of(seg_off, P, e + 1);
+            if (p + 1 < P && seg_off[p + 1] <= e + 1) p = mst::segment_of(seg_off, 0, P, e + 1);
             o.y = (vv.y / genome_bias_at(bias, n, row_off[p], xx.y)) / genome_bias_at(bias, n, col_off[p], yy.y);
             *reinterpret_cast<double2 *>(out + e) = o;
         }
         if ((N & 1) && t0 == 0) {                                // the odd record at the end
             const int64_t e = N - 1;
-            const int32_t p = pair_of(seg_off, P, e);
+            const int32_t p = mst::segment_of(seg_off, 0, P, e);
             out[e] = (v[e] / genome_bias_at(bias, n, row_off[p], x[e])) / genome_bias_at(bias, n, col_off[p], y[e]);
         }
     } else {
         for (int64_t e = t0; e < N; e += stride) {
-            const int32_t p = pair_of(seg_off, P, e);
+            const int32_t p = mst::segment_of(seg_off, 0, P, e);
             out[e] = (v[e] / genome_bias_at(bias, n, row_off[p], x[e])) / genome_bias_at(bias, n, col_off[p], y[e]);
         }
     }

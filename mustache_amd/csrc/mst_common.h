@@ -1,4 +1,5 @@
-// Shared host-side helpers for libmustache_hip.so (error reporting, launch checks).
+// Shared helpers for libmustache_hip.so: host side (error reporting, launch checks), and the one device routine that several
+// files need (segment_of).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -24,6 +25,17 @@ int fail(int code, const char *fmt, ...);   // formats into error_buffer(), retu
 #define MST_LAUNCH_CHECK() MST_HIP(hipGetLastError())
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// The segment that holds e: the largest p in [lo, hi) with off[p] <= e.  off is non-decreasing and off[lo] <= e is the caller's
+// word; empty segments (equal offsets) are stepped over; the result stays in [lo, hi) whatever off holds, so a table indexed
+// by it is never read out of bounds.
+__device__ __forceinline__ int32_t segment_of(const int64_t *__restrict__ off, int32_t lo, int32_t hi, int64_t e) {
+    while (hi - lo > 1) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (off[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel: raise it once per (call site, device),
 // so a process that drives several GPUs gets it on each of them.  `done` = the call site's static bit mask of devices.

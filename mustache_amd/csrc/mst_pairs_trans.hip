@@ -5,16 +5,14 @@
 // posA and the position on b in posB.  A pixel's key is cell_off[p] + x * n_b + y (x = bin on a, y = bin on b; cell_off = the
 // running sum of n_a * n_b over the pairs before p): unique across pairs, and ascending keys are pair-major.
 //
-//   mst_pairs_bin_trans      one grid-stride pass over the rows: each lane finds its row's pair (wave-uniform when lanes 0 and 63
-//                            lie in one segment, a per-lane binary search of seg_off otherwise), bins its row or marks it
-//                            dropped; runs of adjacent lanes with equal keys are merged as in mst_pairs_bin and only a run's head
-//                            lane writes -- one no-return integer atomic add of the run length into dense[key] for
-//                            key < dense_cells, one (key, multiplicity) entry of the far list otherwise.  The far list's slots are
-//                            reserved ONCE PER WORKGROUP AND TRIP: the waves' counts go through LDS, thread 0 issues one
-//                            returning atomic, the base is broadcast (returning atomics on one address are served one after the
-//                            other: DESIGN section 8b).
-//   mst_pairs_trans_compact  the non-zero counters -> (key, count) in ascending key order: count per tile, scan, write
-//                            (mst_pairs_tiles.h).  No atomics.
+//   mst_pairs_bin_trans      one grid-stride pass over the rows.  The kernel holds the trans rule alone: each lane finds its row's
+//                            pair (wave-uniform when lanes 0 and 63 lie in one segment, a per-lane binary search of seg_off
+//                            otherwise), bins its row or marks it dropped (counted per pair); the key is the cell, its counter
+//                            dense[key] when key < dense_cells, the far list otherwise.  The run merge, the head lane's add and
+//                            the far list with its one reservation per workgroup and trip are the shared trip body
+//                            (mst_pairs_tiles.h), as in mst_pairs_bin.
+//   mst_pairs_trans_compact  the non-zero counters -> (key, count) in ascending key order: the shared compaction with the
+//                            emitter that writes the index as the key.  No atomics.
 //   mst_pairs_trans_decode   ascending keys + int64 counts -> (x int32, y int32, v float64): a binary search of cell_off per key.
 //
 // Every sum is an integer sum: the counters, the far list as a multiset and the dropped counts are the same from run to run and
@@ -23,21 +21,6 @@
 
 namespace {
 
-constexpr int kUnroll = 8;                          // groups of 64 consecutive rows per wave and trip
-constexpr int kWaves = kThreads / 64;
-constexpr int kRowsPerBlock = kThreads * kUnroll;   // 2048 rows per workgroup and trip
-
-// the largest p in [lo, P) with off[p] <= e; off[lo] <= e is the caller's word.  With empty segments (equal offsets) that is the
-// one that holds e.
-__device__ __forceinline__ int32_t find_segment(const int64_t *__restrict__ off, int32_t lo, int32_t P, int64_t e) {
-    int32_t hi = P;
-    while (hi - lo > 1) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= e) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(kThreads) void
 pairs_bin_trans_kernel(const int32_t *__restrict__ posA, const int32_t *__restrict__ posB, int64_t N,
                        const int64_t *__restrict__ seg_off, int32_t P, const int64_t *__restrict__ limA,
@@ -45,35 +28,30 @@ pairs_bin_trans_kernel(const int32_t *__restrict__ posA, const int32_t *__restri
                        const int64_t *__restrict__ cell_off, int32_t res, int32_t zero_based, int64_t dense_cells,
                        uint32_t *__restrict__ dense, int64_t *__restrict__ far_key, uint32_t *__restrict__ far_mult,
                        int64_t far_cap, unsigned long long *__restrict__ n_far_out, unsigned long long *__restrict__ dropped) {
-    __shared__ uint32_t wave_far[2][kWaves];        // by trip parity: a fast wave's next trip leaves this trip's counts alone
-    __shared__ unsigned long long slot_base[2];
+    __shared__ BinSlots slots;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t stride = (int64_t)gridDim.x * kRowsPerBlock;
     const int32_t lo = zero_based ? 0 : 1;
-    const unsigned long long below = (1ull << lane) - 1ull;      // the lanes before this one
     int32_t p_wave = 0;                             // wave-uniform: the pair of the wave's first row; rows only go forward
     int parity = 0;
-    // the trip count is the same for every wave of a workgroup (the barriers need that) and for every lane of a wave (the
-    // shuffles and ballots do)
+    // the trip count is the same for every wave of a workgroup (bin_far's barriers need that) and for every lane of a wave (the
+    // shuffles and ballots do); `base < N` and `e0 < N` guard the loads only
     for (int64_t block_base = (int64_t)blockIdx.x * kRowsPerBlock; block_base < N; block_base += stride, parity ^= 1) {
         const int64_t base = block_base + (int64_t)wave * (64 * kUnroll);
-        long long key[kUnroll];
-        uint32_t run[kUnroll];
-        unsigned long long fars[kUnroll];
-        uint32_t n_far = 0;
-        if (base < N) p_wave = __builtin_amdgcn_readfirstlane(find_segment(seg_off, p_wave, P, base));
+        BinTrip t;
+        if (base < N) p_wave = __builtin_amdgcn_readfirstlane(mst::segment_of(seg_off, p_wave, P, base));
         int32_t p_group = p_wave;
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
             const int64_t e0 = base + u * 64, e = e0 + lane;
             const bool active = e < N;
             bool ok = false;
-            long long k = active ? -1 : -2;
+            long long cell = 0;
             if (e0 < N) {                           // wave-uniform
                 const int64_t last = e0 + 63 < N ? e0 + 63 : N - 1;
-                p_group = __builtin_amdgcn_readfirstlane(find_segment(seg_off, p_group, P, e0));
+                p_group = __builtin_amdgcn_readfirstlane(mst::segment_of(seg_off, p_group, P, e0));
                 const bool one_pair = p_group + 1 >= P || last < seg_off[p_group + 1];       // lanes 0 and 63 in one segment
-                const int32_t p = one_pair ? p_group : (active ? find_segment(seg_off, p_group, P, e) : p_group);
+                const int32_t p = one_pair ? p_group : (active ? mst::segment_of(seg_off, p_group, P, e) : p_group);
                 if (active) {
                     const int32_t a = posA[e], b = posB[e];
                     const int64_t la = limA[p], lb = limB[p], na = nA[p], nb = nB[p];
@@ -81,10 +59,10 @@ pairs_bin_trans_kernel(const int32_t *__restrict__ posA, const int32_t *__restri
                                                            : ((int64_t)a <= la && (int64_t)b <= lb));
                     if (ok) {
                         const int64_t x = (a - lo) / res, y = (b - lo) / res;
-                        ok = x < na && y < nb;      // never a key outside the pair's cells, whatever limits the caller gave
-                        const long long cell = cell_off[p] + x * nb + y;
-                        ok = ok && cell >= 0;       // (a table with a negative entry: dropped, not written)
-                        if (ok) k = cell;
+                        cell = cell_off[p] + x * nb + y;
+                        // never a key outside the pair's cells, whatever limits the caller gave; a table with a negative
+                        // entry: dropped, not written
+                        ok = x < na && y < nb && cell >= 0;
                     }
                 }
                 if (one_pair) {
@@ -94,72 +72,21 @@ pairs_bin_trans_kernel(const int32_t *__restrict__ posA, const int32_t *__restri
                     atomicAdd(&dropped[p], 1ull);
                 }
             }
-            key[u] = k;
-            const long long prev = __shfl_up(k, 1, 64);
-            const bool start = lane == 0 || prev != k;                      // the first lane of a run of equal keys
-            const unsigned long long starts = __ballot(start);
-            const bool head = start && ok;
-            const unsigned long long above = lane == 63 ? 0ull : (starts >> (lane + 1));
-            run[u] = above ? (uint32_t)__ffsll((long long)above) : (uint32_t)(64 - lane);
-            const bool far = head && k >= dense_cells;
-            if (head && !far) atomicAdd(&dense[k], run[u]);
-            fars[u] = __ballot(far);
-            n_far += (uint32_t)__popcll(fars[u]);
+            bin_group(t, u, active, ok, cell, cell < dense_cells, cell, dense);
         }
-        // one returning atomic per workgroup and trip
-        if (lane == 0) wave_far[parity][wave] = n_far;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t all = 0;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) all += wave_far[parity][w];
-            slot_base[parity] = all ? atomicAdd(n_far_out, (unsigned long long)all) : 0ull;
-        }
-        __syncthreads();
-        if (n_far) {                                // wave-uniform
-            int64_t slot = (int64_t)slot_base[parity];
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w)
-                if (w < wave) slot += wave_far[parity][w];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                if ((fars[u] >> lane) & 1ull) {
-                    const int64_t mine = slot + __popcll(fars[u] & below);
-                    if (mine < far_cap) {           // the count goes on: the caller sees an overflow in *n_far > far_cap
-                        far_key[mine] = key[u];
-                        far_mult[mine] = run[u];
-                    }
-                }
-                slot += __popcll(fars[u]);
-            }
-        }
+        bin_far<true>(t, slots, parity, far_key, far_mult, far_cap, n_far_out);
     }
 }
 
-// pass 2 of the compaction: the (key, count) of each tile's non-zero counters, behind those of the tiles before it
-__global__ __launch_bounds__(kThreads) void
-trans_compact_write_kernel(const uint32_t *__restrict__ dense, int64_t total, const int64_t *__restrict__ tile_off,
-                           int64_t *__restrict__ out_key, uint32_t *__restrict__ out_count, int64_t cap) {
-    __shared__ uint32_t wave_sum[kThreads / 64];
-    uint32_t c[kPerThread];
-    const int64_t first = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kPerThread;
-    load_tile(dense, total, first, c);
-    uint32_t mine = 0;
-#pragma unroll
-    for (int k = 0; k < kPerThread; ++k) mine += c[k] != 0u;
-    uint32_t all;
-    const uint32_t incl = block_scan(mine, wave_sum, &all);
-    if (!mine) return;
-    int64_t o = tile_off[blockIdx.x] + (int64_t)(incl - mine);
-#pragma unroll
-    for (int k = 0; k < kPerThread; ++k) {
-        if (c[k] != 0u && o < cap) {
-            out_key[o] = first + k;
-            out_count[o] = c[k];
-            ++o;
-        }
+struct EmitKey {                                    // a counter's index is its key
+    int64_t *key;
+    uint32_t *count;
+    __device__ void seek(int64_t) {}
+    __device__ void operator()(int64_t o, int64_t index, uint32_t c) {
+        key[o] = index;
+        count[o] = c;
     }
-}
+};
 
 __global__ __launch_bounds__(kThreads) void
 trans_decode_kernel(const int64_t *__restrict__ keys, const int64_t *__restrict__ counts, int64_t N,
@@ -168,7 +95,7 @@ trans_decode_kernel(const int64_t *__restrict__ keys, const int64_t *__restrict_
     const int64_t stride = (int64_t)gridDim.x * kThreads;
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < N; i += stride) {
         const int64_t key = keys[i];
-        const int32_t p = find_segment(cell_off, 0, P, key);
+        const int32_t p = mst::segment_of(cell_off, 0, P, key);
         const int64_t cell = key - cell_off[p], nb = nB[p], x = cell / nb;
         out_x[i] = (int32_t)x;
         out_y[i] = (int32_t)(cell - x * nb);
@@ -197,30 +124,13 @@ extern "C" int mst_pairs_bin_trans(const int32_t *posA, const int32_t *posB, int
 }
 
 extern "C" uint64_t mst_pairs_trans_compact_workspace_bytes(int64_t dense_cells) {
-    if (dense_cells < 0) return 0;
-    return (uint64_t)((dense_cells + kTile - 1) / kTile + 1) * sizeof(int64_t);
+    return dense_cells < 0 ? 0 : compact_workspace_bytes(dense_cells);
 }
 
 extern "C" int mst_pairs_trans_compact(const uint32_t *dense, int64_t dense_cells, int64_t *out_key, uint32_t *out_count, int64_t cap,
                                        int64_t *n_out, void *workspace, uint64_t workspace_bytes, void *stream) {
-    if (dense_cells < 0 || cap < 0 || !n_out || (cap > 0 && (!out_key || !out_count)))
-        return mst::fail(MST_E_ARG, "mst_pairs_trans_compact: bad argument");
-    hipStream_t s = mst::as_stream(stream);
-    if (dense_cells == 0) {
-        MST_HIP(hipMemsetAsync(n_out, 0, sizeof(int64_t), s));
-        return MST_OK;
-    }
-    const int64_t tiles = (dense_cells + kTile - 1) / kTile;
-    if (!dense || !workspace || workspace_bytes < mst_pairs_trans_compact_workspace_bytes(dense_cells) || tiles > 0x7fffffff)
-        return mst::fail(MST_E_ARG, "mst_pairs_trans_compact: bad argument");
-    int64_t *tile_off = static_cast<int64_t *>(workspace);
-    compact_count_kernel<<<(int)tiles, kThreads, 0, s>>>(dense, dense_cells, tile_off);
-    MST_LAUNCH_CHECK();
-    compact_scan_kernel<<<1, kThreads, 0, s>>>(tile_off, tiles, n_out);
-    MST_LAUNCH_CHECK();
-    trans_compact_write_kernel<<<(int)tiles, kThreads, 0, s>>>(dense, dense_cells, tile_off, out_key, out_count, cap);
-    MST_LAUNCH_CHECK();
-    return MST_OK;
+    return compact_counters("mst_pairs_trans_compact", dense, dense_cells, EmitKey{out_key, out_count}, out_key && out_count, cap,
+                            n_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mst_pairs_trans_decode(const int64_t *keys, const int64_t *counts, int64_t n, const int64_t *cell_off, const int64_t *nB,

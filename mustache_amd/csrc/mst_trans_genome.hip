@@ -44,16 +44,6 @@ __global__ void chunk_table_kernel(const int64_t *__restrict__ seg_off, int P, i
     chunk_first[P] = run;
 }
 
-// the last p in [lo, hi) with first[p] <= k (first is non-decreasing, first[lo] <= k): the pair of chunk k, or of record k
-__device__ __forceinline__ int last_not_above(const int64_t *__restrict__ first, int lo, int hi, int64_t k) {
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first[mid] <= k) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ int wave_max(int a) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -82,7 +72,7 @@ zseg_sum_kernel(const int32_t *__restrict__ x, const int32_t *__restrict__ y, co
         ext[0] = ext[1] = -1;
     }
     __syncthreads();
-    int cur = last_not_above(chunk_first, 0, P, k0);
+    int cur = mst::segment_of(chunk_first, 0, P, k0);
     for (int64_t k = k0; k < k1; ++k) {
         int p = cur;
         while (k >= chunk_first[p + 1]) ++p;                       // pairs without a record hold no chunk
@@ -173,7 +163,7 @@ zseg_apply_kernel(const double *__restrict__ v, const int64_t *__restrict__ seg_
                   const double *__restrict__ stats, double *__restrict__ out) {
     const int64_t total = chunk_first[P];
     for (int64_t k = blockIdx.x; k < total; k += gridDim.x) {
-        const int q = last_not_above(chunk_first, 0, P, k);        // chunk_first[q] <= k < chunk_first[q + 1]: q holds records
+        const int q = mst::segment_of(chunk_first, 0, P, k);       // chunk_first[q] <= k < chunk_first[q + 1]: q holds records
         const int64_t r0 = seg_off[q] + (k - chunk_first[q]) * kChunk;
         const int64_t end = seg_off[q + 1];
         const int64_t r1 = r0 + kChunk < end ? r0 + kChunk : end;
@@ -243,7 +233,7 @@ count_tiles_kernel(const int32_t *__restrict__ x, const int32_t *__restrict__ y,
     for (int64_t b0 = (int64_t)blockIdx.x * kThreads; b0 < n; b0 += (int64_t)gridDim.x * kThreads) {
         const int64_t i = b0 + threadIdx.x;
         if (i >= n) continue;
-        const int p = pair_of(seg_off, last_not_above(seg_off, 0, P, b0), P, i);
+        const int p = pair_of(seg_off, mst::segment_of(seg_off, 0, P, b0), P, i);
         if (!(v[i] != 0.0)) continue;
         const mst_trans_pair pr = pairs[p];
         const AxisWindows wr = axis_windows(x[i], pr.n1, pr.C, pr.K1), wc = axis_windows(y[i], pr.n2, pr.C, pr.K2);
@@ -266,7 +256,7 @@ scatter_worklist_kernel(const int32_t *__restrict__ x, const int32_t *__restrict
     for (int64_t b0 = first + (int64_t)blockIdx.x * kThreads; b0 < n; b0 += (int64_t)gridDim.x * kThreads) {
         const int64_t i = b0 + threadIdx.x;
         if (i >= n) continue;
-        const int p = pair_of(seg_off, last_not_above(seg_off, p0, p1, b0), p1, i);
+        const int p = pair_of(seg_off, mst::segment_of(seg_off, p0, p1, b0), p1, i);
         const mst_trans_pair pr = pairs[p];
         if (pr.C != C) continue;                                   // a pair of another tile size inside the range: no tile here
         const int xi = x[i], yi = y[i];

@@ -293,6 +293,39 @@ def sum_far_list(keys, mult):
     return keys[last], counts
 
 
+def _bin_and_collect(who, dev, rows, cells, far_capacity, n_words, far_word, launch, compact):
+    """What bin_pairs_device and bin_trans_keys (`who`) share around their kernels: `cells` zeroed uint32 counters, a far list
+    with room for far_capacity entries (None: one per row, which always suffices) and n_words zeroed int64 words, of which
+    word far_word receives the far entries.  launch(dense, far_key, far_mult, cap, words) enqueues the binning;
+    compact(dense, room, found) enqueues the compaction into arrays of `room` records that it returns, counts last, with the
+    number of non-zero counters in found.  Returns (the words as a host array, the dense records cut to their number with int64
+    counts or None, the summed far list (keys ascending, counts) or None).  Two host waits: the words, and found."""
+    import torch
+    from . import _lib
+    cap = rows if far_capacity is None else int(far_capacity)
+    dense = torch.zeros(cells, dtype=torch.int32, device=dev)                     # uint32 counters
+    far_key = torch.empty(cap, dtype=torch.int64, device=dev)
+    far_mult = torch.empty(cap, dtype=torch.int32, device=dev)                    # uint32, at most 64
+    words = torch.zeros(n_words, dtype=torch.int64, device=dev)
+    launch(dense, far_key, far_mult, cap, words)
+    counted = words.cpu().numpy()
+    far_entries = int(counted[far_word])
+    if far_entries > cap:
+        raise _lib.MstOverflow(_lib.MST_E_OVERFLOW, "%s: the far list holds %d entries, %d were needed" % (who, cap, far_entries))
+    records = None
+    if cells:
+        room = min(rows, cells)
+        found = torch.zeros(1, dtype=torch.int64, device=dev)
+        records = compact(dense, room, found)
+        m = int(found.item())
+        if m > room:
+            raise RuntimeError("%s: %d non-zero counters from %d rows" % (who, m, rows))
+        records = tuple(r[:m] for r in records[:-1]) + (records[-1][:m].to(torch.int64) & 0xFFFFFFFF,)
+    del dense
+    far = sum_far_list(far_key[:far_entries], far_mult[:far_entries]) if far_entries else None
+    return counted, records, far
+
+
 def bin_pairs_device(pos1, pos2, res, zero_based=False, length=None, distance_bins=None, dense_bytes=None, device=None,
                      far_capacity=None, dense_diags=None):
     """Rows (pos1, pos2: int32 host arrays or device tensors) -> Pixels on the device.  length: the chromosome's length in bp
@@ -329,39 +362,27 @@ def bin_pairs_device(pos1, pos2, res, zero_based=False, length=None, distance_bi
             K = dense_diagonals(n, n if distance_bins is None else distance_bins, budget)
         else:
             K = max(0, min(int(dense_diags), n))
-        cap = rows if far_capacity is None else int(far_capacity)
-        dense = torch.zeros(K * n, dtype=torch.int32, device=dev)                 # uint32 counters
-        far_key = torch.empty(cap, dtype=torch.int64, device=dev)
-        far_mult = i32(cap)                                                       # uint32, at most 64
-        counters = torch.zeros(2, dtype=torch.int64, device=dev)
-        _lib.check(lib.mst_pairs_bin(_ptr(p1), _ptr(p2), rows, res, int(bool(zero_based)), limit, n, K, _ptr(dense) if K else None,
-                                     _ptr(far_key) if cap else None, _ptr(far_mult) if cap else None, cap, _ptr(counters), _stream()))
-        far_entries, dropped = (int(v) for v in counters.cpu().tolist())
-        if far_entries > cap:
-            raise _lib.MstOverflow(_lib.MST_E_OVERFLOW, "bin_pairs_device: the far list holds %d entries, %d were needed"
-                                   % (cap, far_entries))
-        xs, ds, cs = [], [], []
-        if K:
-            room = min(rows, K * n)
+
+        def launch(dense, far_key, far_mult, cap, words):
+            _lib.check(lib.mst_pairs_bin(_ptr(p1), _ptr(p2), rows, res, int(bool(zero_based)), limit, n, K, _ptr(dense) if K else None,
+                                         _ptr(far_key) if cap else None, _ptr(far_mult) if cap else None, cap, _ptr(words), _stream()))
+
+        def compact(dense, room, found):
             x, d, c = i32(room), i32(room), i32(room)
-            found = torch.zeros(1, dtype=torch.int64, device=dev)
             ws = torch.empty(int(lib.mst_pairs_compact_workspace_bytes(K, n)), dtype=torch.uint8, device=dev)
             _lib.check(lib.mst_pairs_compact(_ptr(dense), K, n, _ptr(x), _ptr(d), _ptr(c), room, _ptr(found), _ptr(ws), ws.numel(),
                                              _stream()))
-            m = int(found.item())
-            if m > room:
-                raise RuntimeError("bin_pairs_device: %d non-zero counters from %d rows" % (m, rows))
-            xs.append(x[:m])
-            ds.append(d[:m])
-            cs.append(c[:m].to(torch.int64) & 0xFFFFFFFF)
-            del dense, ws
-        if far_entries:
-            keys, counts = sum_far_list(far_key[:far_entries], far_mult[:far_entries])
+            return x, d, c
+
+        counted, near, far = _bin_and_collect("bin_pairs_device", dev, rows, K * n, far_capacity, 2, 0, launch, compact)
+        far_entries, dropped = (int(v) for v in counted)
+        xs, ds, cs = ([r] for r in near) if near is not None else ([], [], [])
+        if far is not None:
+            keys, counts = far
             fx = torch.div(keys, n, rounding_mode="floor")
             xs.append(fx.to(torch.int32))
             ds.append((keys - fx * n - fx).to(torch.int32))
             cs.append(counts)
-        del far_key, far_mult
         if not xs:
             return Pixels(i32(0), i32(0), torch.empty(0, dtype=torch.int64, device=dev), 0, dropped, K, far_entries, n)
         x, d, c = (torch.cat(xs), torch.cat(ds), torch.cat(cs)) if len(xs) > 1 else (xs[0], ds[0], cs[0])
@@ -424,48 +445,32 @@ def bin_trans_keys(posA, posB, seg_off, tables, res, zero_based=False, dense_cel
         if int(pb.numel()) != rows or (P and (int(seg_off[0]) != 0 or int(seg_off[-1]) != rows or np.any(np.diff(seg_off) < 0))):
             raise ValueError("bin_trans_keys: posA and posB of seg_off[P] rows, seg_off ascending from 0")
         i64 = lambda k: torch.empty(k, dtype=torch.int64, device=dev)
-        dropped = torch.zeros(P + 1, dtype=torch.int64, device=dev)              # [P] dropped rows, then the far entries
         if rows == 0 or P == 0:
             return i64(0), i64(0), np.zeros(P, np.int64), 0
         dense_cells = max(0, int(dense_cells))
-        cap = rows if far_capacity is None else int(far_capacity)
         table_d = torch.from_numpy(np.concatenate([tables.reshape(-1), seg_off])).to(dev)
         lim_a, lim_b, n_a, n_b, cell_off = (table_d[k * P:(k + 1) * P] for k in range(5))
-        dense = torch.zeros(dense_cells, dtype=torch.int32, device=dev)           # uint32 counters
-        far_key = i64(cap)
-        far_mult = torch.empty(cap, dtype=torch.int32, device=dev)                # uint32, at most 64
-        _lib.check(lib.mst_pairs_bin_trans(_ptr(pa), _ptr(pb), rows, _ptr(table_d[5 * P:]), P, _ptr(lim_a), _ptr(lim_b), _ptr(n_a),
-                                           _ptr(n_b), _ptr(cell_off), res, int(bool(zero_based)), dense_cells,
-                                           _ptr(dense) if dense_cells else None, _ptr(far_key) if cap else None,
-                                           _ptr(far_mult) if cap else None, cap, _ptr(dropped[P:]), _ptr(dropped), _stream()))
-        counted = dropped.cpu().numpy()
-        far_entries = int(counted[P])
-        if far_entries > cap:
-            raise _lib.MstOverflow(_lib.MST_E_OVERFLOW, "bin_trans_keys: the far list holds %d entries, %d were needed"
-                                   % (cap, far_entries))
-        ks, cs = [], []
-        if dense_cells:
-            room = min(rows, dense_cells)
+
+        def launch(dense, far_key, far_mult, cap, words):               # words: [P] dropped rows, then the far entries
+            _lib.check(lib.mst_pairs_bin_trans(_ptr(pa), _ptr(pb), rows, _ptr(table_d[5 * P:]), P, _ptr(lim_a), _ptr(lim_b), _ptr(n_a),
+                                               _ptr(n_b), _ptr(cell_off), res, int(bool(zero_based)), dense_cells,
+                                               _ptr(dense) if dense_cells else None, _ptr(far_key) if cap else None,
+                                               _ptr(far_mult) if cap else None, cap, _ptr(words[P:]), _ptr(words), _stream()))
+
+        def compact(dense, room, found):
             k, c = i64(room), torch.empty(room, dtype=torch.int32, device=dev)
-            found = torch.zeros(1, dtype=torch.int64, device=dev)
             ws = torch.empty(int(lib.mst_pairs_trans_compact_workspace_bytes(dense_cells)), dtype=torch.uint8, device=dev)
             _lib.check(lib.mst_pairs_trans_compact(_ptr(dense), dense_cells, _ptr(k), _ptr(c), room, _ptr(found), _ptr(ws), ws.numel(),
                                                    _stream()))
-            m = int(found.item())
-            if m > room:
-                raise RuntimeError("bin_trans_keys: %d non-zero counters from %d rows" % (m, rows))
-            ks.append(k[:m])
-            cs.append(c[:m].to(torch.int64) & 0xFFFFFFFF)
-            del dense, ws
-        if far_entries:                              # every far key is >= dense_cells: behind the dense part, already ascending
-            keys, counts = sum_far_list(far_key[:far_entries], far_mult[:far_entries])
-            ks.append(keys)
-            cs.append(counts)
-        del far_key, far_mult
-        if not ks:
-            return i64(0), i64(0), counted[:P].copy(), far_entries
-        keys, counts = (torch.cat(ks), torch.cat(cs)) if len(ks) > 1 else (ks[0], cs[0])
-        return keys, counts, counted[:P].copy(), far_entries
+            return k, c
+
+        counted, near, far = _bin_and_collect("bin_trans_keys", dev, rows, dense_cells, far_capacity, P + 1, P, launch, compact)
+        # every far key is >= dense_cells: behind the dense part, already ascending
+        parts = [part for part in (near, far) if part is not None]
+        if not parts:
+            return i64(0), i64(0), counted[:P].copy(), int(counted[P])
+        keys, counts = (torch.cat(kc) for kc in zip(*parts)) if len(parts) > 1 else parts[0]
+        return keys, counts, counted[:P].copy(), int(counted[P])
 
 
 def decode_trans_keys(keys, counts, tables):

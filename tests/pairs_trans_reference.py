@@ -90,6 +90,22 @@ def pair_pixels(posA, posB, res, zero_based, lim_a, lim_b, n_a, n_b):
     return out, int((~keep).sum())
 
 
+def pair_keys(posA, posB, res, zero_based, lim_a, lim_b, n_a, n_b):
+    """pair_pixels for millions of rows, NumPy only: one pair's rows -> (the ascending unique local cells x * n_b + y int64,
+    their counts int64, dropped).  The rule of mustache_amd/pairs.py once more: each side in [lo, limit] (0-based: [0, limit)),
+    bin = (pos - lo) // res, a bin >= its side's bin count drops the row."""
+    pa, pb = np.asarray(posA, np.int64), np.asarray(posB, np.int64)
+    lo = 0 if zero_based else 1
+    keep = np.ones(len(pa), bool)
+    for pos, lim, n in ((pa, lim_a, n_a), (pb, lim_b, n_b)):
+        keep &= pos >= lo
+        if lim is not None and lim >= 0:
+            keep &= pos < lim + lo
+        keep &= (pos - lo) // res < n
+    cells, counts = np.unique((pa[keep] - lo) // res * n_b + (pb[keep] - lo) // res, return_counts=True)
+    return cells.astype(np.int64), counts.astype(np.int64), int(len(pa) - keep.sum())
+
+
 def genome_pixels(parsed, res, zero_based=False):
     """parse_trans's result -> ({(a, b): {(x, y): count}} of the pairs that have a pixel, dropped int64 [P]); a chromosome has
     length // res + 1 bins"""

@@ -115,6 +115,43 @@ def test_bin_compact_decode_match_the_restatement(res, zero_based):
         assert np.array_equal(raw[0], first[0]) and np.array_equal(raw[1], first[1])     # the same records whatever is dense
 
 
+def test_a_second_trip():
+    """2048 workgroups of 2048 rows are the grid's cap: row 2048 * 2048 is the first row of workgroup 0's second trip, on the
+    other parity of the LDS slots.  The array is no multiple of 2048 long, the middle pair is empty, the last one starts at lane 5
+    of the second trip's first group, a run of identical rows crosses the cut between the trips and each trip has rows out of
+    range.  Expected values: ptr.pair_keys per pair."""
+    res, cut = 5000, 2048 * 2048
+    bins, rows = [(60, 45), (30, 20), (9, 4)], [cut + 5, 0, 316]
+    tables = np.zeros((5, 3), np.int64)
+    for p, (na, nb) in enumerate(bins):
+        tables[:, p] = (na * res - 1, nb * res - 1, na, nb, sum(a * b for a, b in bins[:p]))
+    cells = sum(a * b for a, b in bins)
+    seg = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    rng = np.random.default_rng(23)
+    pa, pb = (np.concatenate([rng.integers(1, bins[p][side] * res, rows[p]) for p in range(3)]).astype(np.int32) for side in (0, 1))
+    pa[cut - 8:cut + 4], pb[cut - 8:cut + 4] = 41 * res + 7, 12 * res + 9           # twelve rows of one pixel across the cut
+    lim_a, lim_b = int(tables[0, 0]), int(tables[1, 0])
+    pa[[10, 70000, cut - 9]], pb[[3000, cut - 2048, cut - 100]] = [0, lim_a + 1, I32_MIN], [lim_b + 1, 0, -5]     # the first trip
+    pa[cut + 4] = lim_a + 1                                                         # the second trip: pair 0's last row ...
+    pa[[cut + 5, cut + 200]], pb[cut + 320] = [int(tables[0, 2]) + 1, 0], I32_MIN   # ... and pair 2's first, last and one between
+    want_keys, want_counts, want_dropped = [], [], []
+    for p in range(3):
+        k, c, d = ptr.pair_keys(pa[seg[p]:seg[p + 1]], pb[seg[p]:seg[p + 1]], res, False, *(int(v) for v in tables[:4, p]))
+        want_keys.append(k + tables[4, p])
+        want_counts.append(c)
+        want_dropped.append(d)
+    want_keys, want_counts = np.concatenate(want_keys), np.concatenate(want_counts)
+    assert want_dropped == [7, 0, 3] and int(want_counts.sum()) == sum(rows) - 10 and sum(rows) % 2048 == 321
+    assert want_counts[list(want_keys).index(41 * 45 + 12)] >= 12
+    shuffled = np.concatenate([seg[p] + rng.permutation(rows[p]) for p in range(3)]).astype(np.int64)
+    from mustache_amd.pairs import bin_trans_keys
+    for dense_cells in (0, cells):
+        for order in (slice(None), shuffled):
+            keys, counts, dropped, far = bin_trans_keys(pa[order], pb[order], seg, tables, res, False, dense_cells)
+            assert np.array_equal(keys.cpu().numpy(), want_keys) and np.array_equal(counts.cpu().numpy(), want_counts)
+            assert dropped.tolist() == want_dropped and (far == 0) == (dense_cells == cells)
+
+
 def test_keys_beyond_32_bits():
     """one pair of 70 000 x 70 000 bins behind another of the same size: cell_off = 4.9e9 > 2^32; positions up to 2^31 - 1 at
     res 30 000 reach bin 71 582, so a bin >= n drops rows as well"""

@@ -181,6 +181,31 @@ def test_tables_and_pair_order():
     assert t.tolist() == [[99, 99, 1 << 31], [1 << 31, 30, 30], [10, 10, 7], [7, 4, 4], [0, 70, 110]] and cells == 138
 
 
+@pytest.mark.parametrize("res", [1, 5000])
+@pytest.mark.parametrize("zero_based", [False, True])
+def test_the_vectorised_restatement_is_the_per_row_one(res, zero_based):
+    """pair_keys (NumPy, for the GPU tests' millions of rows) against pair_pixels (a Python loop over the rows) on a 60 x 45 pair"""
+    n_a, n_b = 60, 45
+    len_a, len_b = (n_a - 1) * res + res // 4, (n_b - 1) * res + res // 7          # length // res + 1 = 60 and 45 bins
+    rng = np.random.default_rng(17)
+    pa, pb = rng.integers(1, len_a, 5000), rng.integers(1, len_b, 5000)            # [1, length - 1]: kept under both conventions
+    special = [(-1, None), (None, -1),                                             # below the range on each side: dropped
+               (0, None), (0, None), (0, None), (None, 0),                         # 0: dropped when positions are 1-based
+               (len_a + 1, None), (None, len_b + 1),                               # above the range on each side: dropped
+               (len_a, None), (None, len_b),                                       # the length itself: dropped when they are 0-based
+               (-2 ** 31, None), (None, -2 ** 31),                                 # what the reader stores for a position beyond int32
+               (1, 1), (len_a - 1, len_b - 1)]                                     # the edges both conventions keep
+    for k, (a, b) in enumerate(special):
+        row = 37 + 331 * k
+        pa[row], pb[row] = (pa[row] if a is None else a), (pb[row] if b is None else b)
+    pix, dropped = ptr.pair_pixels(pa, pb, res, zero_based, len_a, len_b, n_a, n_b)
+    cells, counts, dropped_too = ptr.pair_keys(pa, pb, res, zero_based, len_a, len_b, n_a, n_b)
+    assert dropped == dropped_too == (8 if zero_based else 10)
+    assert cells.dtype == counts.dtype == np.int64 and np.all(np.diff(cells) > 0)
+    assert dict(zip(cells.tolist(), counts.tolist())) == {x * n_b + y: c for (x, y), c in pix.items()}
+    assert int(counts.sum()) == 5000 - dropped and len(cells) > 1000
+
+
 # ---- what the command lines refuse ------------------------------------------------------------------------------------------
 @pytest.fixture
 def inputs(tmp_path, monkeypatch):
