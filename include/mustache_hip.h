@@ -682,6 +682,28 @@ MST_STABLE int mst_pairs_trans_compact(const uint32_t *dense, int64_t dense_cell
 MST_STABLE int mst_pairs_trans_decode(const int64_t *keys, const int64_t *counts, int64_t n, const int64_t *cell_off, const int64_t *nB,
                                       int32_t n_pairs, int32_t *out_x, int32_t *out_y, double *out_v, void *stream);
 
+/* ---- binomial thinning of raw pixel counts (the rule: mustache_amd/downsample.py; tests/downsample_reference.py restates it).
+ * Added without a change of MST_ABI_REVISION, as mst_pairs_bin was. */
+/* A pixel whose count is at least this is thinned by its whole wave, 64 Philox calls at a time; below it, by its own lane
+ * (csrc/mst_thin.hip; mirrored as downsample.HEAVY).  A value above 2^32 - 1 builds the plain one-lane-per-pixel kernel. */
+#ifndef MST_THIN_HEAVY
+#define MST_THIN_HEAVY 256
+#endif
+/* count_kind: the type of count_in */
+#define MST_THIN_COUNT_I64 0
+#define MST_THIN_COUNT_F32 1
+#define MST_THIN_COUNT_F64 2
+/* Records (x, dist: dev int32 [n_records]; count_in: dev int64 / float / double [n_records] by count_kind) of the pixels
+ * (x, y = x + dist).  A count n that is an integer value in [0, 2^32 - 1] keeps count_out[e] = k = #{ j in [0, n) : u_j < T }
+ * (dev int64 [n_records]), u_j = word j & 3 of Philox4x32-10(counter = (x, y, j >> 2, tag), key = (seed, sample)); 0 < T < 2^32.
+ * Any other count (negative, above 2^32 - 1, not an integer, not finite) counts as 0 and sets words[2] = 1.  words (dev int64
+ * [3], ACCUMULATED: the caller zeroes them): [0] the sum of the counts, [1] the sum of the k, [2] the bad-count flag.
+ * count_out = NULL: nothing is drawn or written but words[0] and words[2] (T is then not looked at).  k depends on the pixel,
+ * tag, seed, sample and T alone, and all sums are integer sums: the results do not depend on the order of the records. */
+MST_STABLE int mst_thin_counts(const int32_t *x, const int32_t *dist, const void *count_in, int32_t count_kind, int64_t n_records,
+                               uint32_t tag, uint32_t seed, uint32_t sample, uint64_t T, int64_t *count_out, int64_t *words,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

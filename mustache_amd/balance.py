@@ -393,6 +393,16 @@ def balance_text(p1, p2, cnt, res, method="ICE", **kw):
 def read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res, device=None, method="ICE", **kw):
     """`.hic` under --balance: every raw record of the chromosome (norm NONE, no distance limit), `method` on the device, the
     bias applied on the device, then the reader's distance rule -> (x, y, v) host arrays, None when nothing is left."""
+    raw = read_hic_raw(f, CHRM_SIZE, chromosome, res, device=device, method=method)
+    if raw is None:
+        return None
+    xd, dd, vd, dev = raw
+    return balance_records_device(xd, dd, vd, distance_in_bp, chromosome, res, dev, method=method, **kw)
+
+
+def read_hic_raw(f, CHRM_SIZE, chromosome, res, device=None, method="ICE"):
+    """The first half of read_hic_balanced, the raw pixel set on the device: -> (x int32, dist int32, v float32, device), None
+    when the chromosome has no record."""
     import torch
     from ._lib import require_gpu
     from .hicfile import read_intra_packed
@@ -416,7 +426,7 @@ def read_hic_balanced(f, CHRM_SIZE, distance_in_bp, chromosome, res, device=None
         xd = torch.from_numpy(pc.x[:pc.count]).to(dev)
         dd = torch.from_numpy(pc.dist[:pc.count]).to(dev)
         vd = torch.from_numpy(pc.v[:pc.count]).to(dev)
-    return balance_records_device(xd, dd, vd, distance_in_bp, chromosome, res, dev, method=method, **kw)
+    return xd, dd, vd, dev
 
 
 def balance_records_device(xd, dd, vd, distance_in_bp, chromosome, res, dev, method="ICE", **kw):

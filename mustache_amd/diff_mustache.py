@@ -24,6 +24,7 @@ import time
 
 import numpy as np
 
+from .downsample import error_line
 from .mustache import (_engine, block_tiling, block_mask_size, genome_biases_or_error, octave_values, owned_chromosomes,
                        parseBP, read_sample, run_trans_all)
 from .tail import (fdr_candidates_multi, diag_mean_filter_multi, cluster_representatives, loops_from_reps,
@@ -252,10 +253,13 @@ def _pairs_from_filled(eng, pipe, dbands, n, dpx, starts, CH, dense=False, pt=No
 
 
 def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2, chromosome, chromosome2, verbose=True,
-              balance=None, pairs_zero_based=False):
+              balance=None, pairs_zero_based=False, downsample=None, seed=0, match_depth=False):
     """The reading half of regulator() (diff_mustache.py:591-626): -> (coo1, coo2, res) or None when a sample is empty.
     balance="ICE" or "NEWTON": each sample's raw map is balanced on its own on the GPU (mustache_amd.balance), as
-    mustache.read_contacts does for one sample; bias1 / bias2 and a stored normalisation are then not used."""
+    mustache.read_contacts does for one sample; bias1 / bias2 and a stored normalisation are then not used.
+    downsample=P: both samples' raw maps are thinned to the fraction P before the balancing; match_depth=True: the deeper
+    sample of this chromosome is thinned to the other's depth (mustache_amd/downsample.py); seed=S seeds either.  Both are for
+    `.hic` and pairs input under `balance`."""
     if not chromosome2 or chromosome2 == 'n':
         chromosome2 = chromosome
     if chromosome != chromosome2:
@@ -266,10 +270,15 @@ def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2,
         from .balance import check_request
         check_request(balance, [f1, f2], bias1 or bias2, norm_method, bias_flag="-b1/-b2")
     from .hicfile import PackedContacts
+    if match_depth:
+        if downsample is not None:
+            from .downsample import DownsampleError
+            raise DownsampleError("match_depth and downsample: give one of them")
+        return read_pair_matched(f1, f2, CHRM_SIZE, res, distance_in_bp, chromosome, balance, pairs_zero_based, seed, verbose)
     coos = []
-    for f, bias in ((f1, bias1), (f2, bias2)):
+    for k, (f, bias) in enumerate(((f1, bias1), (f2, bias2))):
         coo = read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome, balance=balance,
-                          pairs_zero_based=pairs_zero_based, verbose=verbose)
+                          pairs_zero_based=pairs_zero_based, verbose=verbose, downsample=downsample, seed=seed, sample=k)
         if coo is not None and not isinstance(coo, PackedContacts):
             if coos and coo[3] != res:                # only a `.cool` file brings a resolution of its own
                 raise ValueError('Both contact maps should have the same resolution.')
@@ -281,20 +290,52 @@ def read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_in_bp, bias1, bias2,
     return coos[0], coos[1], res
 
 
+def read_pair_matched(f1, f2, CHRM_SIZE, res, distance_in_bp, chromosome, balance, pairs_zero_based=False, seed=0, verbose=True):
+    """read_pair under match_depth: both samples' raw pixel sets on the device, their depths N_1 and N_2 (the kernel's integer
+    sum; a pairs file's host counters must agree with it), the deeper one thinned with T = (N_small << 32) // N_large, then
+    each balanced -> (coo1, coo2, res), None when a sample is empty."""
+    from .downsample import depth_of, match_depth
+    from .mustache import read_raw_sample, thin_and_balance
+    raws, depths = [], []
+    for f in (f1, f2):
+        raw = read_raw_sample(f, CHRM_SIZE, res, distance_in_bp, chromosome, balance=balance, pairs_zero_based=pairs_zero_based,
+                              verbose=verbose)
+        if raw is None:
+            return None
+        depth = depth_of(raw[0], raw[1], raw[2], chromosome, raw[3])
+        if raw[4] is not None and raw[4] != depth:
+            raise RuntimeError("match_depth: the device summed %d contacts of %s in %s, the host reader counted %d"
+                               % (depth, chromosome, f, raw[4]))
+        raws.append(raw)
+        depths.append(depth)
+    coos = []
+    for k, T in enumerate(match_depth(*depths)):
+        r = thin_and_balance(raws[k], T, seed, k, distance_in_bp, chromosome, res, balance)
+        raws[k] = None
+        if r is None or len(r[2]) == 0:
+            return None
+        coos.append((np.asarray(r[0]), np.asarray(r[1]), np.asarray(r[2], dtype=np.float64)))
+    return coos[0], coos[1], res
+
+
 def regulator(f1, f2, norm_method, CHRM_SIZE, outdir, bed1="", bed2="", res=5000, sigma0=1.6, s=10, pt=0.1, pt2=0.1,
               st=0.88, octaves=2, verbose=True, nprocesses=4, distance_filter=2000000, bias1=False, bias2=False,
-              chromosome='n', chromosome2=None, balance=None, pairs_zero_based=False):
+              chromosome='n', chromosome2=None, balance=None, pairs_zero_based=False, downsample=None, seed=0, match_depth=False):
     """Two-sample loop calling for one chromosome (diff_mustache.py:572-690); returns [x, y, fdr, sigma, tag] rows.
     chromosome2 = B != chromosome: the inter-chromosomal pair (A, B), which the reference cannot run (diff_trans.py).
     `balance="ICE"` or `"NEWTON"` (not in the reference): balance each sample's raw map on the GPU instead of applying
-    bias1 / bias2; `pairs_zero_based`: the position convention of `.pairs` input (mustache_amd/pairs.py)."""
+    bias1 / bias2; `pairs_zero_based`: the position convention of `.pairs` input (mustache_amd/pairs.py); `downsample=P`,
+    `seed=S`, `match_depth=True`: thin the raw maps before the balancing (read_pair; intra-chromosomal only)."""
     octave_values = [sigma0 * (2 ** i) for i in range(octaves)]
     if chromosome2 and chromosome2 != 'n' and chromosome != chromosome2:      # the trans pair (A, B): mustache_amd/diff_trans.py
+        if downsample is not None or match_depth:
+            from .downsample import DownsampleError
+            raise DownsampleError("thinning on a run with an inter-chromosomal pair: only intra-chromosomal maps are thinned")
         from .diff_trans import regulate
         return regulate(f1, f2, norm_method, res, octave_values, st, pt, pt2, chromosome, chromosome2, verbose=verbose,
                         balance=balance)
     got = read_pair(f1, f2, norm_method, CHRM_SIZE, res, distance_filter, bias1, bias2, chromosome, chromosome2, verbose,
-                    balance=balance, pairs_zero_based=pairs_zero_based)
+                    balance=balance, pairs_zero_based=pairs_zero_based, downsample=downsample, seed=seed, match_depth=match_depth)
     if got is None:
         return []
     coo1, coo2, res = got
@@ -337,6 +378,11 @@ def parse_args(args):
                         "intra-chromosomal rows.")
     p.add_argument("--pairs-zero-based", dest="pairs_zero_based", action="store_true",
                    help="OPTIONAL: .pairs / .pairs.gz input only: positions are 0-based (bin = pos // res)")
+    from .mustache import add_downsample_arguments
+    add_downsample_arguments(p)
+    p.add_argument("--match-depth", dest="match_depth", action="store_true",
+                   help="OPTIONAL: per chromosome, thin the deeper sample's raw map to the depth of the other before --balance "
+                        "(binomial thinning on the GPU; .hic and .pairs / .pairs.gz input, intra-chromosomal runs)")
     from .balance_genome import add_arguments
     add_arguments(p)
     return p.parse_args(args)
@@ -431,6 +477,7 @@ def balanced_trans_rows(genomes, files, pair, args):
                                label="%s,%s" % pair)
 
 
+@error_line
 def main(argv=None):
     t0 = time.time()
     args = parse_args(sys.argv[1:] if argv is None else argv)
@@ -493,6 +540,7 @@ def main(argv=None):
     run_many = lambda items, ns, dpx: run_pair_genome(pipe, list(zip(items, ns)), dpx, args.st, args.pt, args.pt2)
     genome = GenomeBatcher(lambda: pipe.device, run_many, lambda dbands, n, dpx: run_many([dbands], [n], dpx)[0], emit)
 
+    thin = dict(downsample=args.downsample, seed=args.seed or 0, match_depth=args.match_depth)
     for i in mine:
         chromosome, chromosome2 = pairs[i]
         if not batched:
@@ -500,10 +548,10 @@ def main(argv=None):
                               sigma0=args.s_z, s=args.s, verbose=args.verbose, pt=args.pt, pt2=args.pt2, st=args.st,
                               distance_filter=distFilter, nprocesses=args.nprocesses, bias1=biasf1, bias2=biasf2,
                               chromosome=chromosome, chromosome2=chromosome2, octaves=args.octaves, balance=run.balance,
-                              pairs_zero_based=args.pairs_zero_based))
+                              pairs_zero_based=args.pairs_zero_based, **thin))
             continue
         got = read_pair(f1, f2, args.norm_method, False, res, distFilter, biasf1, biasf2, chromosome, chromosome2,
-                        args.verbose, balance=run.balance, pairs_zero_based=args.pairs_zero_based)
+                        args.verbose, balance=run.balance, pairs_zero_based=args.pairs_zero_based, **thin)
         if got is None:
             genome.skip(i)
             continue

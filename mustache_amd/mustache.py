@@ -23,6 +23,7 @@ from collections import defaultdict
 
 import numpy as np
 
+from .downsample import error_line
 from .tail import block_tail
 
 _ENGINES = {}
@@ -323,14 +324,16 @@ def call_trans_coo(x, y, v, octave_values, st, pt, verbose=True, label=""):
 
 
 def read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromosome, chromosome2, verbose=True,
-                  packed=False, part=(0, 1), device=None, balance=None, pairs_zero_based=False):
+                  packed=False, part=(0, 1), device=None, balance=None, pairs_zero_based=False, downsample=None, seed=0):
     """The reading half of regulator() (reference mustache.py:866-889): host I/O only, so main() can fetch the next
     chromosome while the GPU works on the current one.  Returns (x, y, v, res) or None when nothing was read.
     packed=True: a `.hic` file read by the native reader comes back as hicfile.PackedContacts (12 bytes per record, what
     the GPU loader takes) instead of the int64 / float64 triple.
     balance="ICE" or "NEWTON": the map's raw counts are balanced on the GPU (mustache_amd.balance) instead of using a bias file or a
     stored normalisation; the result is always the int64 / float64 triple.
-    pairs_zero_based: the position convention of a `.pairs` / `.pairs.gz` file (mustache_amd/pairs.py), which needs `balance`."""
+    pairs_zero_based: the position convention of a `.pairs` / `.pairs.gz` file (mustache_amd/pairs.py), which needs `balance`.
+    downsample=P, seed=S: the raw map of a `.hic` or pairs file is thinned to the fraction P before the balancing
+    (mustache_amd/downsample.py); intra-chromosomal only, and it needs `balance`."""
     chromosome2 = _check_pair(f, chromosome, chromosome2)
     distance_in_bp = distance_filter
     if verbose:
@@ -341,28 +344,80 @@ def read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromos
         why = balance_on_trans(balance or None) or trans_ranks(part[1], count=False)
         if why:
             raise TransError(why)
+        if downsample is not None:
+            raise TransError("--downsample on a run with an inter-chromosomal pair: only intra-chromosomal maps are thinned")
         return read_trans_contacts(f, norm_method, chromosome, chromosome2, res, device=device)
     if balance:
         from .balance import check_request
         check_request(balance, f, bias, norm_method, world=part[1])
     r = read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome, packed=packed, part=part,
-                    device=device, balance=balance, pairs_zero_based=pairs_zero_based, verbose=verbose)
+                    device=device, balance=balance, pairs_zero_based=pairs_zero_based, verbose=verbose, downsample=downsample,
+                    seed=seed)
     if isinstance(r, tuple) and len(r[2]) == 0:
         return None
     return r
 
 
+def read_raw_sample(f, CHRM_SIZE, res, distance_in_bp, chromosome, device=None, balance=None, pairs_zero_based=False, verbose=True):
+    """The raw pixel set of one chromosome on the device, the form mustache_amd/downsample.py thins: a `.hic` file
+    (balance.read_hic_raw) or a pairs file (pairs.read_pairs_raw) -> (x int32, dist int32, counts, device, the host reader's
+    depth or None), None when the chromosome has no pixel.  balance: the method the balancing that follows will use."""
+    from .balance import method_of
+    from .pairs import is_pairs
+    if not balance:
+        from .downsample import DownsampleError
+        raise DownsampleError("thinning needs raw integer counts; give balance='ICE' or 'NEWTON'")
+    if is_pairs(f):
+        from .pairs import read_pairs_raw
+        return read_pairs_raw(f, distance_in_bp, chromosome, res, device=device, method=method_of(balance),
+                              zero_based=pairs_zero_based, verbose=verbose)
+    if not str(f).endswith(".hic"):
+        from .downsample import DownsampleError
+        from .request import THIN_INPUT
+        raise DownsampleError(THIN_INPUT % ("downsample", f))
+    from .balance import read_hic_raw
+    raw = read_hic_raw(f, CHRM_SIZE, chromosome, res, device=device, method=method_of(balance))
+    return None if raw is None else raw + (None,)
+
+
+def thin_and_balance(raw, T, seed, sample, distance_in_bp, chromosome, res, balance):
+    """What follows read_raw_sample: the optional thinning (T = the threshold of downsample.thin_records, None: none; one
+    printed line), then balance.balance_records_device -> (x, y, v) host arrays, None when nothing is left."""
+    import torch
+    from .balance import balance_records_device, method_of
+    xd, dd, counts, dev, host_depth = raw
+    if T is not None:
+        from .downsample import report, thin_records
+        (xd, dd, counts), total, kept = thin_records(xd, dd, counts, chromosome, T, seed, sample, dev)
+        if host_depth is not None and total != host_depth:
+            raise RuntimeError("downsample: the device summed %d contacts of %s, the host reader counted %d" % (total, chromosome, host_depth))
+        report(chromosome, sample, total, kept, T, seed)
+        if kept == 0:
+            print(f'There is no contact in chrmosome {chromosome} to work on.')
+            return None
+    vd = counts if counts.dtype == torch.float32 else counts.to(torch.float64)
+    return balance_records_device(xd, dd, vd, distance_in_bp, chromosome, res, dev, method=method_of(balance))
+
+
 def read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome, packed=True, part=(0, 1), device=None,
-                balance=None, pairs_zero_based=False, verbose=True):
+                balance=None, pairs_zero_based=False, verbose=True, downsample=None, seed=0, sample=0):
     """One sample's intra-chromosomal records by file type, for read_contacts and diff_mustache.read_pair.  Returns
     (x, y, v, res) host arrays (res: the file's own for `.cool`), possibly empty; hicfile.PackedContacts for a `.hic` file
     when `packed` and the native reader serves it (a rank's share of `part` may be empty and is still returned: every
     rank takes part in the exchange); None when a text reader finds no record of the chromosome.
     balance="ICE" or "NEWTON": the raw counts balanced on the GPU by that method (`.hic` through the native reader whatever MUSTACHE_HIC_BACKEND says,
     text otherwise); the caller has already checked the request (balance.check_request).
-    A `.pairs` / `.pairs.gz` file (raw read pairs, mustache_amd/pairs.py) is binned on the GPU and needs `balance`."""
+    A `.pairs` / `.pairs.gz` file (raw read pairs, mustache_amd/pairs.py) is binned on the GPU and needs `balance`.
+    downsample=P (0 < P < 1; `.hic` and pairs input under `balance`): every raw contact is kept with probability P before the
+    balancing (mustache_amd/downsample.py), seeded by `seed`; `sample` = 0 or 1 is the sample's place in a two-sample run."""
     from .pairs import is_pairs
-    if is_pairs(f):
+    if downsample is not None:
+        from .downsample import threshold_of
+        raw = read_raw_sample(f, CHRM_SIZE, res, distance_in_bp, chromosome, device=device, balance=balance,
+                              pairs_zero_based=pairs_zero_based, verbose=verbose)
+        r = None if raw is None else thin_and_balance(raw, threshold_of(downsample), seed, sample, distance_in_bp, chromosome, res,
+                                                      balance)
+    elif is_pairs(f):
         from .pairs import PairsError, read_pairs_balanced
         if not balance:
             from .request import RAW_PAIRS
@@ -397,13 +452,14 @@ def read_sample(f, norm_method, CHRM_SIZE, res, distance_in_bp, bias, chromosome
 
 def regulator(f, norm_method, CHRM_SIZE, outdir, bed="", res=5000, sigma0=1.6, s=10, pt=0.1, st=0.88, octaves=2,
               verbose=True, nprocesses=4, distance_filter=2000000, bias=False, chromosome='n', chromosome2=None,
-              contacts=None, shard_blocks=True, balance=None, pairs_zero_based=False):
+              contacts=None, shard_blocks=True, balance=None, pairs_zero_based=False, downsample=None, seed=0):
     """Loop calling for one chromosome (reference mustache.py:853-942).  `s` is accepted and ignored like in the
     reference (s = 10 is hard-wired at :711); `nprocesses` is ignored: all blocks run as one GPU batch.
     `contacts` (not in the reference): what read_contacts() returned for this chromosome, when the caller read ahead;
     `shard_blocks=False`: in a multi-GPU job this rank runs the whole chromosome alone (whole-genome sharding by chromosome).
     `balance="ICE"` or `"NEWTON"` (not in the reference): balance the raw map on the GPU instead of applying `bias`
-    (read_contacts); `pairs_zero_based`: the position convention of `.pairs` input (read_contacts)."""
+    (read_contacts); `pairs_zero_based`: the position convention of `.pairs` input (read_contacts); `downsample=P`, `seed=S`:
+    thin the raw map to the fraction P before the balancing (read_contacts)."""
     if contacts is None:
         chromosome2 = _check_pair(f, chromosome, chromosome2)
     elif not chromosome2 or chromosome2 == 'n':            # read already (a pairs file's trans records among them): nothing to refuse
@@ -412,14 +468,14 @@ def regulator(f, norm_method, CHRM_SIZE, outdir, bed="", res=5000, sigma0=1.6, s
     if chromosome != chromosome2:          # chromosome2 = B: the trans pair (A, B), mustache_amd/trans.py
         if contacts is None:
             contacts = read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromosome, chromosome2, verbose,
-                                     balance=balance, pairs_zero_based=pairs_zero_based)
+                                     balance=balance, pairs_zero_based=pairs_zero_based, downsample=downsample, seed=seed)
             if contacts is None:
                 return []
         x, y, v, _res = contacts
         return call_trans_coo(x, y, v, octave_values, st, pt, verbose=verbose, label="%s,%s" % (chromosome, chromosome2))
     if contacts is None:
         contacts = read_contacts(f, norm_method, CHRM_SIZE, res, distance_filter, bias, chromosome, chromosome2, verbose,
-                                 balance=balance, pairs_zero_based=pairs_zero_based)
+                                 balance=balance, pairs_zero_based=pairs_zero_based, downsample=downsample, seed=seed)
         if contacts is None:
             return []
     from .hicfile import PackedContacts
@@ -481,9 +537,19 @@ def parse_args(args):
     p.add_argument("--pairs-zero-based", dest="pairs_zero_based", action="store_true",
                    help="OPTIONAL: .pairs / .pairs.gz input only: positions are 0-based (bin = pos // res) instead of the "
                         "format's 1-based ones (bin = (pos - 1) // res)")
+    add_downsample_arguments(p)
     from .balance_genome import add_arguments
     add_arguments(p)
     return p.parse_args(args)
+
+
+def add_downsample_arguments(p):
+    """--downsample and --seed of both command lines (mustache_amd/downsample.py)"""
+    p.add_argument("--downsample", dest="downsample", type=float, default=None, metavar="P",
+                   help="OPTIONAL: keep every raw contact with probability P (0 < P < 1) before --balance: binomial thinning on the "
+                        "GPU, .hic and .pairs / .pairs.gz input, intra-chromosomal runs")
+    p.add_argument("--seed", dest="seed", type=int, default=None, metavar="S",
+                   help="OPTIONAL: the seed of the thinning, a 32-bit unsigned integer (default 0)")
 
 
 def resolve_distance_filter(dist_arg, res, quiet=False):
@@ -678,7 +744,8 @@ def call_cis_pairs(f, args, res, pairs, balance, distFilter, rank, world, device
         with stage("read %s" % chromosome):
             return read_contacts(f, args.norm_method, CHRM_SIZE, res, distFilter, biasf, chromosome, chromosome2,
                                  verbose=args.verbose, packed=True, part=(0, 1) if by_chromosome else (rank, world),
-                                 device=device, balance=balance, pairs_zero_based=args.pairs_zero_based)
+                                 device=device, balance=balance, pairs_zero_based=args.pairs_zero_based,
+                                 downsample=args.downsample, seed=args.seed or 0)
 
     results = {}
 
@@ -776,6 +843,7 @@ def call_trans_pairs(f, args, res, run, distFilter, device):
             first = False
 
 
+@error_line
 def main(argv=None):
     start_time = time.time()
     args = parse_args(sys.argv[1:] if argv is None else argv)

@@ -530,11 +530,22 @@ def bin_trans_device(posA, posB, seg_off, lengths, res, zero_based=False, bins=N
 # the reader under --balance
 # ----------------------------------------------------------------------------------------------------------------------
 def read_pairs_balanced(f, distance_in_bp, chromosome, res, device=None, method="ICE", zero_based=False, verbose=True, **kw):
-    """A pairs file under --balance: the chromosome's rows binned on the device, then balance.balance_records_device -> (x, y, v)
-    host arrays, None when nothing is left."""
+    """A pairs file under --balance: the chromosome's rows binned on the device (read_pairs_raw), then
+    balance.balance_records_device -> (x, y, v) host arrays, None when nothing is left."""
+    import torch
+    from .balance import balance_records_device
+    raw = read_pairs_raw(f, distance_in_bp, chromosome, res, device=device, method=method, zero_based=zero_based, verbose=verbose)
+    if raw is None:
+        return None
+    xd, dd, counts, dev, _ = raw
+    return balance_records_device(xd, dd, counts.to(torch.float64), distance_in_bp, chromosome, res, dev, method=method, **kw)
+
+
+def read_pairs_raw(f, distance_in_bp, chromosome, res, device=None, method="ICE", zero_based=False, verbose=True):
+    """The first half of read_pairs_balanced, the raw pixel set on the device: -> (x int32, dist int32, count int64, device,
+    kept rows by the host reader's counters), None when the chromosome has no pixel."""
     import torch
     from ._lib import require_gpu
-    from .balance import balance_records_device
     require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     with _LOCK:
@@ -559,4 +570,4 @@ def read_pairs_balanced(f, distance_in_bp, chromosome, res, device=None, method=
     if len(px) == 0:
         print(f'There is no contact in chrmosome {chromosome} to work on.')
         return None
-    return balance_records_device(px.x, px.dist, px.count.to(torch.float64), distance_in_bp, chromosome, res, dev, method=method, **kw)
+    return px.x, px.dist, px.count, dev, len(p1) - out_of_range

@@ -5,7 +5,8 @@ of one that goes ahead.  Every rule is stated here once, with its sentence once,
 for both command lines ("The order of refusals").  The guards of the library (mustache.read_contacts, read_sample,
 diff_trans.regulate, pileup's trans mode, balance_genome.check_genome_request, trans.read_trans_contacts) raise their own
 exception types with the rule functions and sentences of this module.  balance.check_request (`--balance`) and
-balance_genome.check_genome_request (`--balance-genome`) are the two rules that live beside what they guard.
+balance_genome.check_genome_request (`--balance-genome`) are the two rules that live beside what they guard; the rule of
+`--downsample` / `--seed` / `--match-depth` (thinning) is here, with the helpers of mustache_amd/downsample.py for P and the seed.
 
 Host only: no torch and no native library at import; plan() reads no contact data except the one parse of a pairs file under
 --pairs-trans (keep_trans_rows) and the chromosome list of a run without -ch."""
@@ -20,12 +21,15 @@ ONE_GPU = "inter-chromosomal pairs run on one GPU only"
 NEED_CH = "inter-chromosomal pairs need -ch and -ch2 (all-pairs runs are not supported)"
 TRANS_ALL_CH2 = "--trans-all pairs the -ch list with itself; give -ch2 without it"
 RAW_PAIRS = "%s holds raw read pairs: give --balance ICE|NEWTON"
+THIN_INPUT = "%s and %s: raw counts are thinned from .hic and .pairs / .pairs.gz input only"
 
 # files: the contact file(s), one or two (None: not given); bias: [(the -b / -b1 / -b2 file or None, the sentence when it is
 # missing)]; bias_flag: the flag to quote; ch, ch2: the -ch / -ch2 lists ('n' when absent); ranks: the ranks of the run;
 # text_pair_raises: a trans pair on text input ends the run as the reference's one-sample caller does (Raises)
 Request = namedtuple("Request", "files bias bias_flag norm_method balance balance_genome balance_pixels balance_pixels_given "
-                                "pairs_trans pairs_zero_based trans_all ch ch2 ranks text_pair_raises")
+                                "pairs_trans pairs_zero_based trans_all ch ch2 ranks text_pair_raises downsample seed match_depth",
+                     defaults=(None, None, False))
+# downsample: --downsample's fraction (None: not given); seed: --seed (None: not given); match_depth: diff_mustache's --match-depth
 
 # cis, trans: the (chromosome, chromosome2) pairs in run order, every cis pair before the first trans pair; trans_all: a
 # --trans-all run; balance: the --balance method in upper case, or None; genome: --balance-genome's (method, pixels), or None
@@ -36,7 +40,7 @@ def request_of(args, files, bias, bias_flag, ranks, text_pair_raises=False):
     """the Request of a command line's parsed arguments"""
     return Request(list(files), bias, bias_flag, args.norm_method, args.balance, args.balance_genome, args.balance_pixels,
                    args.balance_pixels_given, args.pairs_trans, args.pairs_zero_based, args.trans_all, args.chromosome,
-                   args.chromosome2, ranks, text_pair_raises)
+                   args.chromosome2, ranks, text_pair_raises, args.downsample, args.seed, getattr(args, "match_depth", False))
 
 
 class Raises(str):
@@ -78,6 +82,11 @@ def trans_input(files, pairs_trans=False):
     return TEXT_ON_TRANS
 
 
+def other_chromosome(ch, ch2):
+    """does -ch2 name another chromosome than -ch somewhere (an inter-chromosomal pair, or lists that do not zip)?"""
+    return isinstance(ch2, list) and (not isinstance(ch, list) or len(ch) != len(ch2) or any(a != b for a, b in zip(ch, ch2)))
+
+
 def pairs_input(rq):
     """What pairs input (or --pairs-zero-based / --pairs-trans without one) rules out.  Reads nothing."""
     from .pairs import is_pairs
@@ -90,7 +99,7 @@ def pairs_input(rq):
         if rq.pairs_zero_based:
             return "--pairs-zero-based is for .pairs / .pairs.gz input (%s is none)" % ", ".join(str(f) for f in files)
         return None
-    other = isinstance(ch2, list) and (not isinstance(ch, list) or len(ch) != len(ch2) or any(a != b for a, b in zip(ch, ch2)))
+    other = other_chromosome(ch, ch2)
     if rq.pairs_trans:                       # the trans rows are kept for --balance-genome (balance_genome.py)
         if not rq.trans_all and not other:
             return "--pairs-trans on a run with no inter-chromosomal pair: give --trans-all, or -ch A -ch2 B"
@@ -116,6 +125,36 @@ def pairs_input(rq):
         check_request(rq.balance, files, bias, rq.norm_method, rq.ranks, bias_flag=rq.bias_flag)
     except BalanceError as e:
         return str(e)
+    return None
+
+
+def thinning(rq):
+    """What --downsample / --match-depth / --seed (mustache_amd/downsample.py) rule out.  Reads nothing."""
+    from .downsample import DownsampleError, check_seed, threshold_of
+    from .pairs import is_pairs
+    if rq.downsample is None and not rq.match_depth:
+        if rq.seed is not None:
+            return "--seed without --downsample or --match-depth: it seeds the thinning and nothing else"
+        return None
+    if rq.match_depth and rq.downsample is not None:
+        return "--match-depth and --downsample: give one of them (--match-depth thins the deeper sample to the other's depth)"
+    flag = "--match-depth" if rq.match_depth else "--downsample"
+    try:
+        if rq.downsample is not None:
+            threshold_of(rq.downsample)
+        if rq.seed is not None:
+            check_seed(rq.seed)
+    except DownsampleError as e:
+        return str(e)
+    if rq.trans_all or rq.balance_genome is not None or rq.pairs_trans or other_chromosome(rq.ch, rq.ch2):
+        return "%s on a run with an inter-chromosomal pair: only intra-chromosomal maps are thinned" % flag
+    if given_bias(rq) or (rq.norm_method and str(rq.norm_method).upper() != "NONE"):
+        return "%s with %s or -norm: thinning needs raw integer counts; give --balance ICE|NEWTON alone" % (flag, rq.bias_flag)
+    if rq.balance is None:
+        return "%s without --balance: thinning needs raw integer counts; give --balance ICE|NEWTON" % flag
+    for f in rq.files:
+        if not (is_pairs(f) or str(f).endswith(".hic")):
+            return THIN_INPUT % (flag, f)
     return None
 
 
@@ -195,7 +234,7 @@ def plan(rq, res):
         return "Error: Couldn't find the specified contact files"
     if not res:
         return "Error: Invalid resolution"
-    why = pairs_input(rq) or (rq.pairs_trans and keep_trans_rows(files, rq.pairs_zero_based))
+    why = pairs_input(rq) or thinning(rq) or (rq.pairs_trans and keep_trans_rows(files, rq.pairs_zero_based))
     if why:
         return "Error: %s" % why
     balance = None
