@@ -704,6 +704,32 @@ MST_STABLE int mst_thin_counts(const int32_t *x, const int32_t *dist, const void
                                uint32_t tag, uint32_t seed, uint32_t sample, uint64_t T, int64_t *count_out, int64_t *words,
                                void *stream);
 
+/* ---- raw records of one resolution -> the pixels of a coarser one (the rule: mustache_amd/multires.py;
+ * tests/multires_reference.py restates it).  Added without a change of MST_ABI_REVISION, as mst_thin_counts was. */
+/* Records (x, dist: dev int32 [n_records]; count_in: dev int64 / float / double [n_records] by count_kind, MST_THIN_COUNT_*) of
+ * the pixels (x, y = x + dist) at some resolution r.  With factor k >= 1 a record goes to X = x / k, Y = y / k of the
+ * resolution r * k, whose bin count is n (the caller's: a record with x < 0, dist < 0 or Y >= n is read and not written, so the
+ * sums below then differ).  A pixel with Y - X < dense_diags adds its count to dense[(Y - X) * n + X] (dev uint64
+ * [dense_diags][n], ACCUMULATED: the caller zeroes it; 64-bit integer atomics, so a cell that receives 3 * 2^31 holds 3 * 2^31);
+ * any other pixel appends (far_key = X * n + Y, far_count) to the far list (dev int64 [far_cap] each), one entry per run of
+ * adjacent records of a wave that share the key, in no fixed order.  A count that is no integer value in [0, 2^32 - 1]
+ * (negative, above, fractional, not finite) counts as 0 and sets words[2] = 1.  words (dev int64 [3], ACCUMULATED: the caller
+ * zeroes them): [0] the far entries -- more than far_cap means entries were lost (nothing is written past far_cap; far_cap =
+ * n_records always suffices) --, [1] the sum of the counts read, [2] the bad-count flag.  Runs whose counts sum to 0 write
+ * nothing.  dense_diags = 0 is legal (dense may be NULL); dense_diags <= n.  Adjacent lanes with equal keys combine their
+ * counts before the atomic; every sum is an integer sum, so the results do not depend on the order of the records. */
+MST_STABLE int mst_coarsen_records(const int32_t *x, const int32_t *dist, const void *count_in, int32_t count_kind, int64_t n_records,
+                                   int32_t factor, int64_t n, int32_t dense_diags, uint64_t *dense, int64_t *far_key,
+                                   int64_t *far_count, int64_t far_cap, int64_t *words, void *stream);
+/* The non-zero counters of dense [dense_diags][n] (uint64) -> records (out_x, out_dist: dev int32 [cap]; out_count: dev int64
+ * [cap]) in position order (by diagonal, then by x); *n_out (dev int64) = their number, which may exceed cap: nothing is
+ * written past cap.  Two passes and a scan, no atomics.  workspace: dev, mst_coarsen_compact_workspace_bytes(dense_diags, n)
+ * bytes. */
+MST_STABLE uint64_t mst_coarsen_compact_workspace_bytes(int32_t dense_diags, int64_t n);
+MST_STABLE int mst_coarsen_compact(const uint64_t *dense, int32_t dense_diags, int64_t n, int32_t *out_x, int32_t *out_dist,
+                                   int64_t *out_count, int64_t cap, int64_t *n_out, void *workspace, uint64_t workspace_bytes,
+                                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -380,21 +380,31 @@ def read_raw_sample(f, CHRM_SIZE, res, distance_in_bp, chromosome, device=None, 
     return None if raw is None else raw + (None,)
 
 
+def thin_raw(raw, T, seed, sample, chromosome):
+    """read_raw_sample's result thinned with the threshold T of downsample.thin_records (one printed line) -> the same tuple
+    with the kept pixels and int64 counts, None when nothing is kept"""
+    from .downsample import report, thin_records
+    xd, dd, counts, dev, host_depth = raw
+    (xd, dd, counts), total, kept = thin_records(xd, dd, counts, chromosome, T, seed, sample, dev)
+    if host_depth is not None and total != host_depth:
+        raise RuntimeError("downsample: the device summed %d contacts of %s, the host reader counted %d" % (total, chromosome, host_depth))
+    report(chromosome, sample, total, kept, T, seed)
+    if kept == 0:
+        print(f'There is no contact in chrmosome {chromosome} to work on.')
+        return None
+    return xd, dd, counts, dev, host_depth
+
+
 def thin_and_balance(raw, T, seed, sample, distance_in_bp, chromosome, res, balance):
     """What follows read_raw_sample: the optional thinning (T = the threshold of downsample.thin_records, None: none; one
     printed line), then balance.balance_records_device -> (x, y, v) host arrays, None when nothing is left."""
     import torch
     from .balance import balance_records_device, method_of
-    xd, dd, counts, dev, host_depth = raw
     if T is not None:
-        from .downsample import report, thin_records
-        (xd, dd, counts), total, kept = thin_records(xd, dd, counts, chromosome, T, seed, sample, dev)
-        if host_depth is not None and total != host_depth:
-            raise RuntimeError("downsample: the device summed %d contacts of %s, the host reader counted %d" % (total, chromosome, host_depth))
-        report(chromosome, sample, total, kept, T, seed)
-        if kept == 0:
-            print(f'There is no contact in chrmosome {chromosome} to work on.')
+        raw = thin_raw(raw, T, seed, sample, chromosome)
+        if raw is None:
             return None
+    xd, dd, counts, dev, _ = raw
     vd = counts if counts.dtype == torch.float32 else counts.to(torch.float64)
     return balance_records_device(xd, dd, vd, distance_in_bp, chromosome, res, dev, method=method_of(balance))
 
@@ -538,6 +548,13 @@ def parse_args(args):
                    help="OPTIONAL: .pairs / .pairs.gz input only: positions are 0-based (bin = pos // res) instead of the "
                         "format's 1-based ones (bin = (pos - 1) // res)")
     add_downsample_arguments(p)
+    p.add_argument("--coarser", dest="coarser", nargs='+', default=None, metavar="R",
+                   help="OPTIONAL: further resolutions, integer multiples of -r, to call from the same read and merge into one "
+                        "list (mustache_amd/multires.py): .hic and .pairs / .pairs.gz input under --balance, intra-chromosomal "
+                        "runs, one GPU")
+    p.add_argument("--merge-distance", dest="merge_distance", type=int, default=None, metavar="M",
+                   help="OPTIONAL: with --coarser, a coarser loop is dropped when a kept loop lies within M bins of the coarser "
+                        "resolution in both coordinates (default 2)")
     from .balance_genome import add_arguments
     add_arguments(p)
     return p.parse_args(args)
@@ -810,6 +827,74 @@ def call_cis_pairs(f, args, res, pairs, balance, distFilter, rank, world, device
     return results if by_chromosome else None
 
 
+def call_multires(f, args, res, coarser, pairs, balance, device):
+    """The --coarser run (mustache_amd/multires.py): per chromosome one read of the raw pixel set at -r -- the next
+    chromosome's on a reader thread meanwhile --, one thinning under --downsample, then for -r and each coarser resolution in
+    ascending order the coarsening (factor > 1), the balancing and the call, each with the distance limit a run at that
+    resolution resolves; the merged lists are written chromosome by chromosome."""
+    from .balance import balance_records_device, method_of
+    from .downsample import threshold_of
+    from .multires import MERGE_DISTANCE, coarsen_records, merge_loops, report
+    import torch
+    resolutions = [res] + list(coarser)
+    limits = [resolve_distance_filter(args.distFilter, R) for R in resolutions]
+    M = MERGE_DISTANCE if args.merge_distance is None else args.merge_distance
+    T = None if args.downsample is None else threshold_of(args.downsample)
+    chrSize_in_bp = False
+    if args.chrSize_file:
+        import pandas as pd
+        csz = pd.read_csv(args.chrSize_file, header=None, sep='\t')
+        chrSize_in_bp = {"chr" + str(csz.iloc[i, 0]).replace('chr', ''): csz.iloc[i, 1] for i in range(csz.shape[0])}
+
+    def fetch(k):                            # on the reader thread: the parse (or inflate) and the binning at -r
+        chromosome = pairs[k][0]
+        CHRM_SIZE = chrSize_in_bp["chr" + str(chromosome).replace('chr', '')] if chrSize_in_bp else False
+        from ._lib import stage
+        if args.verbose:
+            print("Reading contact map...")
+        with stage("read %s" % chromosome):
+            return read_raw_sample(f, CHRM_SIZE, res, limits[0], chromosome, device=device, balance=balance,
+                                   pairs_zero_based=args.pairs_zero_based, verbose=args.verbose)
+
+    for i, raw in read_ahead(len(pairs), fetch):
+        start_time = time.time()
+        chromosome = pairs[i][0]
+        if raw is not None and T is not None:
+            raw = thin_raw(raw, T, args.seed or 0, 0, chromosome)
+        lists = [[] for _ in resolutions]
+        if raw is not None:
+            xd, dd, counts, dev, _ = raw
+            del raw
+            # every coarse pixel set first: a count that is no integer ends the run before anything of the chromosome is called
+            sets = [(xd, dd, counts)] + [coarsen_records(xd, dd, counts, R // res, distance_bins=limit // R, device=dev,
+                                                         chromosome=chromosome)
+                                         for R, limit in zip(resolutions[1:], limits[1:])]
+            del xd, dd, counts
+            for j, (R, limit) in enumerate(zip(resolutions, limits)):
+                x, d, c = sets[j]
+                sets[j] = None                   # the raw records of a resolution are released once it is balanced
+                contacts = None
+                if c.numel():
+                    vd = c if c.dtype == torch.float32 else c.to(torch.float64)
+                    contacts = balance_records_device(x, d, vd, limit, chromosome, R, dev, method=method_of(balance))
+                    del vd
+                del x, d, c
+                if contacts is not None:
+                    lists[j] = regulator(f, args.norm_method, False, args.outdir, bed=args.bed, res=R, sigma0=args.s_z, s=args.s,
+                                         verbose=args.verbose, pt=args.pt, st=args.st, distance_filter=limit,
+                                         nprocesses=args.nprocesses, chromosome=chromosome, chromosome2=chromosome,
+                                         octaves=args.octaves, contacts=contacts + (R,))
+                print("{0} loops found for chrmosome={1} at {2} bp, fdr<{3} in {4}sec".format(
+                    len(lists[j]), chromosome, R, args.pt, "%.2f" % (time.time() - start_time)))
+                start_time = time.time()
+        kept = merge_loops(lists, resolutions, M)
+        for j, R in enumerate(resolutions):
+            if j:
+                report(chromosome, R, len(kept[j]), len(lists[j]), M)
+            if kept[j] or (i == 0 and j == 0):
+                write_loops(args.outdir, chromosome, chromosome, R, kept[j], first=(i == 0 and j == 0))
+
+
 def call_trans_pairs(f, args, res, run, distFilter, device):
     """The inter-chromosomal pairs of a mustache run (mustache_amd/trans.py), one by one in pair order after every
     intra-chromosomal pair; the header is written with the run's first pair's rows."""
@@ -847,18 +932,27 @@ def call_trans_pairs(f, args, res, run, distFilter, device):
 def main(argv=None):
     start_time = time.time()
     args = parse_args(sys.argv[1:] if argv is None else argv)
-    from .request import plan, refuse, request_of
+    from .request import coarser_resolutions, plan, refuse, request_of
     from .sharding import init_from_env
     rank, world = init_from_env()       # multi-GPU: blocks of each chromosome are sharded, rank 0 writes the TSV
     print("\n")
     f = args.mat if args.bed and args.mat else args.f_path
     res = parseBP(args.resolution)
-    run = plan(request_of(args, [f], [(args.biasfile, "Couldn't find specified bias file")], "-b", world, text_pair_raises=True),
-               res)
+    asked = request_of(args, [f], [(args.biasfile, "Couldn't find specified bias file")], "-b", world, text_pair_raises=True)
+    run = plan(asked, res)
     if isinstance(run, str):
         return refuse(run)
     if run.trans_all:
         return call_trans_all(f, args, res, run)
+    coarser = coarser_resolutions(asked, res)
+    if coarser:                          # plan() has refused every run but a single-rank, intra-chromosomal --balance run
+        import torch
+        from .multires import MultiresError
+        try:
+            return call_multires(f, args, res, coarser, run.cis, run.balance, torch.device("cuda", torch.cuda.current_device()))
+        except MultiresError as e:
+            print("Error: %s" % e)
+            return None
     distFilter = resolve_distance_filter(args.distFilter, res)
     try:
         import torch

@@ -6,7 +6,8 @@ for both command lines ("The order of refusals").  The guards of the 
 diff_trans.regulate, pileup's trans mode, balance_genome.check_genome_request, trans.read_trans_contacts) raise their own
 exception types with the rule functions and sentences of this module.  balance.check_request (`--balance`) and
 balance_genome.check_genome_request (`--balance-genome`) are the two rules that live beside what they guard; the rule of
-`--downsample` / `--seed` / `--match-depth` (thinning) is here, with the helpers of mustache_amd/downsample.py for P and the seed.
+`--downsample` / `--seed` / `--match-depth` (thinning) is here, with the helpers of mustache_amd/downsample.py for P and the seed;
+so is the rule of `--coarser` / `--merge-distance` (multires), with mustache_amd/multires.py's parse of the resolutions.
 
 Host only: no torch and no native library at import; plan() reads no contact data except the one parse of a pairs file under
 --pairs-trans (keep_trans_rows) and the chromosome list of a run without -ch."""
@@ -26,10 +27,26 @@ THIN_INPUT = "%s and %s: raw counts are thinned from .hic and .pairs / .pairs.gz
 # files: the contact file(s), one or two (None: not given); bias: [(the -b / -b1 / -b2 file or None, the sentence when it is
 # missing)]; bias_flag: the flag to quote; ch, ch2: the -ch / -ch2 lists ('n' when absent); ranks: the ranks of the run;
 # text_pair_raises: a trans pair on text input ends the run as the reference's one-sample caller does (Raises)
-Request = namedtuple("Request", "files bias bias_flag norm_method balance balance_genome balance_pixels balance_pixels_given "
-                                "pairs_trans pairs_zero_based trans_all ch ch2 ranks text_pair_raises downsample seed match_depth",
-                     defaults=(None, None, False))
+_RequestTuple = namedtuple("Request", "files bias bias_flag norm_method balance balance_genome balance_pixels balance_pixels_given "
+                                      "pairs_trans pairs_zero_based trans_all ch ch2 ranks text_pair_raises downsample seed match_depth",
+                           defaults=(None, None, False))
 # downsample: --downsample's fraction (None: not given); seed: --seed (None: not given); match_depth: diff_mustache's --match-depth
+
+
+class Request(_RequestTuple):
+    """The tuple above, and behind it -- by keyword only, with defaults -- what `mustache` asks of mustache_amd/multires.py:
+    coarser = the --coarser strings (None: not given), merge_distance = --merge-distance (None: not given).  They are attributes
+    beside the tuple, not fields of it: tests/test_cli_downsample_requests.py pins the tuple's last three fields, and a
+    positional caller keeps working either way."""
+
+    def __new__(cls, *fields, coarser=None, merge_distance=None, **named):
+        self = super().__new__(cls, *fields, **named)
+        self.coarser, self.merge_distance = coarser, merge_distance
+        return self
+
+    def _replace(self, **changes):
+        extra = {k: changes.pop(k, getattr(self, k)) for k in ("coarser", "merge_distance")}
+        return type(self)(*super()._replace(**changes), **extra)
 
 # cis, trans: the (chromosome, chromosome2) pairs in run order, every cis pair before the first trans pair; trans_all: a
 # --trans-all run; balance: the --balance method in upper case, or None; genome: --balance-genome's (method, pixels), or None
@@ -40,7 +57,8 @@ def request_of(args, files, bias, bias_flag, ranks, text_pair_raises=False):
     """the Request of a command line's parsed arguments"""
     return Request(list(files), bias, bias_flag, args.norm_method, args.balance, args.balance_genome, args.balance_pixels,
                    args.balance_pixels_given, args.pairs_trans, args.pairs_zero_based, args.trans_all, args.chromosome,
-                   args.chromosome2, ranks, text_pair_raises, args.downsample, args.seed, getattr(args, "match_depth", False))
+                   args.chromosome2, ranks, text_pair_raises, args.downsample, args.seed, getattr(args, "match_depth", False),
+                   coarser=getattr(args, "coarser", None), merge_distance=getattr(args, "merge_distance", None))
 
 
 class Raises(str):
@@ -158,6 +176,44 @@ def thinning(rq):
     return None
 
 
+def coarser_resolutions(rq, res):
+    """the --coarser resolutions of the request in bp, ascending ([] without the flag); multires.MultiresError for a value
+    the rule below refuses"""
+    if rq.coarser is None:
+        return []
+    from .multires import parse_resolutions
+    return parse_resolutions(int(res), rq.coarser)
+
+
+def multires(rq, res):
+    """What --coarser / --merge-distance (mustache_amd/multires.py) rule out at -r = res bp.  Reads nothing."""
+    from .multires import NOT_RAW, MultiresError
+    from .pairs import is_pairs
+    if rq.coarser is None:
+        if rq.merge_distance is not None:
+            return "--merge-distance without --coarser: it is the tolerance of the multi-resolution merge and nothing else"
+        return None
+    if rq.merge_distance is not None and int(rq.merge_distance) < 0:
+        return "--merge-distance %d: the distance is a number of bins >= 0" % rq.merge_distance
+    try:
+        coarser_resolutions(rq, res)
+    except MultiresError as e:
+        return str(e)
+    if rq.trans_all or rq.balance_genome is not None or rq.pairs_trans or other_chromosome(rq.ch, rq.ch2):
+        return "--coarser on a run with an inter-chromosomal pair: only intra-chromosomal maps are coarsened"
+    if given_bias(rq) or (rq.norm_method and str(rq.norm_method).upper() != "NONE"):
+        return "--coarser with %s or -norm: %s" % (rq.bias_flag, NOT_RAW)
+    if rq.balance is None:
+        return "--coarser without --balance: %s" % NOT_RAW
+    for f in rq.files:
+        if not (is_pairs(f) or str(f).endswith(".hic")):
+            return "--coarser and %s: raw counts are coarsened from .hic and .pairs / .pairs.gz input only" % f
+    if rq.ranks > 1:
+        return "--coarser in a multi-rank run (world size %d): every resolution of a chromosome is called on one GPU; start a " \
+               "single process" % rq.ranks
+    return None
+
+
 def keep_trans_rows(files, zero_based):
     """--pairs-trans: each pairs file's one parse of the run keeps the trans rows, whoever asks for the handle first, and
     happens here, before a GPU is touched: a file without `#chromsize` lines ends the run with the reader's sentence."""
@@ -234,7 +290,7 @@ def plan(rq, res):
         return "Error: Couldn't find the specified contact files"
     if not res:
         return "Error: Invalid resolution"
-    why = pairs_input(rq) or thinning(rq) or (rq.pairs_trans and keep_trans_rows(files, rq.pairs_zero_based))
+    why = pairs_input(rq) or thinning(rq) or multires(rq, res) or (rq.pairs_trans and keep_trans_rows(files, rq.pairs_zero_based))
     if why:
         return "Error: %s" % why
     balance = None
