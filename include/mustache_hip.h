@@ -703,6 +703,26 @@ MST_STABLE int mst_pairs_trans_decode(const int64_t *keys, const int64_t *counts
 MST_STABLE int mst_thin_counts(const int32_t *x, const int32_t *dist, const void *count_in, int32_t count_kind, int64_t n_records,
                                uint32_t tag, uint32_t seed, uint32_t sample, uint64_t T, int64_t *count_out, int64_t *words,
                                void *stream);
+/* The same thinning for the trans records of MANY chromosome pairs in one launch (`--downsample-genome`, `--match-depth-genome`;
+ * tests/downsample_genome_reference.py restates it).  Added without a change of MST_ABI_REVISION, as mst_thin_counts was.
+ * tag: zlib.crc32 of the pair's two stripped names, first + "\t" + second; swap != 0: the records' y is the bin on the first. */
+typedef struct mst_thin_pair {
+    uint32_t tag;
+    uint32_t swap;
+} mst_thin_pair;
+/* Records (x, y: dev int32 [n_records]; count_in as above) of n_pairs pairs, pair p in [seg_off[p], seg_off[p + 1]) (seg_off: dev
+ * int64 [n_pairs + 1], non-decreasing, seg_off[0] = 0, seg_off[n_pairs] = n_records; empty pairs are legal; whatever it holds,
+ * nothing is read or written out of bounds).  table: dev [n_pairs].  A record of pair p keeps count_out[e] = k = #{ j in [0, n) :
+ * u_j < T }, u_j = word j & 3 of Philox4x32-10(counter = (a, b, j >> 2, table[p].tag), key = (seed, key1)) with (a, b) = (y, x)
+ * when table[p].swap and (x, y) otherwise -- with swap = 0 exactly mst_thin_counts' k for (x, dist = y - x, tag, sample = key1).
+ * words (dev int64 [2 * n_pairs + 1], ACCUMULATED: the caller zeroes them): [2p] the sum of pair p's counts, [2p + 1] the sum of
+ * its k, [2 * n_pairs] the bad-count flag (a bad count counts as 0).  count_out = NULL: nothing is drawn or written but the
+ * sums of the counts and the flag (T is then not looked at).  max_blocks: the most workgroups (of 256 records a trip) to launch,
+ * 0 for the default; the results do not depend on it, nor on the order of the records within a pair.  n_records = 0 launches
+ * nothing. */
+MST_STABLE int mst_thin_pairs(const int32_t *x, const int32_t *y, const void *count_in, int32_t count_kind, int64_t n_records,
+                              const int64_t *seg_off, const mst_thin_pair *table, int32_t n_pairs, uint32_t seed, uint32_t key1,
+                              uint64_t T, int64_t *count_out, int64_t *words, int32_t max_blocks, void *stream);
 
 /* ---- raw records of one resolution -> the pixels of a coarser one (the rule: mustache_amd/multires.py;
  * tests/multires_reference.py restates it).  Added without a change of MST_ABI_REVISION, as mst_thin_counts was. */

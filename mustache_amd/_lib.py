@@ -136,6 +136,7 @@ _SIGNATURES = {
     "mst_pairs_trans_compact": (ctypes.c_int, [_p, _i64, _p, _p, _i64, _p, _p, _u64, _p]),
     "mst_pairs_trans_decode": (ctypes.c_int, [_p, _p, _i64, _p, _p, _i32, _p, _p, _p, _p]),
     "mst_thin_counts": (ctypes.c_int, [_p, _p, _p, _i32, _i64, _u32, _u32, _u32, _u64, _p, _p, _p]),
+    "mst_thin_pairs": (ctypes.c_int, [_p, _p, _p, _i32, _i64, _p, _p, _i32, _u32, _u32, _u64, _p, _p, _i32, _p]),
     "mst_coarsen_records": (ctypes.c_int, [_p, _p, _p, _i32, _i64, _i32, _i64, _i32, _p, _p, _p, _i64, _p, _p]),
     "mst_coarsen_compact_workspace_bytes": (_u64, [_i32, _i64]),
     "mst_coarsen_compact": (ctypes.c_int, [_p, _i32, _i64, _p, _p, _p, _i64, _p, _p, _u64, _p]),

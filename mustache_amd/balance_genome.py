@@ -40,6 +40,14 @@ pairs.bin_pairs_device with every diagonal and lose their pixels below IGNORE_DI
 Unlike a `.hic` matrix the rows' count is known before the upload, so the memory check comes first: pairs_upload_bytes against
 torch.cuda.mem_get_info.  Integer counts reach float64 unrounded, so a pairs file and a `.hic` file of the same contacts give
 the same bias to the bit.
+
+genome_bias is two phases: read_genome (everything above up to the assembly: the per-chromosome cis parts, kept apart, and the
+resident trans records) and solve_genome (the assembly and the solver).  Between them an optional thin_genome
+(`--downsample-genome`, `--match-depth-genome`; the rule is mustache_amd/downsample.py's): each cis part through
+mst_thin_counts, one launch per chromosome; the resident trans records through mst_thin_pairs, consecutive pairs sharing a
+launch up to APPLY_BATCH_RECORDS records, as balanced_batches forms its batches.  The memory check counts what a launch adds
+(THIN_CIS_BYTES, THIN_TRANS_BYTES per record), and under `--match-depth-genome` that both samples' raw sets are resident before
+either is solved (check_solve_memory).
 """
 import numpy as np
 
@@ -316,19 +324,37 @@ def _pairs_source(h, f, res, dev, pixels, verbose, zero_based):
     return names, lengths, cis, trans
 
 
-def genome_bias(f, res, method="NEWTON", pixels="all", device=None, keep_records=True, pairs_zero_based=False, verbose=False,
-                **solver_args):
-    """Balance the whole genome of f at resolution res -> GenomeBias.  f is a `.hic` file, or a `.pairs` / `.pairs.gz` file with
-    `#chromsize` lines (pairs_zero_based: its position convention).  Every matrix is read once -- a pairs file is parsed once
-    and its rows are binned on the device; the trans pairs' raw records stay on the device when keep_records.  Both sources
-    feed one assembly: per-chromosome cis pixels (`all` only), per-pair trans records, then solve(..., ignore_diags=0).
-    Raises BalanceError for an unknown method or pixels value and when the records do not fit the device's free memory."""
+class GenomeRead:
+    """What read_genome returns, and solve_genome takes: the genome's raw pixels on the device, not yet assembled.  names,
+    lengths, bins, offsets, n: the layout; pixels: `all` or `inter`; cis: [(c, x, dist, v)] int64 / int64 / float64 device
+    tensors of chromosome c's pixels that enter the assembly (inside the chromosome, dist >= IGNORE_DIAGS; `all` only), kept
+    apart; records: {(i, j), i < j: (x of i, y of j, v)} int32 / int32 / float64 resident device tensors of every pair that
+    has any, in reading order; source: the file's name."""
+
+    def __init__(self, names, lengths, bins, offsets, n, pixels, device, source):
+        self.names, self.lengths, self.bins, self.offsets, self.n = list(names), list(lengths), list(bins), list(offsets), int(n)
+        self.pixels, self.device, self.source = pixels, device, source
+        self.cis, self.records = [], {}
+
+    def entering(self):
+        """the pixels the assembly will hold"""
+        total = sum(int(v.numel()) for _, _, _, v in self.cis)
+        for (i, j), (x, y, v) in self.records.items():
+            total += int(((x >= 0) & (x < self.bins[i]) & (y >= 0) & (y < self.bins[j])).sum())
+        return total
+
+    def resident(self):
+        return sum(int(v.numel()) for _, _, v in self.records.values())
+
+
+def read_genome(f, res, pixels="all", device=None, pairs_zero_based=False, verbose=False):
+    """The read phase of genome_bias: every matrix of f read once (a pairs file parsed once and binned on the device) ->
+    GenomeRead.  The memory check runs after each matrix, as the module's header says.  pixels is `all` or `inter` as
+    check_genome_request returns it."""
     import torch
     from . import pairs as pairs_mod
-    from .balance import solve
     from ._lib import require_gpu
     from_pairs = pairs_mod.is_pairs(f)
-    method, pixels = check_genome_request(method, pixels, [f], None, None, None, 1, True, pairs_trans=from_pairs)
     handle = pairs_open(f, pairs_zero_based) if from_pairs else None
     require_gpu()
     res = int(res)
@@ -339,38 +365,179 @@ def genome_bias(f, res, method="NEWTON", pixels="all", device=None, keep_records
         else:
             names, lengths, cis, trans = _hic_source(f, res, dev, pixels, verbose)
         bins, offsets, n = genome_layout(lengths, res)
-        los, his, vs = [], [], []
-        records, total, resident = {}, 0, 0
+        read = GenomeRead(names, lengths, bins, offsets, n, pixels, dev, f)
+        total, resident = 0, 0
         if pixels == "all":
             for c, x, d, v in cis():
                 keep = (d >= IGNORE_DIAGS) & (x >= 0) & (x + d < bins[c])
-                x, d, v = x[keep], d[keep], v[keep]
-                los.append(x + offsets[c])
-                his.append(x + d + offsets[c])
-                vs.append(v)
-                total += int(v.numel())
+                read.cis.append((c, x[keep], d[keep], v[keep]))
+                del x, d, v
+                total += int(read.cis[-1][3].numel())
                 _check_memory(total, resident)
         for (i, j), (x, y, v) in trans():
             if v.numel() == 0:
                 continue
-            if keep_records:
-                records[(i, j)] = (x, y, v)
-                resident += RESIDENT_BYTES * int(v.numel())
+            read.records[(i, j)] = (x, y, v)
+            resident += RESIDENT_BYTES * int(v.numel())
+            total += int(((x >= 0) & (x < bins[i]) & (y >= 0) & (y < bins[j])).sum())
+            _check_memory(total, resident)
+    return read
+
+
+THIN_CIS_BYTES = 8 + 8 + 1 + 24   # thinning a cis part, per pixel: the int32 x and dist, k, the mask, the compacted copy
+THIN_TRANS_BYTES = 16 + 8 + 1 + 16   # thinning a batch of pairs, per record: the concatenated copy, k, the mask, the compacted copy
+
+
+def _check_thin_memory(records, per_record, resident):
+    import torch
+    free = int(torch.cuda.mem_get_info()[0])
+    need = int(records) * per_record
+    if need > free:
+        raise BalanceError("--balance-genome: thinning %d pixels needs about %d bytes of device memory beside the %d resident "
+                           "ones, %d bytes are free" % (records, need, resident, free))
+
+
+def check_solve_memory(reads):
+    """Under --match-depth-genome both samples' raw sets are on the device before either is solved: BalanceError unless the
+    larger assembly fits what is free now."""
+    import torch
+    if not reads:
+        return
+    most = max(r.entering() for r in reads)
+    free = int(torch.cuda.mem_get_info()[0])
+    if estimate_bytes(most) > free:
+        raise BalanceError("--balance-genome: balancing %d pixels needs about %d bytes of device memory beside the %d resident "
+                           "ones of both samples, %d bytes are free"
+                           % (most, estimate_bytes(most), RESIDENT_BYTES * sum(r.resident() for r in reads), free))
+
+
+def _pair_batches(read, max_records):
+    """the keys of read.records in order, consecutive pairs together until their records reach max_records"""
+    batch, held = [], 0
+    for key, (_, _, v) in read.records.items():
+        batch.append(key)
+        held += int(v.numel())
+        if held >= max_records:
+            yield batch
+            batch, held = [], 0
+    if batch:
+        yield batch
+
+
+def _batch_tensors(read, keys):
+    import torch
+    recs = [read.records[key] for key in keys]
+    seg = np.zeros(len(keys) + 1, np.int64)
+    np.cumsum([int(r[2].numel()) for r in recs], out=seg[1:])
+    if len(recs) == 1:
+        return tuple(t.contiguous() for t in recs[0]) + (seg,)
+    return tuple(torch.cat([r[k] for r in recs]) for k in range(3)) + (seg,)
+
+
+def genome_depth(read, max_records=APPLY_BATCH_RECORDS):
+    """N of mustache_amd/downsample.py for a GenomeRead: (the cis contacts, the trans contacts), integer sums from the kernels
+    (mst_thin_counts per chromosome, mst_thin_pairs per batch of pairs; nothing is drawn).  DownsampleError for a count that
+    is no integer."""
+    import torch
+    from .downsample import depth_of, depth_of_pairs
+    n_cis = n_trans = 0
+    with torch.cuda.device(read.device):
+        for c, x, d, v in read.cis:
+            n_cis += depth_of(x.to(torch.int32), d.to(torch.int32), v, read.names[c], device=read.device)
+        for keys in _pair_batches(read, max_records):
+            x, y, v, seg = _batch_tensors(read, keys)
+            n_trans += sum(depth_of_pairs(x, y, v, seg, [(read.names[i], read.names[j]) for i, j in keys], device=read.device))
+    return n_cis, n_trans
+
+
+def thin_genome(read, T, seed=0, sample=0, max_records=APPLY_BATCH_RECORDS):
+    """The optional step between read_genome and solve_genome: the rule of mustache_amd/downsample.py on a GenomeRead, in place.
+    Each cis part goes through mst_thin_counts (one launch per chromosome, the one-chromosome draw unchanged), the resident
+    trans records through mst_thin_pairs, consecutive pairs sharing a launch until their records reach max_records.  Pixels
+    and records with k = 0 are dropped, a pair left without a record leaves `records`, the counts come back as float64: from
+    here on nothing knows the map was thinned.  -> ((cis contacts kept, in), (trans contacts kept, in)).  DownsampleError for
+    a count that is no integer and for two chromosomes whose stripped names are equal; BalanceError when the device's free
+    memory cannot hold what a launch adds."""
+    import torch
+    from .downsample import pair_tag, thin_pairs, thin_records
+    for i in range(len(read.names)):                  # before anything is drawn: every pair of the file has a stream of its own
+        for j in range(i + 1, len(read.names)):
+            pair_tag(read.names[i], read.names[j])
+    cis_kept = cis_in = trans_kept = trans_in = 0
+    with torch.cuda.device(read.device):
+        resident = RESIDENT_BYTES * read.resident()
+        for at, (c, x, d, v) in enumerate(read.cis):
+            _check_thin_memory(int(v.numel()), THIN_CIS_BYTES, resident)
+            (tx, td, tk), total, kept = thin_records(x.to(torch.int32), d.to(torch.int32), v, read.names[c], T, seed=seed,
+                                                     sample=sample, device=read.device)
+            read.cis[at] = (c, tx.to(torch.int64), td.to(torch.int64), tk.to(torch.float64))
+            cis_in, cis_kept = cis_in + total, cis_kept + kept
+            del x, d, v, tx, td, tk
+        for keys in list(_pair_batches(read, max_records)):
+            _check_thin_memory(sum(int(read.records[key][2].numel()) for key in keys), THIN_TRANS_BYTES, resident)
+            x, y, v, seg = _batch_tensors(read, keys)
+            k, totals = thin_pairs(x, y, v, seg, [(read.names[i], read.names[j]) for i, j in keys], T, seed=seed, sample=sample,
+                                   device=read.device)
+            del v
+            keep = k > 0
+            for p, key in enumerate(keys):
+                s, e = int(seg[p]), int(seg[p + 1])
+                m = keep[s:e]
+                got = (x[s:e][m], y[s:e][m], k[s:e][m].to(torch.float64))
+                if got[2].numel():
+                    read.records[key] = got
+                else:
+                    del read.records[key]
+                trans_in, trans_kept = trans_in + totals[p][0], trans_kept + totals[p][1]
+            del x, y, k, keep
+    return (cis_kept, cis_in), (trans_kept, trans_in)
+
+
+def solve_genome(read, method="NEWTON", keep_records=True, **solver_args):
+    """The solve phase of genome_bias: the assembly of a GenomeRead's pixels in genome coordinates, then
+    solve(..., ignore_diags=0) -> GenomeBias.  The cis parts are consumed."""
+    import torch
+    from .balance import solve
+    dev, bins, offsets = read.device, read.bins, read.offsets
+    with torch.cuda.device(dev):
+        los, his, vs = [], [], []
+        total = 0
+        while read.cis:
+            c, x, d, v = read.cis.pop(0)
+            los.append(x + offsets[c])
+            his.append(x + d + offsets[c])
+            vs.append(v)
+            total += int(v.numel())
+            del x, d, v
+        for (i, j), (x, y, v) in read.records.items():
             inside = (x >= 0) & (x < bins[i]) & (y >= 0) & (y < bins[j])
             los.append(x[inside].to(torch.int64) + offsets[i])
             his.append(y[inside].to(torch.int64) + offsets[j])
             vs.append(v[inside])
             total += int(vs[-1].numel())
-            _check_memory(total, resident)
         if vs:
             lo, hi, v = torch.cat(los), torch.cat(his), torch.cat(vs)
         else:
             lo = hi = torch.zeros(0, dtype=torch.int64, device=dev)
             v = torch.zeros(0, dtype=torch.float64, device=dev)
         del los, his, vs
-        bias, info = solve(method, lo, hi, v, n, ignore_diags=0, device=dev, **solver_args)
-    info["pixels"], info["records"] = pixels, total
-    return GenomeBias(names, bins, offsets, n, bias, info, dev, records)
+        bias, info = solve(method, lo, hi, v, read.n, ignore_diags=0, device=dev, **solver_args)
+    info["pixels"], info["records"] = read.pixels, total
+    return GenomeBias(read.names, bins, offsets, read.n, bias, info, dev, read.records if keep_records else {})
+
+
+def genome_bias(f, res, method="NEWTON", pixels="all", device=None, keep_records=True, pairs_zero_based=False, verbose=False,
+                **solver_args):
+    """Balance the whole genome of f at resolution res -> GenomeBias.  f is a `.hic` file, or a `.pairs` / `.pairs.gz` file with
+    `#chromsize` lines (pairs_zero_based: its position convention).  Every matrix is read once -- a pairs file is parsed once
+    and its rows are binned on the device; the trans pairs' raw records stay on the device when keep_records.  Both sources
+    feed one assembly: per-chromosome cis pixels (`all` only), per-pair trans records, then solve(..., ignore_diags=0) --
+    read_genome, then solve_genome; a thinning (thin_genome) may stand between the two.
+    Raises BalanceError for an unknown method or pixels value and when the records do not fit the device's free memory."""
+    from . import pairs as pairs_mod
+    method, pixels = check_genome_request(method, pixels, [f], None, None, None, 1, True, pairs_trans=pairs_mod.is_pairs(f))
+    read = read_genome(f, res, pixels, device, pairs_zero_based, verbose)
+    return solve_genome(read, method, keep_records, **solver_args)
 
 
 def apply_pairs(x, y, v, seg_off, row_off, col_off, bias, out=None):

@@ -383,6 +383,9 @@ def parse_args(args):
     p.add_argument("--match-depth", dest="match_depth", action="store_true",
                    help="OPTIONAL: per chromosome, thin the deeper sample's raw map to the depth of the other before --balance "
                         "(binomial thinning on the GPU; .hic and .pairs / .pairs.gz input, intra-chromosomal runs)")
+    p.add_argument("--match-depth-genome", dest="match_depth_genome", action="store_true",
+                   help="OPTIONAL: with --balance-genome: thin the deeper sample's whole genome map (cis and inter-chromosomal) to "
+                        "the depth of the other before the balancing, with one probability for the whole genome")
     from .balance_genome import add_arguments
     add_arguments(p)
     return p.parse_args(args)
@@ -447,7 +450,8 @@ def call_trans_all(files, args, res, run):
     device = torch.device("cuda", torch.cuda.current_device())
     genomes = None
     if run.genome is not None:
-        genomes = genome_biases_or_error(files, res, run.genome, device, args.pairs_zero_based, args.verbose)
+        genomes = genome_biases_or_error(files, res, run.genome, device, args.pairs_zero_based, args.verbose,
+                                         thinning=getattr(args, "genome_thinning", None))
         if genomes is None:
             return
     pairs, state = run.trans, {"t0": time.time()}
@@ -481,7 +485,7 @@ def balanced_trans_rows(genomes, files, pair, args):
 def main(argv=None):
     t0 = time.time()
     args = parse_args(sys.argv[1:] if argv is None else argv)
-    from .request import plan, refuse, request_of
+    from .request import genome_thinning_of, plan, refuse, request_of
     from .sharding import gather_chromosome_rows, init_from_env
     f1 = args.mat1 if args.bed1 and args.mat1 else args.f_path1
     f2 = args.mat2 if args.bed2 and args.mat2 else args.f_path2
@@ -498,6 +502,7 @@ def main(argv=None):
             run = plan(rq._replace(ranks=world_size), res)
     if isinstance(run, str):
         return refuse(run)
+    args.genome_thinning = genome_thinning_of(rq)
     if run.trans_all:
         return call_trans_all([f1, f2], args, res, run)
     distFilter = resolve_distance_filter(args.distFilter, res)
@@ -505,7 +510,8 @@ def main(argv=None):
     biasf2 = args.biasfile2 if args.biasfile2 else False
     genomes = None
     if run.genome is not None:               # --balance-genome: every matrix of both files is read once, here
-        genomes = genome_biases_or_error([f1, f2], res, run.genome, None, args.pairs_zero_based, args.verbose)
+        genomes = genome_biases_or_error([f1, f2], res, run.genome, None, args.pairs_zero_based, args.verbose,
+                                         thinning=getattr(args, "genome_thinning", None))
         if genomes is None:
             return
     # multi-GPU (`torchrun -m mustache_amd.diff_mustache ...`): chromosomes are dealt to the ranks largest first, each rank

@@ -561,12 +561,15 @@ def parse_args(args):
 
 
 def add_downsample_arguments(p):
-    """--downsample and --seed of both command lines (mustache_amd/downsample.py)"""
+    """--downsample, --seed and --downsample-genome of both command lines (mustache_amd/downsample.py)"""
     p.add_argument("--downsample", dest="downsample", type=float, default=None, metavar="P",
                    help="OPTIONAL: keep every raw contact with probability P (0 < P < 1) before --balance: binomial thinning on the "
                         "GPU, .hic and .pairs / .pairs.gz input, intra-chromosomal runs")
     p.add_argument("--seed", dest="seed", type=int, default=None, metavar="S",
                    help="OPTIONAL: the seed of the thinning, a 32-bit unsigned integer (default 0)")
+    p.add_argument("--downsample-genome", dest="downsample_genome", type=float, default=None, metavar="P",
+                   help="OPTIONAL: with --balance-genome: keep every raw contact of the genome's map (the cis pixels it balances on "
+                        "and every inter-chromosomal record) with probability P (0 < P < 1) before the balancing")
 
 
 def resolve_distance_filter(dist_arg, res, quiet=False):
@@ -656,22 +659,39 @@ def octave_values(args):
     return [args.s_z * (2 ** i) for i in range(args.octaves)]
 
 
-def genome_biases_or_error(files, res, request, device=None, pairs_zero_based=False, verbose=True):
+def genome_biases_or_error(files, res, request, device=None, pairs_zero_based=False, verbose=True, thinning=None):
     """--balance-genome: each sample's file balanced on its own (`.hic` or, under --pairs-trans, a pairs file), one
     balance.report line each -> their GenomeBias in order; None after the `Error:` line of a run the device's memory cannot hold
-    (or of a pairs file without `#chromsize` lines).  request = (method, pixels): request.Plan.genome."""
+    (or of a pairs file without `#chromsize` lines).  request = (method, pixels): request.Plan.genome.
+    thinning = (T, seed) (--downsample-genome: each sample is read, thinned with the threshold T and solved in turn), or
+    ("match", seed) (--match-depth-genome: both are read, the depths N_1 and N_2 compared, the deeper one thinned, both
+    solved, after one line that states both depths), or None; one downsample.report_genome line per thinned sample.  A count
+    that is no integer raises downsample.DownsampleError (the command lines' error_line prints it)."""
     from .balance import BalanceError, report
-    from .balance_genome import genome_bias
+    from .balance_genome import check_solve_memory, genome_depth, read_genome, solve_genome, thin_genome
+    from .downsample import match_depth, report_genome
+    how, seed = thinning if thinning is not None else (None, 0)
     out = []
-    for f in files:
-        try:
-            gb = genome_bias(f, res, method=request[0], pixels=request[1], device=device, pairs_zero_based=pairs_zero_based,
-                             verbose=verbose)
-        except BalanceError as e:
-            print("Error: %s" % e)
-            return None
-        report(gb.info, gb.label)
-        out.append(gb)
+    try:
+        thresholds, waiting = [how] * len(files), []
+        if how == "match":
+            waiting = [read_genome(f, res, request[1], device, pairs_zero_based, verbose) for f in files]
+            check_solve_memory(waiting)
+            depths = [sum(genome_depth(r)) for r in waiting]
+            print("depth of the genome: sample 1 holds %d contacts, sample 2 holds %d" % tuple(depths))
+            thresholds = match_depth(*depths)
+        for k, f in enumerate(files):
+            read = waiting.pop(0) if waiting else read_genome(f, res, request[1], device, pairs_zero_based, verbose)
+            if thresholds[k] is not None:
+                cis, trans = thin_genome(read, thresholds[k], seed, k)
+                report_genome(k, cis, trans, thresholds[k], seed)
+            gb = solve_genome(read, request[0])
+            del read
+            report(gb.info, gb.label)
+            out.append(gb)
+    except BalanceError as e:
+        print("Error: %s" % e)
+        return None
     return out
 
 
@@ -720,7 +740,8 @@ def call_trans_all(f, args, res, run):
     device = torch.device("cuda", torch.cuda.current_device())
     genomes = None
     if run.genome is not None:
-        genomes = genome_biases_or_error([f], res, run.genome, device, args.pairs_zero_based, args.verbose)
+        genomes = genome_biases_or_error([f], res, run.genome, device, args.pairs_zero_based, args.verbose,
+                                         thinning=getattr(args, "genome_thinning", None))
         if genomes is None:
             return
     state = {"first": True, "t0": time.time()}
@@ -903,7 +924,8 @@ def call_trans_pairs(f, args, res, run, distFilter, device):
     gbias = None
     if run.genome is not None:               # --balance-genome: every matrix is read once, here; the pairs are called from it
         from .balance_genome import balanced_pair
-        gbias = genome_biases_or_error([f], res, run.genome, device, args.pairs_zero_based, args.verbose)
+        gbias = genome_biases_or_error([f], res, run.genome, device, args.pairs_zero_based, args.verbose,
+                                       thinning=getattr(args, "genome_thinning", None))
         if gbias is None:
             return
     for chromosome, chromosome2 in run.trans:
@@ -932,7 +954,7 @@ def call_trans_pairs(f, args, res, run, distFilter, device):
 def main(argv=None):
     start_time = time.time()
     args = parse_args(sys.argv[1:] if argv is None else argv)
-    from .request import coarser_resolutions, plan, refuse, request_of
+    from .request import coarser_resolutions, genome_thinning_of, plan, refuse, request_of
     from .sharding import init_from_env
     rank, world = init_from_env()       # multi-GPU: blocks of each chromosome are sharded, rank 0 writes the TSV
     print("\n")
@@ -942,6 +964,7 @@ def main(argv=None):
     run = plan(asked, res)
     if isinstance(run, str):
         return refuse(run)
+    args.genome_thinning = genome_thinning_of(asked)
     if run.trans_all:
         return call_trans_all(f, args, res, run)
     coarser = coarser_resolutions(asked, res)

@@ -6,7 +6,8 @@ for both command lines ("The order of refusals").  The guards of the 
 diff_trans.regulate, pileup's trans mode, balance_genome.check_genome_request, trans.read_trans_contacts) raise their own
 exception types with the rule functions and sentences of this module.  balance.check_request (`--balance`) and
 balance_genome.check_genome_request (`--balance-genome`) are the two rules that live beside what they guard; the rule of
-`--downsample` / `--seed` / `--match-depth` (thinning) is here, with the helpers of mustache_amd/downsample.py for P and the seed;
+`--downsample` / `--seed` / `--match-depth` (thinning) is here, with the helpers of mustache_amd/downsample.py for P and the seed,
+and so is the rule of `--downsample-genome` / `--match-depth-genome` (thinning_genome);
 so is the rule of `--coarser` / `--merge-distance` (multires), with mustache_amd/multires.py's parse of the resolutions.
 
 Host only: no torch and no native library at import; plan() reads no contact data except the one parse of a pairs file under
@@ -35,17 +36,20 @@ _RequestTuple = namedtuple("Request", "files bias bias_flag norm_method balance 
 
 class Request(_RequestTuple):
     """The tuple above, and behind it -- by keyword only, with defaults -- what `mustache` asks of mustache_amd/multires.py:
-    coarser = the --coarser strings (None: not given), merge_distance = --merge-distance (None: not given).  They are attributes
-    beside the tuple, not fields of it: tests/test_cli_downsample_requests.py pins the tuple's last three fields, and a
-    positional caller keeps working either way."""
+    coarser = the --coarser strings (None: not given), merge_distance = --merge-distance (None: not given); and what either
+    command line asks of the genome thinning: downsample_genome = --downsample-genome's fraction (None: not given),
+    match_depth_genome = diff_mustache's --match-depth-genome.  They are attributes beside the tuple, not fields of it:
+    tests/test_cli_downsample_requests.py pins the tuple's last three fields, and a positional caller keeps working either way."""
+    EXTRA = ("coarser", "merge_distance", "downsample_genome", "match_depth_genome")
 
-    def __new__(cls, *fields, coarser=None, merge_distance=None, **named):
+    def __new__(cls, *fields, coarser=None, merge_distance=None, downsample_genome=None, match_depth_genome=False, **named):
         self = super().__new__(cls, *fields, **named)
         self.coarser, self.merge_distance = coarser, merge_distance
+        self.downsample_genome, self.match_depth_genome = downsample_genome, bool(match_depth_genome)
         return self
 
     def _replace(self, **changes):
-        extra = {k: changes.pop(k, getattr(self, k)) for k in ("coarser", "merge_distance")}
+        extra = {k: changes.pop(k, getattr(self, k)) for k in self.EXTRA}
         return type(self)(*super()._replace(**changes), **extra)
 
 # cis, trans: the (chromosome, chromosome2) pairs in run order, every cis pair before the first trans pair; trans_all: a
@@ -58,7 +62,9 @@ def request_of(args, files, bias, bias_flag, ranks, text_pair_raises=False):
     return Request(list(files), bias, bias_flag, args.norm_method, args.balance, args.balance_genome, args.balance_pixels,
                    args.balance_pixels_given, args.pairs_trans, args.pairs_zero_based, args.trans_all, args.chromosome,
                    args.chromosome2, ranks, text_pair_raises, args.downsample, args.seed, getattr(args, "match_depth", False),
-                   coarser=getattr(args, "coarser", None), merge_distance=getattr(args, "merge_distance", None))
+                   coarser=getattr(args, "coarser", None), merge_distance=getattr(args, "merge_distance", None),
+                   downsample_genome=getattr(args, "downsample_genome", None),
+                   match_depth_genome=getattr(args, "match_depth_genome", False))
 
 
 class Raises(str):
@@ -151,7 +157,7 @@ def thinning(rq):
     from .downsample import DownsampleError, check_seed, threshold_of
     from .pairs import is_pairs
     if rq.downsample is None and not rq.match_depth:
-        if rq.seed is not None:
+        if rq.seed is not None and rq.downsample_genome is None and not rq.match_depth_genome:
             return "--seed without --downsample or --match-depth: it seeds the thinning and nothing else"
         return None
     if rq.match_depth and rq.downsample is not None:
@@ -173,6 +179,46 @@ def thinning(rq):
     for f in rq.files:
         if not (is_pairs(f) or str(f).endswith(".hic")):
             return THIN_INPUT % (flag, f)
+    return None
+
+
+def thinning_genome(rq):
+    """What --downsample-genome / --match-depth-genome (the genome thinning of mustache_amd/downsample.py) rule out, before
+    thinning(): the flags of one chromosome's thinning and these exclude each other.  What --balance-genome itself refuses --
+    a run that is not all inter-chromosomal pairs, text / `.cool` input, several ranks, pairs input without --pairs-trans --
+    keeps check_genome_request's and pairs_input's sentences.  Reads nothing."""
+    from .downsample import DownsampleError, check_seed, threshold_of
+    if rq.downsample_genome is None and not rq.match_depth_genome:
+        return None
+    flag = "--match-depth-genome" if rq.match_depth_genome else "--downsample-genome"
+    if rq.balance_genome is None:
+        return "%s without --balance-genome: thinning the genome's map needs raw integer counts; give --balance-genome " \
+               "ICE|NEWTON" % flag
+    if rq.match_depth_genome and rq.downsample_genome is not None:
+        return "--match-depth-genome and --downsample-genome: give one of them (--match-depth-genome thins the deeper sample's " \
+               "genome to the other's depth)"
+    if rq.downsample is not None or rq.match_depth:
+        return "%s and %s: give one of them (%s thins each chromosome's own map, %s the whole genome's)" \
+               % (("--match-depth" if rq.match_depth else "--downsample", flag) * 2)
+    if rq.match_depth_genome and len(rq.files) < 2:
+        return "--match-depth-genome matches the depths of two samples: it is diff_mustache's"
+    try:
+        if rq.downsample_genome is not None:
+            threshold_of(rq.downsample_genome, "--downsample-genome")
+        if rq.seed is not None:
+            check_seed(rq.seed)
+    except DownsampleError as e:
+        return str(e)
+    return None
+
+
+def genome_thinning_of(rq):
+    """what mustache.genome_biases_or_error takes of an accepted request: (T, seed), ("match", seed) or None"""
+    from .downsample import threshold_of
+    if rq.match_depth_genome:
+        return "match", int(rq.seed or 0)
+    if rq.downsample_genome is not None:
+        return threshold_of(rq.downsample_genome, "--downsample-genome"), int(rq.seed or 0)
     return None
 
 
@@ -290,7 +336,8 @@ def plan(rq, res):
         return "Error: Couldn't find the specified contact files"
     if not res:
         return "Error: Invalid resolution"
-    why = pairs_input(rq) or thinning(rq) or multires(rq, res) or (rq.pairs_trans and keep_trans_rows(files, rq.pairs_zero_based))
+    why = pairs_input(rq) or thinning_genome(rq) or thinning(rq) or multires(rq, res) \
+        or (rq.pairs_trans and keep_trans_rows(files, rq.pairs_zero_based))
     if why:
         return "Error: %s" % why
     balance = None

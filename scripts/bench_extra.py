@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Side legs of bench.py (`python bench.py --extra`, one GPU): everything that is not the driver's line -- FMA mode, the COO
 scatter of row 2, normalisation against HBM, a whole hg19-shaped genome at 5 kb (one and two samples), the wide-radius and
-large-window instantiations, the thinned band of the file leg through the headline step, and the -p 4 / per-node CPU legs.
-bench.py constructs `Extra` and calls its three hooks; every leg adds one key to the same JSON line."""
+large-window instantiations, the thinned band of the file leg through the headline step, the thinning of a whole genome's trans
+records in one launch (thin_pairs_leg), and the -p 4 / per-node CPU legs.
+bench.py constructs `Extra` and calls its three hooks; every leg of `Extra` adds one key to the same JSON line, whose keys
+tests/test_gpu_bench.py pins.  thin_pairs_leg stands beside them: `python scripts/bench_extra.py thin-pairs` runs it and prints
+its own JSON line."""
 import os
 import time
 
@@ -44,6 +47,87 @@ def genome_workload(B, name, res, dpx, depth, seed, device, sizes=HG19, two_samp
             self.kernel_ms = []
 
     return GenomeWorkload()
+
+
+def thin_pairs_leg(device, res=100000, density=0.05, reps=9):
+    """mst_thin_pairs (mustache_amd/downsample.py, `--downsample-genome`) on the trans records of an hg19-shaped genome at
+    100 kb: 24 chromosomes, 276 pairs, every cell of every trans matrix a record with probability `density` (in cell order, as a
+    reader delivers them), counts 1 + Poisson(0.4) as float64.  Timed beside what the code had before the entry point existed:
+    the same records pair by pair through mst_thin_counts, one launch and one host wait per pair (downsample._launch).  Both
+    are host clocks around calls that end in the read-back of their totals, alternating, 3 warm-ups, the median of `reps`; the
+    kernel alone by device events.  The two ways draw from different streams (pair tags and key words), so only the totals in are
+    compared."""
+    import numpy as np
+    import torch
+    from mustache_amd import _lib
+    from mustache_amd.downsample import _launch, launch_pairs, pair_tag
+    names = [str(c + 1) for c in range(22)] + ["X", "Y"]
+    bins = [s // res + 1 for s in HG19]
+    gen = torch.Generator(device=device).manual_seed(1000)
+    keys, xs, ys, lens = [], [], [], []
+    for i in range(len(bins)):
+        for j in range(i + 1, len(bins)):
+            cell = torch.nonzero(torch.rand(bins[i] * bins[j], device=device, generator=gen) < density).flatten()
+            keys.append((names[i], names[j]))
+            xs.append((cell // bins[j]).to(torch.int32))
+            ys.append((cell % bins[j]).to(torch.int32))
+            lens.append(int(cell.numel()))
+    x, y = torch.cat(xs), torch.cat(ys)
+    del xs, ys
+    N = int(x.numel())
+    counts = 1.0 + torch.poisson(torch.full((N,), 0.4, device=device, dtype=torch.float64), generator=gen)
+    seg = np.zeros(len(keys) + 1, np.int64)
+    np.cumsum(lens, out=seg[1:])
+    seg_d = torch.from_numpy(seg).to(device)
+    table = [pair_tag(a, b) for a, b in keys]
+    parts = [(x[s:e], (y[s:e] - x[s:e]), counts[s:e]) for s, e in zip(seg[:-1].tolist(), seg[1:].tolist())]
+    T, seed = 1 << 31, 7
+
+    def one_launch():
+        return launch_pairs(x, y, counts, seg_d, table, seed, 2, T)
+
+    def per_pair():
+        return [_launch(px, pd, pc, a, T, seed, 0, device, True)[1:] for (px, pd, pc), (a, _) in zip(parts, keys)]
+
+    times = {"one": [], "pairs": []}
+    for it in range(3 + reps):
+        for key, fn in (("one", one_launch), ("pairs", per_pair)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = fn()
+            torch.cuda.synchronize()
+            if it >= 3:
+                times[key].append(time.perf_counter() - t0)
+            if key == "one":
+                totals = got[1]
+            else:
+                assert [t[0] for t in got] == [t[0] for t in totals]
+    # the kernel alone: the entry point between two events, everything it needs already on the device
+    lib = _lib.require_gpu()
+    table_d = torch.from_numpy(np.asarray(table, np.uint32).view(np.int32)).to(device)
+    k = torch.empty(N, dtype=torch.int64, device=device)
+    kernel_ms = []
+    for it in range(3 + reps):
+        words = torch.zeros(2 * len(keys) + 1, dtype=torch.int64, device=device)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _lib.check(lib.mst_thin_pairs(_lib.ptr(x), _lib.ptr(y), _lib.ptr(counts), 2, N, _lib.ptr(seg_d), _lib.ptr(table_d), len(keys),
+                                      seed, 2, T, _lib.ptr(k), _lib.ptr(words), 0, _lib.stream()))
+        e1.record()
+        torch.cuda.synchronize()
+        if it >= 3:
+            kernel_ms.append(e0.elapsed_time(e1))
+    one, pairs, kern = (sorted(t)[len(t) // 2] for t in (times["one"], times["pairs"], kernel_ms))
+    return {"records": N, "pairs": len(keys), "reads": sum(t[0] for t in totals), "reads_kept": sum(t[1] for t in totals),
+            "largest_pair_records": max(lens), "smallest_pair_records": min(lens),
+            "one_launch_ms": round(one * 1e3, 3), "per_pair_ms": round(pairs * 1e3, 3), "speedup": round(pairs / one, 2),
+            "one_launch_ms_spread": [round(min(times["one"]) * 1e3, 3), round(max(times["one"]) * 1e3, 3)],
+            "per_pair_ms_spread": [round(min(times["pairs"]) * 1e3, 3), round(max(times["pairs"]) * 1e3, 3)],
+            "kernel_ms": round(kern, 4), "kernel_GB/s": round(24.0 * N / (kern * 1e-3) / 1e9, 1),
+            "note": "hg19 layout at 100 kb, density %g of the trans cells, counts 1 + Poisson(0.4) float64, T = 2^31; one_launch = "
+                    "downsample.launch_pairs (table upload, zeroed totals, mst_thin_pairs, read-back of 2 P + 1 words); per_pair = "
+                    "mst_thin_counts per pair with its own read-back; host clock, alternating, median of %d; kernel = HIP events "
+                    "around the entry point; GB/s on 24 B per record (x, y, count read, k written)" % (density, reps)}
 
 
 def _pool(B, w, block_indices, procs):
@@ -285,3 +369,13 @@ class Extra:
                                                   "8401-16384 bins = resolutions below ~238 bp; no scratch)"}
         del raww
         out["variants"] = var
+
+
+if __name__ == "__main__":
+    import json
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    if sys.argv[1:] != ["thin-pairs"]:
+        sys.exit("usage: python scripts/bench_extra.py thin-pairs   (the other legs run through `python bench.py --extra`)")
+    import torch
+    print(json.dumps({"thin_pairs_genome_100kb": thin_pairs_leg(torch.device("cuda", 0))}))
