@@ -750,6 +750,36 @@ MST_STABLE int mst_coarsen_compact(const uint64_t *dense, int32_t dense_diags, i
                                    int64_t *out_count, int64_t cap, int64_t *n_out, void *workspace, uint64_t workspace_bytes,
                                    void *stream);
 
+/* ---- the trans records of MANY chromosome pairs -> the pixels of a coarser resolution in one launch (`--coarser-genome`; the
+ * rule: mustache_amd/multires.py; tests/coarsen_genome_reference.py restates it).  Added without a change of
+ * MST_ABI_REVISION, as mst_thin_pairs was. */
+/* Records (x, y: dev int32 [n_records]; count_in by count_kind, MST_THIN_COUNT_*) of n_pairs pairs, pair p in [seg_off[p],
+ * seg_off[p + 1]) (seg_off: dev int64 [n_pairs + 1], non-decreasing, seg_off[0] = 0, seg_off[n_pairs] = n_records; empty pairs
+ * are legal; whatever it holds, no table is read out of bounds).  n_a, n_b, cell_off (dev int64 [n_pairs]): the bin counts of
+ * pair p's two chromosomes at the COARSE resolution and the first key of its cells, cell_off[p + 1] = cell_off[p] + n_a[p] *
+ * n_b[p] (pairs.trans_tables).  With factor k >= 1 a record goes to X = x / k, Y = y / k.  A record with x < 0, y < 0,
+ * X >= n_a[p] or Y >= n_b[p] is dropped and counted in words[3] before a key is formed, so that it aliases no other cell.
+ * Any other record's key is cell_off[p] + X * n_b[p] + Y: a key below dense_cells adds its count to dense[key] (dev uint64
+ * [dense_cells], ACCUMULATED: the caller zeroes it; 64-bit integer atomics), any other appends (far_key, far_count) to the far
+ * list (dev int64 [far_cap] each), one entry per run of adjacent records of a wave that share the key, in no fixed order --
+ * every far key is >= dense_cells.  dense_cells is at most the cells of all pairs; 0 is legal (dense may be NULL).  A count that
+ * is no integer value in [0, 2^32 - 1] counts as 0 and sets words[2] = 1.  words (dev int64 [4], ACCUMULATED: the caller zeroes
+ * them): [0] the far entries -- more than far_cap means entries were lost (nothing is written past far_cap; far_cap =
+ * n_records always suffices) --, [1] the sum of the counts of the records that were not dropped, [2] the bad-count flag, [3]
+ * the records dropped as outside.  Runs whose counts sum to 0 write nothing.  max_blocks: the most workgroups (of 256 records
+ * a trip) to launch, 0 for the default; the results do not depend on it, nor on the order of the records within a pair.
+ * n_records = 0 launches nothing. */
+MST_STABLE int mst_coarsen_pairs(const int32_t *x, const int32_t *y, const void *count_in, int32_t count_kind, int64_t n_records,
+                                 const int64_t *seg_off, const int64_t *n_a, const int64_t *n_b, const int64_t *cell_off,
+                                 int32_t n_pairs, int32_t factor, int64_t dense_cells, uint64_t *dense, int64_t *far_key,
+                                 int64_t *far_count, int64_t far_cap, int64_t *words, int32_t max_blocks, void *stream);
+/* The non-zero counters of dense [dense_cells] (uint64) -> (out_key: dev int64 [cap] = the counter's index, out_count: dev
+ * int64 [cap]) in ascending key order; *n_out (dev int64) = their number, which may exceed cap: nothing is written past cap.
+ * Two passes and a scan, no atomics.  workspace: dev, mst_coarsen_pairs_compact_workspace_bytes(dense_cells) bytes. */
+MST_STABLE uint64_t mst_coarsen_pairs_compact_workspace_bytes(int64_t dense_cells);
+MST_STABLE int mst_coarsen_pairs_compact(const uint64_t *dense, int64_t dense_cells, int64_t *out_key, int64_t *out_count, int64_t cap,
+                                         int64_t *n_out, void *workspace, uint64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,9 @@ _SIGNATURES = {
     "mst_coarsen_records": (ctypes.c_int, [_p, _p, _p, _i32, _i64, _i32, _i64, _i32, _p, _p, _p, _i64, _p, _p]),
     "mst_coarsen_compact_workspace_bytes": (_u64, [_i32, _i64]),
     "mst_coarsen_compact": (ctypes.c_int, [_p, _i32, _i64, _p, _p, _p, _i64, _p, _p, _u64, _p]),
+    "mst_coarsen_pairs": (ctypes.c_int, [_p, _p, _p, _i32, _i64, _p, _p, _p, _p, _i32, _i32, _i64, _p, _p, _p, _i64, _p, _i32, _p]),
+    "mst_coarsen_pairs_compact_workspace_bytes": (_u64, [_i64]),
+    "mst_coarsen_pairs_compact": (ctypes.c_int, [_p, _i64, _p, _p, _i64, _p, _p, _u64, _p]),
 }
 
 _lib = None

@@ -48,6 +48,11 @@ mst_thin_counts, one launch per chromosome; the resident trans records through m
 launch up to APPLY_BATCH_RECORDS records, as balanced_batches forms its batches.  The memory check counts what a launch adds
 (THIN_CIS_BYTES, THIN_TRANS_BYTES per record), and under `--match-depth-genome` that both samples' raw sets are resident before
 either is solved (check_solve_memory).
+
+coarsen_genome (`--coarser-genome`; the rule is mustache_amd/multires.py's) derives a NEW GenomeRead at R = k r from one at r,
+after the thinning and before any solve: each cis part through mst_coarsen_records, the resident trans records through
+mst_coarsen_pairs in the same batches of pairs, each batch with a key space of its own.  Its memory check counts what a launch
+adds (COARSEN_CIS_BYTES, COARSEN_TRANS_BYTES per record and 8 bytes per dense counter).
 """
 import numpy as np
 
@@ -329,9 +334,10 @@ class GenomeRead:
     lengths, bins, offsets, n: the layout; pixels: `all` or `inter`; cis: [(c, x, dist, v)] int64 / int64 / float64 device
     tensors of chromosome c's pixels that enter the assembly (inside the chromosome, dist >= IGNORE_DIAGS; `all` only), kept
     apart; records: {(i, j), i < j: (x of i, y of j, v)} int32 / int32 / float64 resident device tensors of every pair that
-    has any, in reading order; source: the file's name."""
+    has any, in reading order; source: the file's name; res: the resolution in bp (None: not stated)."""
 
-    def __init__(self, names, lengths, bins, offsets, n, pixels, device, source):
+    def __init__(self, names, lengths, bins, offsets, n, pixels, device, source, res=None):
+        self.res = None if res is None else int(res)
         self.names, self.lengths, self.bins, self.offsets, self.n = list(names), list(lengths), list(bins), list(offsets), int(n)
         self.pixels, self.device, self.source = pixels, device, source
         self.cis, self.records = [], {}
@@ -365,7 +371,7 @@ def read_genome(f, res, pixels="all", device=None, pairs_zero_based=False, verbo
         else:
             names, lengths, cis, trans = _hic_source(f, res, dev, pixels, verbose)
         bins, offsets, n = genome_layout(lengths, res)
-        read = GenomeRead(names, lengths, bins, offsets, n, pixels, dev, f)
+        read = GenomeRead(names, lengths, bins, offsets, n, pixels, dev, f, res)
         total, resident = 0, 0
         if pixels == "all":
             for c, x, d, v in cis():
@@ -491,6 +497,64 @@ def thin_genome(read, T, seed=0, sample=0, max_records=APPLY_BATCH_RECORDS):
                 trans_in, trans_kept = trans_in + totals[p][0], trans_kept + totals[p][1]
             del x, y, k, keep
     return (cis_kept, cis_in), (trans_kept, trans_in)
+
+
+COARSEN_CIS_BYTES = 8 + 16 + 16 + 24   # coarsening a cis part, per pixel: the int32 x and dist, a far entry, a compacted record, its int64 / float64 copy
+COARSEN_TRANS_BYTES = 16 + 16 + 16 + 16   # coarsening a batch of pairs, per record: the concatenated copy, a far entry, key and sum, the decoded record
+COARSEN_CELL_BYTES = 8            # a dense counter
+
+
+def _check_coarsen_memory(records, per_record, cells, resident):
+    import torch
+    free = int(torch.cuda.mem_get_info()[0])
+    need = int(records) * per_record + COARSEN_CELL_BYTES * int(cells)
+    if need > free:
+        raise BalanceError("--balance-genome: coarsening %d pixels needs about %d bytes of device memory beside the %d resident "
+                           "ones, %d bytes are free" % (records, need, resident, free))
+
+
+def coarsen_genome(read, factor, max_records=APPLY_BATCH_RECORDS):
+    """The genome's map of a GenomeRead at r -> a NEW GenomeRead at R = factor * r (mustache_amd/multires.py states the rule):
+    the names, lengths and pixels of `read`, genome_layout(lengths, R).  Each cis part goes through multires.coarsen_records
+    and keeps D >= IGNORE_DIAGS, X + D < n'_c; the resident trans records go through multires.coarsen_pairs, consecutive pairs
+    sharing a launch until their records reach max_records (_pair_batches).  `read` is left untouched.  MultiresError for a
+    count that is no integer; BalanceError when the device's free memory cannot hold what a launch adds."""
+    import torch
+    from .multires import coarsen_pairs, coarsen_records
+    from .pairs import dense_budget, pair_list, trans_tables
+    k = int(factor)
+    if k < 1:
+        raise ValueError("coarsen_genome: the factor is an integer >= 1")
+    if not read.res:
+        raise ValueError("coarsen_genome: the GenomeRead does not know its resolution (read_genome sets it)")
+    R = int(read.res) * k
+    bins, offsets, n = genome_layout(read.lengths, R)
+    out = GenomeRead(read.names, read.lengths, bins, offsets, n, read.pixels, read.device, read.source, R)
+    tables = trans_tables(read.lengths, bins)[0]
+    index = {pair: p for p, pair in enumerate(pair_list(len(bins)))}
+    with torch.cuda.device(read.device):
+        resident = RESIDENT_BYTES * read.resident()
+        for c, x, d, v in read.cis:
+            _check_coarsen_memory(int(v.numel()), COARSEN_CIS_BYTES, 0, resident)
+            X, D, V = coarsen_records(x.to(torch.int32), d.to(torch.int32), v, k, device=read.device, chromosome=read.names[c])
+            keep = (D >= IGNORE_DIAGS) & (X + D < bins[c])
+            if bool(keep.any()):
+                out.cis.append((c, X[keep].to(torch.int64), D[keep].to(torch.int64), V[keep].to(torch.float64)))
+            del X, D, V, keep
+        budget = dense_budget(read.device)
+        for keys in _pair_batches(read, max_records):
+            # the batch's pairs get a key space of their own: the counters cover their cells only
+            sub = np.ascontiguousarray(tables[:, [index[key] for key in keys]])
+            cells = sub[2] * sub[3]
+            sub[4] = np.cumsum(cells) - cells
+            dense = int(cells.sum()) if COARSEN_CELL_BYTES * int(cells.sum()) <= budget else 0
+            _check_coarsen_memory(sum(int(read.records[key][2].numel()) for key in keys), COARSEN_TRANS_BYTES, dense, resident)
+            x, y, v, seg = _batch_tensors(read, keys)
+            got = coarsen_pairs(x, y, v, seg, sub, k, dense_cells=dense, device=read.device)
+            del x, y, v
+            for p in sorted(got):
+                out.records[keys[p]] = got[p]
+    return out
 
 
 def solve_genome(read, method="NEWTON", keep_records=True, **solver_args):

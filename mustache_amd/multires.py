@@ -16,6 +16,29 @@ set is the one a run at R sees, which is why each resolution can be balanced and
 A count that is not an integer value in [0, 2^32 - 1] (float `.hic` files exist) ends the run with an `Error:` line naming the
 chromosome: one flag word written by the kernel, the thinning's rule.
 
+Coarsening the genome's map (`--trans-all --balance-genome NEWTON -r 50kb --coarser-genome 250kb 500kb`)
+
+A trans record (x, y, c) of the chromosome pair (A, B) at resolution r -- x a bin of A, y a bin of B, c an integer in
+[0, 2^32 - 1] held as float64 in balance_genome.GenomeRead.records -- goes, with k = R / r, to X = x // k, Y = y // k.  The
+count of a coarse pixel is the integer sum of c over its records, exact in 64-bit integers and independent of their order; a
+fine pixel listed twice adds twice; a coarse pixel whose sum is 0 is no pixel.  The layout at R is
+balance_genome.genome_layout(lengths, R): n'_c = length_c // R + 1.  A record with a negative bin, or with X >= n'_A or
+Y >= n'_B, is dropped and counted -- before its key is formed, so that it aliases no other cell.  For a file whose positions lie
+inside the chromosome lengths nothing is dropped (the pairs reader drops rows beyond the length, read_genome filters cis
+pixels the same way), and coarsening the r pixels then equals binning the reads at R by the floor identity above; the equality
+with a run at R is stated for that case only.  A count that is no integer in [0, 2^32 - 1] counts as 0, sets one flag word and
+ends the run with an `Error:` line.  csrc/mst_coarsen_pairs.hip takes the records of many pairs in one launch (coarsen_pairs);
+tests/coarsen_genome_reference.py restates the rule.
+
+The cis parts of the genome's map (`--balance-pixels all`): each (c, x, dist, v) part goes through coarsen_records, unchanged;
+afterwards D >= balance_genome.IGNORE_DIAGS and X + D < n'_c are kept.  That the fine pixels with dist < 2 were dropped by
+read_genome is harmless: D >= 2 implies dist >= k + 1.  Under `inter` there are no cis parts.
+
+The merge below runs per chromosome pair on that pair's lists (x in bins of A, y in bins of B): loops of different pairs
+never meet.  The rows of a pair are written as those of a chromosome are, and one line is printed per pair and coarser
+resolution:
+    multires chr1,chr2: 500000 bp: 3 of 6 loops kept (merge distance 2 bins)
+
 Merge
 
 Take the resolutions r_0 < r_1 < ... and their loop lists L_i, rows [x, y, fdr, sigma] in bins.  The accepted set A starts as
@@ -46,21 +69,21 @@ class MultiresError(ValueError):
     """A multi-resolution request or run that cannot be done (the text of the command line's `Error:` line)."""
 
 
-def parse_resolutions(res, coarser):
-    """-r (bp) and the --coarser strings -> the coarser resolutions in bp, ascending; MultiresError for a value that does not
-    parse, is not greater than -r, is no integer multiple of -r or is given twice"""
+def parse_resolutions(res, coarser, flag="--coarser"):
+    """-r (bp) and the --coarser (or, by `flag`, --coarser-genome) strings -> the coarser resolutions in bp, ascending;
+    MultiresError for a value that does not parse, is not greater than -r, is no integer multiple of -r or is given twice"""
     from .mustache import parseBP
     out = []
     for text in coarser:
         R = parseBP(str(text))
         if not R or R < 1:
-            raise MultiresError("--coarser %s: not a resolution (give base pairs, or a number with kb or mb)" % text)
+            raise MultiresError("%s %s: not a resolution (give base pairs, or a number with kb or mb)" % (flag, text))
         if R <= res:
-            raise MultiresError("--coarser %s: a coarser resolution is greater than -r (%d bp)" % (text, res))
+            raise MultiresError("%s %s: a coarser resolution is greater than -r (%d bp)" % (flag, text, res))
         if R % res:
-            raise MultiresError("--coarser %s: %d bp is not an integer multiple of -r (%d bp)" % (text, R, res))
+            raise MultiresError("%s %s: %d bp is not an integer multiple of -r (%d bp)" % (flag, text, R, res))
         if R in out:
-            raise MultiresError("--coarser %s: %d bp is given twice" % (text, R))
+            raise MultiresError("%s %s: %d bp is given twice" % (flag, text, R))
         out.append(R)
     return sorted(out)
 
@@ -201,3 +224,88 @@ def coarsen_records(xd, dd, counts, factor, distance_bins=None, device=None, chr
         if stats is not None:
             stats.update(n=n, dense_diags=K, far_entries=far_entries, total=total)
         return x, d, c
+
+
+def coarsen_pairs(x, y, counts, seg_off, tables, factor, dense_bytes=None, dense_cells=None, far_capacity=None, device=None,
+                  stats=None, max_blocks=0, library=None):
+    """The genome's coarsening rule on the concatenated device records of P pairs (x, y int32; counts int64, float32 or
+    float64; pair p in [seg_off[p], seg_off[p + 1]), seg_off a host int64 array of P + 1) -> {p: (x int32, y int32, v float64)}
+    device tensors in key order for every pair that has a record.  tables: pairs.trans_tables(lengths, bins at the COARSE
+    resolution)[0] (rows 2, 3, 4 -- nA, nB, cell_off -- are used); factor: k >= 1.  dense_cells: None = every cell when 8 bytes
+    per cell fit dense_bytes (None: pairs.dense_budget()), else 0; a value is clamped to the cell total.  far_capacity: room of
+    the far list (None: one entry per record, which always suffices; too small raises _lib.MstOverflow).  max_blocks: the most
+    workgroups (0: the kernel's default).  library: another build of the same ABI (the timing script's plain build).
+    MultiresError for a count that is no integer in [0, 2^32 - 1].  stats (a dict) receives "dense_cells", "far_entries",
+    "total" (the contacts written), "outside" (the records dropped) and "pixels"."""
+    import torch
+    from . import _lib
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    from .pairs import decode_trans_keys, dense_budget, sum_far_list
+    lib = require_gpu() if library is None else library
+    dev = counts.device if device is None else torch.device(device)
+    k = int(factor)
+    if k < 1 or k > 0x7FFFFFFF:
+        raise ValueError("coarsen_pairs: the factor is an integer >= 1")
+    kind = _COUNT_KIND.get(str(counts.dtype))
+    if kind is None:
+        raise TypeError("coarsen_pairs: counts of dtype %s (int64, float32 or float64 are taken)" % counts.dtype)
+    tables = np.ascontiguousarray(tables, dtype=np.int64)
+    seg_off = np.ascontiguousarray(seg_off, dtype=np.int64)
+    P, rows = int(tables.shape[1]), int(counts.numel())
+    if tables.ndim != 2 or tables.shape[0] != 5 or seg_off.shape != (P + 1,):
+        raise ValueError("coarsen_pairs: tables of [5][P] and seg_off of P + 1 entries")
+    if int(x.numel()) != rows or int(y.numel()) != rows or x.dtype != torch.int32 or y.dtype != torch.int32:
+        raise ValueError("coarsen_pairs: x and y are int32 tensors as long as the counts")
+    if P and (int(seg_off[0]) != 0 or int(seg_off[-1]) != rows or np.any(np.diff(seg_off) < 0)):
+        raise ValueError("coarsen_pairs: seg_off ascending from 0 to the number of records")
+    cells = int((tables[2] * tables[3]).sum())
+    if P and (np.any(tables[2:4] < 0) or np.any(tables[4] != np.cumsum(tables[2] * tables[3]) - tables[2] * tables[3])):
+        raise ValueError("coarsen_pairs: cell_off is the running sum of nA * nB")
+    if stats is not None:
+        stats.update(dense_cells=0, far_entries=0, total=0, outside=0, pixels=0)
+    if rows == 0 or P == 0:
+        return {}
+    with torch.cuda.device(dev):
+        if dense_cells is None:
+            budget = dense_budget(dev) if dense_bytes is None else int(dense_bytes)
+            dense_cells = cells if 8 * cells <= budget else 0
+        dense_cells = max(0, min(int(dense_cells), cells))
+        x, y, counts = x.to(dev).contiguous(), y.to(dev).contiguous(), counts.to(dev).contiguous()
+        i64 = lambda m: torch.empty(m, dtype=torch.int64, device=dev)
+        table_d = torch.from_numpy(np.concatenate([tables[2], tables[3], tables[4], seg_off])).to(dev)
+        cap = rows if far_capacity is None else int(far_capacity)
+        dense = torch.zeros(dense_cells, dtype=torch.int64, device=dev)              # uint64 counters
+        far_key, far_count = i64(cap), i64(cap)
+        words = torch.zeros(4, dtype=torch.int64, device=dev)
+        _lib.check(lib.mst_coarsen_pairs(_ptr(x), _ptr(y), _ptr(counts), kind, rows, _ptr(table_d[3 * P:]), _ptr(table_d[:P]),
+                                         _ptr(table_d[P:2 * P]), _ptr(table_d[2 * P:3 * P]), P, k, dense_cells,
+                                         _ptr(dense) if dense_cells else None, _ptr(far_key) if cap else None,
+                                         _ptr(far_count) if cap else None, cap, _ptr(words), int(max_blocks), _stream()))
+        far_entries, total, bad, outside = (int(v) for v in words.cpu().tolist())
+        if bad:
+            raise MultiresError("the genome holds an inter-chromosomal count that is not an integer between 0 and 4294967295: "
+                                "coarsening needs raw integer counts")
+        if far_entries > cap:
+            raise _lib.MstOverflow(_lib.MST_E_OVERFLOW, "coarsen_pairs: the far list holds %d entries, %d were needed" % (cap, far_entries))
+        parts = []
+        if dense_cells:
+            room = min(rows, dense_cells)
+            found = torch.zeros(1, dtype=torch.int64, device=dev)
+            keys, sums = i64(room), i64(room)
+            ws = torch.empty(int(lib.mst_coarsen_pairs_compact_workspace_bytes(dense_cells)), dtype=torch.uint8, device=dev)
+            _lib.check(lib.mst_coarsen_pairs_compact(_ptr(dense), dense_cells, _ptr(keys), _ptr(sums), room, _ptr(found), _ptr(ws),
+                                                     ws.numel(), _stream()))
+            m = int(found.item())
+            if m > room:
+                raise RuntimeError("coarsen_pairs: %d non-zero counters from %d records" % (m, rows))
+            parts.append((keys[:m], sums[:m]))
+        del dense
+        if far_entries:                              # every far key is >= dense_cells: behind the dense part, ascending
+            parts.append(sum_far_list(far_key[:far_entries], far_count[:far_entries]))
+        keys, sums = (torch.cat(kc) for kc in zip(*parts)) if len(parts) > 1 else parts[0] if parts else (i64(0), i64(0))
+        written = int(sums.sum().item()) if sums.numel() else 0
+        if written != total:
+            raise RuntimeError("coarsen_pairs: %d contacts were read and %d written" % (total, written))
+        if stats is not None:
+            stats.update(dense_cells=dense_cells, far_entries=far_entries, total=total, outside=outside, pixels=int(keys.numel()))
+        return decode_trans_keys(keys, sums, tables)

@@ -555,6 +555,10 @@ def parse_args(args):
     p.add_argument("--merge-distance", dest="merge_distance", type=int, default=None, metavar="M",
                    help="OPTIONAL: with --coarser, a coarser loop is dropped when a kept loop lies within M bins of the coarser "
                         "resolution in both coordinates (default 2)")
+    p.add_argument("--coarser-genome", dest="coarser_genome", nargs='+', default=None, metavar="R",
+                   help="OPTIONAL: with --balance-genome (--trans-all, or -ch A -ch2 B): further resolutions, integer multiples "
+                        "of -r, at which the genome's map -- coarsened on the GPU from the one read at -r -- is balanced and "
+                        "called as well; each pair's loop lists are merged (--merge-distance)")
     from .balance_genome import add_arguments
     add_arguments(p)
     return p.parse_args(args)
@@ -916,6 +920,61 @@ def call_multires(f, args, res, coarser, pairs, balance, device):
                 write_loops(args.outdir, chromosome, chromosome, R, kept[j], first=(i == 0 and j == 0))
 
 
+def call_trans_multires(f, args, res, coarser, run, device):
+    """The --coarser-genome run (mustache_amd/multires.py), for --trans-all and for -ch A -ch2 B: the genome is read once at
+    -r and thinned once under --downsample-genome; EVERY coarse GenomeRead is derived from the fine one before anything is
+    solved, so that a count that is no integer or a memory refusal ends the run before anything is called or written; then for
+    -r and each coarser resolution in ascending order the genome is balanced (one balance.report line) and the run's pairs
+    are called from the balanced records in shared launches; at the end each pair's lists are merged and written in pair
+    order."""
+    from .balance import BalanceError, report as balance_report
+    from .balance_genome import balanced_batches, coarsen_genome, read_genome, solve_genome, thin_genome
+    from .downsample import report_genome
+    from .multires import MERGE_DISTANCE, merge_loops, report
+    from .trans_genome import TransGenomeCaller
+    resolutions = [res] + list(coarser)
+    M = MERGE_DISTANCE if args.merge_distance is None else args.merge_distance
+    pairs = list(run.trans)
+    thinning = getattr(args, "genome_thinning", None)
+    try:
+        fine = read_genome(f, res, run.genome[1], device, args.pairs_zero_based, args.verbose)
+        if thinning is not None:
+            cis, trans = thin_genome(fine, thinning[0], thinning[1], 0)
+            report_genome(0, cis, trans, thinning[0], thinning[1])
+        reads = [fine] + [coarsen_genome(fine, R // res) for R in coarser]
+        del fine
+        lists = [[[] for _ in resolutions] for _ in pairs]
+        for j, R in enumerate(resolutions):
+            gb = solve_genome(reads[j], run.genome[0])
+            reads[j] = None                      # the raw records of a resolution leave as its pairs are applied
+            balance_report(gb.info, gb.label)
+            state = {"t0": time.time()}
+
+            def emit(k, o):
+                lists[k][j] = o
+                print("{0} loops found for chrmosome pair={1},{2} at {3} bp, fdr<{4} in {5}sec".format(
+                    len(o), pairs[k][0], pairs[k][1], R, args.pt, "%.2f" % (time.time() - state["t0"])))
+                state["t0"] = time.time()
+
+            caller = TransGenomeCaller(octave_values(args), args.st, args.pt, emit, verbose=args.verbose)
+            for k, records in balanced_batches(gb, pairs):
+                caller.hold(k, [records], "%s,%s" % pairs[k])
+            caller.flush()
+            del gb, caller
+    except BalanceError as e:
+        print("Error: %s" % e)
+        return None
+    first = True
+    for k, (chromosome, chromosome2) in enumerate(pairs):
+        kept = merge_loops(lists[k], resolutions, M)
+        for j, R in enumerate(resolutions):
+            if j:
+                report("%s,%s" % (chromosome, chromosome2), R, len(kept[j]), len(lists[k][j]), M)
+            if kept[j] or first:
+                write_loops(args.outdir, chromosome, chromosome2, R, kept[j], first=first)
+                first = False
+
+
 def call_trans_pairs(f, args, res, run, distFilter, device):
     """The inter-chromosomal pairs of a mustache run (mustache_amd/trans.py), one by one in pair order after every
     intra-chromosomal pair; the header is written with the run's first pair's rows."""
@@ -954,7 +1013,7 @@ def call_trans_pairs(f, args, res, run, distFilter, device):
 def main(argv=None):
     start_time = time.time()
     args = parse_args(sys.argv[1:] if argv is None else argv)
-    from .request import coarser_resolutions, genome_thinning_of, plan, refuse, request_of
+    from .request import coarser_genome_resolutions, coarser_resolutions, genome_thinning_of, plan, refuse, request_of
     from .sharding import init_from_env
     rank, world = init_from_env()       # multi-GPU: blocks of each chromosome are sharded, rank 0 writes the TSV
     print("\n")
@@ -965,6 +1024,15 @@ def main(argv=None):
     if isinstance(run, str):
         return refuse(run)
     args.genome_thinning = genome_thinning_of(asked)
+    coarser_genome = coarser_genome_resolutions(asked, res)
+    if coarser_genome:                   # plan() has refused every run but a single-rank --balance-genome run of trans pairs
+        import torch
+        from .multires import MultiresError
+        try:
+            return call_trans_multires(f, args, res, coarser_genome, run, torch.device("cuda", torch.cuda.current_device()))
+        except MultiresError as e:
+            print("Error: %s" % e)
+            return None
     if run.trans_all:
         return call_trans_all(f, args, res, run)
     coarser = coarser_resolutions(asked, res)

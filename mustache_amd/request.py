@@ -8,7 +8,8 @@ exception types with the rule functions and sentences of this module.  balance.c
 balance_genome.check_genome_request (`--balance-genome`) are the two rules that live beside what they guard; the rule of
 `--downsample` / `--seed` / `--match-depth` (thinning) is here, with the helpers of mustache_amd/downsample.py for P and the seed,
 and so is the rule of `--downsample-genome` / `--match-depth-genome` (thinning_genome);
-so is the rule of `--coarser` / `--merge-distance` (multires), with mustache_amd/multires.py's parse of the resolutions.
+so is the rule of `--coarser` / `--merge-distance` (multires), with mustache_amd/multires.py's parse of the resolutions, and
+that of `--coarser-genome` (multires_genome), the same for the whole genome's map under --balance-genome.
 
 Host only: no torch and no native library at import; plan() reads no contact data except the one parse of a pairs file under
 --pairs-trans (keep_trans_rows) and the chromosome list of a run without -ch."""
@@ -36,15 +37,17 @@ _RequestTuple = namedtuple("Request", "files bias bias_flag norm_method balance 
 
 class Request(_RequestTuple):
     """The tuple above, and behind it -- by keyword only, with defaults -- what `mustache` asks of mustache_amd/multires.py:
-    coarser = the --coarser strings (None: not given), merge_distance = --merge-distance (None: not given); and what either
+    coarser = the --coarser strings (None: not given), merge_distance = --merge-distance (None: not given), coarser_genome =
+    the --coarser-genome strings (None: not given); and what either
     command line asks of the genome thinning: downsample_genome = --downsample-genome's fraction (None: not given),
     match_depth_genome = diff_mustache's --match-depth-genome.  They are attributes beside the tuple, not fields of it:
     tests/test_cli_downsample_requests.py pins the tuple's last three fields, and a positional caller keeps working either way."""
-    EXTRA = ("coarser", "merge_distance", "downsample_genome", "match_depth_genome")
+    EXTRA = ("coarser", "merge_distance", "downsample_genome", "match_depth_genome", "coarser_genome")
 
-    def __new__(cls, *fields, coarser=None, merge_distance=None, downsample_genome=None, match_depth_genome=False, **named):
+    def __new__(cls, *fields, coarser=None, merge_distance=None, downsample_genome=None, match_depth_genome=False,
+                coarser_genome=None, **named):
         self = super().__new__(cls, *fields, **named)
-        self.coarser, self.merge_distance = coarser, merge_distance
+        self.coarser, self.merge_distance, self.coarser_genome = coarser, merge_distance, coarser_genome
         self.downsample_genome, self.match_depth_genome = downsample_genome, bool(match_depth_genome)
         return self
 
@@ -64,7 +67,8 @@ def request_of(args, files, bias, bias_flag, ranks, text_pair_raises=False):
                    args.chromosome2, ranks, text_pair_raises, args.downsample, args.seed, getattr(args, "match_depth", False),
                    coarser=getattr(args, "coarser", None), merge_distance=getattr(args, "merge_distance", None),
                    downsample_genome=getattr(args, "downsample_genome", None),
-                   match_depth_genome=getattr(args, "match_depth_genome", False))
+                   match_depth_genome=getattr(args, "match_depth_genome", False),
+                   coarser_genome=getattr(args, "coarser_genome", None))
 
 
 class Raises(str):
@@ -236,7 +240,7 @@ def multires(rq, res):
     from .multires import NOT_RAW, MultiresError
     from .pairs import is_pairs
     if rq.coarser is None:
-        if rq.merge_distance is not None:
+        if rq.merge_distance is not None and rq.coarser_genome is None:
             return "--merge-distance without --coarser: it is the tolerance of the multi-resolution merge and nothing else"
         return None
     if rq.merge_distance is not None and int(rq.merge_distance) < 0:
@@ -257,6 +261,38 @@ def multires(rq, res):
     if rq.ranks > 1:
         return "--coarser in a multi-rank run (world size %d): every resolution of a chromosome is called on one GPU; start a " \
                "single process" % rq.ranks
+    return None
+
+
+def coarser_genome_resolutions(rq, res):
+    """the --coarser-genome resolutions of the request in bp, ascending ([] without the flag); multires.MultiresError for a
+    value the rule below refuses"""
+    if rq.coarser_genome is None:
+        return []
+    from .multires import parse_resolutions
+    return parse_resolutions(int(res), rq.coarser_genome, flag="--coarser-genome")
+
+
+def multires_genome(rq, res):
+    """What --coarser-genome (the genome's coarsening of mustache_amd/multires.py) rules out at -r = res bp, before multires():
+    the two flags exclude each other and share --merge-distance.  What --balance-genome itself refuses -- a run that is not
+    all inter-chromosomal pairs, text / `.cool` input, several ranks, pairs input without --pairs-trans -- keeps
+    check_genome_request's and pairs_input's sentences.  Reads nothing."""
+    from .multires import MultiresError
+    if rq.coarser_genome is None:
+        return None
+    if rq.coarser is not None:
+        return "--coarser-genome and --coarser: give one of them (--coarser coarsens each chromosome's own map, " \
+               "--coarser-genome the whole genome's)"
+    if rq.balance_genome is None:
+        return "--coarser-genome without --balance-genome: coarsening the genome's map sums raw integer counts; give " \
+               "--balance-genome ICE|NEWTON"
+    if rq.merge_distance is not None and int(rq.merge_distance) < 0:
+        return "--merge-distance %d: the distance is a number of bins >= 0" % rq.merge_distance
+    try:
+        coarser_genome_resolutions(rq, res)
+    except MultiresError as e:
+        return str(e)
     return None
 
 
@@ -336,7 +372,7 @@ def plan(rq, res):
         return "Error: Couldn't find the specified contact files"
     if not res:
         return "Error: Invalid resolution"
-    why = pairs_input(rq) or thinning_genome(rq) or thinning(rq) or multires(rq, res) \
+    why = pairs_input(rq) or thinning_genome(rq) or thinning(rq) or multires_genome(rq, res) or multires(rq, res) \
         or (rq.pairs_trans and keep_trans_rows(files, rq.pairs_zero_based))
     if why:
         return "Error: %s" % why
