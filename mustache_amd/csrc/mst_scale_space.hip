@@ -46,6 +46,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include "mst_common.h"
 
@@ -54,6 +56,63 @@
 namespace {
 
 __device__ __forceinline__ double dmax(double a, double b) { return __builtin_fmax(a, b); }
+
+// The sieve's two per-level comparisons of two pixels, d == m (-> en) and d > p (-> gn), shifted into bit words:
+// v_addc_co_u32 w, w, w computes 2 w + carry, so each compare result enters its word with ONE instruction and
+// never exists as a 0 / 1 << k select that an or then merges.  After K pixels pixel k sits at bit K - 1 - k.
+// The compiler neither schedules nor pads the inside of an asm statement: a lane mask written by a VALU compare needs two
+// wait states before a VALU instruction reads it (as carry-in here), and the order below leaves two instructions between
+// every compare and the add that consumes it -- three mask registers in rotation, no s_nop.  FIRST starts both words from 0.
+template <bool FIRST>
+__device__ __forceinline__ void sieve_bits2(uint32_t &en, uint32_t &gn, double d0, double m0, double p0, double d1, double m1,
+                                            double p1) {
+    unsigned long long y, z;      // lane-mask temporaries (SGPR pairs)
+    if constexpr (FIRST)
+        asm("v_cmp_eq_f64 vcc, %4, %5\n\t"
+            "v_cmp_gt_f64 %2, %4, %6\n\t"
+            "v_cmp_eq_f64 %3, %7, %8\n\t"
+            "v_addc_co_u32 %0, vcc, 0, 0, vcc\n\t"
+            "v_cmp_gt_f64 vcc, %7, %9\n\t"
+            "v_addc_co_u32 %1, %2, 0, 0, %2\n\t"
+            "v_addc_co_u32 %0, %3, %0, %0, %3\n\t"
+            "v_addc_co_u32 %1, vcc, %1, %1, vcc"
+            : "=&v"(en), "=&v"(gn), "=&s"(y), "=&s"(z)
+            : "v"(d0), "v"(m0), "v"(p0), "v"(d1), "v"(m1), "v"(p1)
+            : "vcc");
+    else
+        asm("v_cmp_eq_f64 vcc, %4, %5\n\t"
+            "v_cmp_gt_f64 %2, %4, %6\n\t"
+            "v_cmp_eq_f64 %3, %7, %8\n\t"
+            "v_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_gt_f64 vcc, %7, %9\n\t"
+            "v_addc_co_u32 %1, %2, %1, %1, %2\n\t"
+            "v_addc_co_u32 %0, %3, %0, %0, %3\n\t"
+            "v_addc_co_u32 %1, vcc, %1, %1, vcc"
+            : "+v"(en), "+v"(gn), "=&s"(y), "=&s"(z)
+            : "v"(d0), "v"(m0), "v"(p0), "v"(d1), "v"(m1), "v"(p1)
+            : "vcc");
+}
+
+// d > t on the lanes whose top bit of `bits` is set; `bits` moves up by one, so the next call tests the next bit.
+// v_add_co_u32 bits, bits, bits shifts the word and delivers the bit shifted out as the carry's lane mask: the gate of a
+// pixel costs ONE vector instruction and a scalar and, where a bit test costs two and an or.  The mask the statement
+// returns was last written by the scalar unit, so the selects that read it need no wait states.
+__device__ __forceinline__ bool gated_greater(uint32_t &bits, double d, double t) {
+    unsigned long long mask;
+    asm("v_add_co_u32 %0, vcc, %0, %0\n\t"
+        "v_cmp_gt_f64 %1, %2, %3\n\t"
+        "s_and_b64 %1, %1, vcc"
+        : "+v"(bits), "=&s"(mask)
+        : "v"(d), "v"(t)
+        : "vcc", "scc");      // s_and_b64 writes SCC: no scalar compare may be kept live across the statement
+    return __builtin_amdgcn_inverse_ballot_w64(mask);
+}
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant expression
+template <int... I, class F>
+__device__ __forceinline__ void for_each_index(std::integer_sequence<int, I...>, F &&f) {
+    (f(std::integral_constant<int, I>()), ...);
+}
 
 // value held by the previous / next lane: DPP wave shifts, no LDS traffic.  bound_ctrl is set, so the lane without a
 // source (0 for prev, 63 for next) reads 0.0 and no `old` operand has to be copied in first; those lanes hold ring
@@ -370,7 +429,8 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
     uint32_t ep = 0, ec = 0, gp = 0;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        gprev[k] = Dc[k] = Mc[k] = best[k] = 0.0;
+        gprev[k] = Dc[k] = Mc[k] = 0.0;
+        best[k] = ((nz_mask >> k) & 1u) ? 0.0 : INFINITY;   // never tested: no D_c exceeds it, lvl stays 0 and best is never written out
         lvl[k] = 0;
     }
     const int wave = tid >> 6, lane = tid & 63;
@@ -457,8 +517,10 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
             // pixels), the row shifts stay inside the wave and the neighbouring column groups read this wave's edge samples
             // from the strip written above -- so a wave that owns no tested pixel has no observable use for its maxima and
             // skips them together with the sieve (its Gaussian levels, DoG values and edge samples are produced as before).
-            uint32_t en = 0, gn = 0;   // en: D_new == M_new;  gn: D_new > M_prev (M of the level before it)
+            uint32_t en = 0, gn = 0;   // en: D_new == M_new;  gn: D_new > M_prev (M of the level before it); pixel k at bit K - 1 - k
             double m[K];
+            // the level statistics of a tested level (kl >= 4); a wave without a tested pixel keeps the identities {inf, 0}
+            double lmin = INFINITY, lsum = 0.0;
             if (wave_has_nz) {
                 const double dl = de_left[0], dr = de_right[0];
                 double hm[K];
@@ -472,42 +534,56 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
                 for (int k = 0; k < K; ++k) m[k] = dmax(dmax(lane_prev(hm[k]), hm[k]), lane_next(hm[k]));
                 // the comparisons belong to the sieve, which the reference evaluates on the tested pixels only
                 // (LocMaxC[nz] == Lc[nz] ..., mustache.py:760-765)
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    if (d[k] == m[k]) en |= 1u << k;
-                    if (d[k] > Mc[k]) gn |= 1u << k;
+                static_assert(K % 2 == 0, "sieve_bits2 takes the pixels in pairs");
+                for_each_index(std::make_integer_sequence<int, K / 2>(), [&](auto jc) __attribute__((always_inline)) {
+                    constexpr int j = decltype(jc)::value;
+                    sieve_bits2<j == 0>(en, gn, d[2 * j], m[2 * j], Mc[2 * j], d[2 * j + 1], m[2 * j + 1], Mc[2 * j + 1]);
+                });
+                // the reference evaluates the sieve and expon.fit on the tested pixels only (Lc[nz], mustache.py:755-768);
+                // a wave that owns none has nothing to do here.  (Under the maxima's own test of wave_has_nz: a second test
+                // behind the join makes the compiler carry the condition there as a per-lane 0 / 1 value.)
+                if (kl >= 4) {
+                    // tested level = D_{kl-2}: previous = D_{kl-3} (ep), current (Dc, ec, gp), next = this one (m, en)
+                    const uint32_t code = (uint32_t)tested + 1u;
+                    // branch-free form: the five terms fold into ONE floating-point comparison per pixel (D_c > best and
+                    // D_c > M_n <=> D_c > max(best, M_n): no NaN reaches here) and one bit of a mask that is combined for all
+                    // K pixels at once; updates and statistics are selects, so the K pixels are independent instruction streams
+                    // instead of K nested exec-mask branches in a row
+                    //
+                    // The mask bit is never tested on its own (a bit test into a second lane mask, then an or of the two): the
+                    // flag word is shifted up pixel by pixel and the bit that falls out IS the gate's lane mask (gated_greater).
+                    // A pixel that is never tested holds best = +inf from the start, so the tested-pixel bits are no term of the
+                    // gate.  What the phase costs is its instruction COUNT: 13 -> 11 vector instructions per pixel here.
+                    uint32_t flags = (ec & (ep | en) & gp) << (32 - K);      // pixel 0 on top (sieve_bits2's bit order)
+                    for_each_index(std::make_integer_sequence<int, K>(), [&](auto kc) __attribute__((always_inline)) {
+                        constexpr int k = decltype(kc)::value;
+                        const bool upd = gated_greater(flags, Dc[k], dmax(best[k], m[k]));
+                        best[k] = upd ? Dc[k] : best[k];
+                        lvl[k] = upd ? code : lvl[k];
+                        // statistics of |D_c| over the tested pixels, on the words of D_c (fabs is a source modifier).  Not
+                        // tested: the sum gets +0.0 (x + 0.0 == x for every x >= +0.0: its bits are unchanged), the minimum
+                        // exactly +inf (0x7ff00000 over the zero low word).  The low word is selected once for both: one
+                        // register pair serves the minimum and then, its high word selected again in place, the sum -- three
+                        // selects where two separate pairs take four.
+                        const bool tz = (nz_mask & (1u << k)) != 0;                  // loop-invariant: a lane mask in scalar registers
+                        const uint32_t alo = tz ? (uint32_t)__double2loint(Dc[k]) : 0u;
+                        uint32_t ahi = tz ? (uint32_t)__double2hiint(Dc[k]) : 0x7ff00000u;
+                        // The empty statement hides that ahi is a select on tz: otherwise `tz ? ahi : 0` below folds to a
+                        // select on D_c's high word, the sum's operand becomes a register pair of its own and needs a copy of
+                        // alo.  It works while scripts/isa_census.py shows 3 v_cndmask_b32 per pixel for the statistics and
+                        // no v_mov_b32 between them (48 selects in the sieve's block at K = 8, 24 of them the updates).
+                        asm("" : "+v"(ahi));
+                        lmin = __builtin_fmin(lmin, fabs(__hiloint2double((int)ahi, (int)alo)));      // both >= 0: operand order immaterial
+                        lsum = lsum + fabs(__hiloint2double((int)(tz ? ahi : 0u), (int)alo));
+                    });
+                    // fixed-order DPP reduction inside the wave (total lands in lane 63), one slot per (level, wave)
+                    if (!MST_VARIANT(2)) wave_reduce_min_sum(lmin, lsum);
                 }
             } else {
 #pragma unroll
                 for (int k = 0; k < K; ++k) m[k] = 0.0;
             }
             if (kl >= 4) {
-                // tested level = D_{kl-2}: previous = D_{kl-3} (ep), current (Dc, ec, gp), next = this one (m, en)
-                double lmin = INFINITY, lsum = 0.0;
-                const uint32_t code = (uint32_t)tested + 1u;
-                // the reference evaluates the sieve and expon.fit on the tested pixels only (Lc[nz], mustache.py:755-768);
-                // a wave that owns none has nothing to do here
-                if (wave_has_nz) {
-                    // branch-free form: the five terms fold into ONE floating-point comparison per pixel (D_c > best and
-                    // D_c > M_n <=> D_c > max(best, M_n): no NaN reaches here) and one bit of a mask that is combined for all
-                    // K pixels at once; updates and statistics are selects, so the K pixels are independent instruction streams
-                    // instead of K nested exec-mask branches in a row
-                    const uint32_t flags = nz_mask & ec & (ep | en) & gp;
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        const bool bit = (flags & (1u << k)) != 0;
-                        const bool upd = bool(int(Dc[k] > dmax(best[k], m[k])) & int(bit));
-                        best[k] = upd ? Dc[k] : best[k];
-                        lvl[k] = upd ? code : lvl[k];
-                        const bool tz = (nz_mask & (1u << k)) != 0;
-                        const double a = fabs(Dc[k]);
-                        lmin = __builtin_fmin(lmin, tz ? a : INFINITY);      // a >= 0, lmin >= 0: the order of the operands is immaterial
-                        lsum = lsum + (tz ? a : 0.0);                          // x + 0.0 == x for every x >= +0.0: the sum's bits are unchanged
-                    }
-                }
-                // fixed-order DPP reduction inside the wave (total lands in lane 63), one slot per (level, wave); a wave without
-                // a tested pixel holds the identities {inf, 0} in every lane already
-                if (wave_has_nz && !MST_VARIANT(2)) wave_reduce_min_sum(lmin, lsum);
                 if (lane == 63) {
                     st[(tested * T::NW + wave) * 2] = lmin;
                     st[(tested * T::NW + wave) * 2 + 1] = lsum;

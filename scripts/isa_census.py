@@ -34,13 +34,46 @@ FLAGS = ("-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast
 KERNEL = re.compile(r"^_ZN\S*scale_space_kernelINS_4TileILi32ELi64ELi14ELi8ELi1ELb0ELb0EEELb1EEE\S*:")
 
 CATS = ["fp64 add/mul", "fp64 max/min", "fp64 compare", "v_mov_b64", "v_mov_b32", "DPP move", "v_cndmask", "int / bit VALU",
-        "LDS read", "LDS write", "SALU", "s_waitcnt / s_nop", "branch", "barrier", "scalar load", "other"]
-VALU = CATS[:8]
+        "int compare -> mask", "LDS read", "LDS write", "SALU", "s_waitcnt / s_nop", "branch", "barrier", "scalar load", "other"]
+VALU = CATS[:9]
+
+
+# Issue slots (one slot = the 4 cycles a SIMD takes to issue one FP64 instruction of a wave64), from the microbenchmarks of
+# scripts/ubench (issue_mix.hip, f32_ops.hip; LABBOOK round 2): FP64 arithmetic, maxima, compares, DPP moves, v_mov_b64 and
+# selects one slot; plain 32-bit integer VALU half a slot; a compare into a scalar mask that an s_or_b64 / s_and_b64 then
+# folds into another mask 2.5 slots for an integer compare and its fold -- charged as half a slot for the compare and 2 for
+# the scalar fold, whichever instruction wrote the masks; s_nop N stalls the wave's issue for N + 1 cycles.  Other scalar
+# instructions, branches and waits are not charged.  v_addc_co_u32 / v_add_co_u32 are charged as the 32-bit integer adds
+# they are (not timed on their own).  The table prices instructions in isolation: LABBOOK "Sieve gate" holds what the
+# kernel's own timing says of it.
+SLOTS = {"fp64 add/mul": 1.0, "fp64 max/min": 1.0, "fp64 compare": 1.0, "v_mov_b64": 1.0, "DPP move": 1.0, "v_cndmask": 1.0,
+         "v_mov_b32": 0.5, "int / bit VALU": 0.5, "int compare -> mask": 0.5}
+FOLD = 2.0
+
+
+def is_fold(op, text):
+    """a scalar and / or of two lane masks (not the exec bookkeeping of a branch)"""
+    return op in ("s_or_b64", "s_and_b64") and "exec" not in text
+
+
+def slots(ins):
+    """issue slots of a list of (op, text)"""
+    s = 0.0
+    for op, text in ins:
+        if op == "s_nop":
+            s += (int(text.split()[1], 0) + 1) / 4.0
+        elif is_fold(op, text):
+            s += FOLD
+        else:
+            s += SLOTS.get(category(op, text), 0.0)
+    return s
 
 
 def category(op, text):
     if "dpp" in op or " row_" in text or " wave_sh" in text or "row_bcast" in text:
         return "DPP move"
+    if op.startswith("v_cmp") and "f64" not in op and re.match(r"\S+\s+s\[", text):
+        return "int compare -> mask"
     if op.startswith(("v_add_f64", "v_mul_f64", "v_fma_f64", "v_fmac_f64")):
         return "fp64 add/mul"
     if op.startswith(("v_max_f64", "v_min_f64")):
@@ -281,6 +314,29 @@ def main():
         if common[cat]:
             print("  %-20s %5d" % (cat, common[cat]))
     print("  %-20s %5d" % ("VALU total", sum(common[c] for c in VALU)))
+    print()
+    # the blocks behind the level's second barrier (the last s_barrier of the loop in layout order): 3 x 3 maxima, sieve bits,
+    # sieve, statistics, wave reduction, state renames.  A wave that owns a tested pixel runs, at a tested level (kl >= 4),
+    # every one of them except the blocks that load constants into registers (zero maxima of an untested wave, the {inf, 0}
+    # statistics of a wave or level without a sieve): wherever the compiler puts the renames, they are counted on that path.
+    last = max(i for i, b in enumerate(in_loop) if any(op == "s_barrier" for op, _ in b[2]))
+    tail = [(in_loop[last][0], in_loop[last][2][[op for op, _ in in_loop[last][2]].index("s_barrier") + 1:])] + \
+           [(lab, ins) for lab, ann, ins in in_loop[last + 1:]]
+    print("behind the second barrier, per thread and level: issue slots by block (one slot = one FP64 issue, 4 cycles; table in the script)")
+    print("  block        VALU  slots  DPP  fp64 cmp  selects  folds  s_nop")
+    tested, tested_valu = 0.0, 0
+    for lab, ins in tail:
+        c = count(ins)
+        if not sum(c[x] for x in VALU) and not any(op == "s_nop" for op, _ in ins):
+            continue
+        on_path = not any(re.match(r"v_mov_b(64|32)\S*\s+v\S+,\s+(0|0x7ff00000)$", text) for _, text in ins)
+        tested += slots(ins) if on_path else 0.0
+        tested_valu += sum(c[x] for x in VALU) if on_path else 0
+        print("  %-10s %5d  %5.1f  %3d  %8d  %7d  %5d  %5d%s" % (lab.lstrip("."), sum(c[x] for x in VALU), slots(ins), c["DPP move"], c["fp64 compare"],
+                                                              c["v_cndmask"], sum(1 for op, text in ins if is_fold(op, text)),
+                                                              sum(1 for op, _ in ins if op == "s_nop"), "   <- tested wave" if on_path else ""))
+    print("  all blocks (static)                     %6.1f slots" % sum(slots(ins) for _, ins in tail))
+    print("  tested wave at a tested level (marked blocks: maxima, sieve, statistics, renames)  %6.1f slots, %d VALU" % (tested, tested_valu))
     print()
     print("per thread and level, radius cases: axis-0 main | axis-0 leftover pieces (first 16 r threads) | axis-1")
     print("  r   blur flops (main, pieces, axis-1)   other VALU (main, pieces, axis-1)   LDS reads   LDS writes")
