@@ -628,6 +628,36 @@ MST_STABLE int mst_pileup_trans_windows(const int32_t *x, const int32_t *y, cons
                                         uint8_t *valid_cols, double *expected, double *obs, double *oe, double *loop_stats,
                                         void *workspace, uint64_t workspace_bytes, void *stream);
 
+/* ---- the same pile-up for P pairs in shared launches (rules: the genome mode of mustache_amd/pileup.py).  Added without a
+ * change of MST_ABI_REVISION, as mst_balance_apply_pairs was.  The records of the pairs are concatenated as
+ * mst_balance_apply_pairs leaves them (x, y dev int32 [N], v dev f64 [N]) and so are the loops (lx, ly dev int64 [L]).  The
+ * segment tables are HOST arrays -- the caller knows every length without a wait -- and are checked before anything is
+ * launched: seg_off int64 [P + 1] rises from 0 to N, loop_off int64 [P + 1] from 0 to L (a pair may have no record, or no
+ * loop), n1, n2 int64 [P] are the pairs' dimensions (1 .. 2^31 - 1).  Pair p's valid flags start at byte sum(n1[0 .. p)) of
+ * valid_rows (dev uint8 [sum n1], overwritten) and at byte sum(n2[0 .. p)) of valid_cols (dev uint8 [sum n2]).
+ * A record with !(v > 0) -- 0.0, negative, NaN -- is ignored altogether (no flag, no share of the sum, no window), and so is a
+ * record outside [0, n1[p]) x [0, n2[p]); +inf counts and makes that pair's expected NaN, and only that pair's.
+ * expected dev f64 [P]; kept dev int64 [P]: the records of the pair that counted; obs, oe dev f64 [L][2w+1][2w+1]; loop_stats
+ * dev f64 [L][3].  For every pair every output has the bits mst_pileup_trans_windows gives on that pair's records with v > 0
+ * alone; no float atomics; bit-identical under any permutation of the records within a segment and of the loops within a
+ * segment.  0 <= w <= 64, 1 <= q <= 2w + 1, 1 <= P <= 65535, N < 2^31; L = 0 and N = 0 are served. */
+/* workspace bytes of one call; 0 for a bad argument (P outside 1 .. 65535, w > 64, tables that do not rise from 0). */
+MST_STABLE uint64_t mst_pileup_trans_batch_workspace_bytes(const int64_t *seg_off, const int64_t *n1, const int64_t *loop_off,
+                                                           int32_t P, int32_t w);
+MST_STABLE int mst_pileup_trans_batch(const int32_t *x, const int32_t *y, const double *v, int64_t N, const int64_t *seg_off,
+                                      const int64_t *n1, const int64_t *n2, const int64_t *lx, const int64_t *ly, int64_t L,
+                                      const int64_t *loop_off, int32_t P, int32_t w, int32_t q, uint8_t *valid_rows,
+                                      uint8_t *valid_cols, double *expected, int64_t *kept, double *obs, double *oe,
+                                      double *loop_stats, void *workspace, uint64_t workspace_bytes, void *stream);
+/* agg dev f64 [P][4][(2w+1)^2]: for pair p what mst_pileup_reduce gives on that pair's windows with that pair's order, to the
+ * bit.  order dev int32 [L]: positions [loop_off[p], loop_off[p + 1]) hold pair p's loops (indices into obs / oe, so inside
+ * that range themselves; any other index is skipped) in the order they are added: chunks of 512 that never cross a segment,
+ * added in chunk order.  A pair without a loop gets zeros.  loop_off: host, as above.  Two launches whatever P is. */
+MST_STABLE uint64_t mst_pileup_reduce_segmented_workspace_bytes(const int64_t *loop_off, int32_t P, int32_t w);
+MST_STABLE int mst_pileup_reduce_segmented(const double *obs, const double *oe, const int32_t *order, int64_t L,
+                                           const int64_t *loop_off, int32_t P, int32_t w, double *agg, void *workspace,
+                                           uint64_t workspace_bytes, void *stream);
+
 /* ---- read pairs -> pixels (rules: mustache_amd/pairs.py; tests/pairs_reference.py restates them).  Added without a change
  * of MST_ABI_REVISION, as mst_balance_apply_pairs was: a library from before the addition is refused by its missing symbols. */
 /* One pass over the rows (pos1, pos2: dev int32 [n_rows]) of one chromosome.  A row is dropped when a position is < 1 or

@@ -30,7 +30,9 @@ dropped.  The reader does not expose a matrix's record count before it is read, 
 what the records read so far will need (estimate_bytes) against torch.cuda.mem_get_info.  The assembly is plain torch
 (BalanceCSR's sort makes the result independent of the record order, so the bias has the same bits whichever way round a pair
 is stored and whichever `.hic` version holds it); the application is one launch of mst_balance_apply_pairs
-(csrc/mst_balance.hip) for any number of pairs.
+(csrc/mst_balance.hip) for any number of pairs.  balanced_pairs / balanced_batches hand each pair its records with v' > 0;
+balanced_segments hands a batch over as the launch left it -- concatenated, unfiltered, with the host segment table -- for a
+consumer that skips such records itself (the pile-up of mustache_amd/pileup.py's genome mode).
 
 A pairs file is the second source of the same assembly (mustache_amd/pairs.py states its rules).  The chromosomes and their
 lengths are the `#chromsize` table's, in table order; the file is parsed once with its trans rows kept (8 bytes of host memory
@@ -626,17 +628,16 @@ def apply_pairs(x, y, v, seg_off, row_off, col_off, bias, out=None):
     return out
 
 
-def balanced_pairs(gb, pairs, release=False):
-    """The batch form: the balanced records of every pair of `pairs` = [(a, b)] through ONE launch of mst_balance_apply_pairs.
-    Per pair (x = bins of a, y = bins of b, v') on the device with the records of v' > 0 only, or None when nothing is left.
-    release: the pairs' raw records leave `gb` once they are applied."""
+def _apply_batch(gb, pairs, release):
+    """ONE launch of mst_balance_apply_pairs over the resident raw records of `pairs` = [(a, b)]: (x, y, v', seg) with the
+    pairs' records concatenated in order, v' unfiltered and seg the host int64 [P + 1] segment table (a pair without a record
+    is an empty segment); None when no pair has a record.  release: the pairs' raw records leave `gb` once they are applied."""
     import torch
     dev = gb.device
     recs = [gb.records(a, b) for a, b in pairs]
     lens = [0 if r is None else int(r[2].numel()) for r in recs]
-    out = [None] * len(pairs)
     if sum(lens) == 0:
-        return out
+        return None
     seg = np.zeros(len(pairs) + 1, np.int64)
     np.cumsum(lens, out=seg[1:])
     row = np.asarray([gb.offsets[gb.index(a)] for a, _ in pairs], np.int64)
@@ -654,10 +655,24 @@ def balanced_pairs(gb, pairs, release=False):
         table = torch.from_numpy(np.concatenate([seg, row, col])).to(dev)
         P = len(pairs)
         vb = apply_pairs(x, y, v, table[:P + 1], table[P + 1:2 * P + 1], table[2 * P + 1:], gb.bias_device())
+    return x, y, vb, seg
+
+
+def balanced_pairs(gb, pairs, release=False):
+    """The batch form: the balanced records of every pair of `pairs` = [(a, b)] through ONE launch of mst_balance_apply_pairs.
+    Per pair (x = bins of a, y = bins of b, v') on the device with the records of v' > 0 only, or None when nothing is left.
+    release: the pairs' raw records leave `gb` once they are applied."""
+    import torch
+    out = [None] * len(pairs)
+    got = _apply_batch(gb, pairs, release)
+    if got is None:
+        return out
+    x, y, vb, seg = got
+    with torch.cuda.device(gb.device):
         keep = vb > 0
-        for p in range(P):
-            if lens[p]:
-                s, e = int(seg[p]), int(seg[p + 1])
+        for p in range(len(pairs)):
+            s, e = int(seg[p]), int(seg[p + 1])
+            if e > s:
                 k = keep[s:e]
                 got = (x[s:e][k], y[s:e][k], vb[s:e][k])
                 out[p] = got if got[2].numel() else None
@@ -672,6 +687,13 @@ def balanced_pair(gb, a, b):
 def balanced_batches(gb, pairs, release=True, max_records=APPLY_BATCH_RECORDS):
     """(k, balanced records of pairs[k] or None) for every k in order; consecutive pairs share a launch until their raw records
     reach max_records"""
+    for k, j in _batch_ends(gb, pairs, max_records):
+        for i, rec in enumerate(balanced_pairs(gb, pairs[k:j], release=release)):
+            yield k + i, rec
+
+
+def _batch_ends(gb, pairs, max_records):
+    """balanced_batches' rule as (k, j) index ranges: consecutive pairs until their raw records reach max_records"""
     k = 0
     while k < len(pairs):
         j, held = k, 0
@@ -681,6 +703,19 @@ def balanced_batches(gb, pairs, release=True, max_records=APPLY_BATCH_RECORDS):
             j += 1
             if held >= max_records:
                 break
-        for i, rec in enumerate(balanced_pairs(gb, pairs[k:j], release=release)):
-            yield k + i, rec
+        yield k, j
         k = j
+
+
+def balanced_segments(gb, pairs, release=True, max_records=APPLY_BATCH_RECORDS):
+    """balanced_batches without the filter: (k, j, x, y, v', seg) per batch of the consecutive pairs pairs[k:j] -- the
+    concatenated records (device int32 / int32 / float64) straight from one mst_balance_apply_pairs launch and the host int64
+    segment table seg [j - k + 1].  Nothing is compacted and the host waits for nothing: a record the balancing removes has
+    v' = 0 (NaN for a NaN count) and the consumer skips it (mst_pileup_trans_batch does).  A batch none of whose pairs has a
+    record comes with x = y = v' = None and a table of zeros.  The batch rule and `release` are balanced_batches'."""
+    for k, j in _batch_ends(gb, pairs, max_records):
+        got = _apply_batch(gb, pairs[k:j], release)
+        if got is None:
+            yield k, j, None, None, None, np.zeros(j - k + 1, np.int64)
+        else:
+            yield (k, j) + got

@@ -50,6 +50,32 @@ restates the rules).  Without the switch nothing changes: rows with two chromoso
     in run order; the same metrics().  Bit-identical under any permutation of the records and of the rows.
 Device work (mustache_amd/csrc/mst_pileup_trans.hip): one pass over the pair's records finds the valid rows and columns, the
 exact total and the window cells together; one host wait per pair.
+
+Genome mode (`--trans --balance-genome ICE|NEWTON [--balance-pixels all|inter] [--pairs-trans]`, `pileup(..., trans=True,
+balance_genome=...)`, `pileup_trans_batch()`): the lists the callers write from a raw `.hic` file or a pairs file, piled up on
+the map they were called from.  The rows, the windows, E, the aggregate and the files are the trans rules above; what differs:
+  * Map of a pair (A, B): the genome-balanced records the trans caller has before its z-score -- GenomeBias.records(A, B)
+    through mst_balance_apply_pairs, the records with v' > 0.  The genome is read and balanced ONCE for the run
+    (balance_genome.read_genome, solve_genome: one `... balancing of the genome (... pixels)` line), on every chromosome of the
+    file whichever pairs the list names; its memory refusal is balance_genome's.
+  * Dimensions: n1 = n_A, n2 = n_B of the genome layout (length // res + 1, GenomeBias.bins), known on the host before anything
+    runs -- NOT max x + 1 as above: under --balance-genome the chromosome's extent is known, so NaN means "off the
+    chromosome".  E does not depend on the choice.
+  * Statuses: `off_map` when a >= n_A or b >= n_B, decided on the host before the launch; `no_pair` when a chromosome of the
+    pair is not in the file, when the pair has no raw record, or when none of its records counts after the balancing (its
+    `kept` comes back 0: the pair's device result is discarded and its partial is the empty one).
+  * Pairs run in order of first appearance; the genome-wide aggregate adds the pair partials in that order on the host.
+  * Batches: consecutive pairs until their raw records reach balance_genome.APPLY_BATCH_RECORDS (balanced_segments), cut
+    earlier where the windows of their loops (16 (2w+1)^2 bytes per loop) would exceed WINDOW_SHARE of the device's free
+    memory; a single pair whose windows do not fit is refused with both numbers.  One host wait per batch: one concatenated
+    copy carries every pair's aggregate, loop statistics, E and kept.
+  * Refused: --balance-genome without --trans, with --balance, -b or -norm other than NONE, on `.cool` / `.mcool` / text input;
+    --balance-pixels without --balance-genome; a pairs file without --pairs-trans; --pairs-trans without --balance-genome or
+    on another input; --pairs-zero-based without --pairs-trans (no other pile-up bins a pairs file with it).  Each is one `Error:` line before anything is read.
+Device work (mustache_amd/csrc/mst_pileup_trans_batch.hip): mst_pileup_trans_batch is mst_pileup_trans_windows for P pairs in
+five launches -- a record whose v' is not > 0 is skipped in the pass, so the balanced records go in without a compaction --
+and mst_pileup_reduce_segmented the reduce for P pairs in two; every pair's values have the bits the single-pair entry points
+give on that pair alone.
 """
 import argparse
 import math
@@ -262,6 +288,93 @@ def pileup_trans_records(x, y, v, n1, n2, xs, ys, w=10, q=6):
             "metrics_oe": metrics(apa_oe, w, q)}
 
 
+def _host_ptr(a):
+    """a contiguous host array as the C ABI takes a host table"""
+    import ctypes
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def pileup_trans_batch(x, y, v, seg_off, dims, loops, w=10, q=6):
+    """pileup_trans_records for P inter-chromosomal pairs in shared launches (csrc/mst_pileup_trans_batch.hip).  x, y, v: the
+    pairs' records concatenated (device int32 / int32 / float64, or host arrays; None when there is none), pair p owning
+    [seg_off[p], seg_off[p + 1]) -- seg_off a HOST table of P + 1 entries; a record whose v is not > 0 is ignored, so the output of
+    mst_balance_apply_pairs goes in unfiltered.  dims: [(n1, n2)] per pair; loops: [(xs, ys)] per pair (host arrays, bins of A
+    and of B; either may be empty).  Returns one dict per pair with pileup_trans_records' keys -- "obs", "oe" and "valid" are
+    views into the batch's device tensors -- and "kept", the records of the pair that counted.  Every value has the bits
+    pileup_trans_records gives on that pair's records with v > 0 alone.  One host wait for the whole batch."""
+    import torch
+    from . import _lib
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    w, q, P = int(w), int(q), len(dims)
+    check_window(w, q)
+    if len(loops) != P:
+        raise PileupError("dims and loops differ in length (%d, %d)" % (P, len(loops)))
+    seg = np.ascontiguousarray(seg_off, np.int64).reshape(-1)
+    if len(seg) != P + 1:
+        raise PileupError("seg_off has %d entries, %d pairs need %d" % (len(seg), P, P + 1))
+    n1 = np.ascontiguousarray([d[0] for d in dims], np.int64)
+    n2 = np.ascontiguousarray([d[1] for d in dims], np.int64)
+    xs = [np.asarray(a, np.int64).reshape(-1) for a, _ in loops]
+    ys = [np.asarray(b, np.int64).reshape(-1) for _, b in loops]
+    for p in range(P):
+        if len(xs[p]) != len(ys[p]):
+            raise PileupError("xs and ys of pair %d differ in length (%d, %d)" % (p, len(xs[p]), len(ys[p])))
+    loop_off = np.zeros(P + 1, np.int64)
+    np.cumsum([len(a) for a in xs], out=loop_off[1:])
+    N, L, S = int(seg[-1]) if P else 0, int(loop_off[-1]), 2 * w + 1
+    if v is None:
+        x = y = np.zeros(0, np.int32)
+        v = np.zeros(0, np.float64)
+    if not (len(x) == len(y) == len(v) == N):
+        raise PileupError("x, y and v hold %d, %d and %d records, seg_off ends at %d" % (len(x), len(y), len(v), N))
+    lib = require_gpu()
+    dev = v.device if isinstance(v, torch.Tensor) and v.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        x = torch.as_tensor(x).to(dev, dtype=torch.int32).contiguous()
+        y = torch.as_tensor(y).to(dev, dtype=torch.int32).contiguous()
+        v = torch.as_tensor(v).to(dev, dtype=torch.float64).contiguous()
+        lxy = np.concatenate(xs + ys) if L else np.zeros(0, np.int64)
+        order = np.concatenate([np.lexsort((ys[p], xs[p])) + loop_off[p] for p in range(P)]).astype(np.int32) if L \
+            else np.zeros(0, np.int32)
+        lxy_d = torch.from_numpy(lxy).to(dev, non_blocking=True)
+        order_d = torch.from_numpy(order).to(dev, non_blocking=True)
+        need = max(int(lib.mst_pileup_trans_batch_workspace_bytes(_host_ptr(seg), _host_ptr(n1), _host_ptr(loop_off), P, w)),
+                   int(lib.mst_pileup_reduce_segmented_workspace_bytes(_host_ptr(loop_off), P, w)), 256)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        rows = torch.empty(max(int(n1.sum()), 1), dtype=torch.uint8, device=dev)
+        cols = torch.empty(max(int(n2.sum()), 1), dtype=torch.uint8, device=dev)
+        E = torch.empty(max(P, 1), dtype=torch.float64, device=dev)
+        kept = torch.empty(max(P, 1), dtype=torch.int64, device=dev)
+        obs = torch.empty((L, S, S), dtype=torch.float64, device=dev)
+        oe = torch.empty_like(obs)
+        st = torch.empty((L, 3), dtype=torch.float64, device=dev)
+        agg = torch.empty((max(P, 1), 4, S * S), dtype=torch.float64, device=dev)
+        _lib.check(lib.mst_pileup_trans_batch(
+            _ptr(x) if N else None, _ptr(y) if N else None, _ptr(v) if N else None, N, _host_ptr(seg), _host_ptr(n1), _host_ptr(n2),
+            _ptr(lxy_d) if L else None, _lib.off(lxy_d, L) if L else None, L, _host_ptr(loop_off), P, w, q, _ptr(rows), _ptr(cols),
+            _ptr(E), _ptr(kept), _ptr(obs) if L else None, _ptr(oe) if L else None, _ptr(st) if L else None, _ptr(ws), ws.numel(),
+            _stream()))
+        _lib.check(lib.mst_pileup_reduce_segmented(_ptr(obs) if L else None, _ptr(oe) if L else None, _ptr(order_d) if L else None,
+                                                   L, _host_ptr(loop_off), P, w, _ptr(agg), _ptr(ws), ws.numel(), _stream()))
+        host = torch.cat([agg.view(-1), st.view(-1), E, kept.view(torch.float64)]).cpu().numpy()      # the one wait
+    agg_h = host[:P * 4 * S * S].reshape(P, 4, S, S)
+    st_h = host[P * 4 * S * S:P * 4 * S * S + 3 * L].reshape(L, 3)
+    E_h, kept_h = host[-2 * P:-P], host[-P:].view(np.int64)
+    row_off = np.concatenate([[0], np.cumsum(n1)])
+    col_off = np.concatenate([[0], np.cumsum(n2)])
+    out = []
+    for p in range(P):
+        l0, l1 = int(loop_off[p]), int(loop_off[p + 1])
+        a = agg_h[p]
+        apa, apa_oe = mean_map(a[0], a[1]), mean_map(a[2], a[3])
+        out.append({"valid": (rows[int(row_off[p]):int(row_off[p + 1])], cols[int(col_off[p]):int(col_off[p + 1])]),
+                    "expected": float(E_h[p]), "kept": int(kept_h[p]), "obs": obs[l0:l1], "oe": oe[l0:l1], "sum_obs": a[0],
+                    "count_obs": a[1], "sum_oe": a[2], "count_oe": a[3], "apa": apa, "apa_oe": apa_oe,
+                    "center_obs": st_h[l0:l1, 0].copy(), "center_oe": st_h[l0:l1, 1].copy(), "p2ll": st_h[l0:l1, 2].copy(),
+                    "metrics": metrics(apa, w, q), "metrics_oe": metrics(apa_oe, w, q)})
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # loop lists
 # ----------------------------------------------------------------------------------------------------------------------
@@ -465,15 +578,141 @@ def _pileup_trans(f, table, res, chromosomes, norm, bias, balance, w, q, n_min, 
     return out
 
 
+WINDOW_SHARE = 0.25               # genome mode: the windows of a batch's loops may take this share of the device's free memory
+
+
+def window_bytes(loops, w):
+    """device bytes of the obs and oe windows of `loops` loops"""
+    return 16 * (2 * int(w) + 1) ** 2 * int(loops)
+
+
+def window_budget():
+    """the bytes the windows of one batch may take: WINDOW_SHARE of the device memory that is free now"""
+    import torch
+    return int(WINDOW_SHARE * int(torch.cuda.mem_get_info()[0]))
+
+
+def _window_batches(loops_of, w, budget, names):
+    """Consecutive pairs (indices into loops_of, the pairs' used-loop counts) whose windows fit `budget` bytes together.  A
+    single pair that does not fit is a PileupError with both numbers, before anything is launched."""
+    for p, n in enumerate(loops_of):
+        if window_bytes(n, w) > budget:
+            raise PileupError("the windows of the pair %s (%d loops, w = %d) need %d bytes of device memory; %d bytes (%d%% of "
+                              "what is free) are allowed" % (names[p], n, w, window_bytes(n, w), budget, round(100 * WINDOW_SHARE)))
+    batch, held = [], 0
+    for p, n in enumerate(loops_of):
+        if batch and held + window_bytes(n, w) > budget:
+            yield batch
+            batch, held = [], 0
+        batch.append(p)
+        held += window_bytes(n, w)
+    if batch:
+        yield batch
+
+
+def _pileup_trans_genome(f, table, res, chromosomes, norm, bias, balance, method, pixels, pairs_zero_based, w, q, n_min, x_max,
+                         device, verbose):
+    """pileup() in trans mode on the genome-balanced map (the module docstring has the rules): the genome read and balanced
+    once, every pair's records balanced and piled up in shared launches, one host wait per batch."""
+    from . import pairs as pairs_mod
+    from .balance import BalanceError, report
+    from .balance_genome import APPLY_BATCH_RECORDS, balanced_segments, check_genome_request, read_genome, solve_genome
+    from .request import keep_trans_rows
+    from_pairs = pairs_mod.is_pairs(f)
+    try:
+        method, pixels = check_genome_request(method, pixels, [f], bias or None, norm, balance or None, 1, "all",
+                                              pairs_trans=from_pairs)
+    except BalanceError as e:
+        raise PileupError(str(e))
+    why = keep_trans_rows([f], pairs_zero_based) if from_pairs else None      # the one parse of a pairs file, host only
+    if why:
+        raise PileupError(why)
+    status, a, b, pairs = classify(table, res, chromosomes, n_min, x_max, trans=True)
+    out = PileupResult(table, status, w, q)
+    import torch
+    try:
+        gb = solve_genome(read_genome(f, res, pixels, device, pairs_zero_based, verbose), method)
+    except BalanceError as e:
+        raise PileupError(str(e))
+    if verbose:
+        report(gb.info, gb.label)
+    at = {frozenset((_key(A), _key(B))): p for p, (A, B) in enumerate(pairs)}
+    rows_of, used_of, live = [[] for _ in pairs], [[] for _ in pairs], []
+    for k in range(len(table)):                         # one pass: every eligible row to its pair
+        if status[k] is None:
+            rows_of[at[frozenset((_key(table.chr1[k]), _key(table.chr2[k])))]].append(k)
+    for p, (A, B) in enumerate(pairs):
+        rows = rows_of[p]
+        try:
+            have = gb.records(A, B) is not None
+        except NameError:                               # a chromosome of the pair is not in the file
+            have = False
+        if not have:
+            for k in rows:
+                status[k] = "no_pair"
+            continue
+        n1, n2 = gb.bins[gb.index(A)], gb.bins[gb.index(B)]
+        for k in rows:
+            status[k] = "off_map" if a[k] >= n1 or b[k] >= n2 else "used"
+        used_of[p] = [k for k in rows if status[k] == "used"]
+        live.append(p)
+    parts = [_empty_result(w, q) for _ in pairs]
+    drop = ("valid", "expected", "obs", "oe", "kept")
+    with torch.cuda.device(gb.device):
+        budget = window_budget()
+        names = ["%s,%s" % pairs[p] for p in live]
+        for group in list(_window_batches([len(used_of[p]) for p in live], w, budget, names)):
+            mine = [live[i] for i in group]
+            for k0, k1, x, y, v, seg in balanced_segments(gb, [pairs[p] for p in mine], release=True,
+                                                          max_records=APPLY_BATCH_RECORDS):
+                batch = mine[k0:k1]
+                dims = [(gb.bins[gb.index(pairs[p][0])], gb.bins[gb.index(pairs[p][1])]) for p in batch]
+                got = pileup_trans_batch(x, y, v, seg, dims, [(a[used_of[p]], b[used_of[p]]) for p in batch], w, q)
+                del x, y, v
+                for p, part in zip(batch, got):
+                    if part["kept"] == 0:               # nothing of the pair survives the balancing: its result is discarded
+                        for k in rows_of[p]:
+                            status[k] = "no_pair"
+                        used_of[p] = []
+                        continue
+                    for j, k in enumerate(used_of[p]):
+                        out.obs_center[k], out.oe_center[k], out.p2ll[k] = part["center_obs"][j], part["center_oe"][j], \
+                            part["p2ll"][j]
+                    parts[p] = {k_: v_ for k_, v_ in part.items() if k_ not in drop}
+                del got
+    S = 2 * w + 1
+    tot = [np.zeros((S, S)) for _ in range(4)]
+    for p, (A, B) in enumerate(pairs):
+        part = {k_: v_ for k_, v_ in parts[p].items() if k_ not in drop}
+        out.chromosomes.append(("%s,%s" % (A, B), len(rows_of[p]), len(used_of[p]), part))
+        for t, name in zip(tot, ("sum_obs", "count_obs", "sum_oe", "count_oe")):
+            t += part[name]                              # genome-wide: in the order of first appearance
+        if verbose:
+            print("pile-up of the pair %s,%s: %d of %d rows used, P2M %r" % (A, B, len(used_of[p]), len(rows_of[p]),
+                                                                            part["metrics"]["P2M"]))
+    apa, apa_oe = mean_map(tot[0], tot[1]), mean_map(tot[2], tot[3])
+    out.all = {"sum_obs": tot[0], "count_obs": tot[1], "sum_oe": tot[2], "count_oe": tot[3], "apa": apa, "apa_oe": apa_oe,
+               "metrics": metrics(apa, w, q), "metrics_oe": metrics(apa_oe, w, q)}
+    return out
+
+
 def pileup(f, loops, res, chromosomes=None, norm=False, bias=False, balance=None, w=10, q=6, n_min=None, x_max=None,
-           device=None, verbose=False, trans=False):
+           device=None, verbose=False, trans=False, balance_genome=None, balance_pixels="all", pairs_zero_based=False):
     """Pile up map `f` around the loops of `loops` (a TSV path or a LoopTable) at resolution `res` (bp).  The reader
     arguments (`norm`, `bias`, `balance`) mean what they mean for the caller; `n_min` is in bins (None: 30), `x_max` in bp.
     trans=True piles up the inter-chromosomal rows instead, pair by pair (the module docstring has the rules); in that mode
-    `chromosomes` of the result holds ("A,B", rows in, loops used, pile-up dict).  Returns a PileupResult."""
+    `chromosomes` of the result holds ("A,B", rows in, loops used, pile-up dict).  balance_genome="NEWTON" | "ICE" (with
+    trans=True; balance_pixels "all" | "inter"; pairs_zero_based for a pairs file) piles the rows up on the genome-balanced map
+    of a raw `.hic` file or a `.pairs` / `.pairs.gz` file, every pair in shared launches.  Returns a PileupResult."""
     w, q, res = int(w), int(q), int(res)
     check_window(w, q)
     table = read_loops(loops) if isinstance(loops, (str, os.PathLike)) else loops
+    if balance_genome is not None:
+        if not trans:
+            raise PileupError("--balance-genome is for inter-chromosomal pile-ups: give --trans (--balance balances one "
+                              "chromosome's own map)")
+        return _pileup_trans_genome(f, table, res, chromosomes, norm, bias, balance, balance_genome, balance_pixels,
+                                    pairs_zero_based, w, q, n_min, x_max, device, verbose)
     if trans:
         return _pileup_trans(f, table, res, chromosomes, norm, bias, balance, w, q, n_min, x_max, device, verbose)
     status, x, y, selected = classify(table, res, chromosomes, n_min, None if x_max is None else int(x_max) // res)
@@ -565,7 +804,44 @@ def parse_args(args):
     p.add_argument("-x", "--max-distance", dest="x_max", default=None, help="largest loop size in bp (default: none)")
     p.add_argument("--trans", dest="trans", action="store_true",
                    help="pile up the inter-chromosomal rows, pair by pair (.hic / .cool; -ch keeps the pairs inside the list)")
+    from .balance_genome import add_arguments
+    add_arguments(p)                 # --balance-genome, --balance-pixels, --pairs-trans: with --trans, the genome-balanced map
+    p.add_argument("--pairs-zero-based", dest="pairs_zero_based", action="store_true",
+                   help="OPTIONAL: .pairs / .pairs.gz input only: positions are 0-based (bin = pos // res)")
     return p.parse_args(args)
+
+
+def genome_request(args, f, world):
+    """What --balance-genome / --balance-pixels / --pairs-trans / --pairs-zero-based ask of a pile-up: (method, pixels) of a
+    genome-mode run, None for a run without them; PileupError with the text of the `Error:` line for a combination that cannot
+    be honoured.  Reads nothing and touches no GPU."""
+    from .balance import BalanceError
+    from .balance_genome import check_genome_request
+    from .pairs import is_pairs
+    pairs_file = is_pairs(f)
+    if args.pairs_trans and not pairs_file:
+        raise PileupError("--pairs-trans is for .pairs / .pairs.gz input (%s is none)" % f)
+    if args.pairs_zero_based and not pairs_file:
+        raise PileupError("--pairs-zero-based is for .pairs / .pairs.gz input (%s is none)" % f)
+    if args.pairs_zero_based and not args.pairs_trans:
+        raise PileupError("--pairs-zero-based without --pairs-trans: only the genome-balanced pile-up (--trans --pairs-trans "
+                          "--balance-genome ICE|NEWTON) bins a pairs file with it")
+    asked = args.balance_genome is not None or args.balance_pixels_given
+    if pairs_file and (args.trans or asked) and not args.pairs_trans:
+        raise PileupError("%s without --pairs-trans: only intra-chromosomal loops are piled up from a pairs file without it; give "
+                          "--trans --pairs-trans --balance-genome ICE|NEWTON" % f)
+    if args.pairs_trans and args.balance_genome is None:
+        raise PileupError("--pairs-trans without --balance-genome: %s holds raw read pairs; give --balance-genome ICE|NEWTON" % f)
+    if not asked:
+        return None
+    if args.balance_genome is not None and not args.trans:
+        raise PileupError("--balance-genome without --trans: it balances the whole genome's map for inter-chromosomal "
+                          "pile-ups; use --balance for one chromosome's own map")
+    try:
+        return check_genome_request(args.balance_genome, args.balance_pixels, [f], args.biasfile, args.norm_method, args.balance,
+                                    world, "all" if args.trans else "none", pairs_trans=args.pairs_trans)
+    except BalanceError as e:
+        raise PileupError(str(e))
 
 
 def main(argv=None):
@@ -590,6 +866,11 @@ def main(argv=None):
     if args.biasfile and not os.path.exists(args.biasfile):
         print("Error: Couldn't find specified bias file")
         return
+    try:
+        genome = genome_request(args, f, world)
+    except PileupError as e:
+        print("Error: %s" % e)
+        return
     balance = None
     if args.balance is not None:
         from .balance import BalanceError, check_request
@@ -609,7 +890,9 @@ def main(argv=None):
     try:
         check_window(args.w, args.q)
         res_ = pileup(f, args.loops, res, chromosomes=args.chromosome, norm=args.norm_method, bias=args.biasfile or False,
-                      balance=balance, w=args.w, q=args.q, n_min=args.n_min, x_max=x_max, verbose=True, trans=args.trans)
+                      balance=balance, w=args.w, q=args.q, n_min=args.n_min, x_max=x_max, verbose=True, trans=args.trans,
+                      balance_genome=genome[0] if genome else None, balance_pixels=genome[1] if genome else "all",
+                      pairs_zero_based=args.pairs_zero_based)
     except (PileupError, TransError) as e:
         print("Error: %s" % e)
         return
