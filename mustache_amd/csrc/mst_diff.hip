@@ -144,16 +144,19 @@ template <class T>
 __device__ __forceinline__ void diff_blur_dispatch(int r, const double *ct, double *vb, const double (&w)[T::RMAX + 1],
                                                    int tid, const double *vsrc, double *vdst, const double *hsrc,
                                                    double (&g)[T::K]) {
+    // No path without a case (mst_scale_space.hip, blur_dispatch): diff_levels refuses a radius outside [1, 28] and diff_which
+    // chooses the tile whose RMAX covers the table's largest radius, so the other cases cannot be reached.
 #define MST_CASE(R_)                                                                  \
     case R_:                                                                          \
         if constexpr (R_ <= T::RMAX) diff_blur<T, R_>(ct, vb, w, tid, vsrc, vdst, hsrc, g); \
+        else __builtin_unreachable();                                                 \
         break;
     switch (r) {
         MST_CASE(1) MST_CASE(2) MST_CASE(3) MST_CASE(4) MST_CASE(5) MST_CASE(6) MST_CASE(7)
         MST_CASE(8) MST_CASE(9) MST_CASE(10) MST_CASE(11) MST_CASE(12) MST_CASE(13) MST_CASE(14)
         MST_CASE(15) MST_CASE(16) MST_CASE(17) MST_CASE(18) MST_CASE(19) MST_CASE(20) MST_CASE(21)
         MST_CASE(22) MST_CASE(23) MST_CASE(24) MST_CASE(25) MST_CASE(26) MST_CASE(27) MST_CASE(28)
-        default: break;
+        default: __builtin_unreachable();
     }
 #undef MST_CASE
 }

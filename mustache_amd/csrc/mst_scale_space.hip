@@ -26,6 +26,10 @@
 //   then vertical 3-max across lanes with DPP wave shifts (lanes of a wave are consecutive rows); the 5-term sieve
 //   and the running best/level per pixel live in registers across all levels and both octaves; per-level min / sum
 //   of |D_c| are reduced per workgroup in a fixed order.
+//   Per-pixel state carried from level to level: G, D, ONE set of maxima, best, level.  The level loop cannot be unrolled, so
+//   G and D are renamed once per level (2 K register-pair copies); nothing else is copied: the maxima are overwritten in
+//   place between the sieve's two comparisons, and the radius switch has no path without a case, so the axis-1 pass
+//   accumulates straight into G (scripts/isa_census.py --state-copies, tests/test_level_state_copies.py).
 // Only the found pixels (~1 % of the block) and 2 x 18 partial statistics per tile are written back.
 // 77 KB of LDS per workgroup -> two independent workgroups per CU, so one's LDS window loads overlap the other's
 // FP64 work instead of every wave of the CU alternating between the two in barrier lock-step.
@@ -57,40 +61,35 @@ namespace {
 
 __device__ __forceinline__ double dmax(double a, double b) { return __builtin_fmax(a, b); }
 
-// The sieve's two per-level comparisons of two pixels, d == m (-> en) and d > p (-> gn), shifted into bit words:
+// One of the sieve's two per-level comparisons for four pixels, shifted into a bit word: GT ? d > p : d == p.
 // v_addc_co_u32 w, w, w computes 2 w + carry, so each compare result enters its word with ONE instruction and
 // never exists as a 0 / 1 << k select that an or then merges.  After K pixels pixel k sits at bit K - 1 - k.
 // The compiler neither schedules nor pads the inside of an asm statement: a lane mask written by a VALU compare needs two
 // wait states before a VALU instruction reads it (as carry-in here), and the order below leaves two instructions between
-// every compare and the add that consumes it -- three mask registers in rotation, no s_nop.  FIRST starts both words from 0.
-template <bool FIRST>
-__device__ __forceinline__ void sieve_bits2(uint32_t &en, uint32_t &gn, double d0, double m0, double p0, double d1, double m1,
-                                            double p1) {
+// every compare and the add that consumes it -- three mask registers in rotation, no s_nop.  FIRST starts the word from 0.
+// One kind of comparison per statement, not both: the level loop takes d > M_prev BEFORE it forms the new maxima and
+// d == M_new behind them, so the new maxima are written over the previous level's and the state holds ONE set of them.
+template <bool GT, bool FIRST>
+__device__ __forceinline__ void sieve_bits4(uint32_t &w, double d0, double p0, double d1, double p1, double d2, double p2,
+                                            double d3, double p3) {
     unsigned long long y, z;      // lane-mask temporaries (SGPR pairs)
-    if constexpr (FIRST)
-        asm("v_cmp_eq_f64 vcc, %4, %5\n\t"
-            "v_cmp_gt_f64 %2, %4, %6\n\t"
-            "v_cmp_eq_f64 %3, %7, %8\n\t"
-            "v_addc_co_u32 %0, vcc, 0, 0, vcc\n\t"
-            "v_cmp_gt_f64 vcc, %7, %9\n\t"
-            "v_addc_co_u32 %1, %2, 0, 0, %2\n\t"
-            "v_addc_co_u32 %0, %3, %0, %0, %3\n\t"
-            "v_addc_co_u32 %1, vcc, %1, %1, vcc"
-            : "=&v"(en), "=&v"(gn), "=&s"(y), "=&s"(z)
-            : "v"(d0), "v"(m0), "v"(p0), "v"(d1), "v"(m1), "v"(p1)
-            : "vcc");
-    else
-        asm("v_cmp_eq_f64 vcc, %4, %5\n\t"
-            "v_cmp_gt_f64 %2, %4, %6\n\t"
-            "v_cmp_eq_f64 %3, %7, %8\n\t"
-            "v_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
-            "v_cmp_gt_f64 vcc, %7, %9\n\t"
-            "v_addc_co_u32 %1, %2, %1, %1, %2\n\t"
-            "v_addc_co_u32 %0, %3, %0, %0, %3\n\t"
-            "v_addc_co_u32 %1, vcc, %1, %1, vcc"
-            : "+v"(en), "+v"(gn), "=&s"(y), "=&s"(z)
-            : "v"(d0), "v"(m0), "v"(p0), "v"(d1), "v"(m1), "v"(p1)
-            : "vcc");
+#define MST_SIEVE4(CMP_, ADD0_, W_)                        \
+    asm("v_cmp_" CMP_ "_f64 vcc, %3, %4\n\t"               \
+        "v_cmp_" CMP_ "_f64 %1, %5, %6\n\t"                \
+        "v_cmp_" CMP_ "_f64 %2, %7, %8\n\t"                \
+        "v_addc_co_u32 %0, vcc, " ADD0_ ", vcc\n\t"        \
+        "v_cmp_" CMP_ "_f64 vcc, %9, %10\n\t"              \
+        "v_addc_co_u32 %0, %1, %0, %0, %1\n\t"            \
+        "v_addc_co_u32 %0, %2, %0, %0, %2\n\t"            \
+        "v_addc_co_u32 %0, vcc, %0, %0, vcc"               \
+        : W_(w), "=&s"(y), "=&s"(z)                        \
+        : "v"(d0), "v"(p0), "v"(d1), "v"(p1), "v"(d2), "v"(p2), "v"(d3), "v"(p3) \
+        : "vcc")
+    if constexpr (GT && FIRST) MST_SIEVE4("gt", "0, 0", "=&v");
+    else if constexpr (GT) MST_SIEVE4("gt", "%0, %0", "+v");
+    else if constexpr (FIRST) MST_SIEVE4("eq", "0, 0", "=&v");
+    else MST_SIEVE4("eq", "%0, %0", "+v");
+#undef MST_SIEVE4
 }
 
 // d > t on the lanes whose top bit of `bits` is set; `bits` moves up by one, so the next call tests the next bit.
@@ -184,16 +183,23 @@ template <class T>
 __device__ __forceinline__ void blur_dispatch(int r, const double *ct, double *vb, const double (&wg)[T::RMAX + 1],
                                               int tid, const double *vsrc, double *vdst, const double *hsrc,
                                               double (&g)[T::K], int variant, unsigned long long *tr MST_INJECT_ARG) {
+    // Every path through the switch runs a case: radii above T::RMAX and outside [1, 28] are UNREACHABLE, not empty.  With an
+    // empty path `g` may leave the switch unwritten, and the compiler then keeps the axis-1 accumulators in registers of their
+    // own and copies them into g behind the join -- K v_mov_b64 per thread and level.  The host cannot get there: check_levels
+    // refuses a table with a radius outside [1, 28]; with_tile and build_list choose the tile from the table's largest radius
+    // (default tile up to 14, the wide one up to 28); MST_FLAG_FMA, whose tile stops at 14, is refused above that; and
+    // enqueue_launch checks the chosen tile's RMAX against the table once more before anything is launched.
 #define MST_CASE(R_)                                                  \
     case R_:                                                          \
         if constexpr (R_ <= T::RMAX) blur_level<T, R_>(ct, vb, wg, tid, vsrc, vdst, hsrc, g, variant, tr MST_INJECT_PASS); \
+        else __builtin_unreachable();                                 \
         break;
     switch (r) {
         MST_CASE(1) MST_CASE(2) MST_CASE(3) MST_CASE(4) MST_CASE(5) MST_CASE(6) MST_CASE(7)
         MST_CASE(8) MST_CASE(9) MST_CASE(10) MST_CASE(11) MST_CASE(12) MST_CASE(13) MST_CASE(14)
         MST_CASE(15) MST_CASE(16) MST_CASE(17) MST_CASE(18) MST_CASE(19) MST_CASE(20) MST_CASE(21)
         MST_CASE(22) MST_CASE(23) MST_CASE(24) MST_CASE(25) MST_CASE(26) MST_CASE(27) MST_CASE(28)
-        default: break;
+        default: __builtin_unreachable();
     }
 #undef MST_CASE
 }
@@ -517,12 +523,21 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
             // pixels), the row shifts stay inside the wave and the neighbouring column groups read this wave's edge samples
             // from the strip written above -- so a wave that owns no tested pixel has no observable use for its maxima and
             // skips them together with the sieve (its Gaussian levels, DoG values and edge samples are produced as before).
+            // The maxima live in ONE set of registers, Mc: the comparisons against the previous level's maxima are taken first,
+            // then the new maxima are written over them, then the comparisons against the new ones.  A wave without a tested
+            // pixel touches neither: its Mc keeps the initial zeros, which nobody reads (every reader is under wave_has_nz).
             uint32_t en = 0, gn = 0;   // en: D_new == M_new;  gn: D_new > M_prev (M of the level before it); pixel k at bit K - 1 - k
-            double m[K];
             // the level statistics of a tested level (kl >= 4); a wave without a tested pixel keeps the identities {inf, 0}
             double lmin = INFINITY, lsum = 0.0;
             if (wave_has_nz) {
-                const double dl = de_left[0], dr = de_right[0];
+                const double dl = de_left[0], dr = de_right[0];      // requested first: the comparisons below cover the LDS latency
+                // the comparisons belong to the sieve, which the reference evaluates on the tested pixels only
+                // (LocMaxC[nz] == Lc[nz] ..., mustache.py:760-765)
+                static_assert(K % 4 == 0, "sieve_bits4 takes the pixels in fours");
+                for_each_index(std::make_integer_sequence<int, K / 4>(), [&](auto jc) __attribute__((always_inline)) {
+                    constexpr int j = 4 * decltype(jc)::value;
+                    sieve_bits4<true, j == 0>(gn, d[j], Mc[j], d[j + 1], Mc[j + 1], d[j + 2], Mc[j + 2], d[j + 3], Mc[j + 3]);
+                });
                 double hm[K];
 #pragma unroll
                 for (int j = 0; j < K / 2; ++j) {      // max(d[2j], d[2j+1]) serves both of its pixels: 12 v_max_f64, not 16
@@ -531,19 +546,16 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
                     hm[2 * j + 1] = dmax(pj, 2 * j + 2 == K ? dr : d[2 * j + 2]);
                 }
 #pragma unroll
-                for (int k = 0; k < K; ++k) m[k] = dmax(dmax(lane_prev(hm[k]), hm[k]), lane_next(hm[k]));
-                // the comparisons belong to the sieve, which the reference evaluates on the tested pixels only
-                // (LocMaxC[nz] == Lc[nz] ..., mustache.py:760-765)
-                static_assert(K % 2 == 0, "sieve_bits2 takes the pixels in pairs");
-                for_each_index(std::make_integer_sequence<int, K / 2>(), [&](auto jc) __attribute__((always_inline)) {
-                    constexpr int j = decltype(jc)::value;
-                    sieve_bits2<j == 0>(en, gn, d[2 * j], m[2 * j], Mc[2 * j], d[2 * j + 1], m[2 * j + 1], Mc[2 * j + 1]);
+                for (int k = 0; k < K; ++k) Mc[k] = dmax(dmax(lane_prev(hm[k]), hm[k]), lane_next(hm[k]));
+                for_each_index(std::make_integer_sequence<int, K / 4>(), [&](auto jc) __attribute__((always_inline)) {
+                    constexpr int j = 4 * decltype(jc)::value;
+                    sieve_bits4<false, j == 0>(en, d[j], Mc[j], d[j + 1], Mc[j + 1], d[j + 2], Mc[j + 2], d[j + 3], Mc[j + 3]);
                 });
                 // the reference evaluates the sieve and expon.fit on the tested pixels only (Lc[nz], mustache.py:755-768);
                 // a wave that owns none has nothing to do here.  (Under the maxima's own test of wave_has_nz: a second test
                 // behind the join makes the compiler carry the condition there as a per-lane 0 / 1 value.)
                 if (kl >= 4) {
-                    // tested level = D_{kl-2}: previous = D_{kl-3} (ep), current (Dc, ec, gp), next = this one (m, en)
+                    // tested level = D_{kl-2}: previous = D_{kl-3} (ep), current (Dc, ec, gp), next = this one (Mc by now, en)
                     const uint32_t code = (uint32_t)tested + 1u;
                     // branch-free form: the five terms fold into ONE floating-point comparison per pixel (D_c > best and
                     // D_c > M_n <=> D_c > max(best, M_n): no NaN reaches here) and one bit of a mask that is combined for all
@@ -554,10 +566,10 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
                     // flag word is shifted up pixel by pixel and the bit that falls out IS the gate's lane mask (gated_greater).
                     // A pixel that is never tested holds best = +inf from the start, so the tested-pixel bits are no term of the
                     // gate.  What the phase costs is its instruction COUNT: 13 -> 11 vector instructions per pixel here.
-                    uint32_t flags = (ec & (ep | en) & gp) << (32 - K);      // pixel 0 on top (sieve_bits2's bit order)
+                    uint32_t flags = (ec & (ep | en) & gp) << (32 - K);      // pixel 0 on top (sieve_bits4's bit order)
                     for_each_index(std::make_integer_sequence<int, K>(), [&](auto kc) __attribute__((always_inline)) {
                         constexpr int k = decltype(kc)::value;
-                        const bool upd = gated_greater(flags, Dc[k], dmax(best[k], m[k]));
+                        const bool upd = gated_greater(flags, Dc[k], dmax(best[k], Mc[k]));
                         best[k] = upd ? Dc[k] : best[k];
                         lvl[k] = upd ? code : lvl[k];
                         // statistics of |D_c| over the tested pixels, on the words of D_c (fabs is a source modifier).  Not
@@ -579,9 +591,6 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
                     // fixed-order DPP reduction inside the wave (total lands in lane 63), one slot per (level, wave)
                     if (!MST_VARIANT(2)) wave_reduce_min_sum(lmin, lsum);
                 }
-            } else {
-#pragma unroll
-                for (int k = 0; k < K; ++k) m[k] = 0.0;
             }
             if (kl >= 4) {
                 if (lane == 63) {
@@ -594,10 +603,7 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
             ec = en;
             gp = gn;
 #pragma unroll
-            for (int k = 0; k < K; ++k) {
-                Mc[k] = m[k];
-                Dc[k] = d[k];
-            }
+            for (int k = 0; k < K; ++k) Dc[k] = d[k];
 #ifdef MST_PROFILE
             MST_STAMP(tr_lvl, 6)
 #endif
@@ -1240,6 +1246,10 @@ static int enqueue_launch(const Launch &a, char *image, hipStream_t s) {
     const int blk0 = staged && a.stage > 0 ? a.cuts[a.stage - 1] : 0, blk1 = staged && a.stage < a.n_cuts ? a.cuts[a.stage] : B;
     if (it1 > it0) {
         const int lrc = with_tile(a.max_radius, a.fma, [&](auto tag) {
+            // the kernel's radius switch has no path for a radius above its tile's RMAX (blur_dispatch)
+            if (a.max_radius > decltype(tag)::type::RMAX)
+                return mst::fail(MST_E_ARG, "blur radius %d: the launch's tile is built for radii <= %d", a.max_radius,
+                                 (int)decltype(tag)::type::RMAX);
             return launch_scale_space<typename decltype(tag)::type, BAND>(
                 a.c, a.nz, src, a.CH, d_lv, a.found, a.found_cap, a.found_count, partial + (size_t)it0 * nt * 2, nt, a.skip_empty,
                 d_items + it0, it1 - it0, s);

@@ -19,7 +19,13 @@ The second form reads a BUILT library (llvm-objdump, default mustache_amd/libmus
 includes mst_fir.h -- the fused kernel at every tile and source, the difference kernel -- and per radius case and pass (axis-0
 main items, axis-0 leftover pieces, axis-1), the count of each LDS read opcode and the VALU that is not tap arithmetic.  A
 window load that is not a ds_read_b128 runs at half the LDS rate (mst_fir.h, fir_chunk); tests/test_window_load_kinds.py
-asserts through window_loads() that no pass holds a ds_read2_b64."""
+asserts through window_loads() that no pass holds a ds_read2_b64.
+
+    python scripts/isa_census.py --state-copies [library.so]
+
+The third form reads a built library too and prints, for every instantiation of the fused kernel, the register-pair copies one
+thread issues per level and how many of them sit behind the radius switch; tests/test_level_state_copies.py asserts through
+state_copies() that only the two renames of D and G are left."""
 import collections
 import os
 import re
@@ -259,7 +265,61 @@ def window_loads_report(lib):
         print("  all passes: " + ", ".join("%d %s" % (tot[op], op) for op in ops))
 
 
+# ---- register-pair copies of the level loop, from a BUILT library (tests/test_level_state_copies.py) -------------------------
+def is_pair_copy(op, text):
+    """v_mov_b64 from a VGPR pair (not a constant load): a rename of per-pixel state, or a merge copy behind a join"""
+    return op.startswith("v_mov_b64") and re.search(r",\s*v\[", text) is not None
+
+
+def branch_edges(ins):
+    """[(address, target)] of every branch of disassemble()'s instruction list; the long form (s_getpc_b64, s_add_u32, s_addc_u32,
+    s_setpc_b64: the wide tile's kernel is longer than a 16-bit branch offset reaches) included"""
+    out = []
+    for i, (addr, op, text, target) in enumerate(ins):
+        if target is not None:
+            out.append((addr, target))
+        elif op.startswith("s_setpc_b64") and i >= 3 and ins[i - 3][1].startswith("s_getpc_b64") and \
+                ins[i - 2][1].startswith("s_add_u32") and ins[i - 1][1].startswith("s_addc_u32"):
+            off = ((int(ins[i - 1][2].split(",")[-1], 0) & 0xffffffff) << 32) | (int(ins[i - 2][2].split(",")[-1], 0) & 0xffffffff)
+            out.append((addr, ins[i - 3][0] + 4 + (off - (1 << 64) if off >= 1 << 63 else off)))
+    return out
+
+
+def state_copies(lib=LIB):
+    """[(title, K, copies per level, copies behind the radius switch)] for every scale_space_kernel of the library.
+    The level loop is the innermost loop around the radius cases: of the backward branches that enclose every tap product, those
+    with the highest target.  Copies per level: the register-pair copies inside it (none lies in a radius case) -- with one
+    static register assignment the floor is 2 K, one rename each of D and G (Dc = d, gprev = g).  Behind the switch: the copies
+    between the last tap product and the first DoG subtraction, where the compiler merges the cases' accumulators into g if
+    some path through the switch runs no case."""
+    is_tap = lambda op: op.startswith(("v_mul_f64", "v_fma_f64", "v_fmac_f64"))
+    res = []
+    for name, ins in sorted(disassemble(lib).items(), key=lambda kv: kernel_title(kv[0])):
+        if "scale_space_kernel" not in name:
+            continue
+        taps = [a for a, op, _, _ in ins if is_tap(op)]
+        around = [(a, t) for a, t in branch_edges(ins) if t <= taps[0] and a >= taps[-1]]
+        head = max(t for _, t in around)
+        end = max(a for a, t in around if t == head)
+        dog = next(a for a, op, text, _ in ins if a > taps[-1] and op.startswith("v_add_f64") and ", -v[" in text)
+        copies = [a for a, op, text, _ in ins if is_pair_copy(op, text)]
+        res.append((kernel_title(name), int(TILE.search(name).group(4)), sum(head <= a <= end for a in copies),
+                    sum(taps[-1] < a < dog for a in copies)))
+    return res
+
+
+def state_copies_report(lib):
+    print("register-pair copies (v_mov_b64 from a VGPR pair) of the fused kernel's level loop, from %s" % os.path.relpath(lib, ROOT))
+    print("  per thread and level | behind the radius switch (of those)")
+    for title, K, per_level, behind in state_copies(lib):
+        print("  %-55s K = %d   %3d | %d" % (title, K, per_level, behind))
+
+
 def main():
+    if "--state-copies" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--state-copies"]
+        state_copies_report(os.path.abspath(rest[0]) if rest else LIB)
+        return
     if "--window-loads" in sys.argv[1:]:
         rest = [a for a in sys.argv[1:] if a != "--window-loads"]
         window_loads_report(os.path.abspath(rest[0]) if rest else LIB)
@@ -314,6 +374,10 @@ def main():
         if common[cat]:
             print("  %-20s %5d" % (cat, common[cat]))
     print("  %-20s %5d" % ("VALU total", sum(common[c] for c in VALU)))
+    # pure copies: per-pixel state renamed once per level (Dc = d, gprev = g: 2 K with one static register assignment) and
+    # whatever else the compiler copies -- merged accumulators behind the radius switch, a second set of maxima
+    print("  %-20s %5d   (v_mov_b64 from a VGPR pair, of the v_mov_b64 above; floor 16 = one rename each of D and G)"
+          % ("state copies", sum(1 for lab, ann, ins in in_loop for op, text in ins if is_pair_copy(op, text))))
     print()
     # the blocks behind the level's second barrier (the last s_barrier of the loop in layout order): 3 x 3 maxima, sieve bits,
     # sieve, statistics, wave reduction, state renames.  A wave that owns a tested pixel runs, at a tested level (kl >= 4),

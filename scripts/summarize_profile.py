@@ -93,7 +93,9 @@ for name, counts, px in (("dense, tiles shared (`value`)", rf.get("work_items_pe
 r0 = ss[0]
 try:
     import kernel_resources
-    res = [k for k in kernel_resources.kernels(os.path.join(ROOT, "mustache_amd", "libmustache_hip.so"))]
+    # the library the profiled run loaded: MUSTACHE_HIP_LIB when the session profiles another build (a parent) beside the product
+    res = [k for k in kernel_resources.kernels(os.environ.get("MUSTACHE_HIP_LIB") or
+                                               os.path.join(ROOT, "mustache_amd", "libmustache_hip.so"))]
     lines += ["", "## Registers / LDS / spills from the code object (`scripts/kernel_resources.py`)", "",
               "| kernel | VGPR | AGPR | SGPR | SGPR spills | VGPR spills | scratch B/lane |", "|---|---|---|---|---|---|---|"]
     for k in res:
