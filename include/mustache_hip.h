@@ -658,6 +658,21 @@ MST_STABLE int mst_pileup_reduce_segmented(const double *obs, const double *oe, 
                                            const int64_t *loop_off, int32_t P, int32_t w, double *agg, void *workspace,
                                            uint64_t workspace_bytes, void *stream);
 
+/* ---- every loop of a pile-up against its local background (rules: "Enrichment" in mustache_amd/pileup.py;
+ * tests/pileup_enrich_reference.py restates them).  Added without a change of MST_ABI_REVISION, as mst_thin_counts was.
+ * obs: dev f64 [L][2w+1][2w+1], the windows mst_pileup_windows / mst_pileup_trans_windows / mst_pileup_trans_batch wrote.  Cell
+ * (a, b), |a|, |b| <= w, is window[a + w][b + w]; the peak box is |a| <= p and |b| <= p; the neighbourhoods, in this order:
+ *   DONUT  outside the peak box, a != 0 and b != 0          LL  1 <= a <= w and -w <= b <= -1, outside the peak box
+ *   H      |a| <= 1 and p < |b| <= w                        V   |b| <= 1 and p < |a| <= w
+ * A cell counts when its obs is not NaN and its expected value e is not 0.  cis: expected dev f64 [D + 1], xs, ys dev int64 [L]
+ * and e = expected[|(ys + b) - (xs + a)|], 0 when that distance is above D; e_loop is NULL.  trans: e_loop dev f64 [L] and e =
+ * e_loop[l]; expected, xs, ys are NULL and D is ignored.  Exactly one of expected and e_loop is given.
+ * sums dev f64 [L][4][3] = the sum of obs, the sum of e and the number of the counted cells.  The order of every sum depends
+ * only on the cell index: a loop's twelve numbers have the same bits in every run, at any position and for any L.  No
+ * workspace, no atomics.  0 <= p < w <= 64, anything else is MST_E_ARG; L = 0 launches nothing. */
+MST_STABLE int mst_pileup_enrich(const double *obs, int64_t L, int32_t w, int32_t p, const double *expected, int32_t D,
+                                 const int64_t *xs, const int64_t *ys, const double *e_loop, double *sums, void *stream);
+
 /* ---- read pairs -> pixels (rules: mustache_amd/pairs.py; tests/pairs_reference.py restates them).  Added without a change
  * of MST_ABI_REVISION, as mst_balance_apply_pairs was: a library from before the addition is refused by its missing symbols. */
 /* One pass over the rows (pos1, pos2: dev int32 [n_rows]) of one chromosome.  A row is dropped when a position is < 1 or

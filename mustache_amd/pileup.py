@@ -76,6 +76,32 @@ Device work (mustache_amd/csrc/mst_pileup_trans_batch.hip): mst_pileup_trans_bat
 five launches -- a record whose v' is not > 0 is skipped in the pass, so the balanced records go in without a compaction --
 and mst_pileup_reduce_segmented the reduce for P pairs in two; every pair's values have the bits the single-pair entry points
 give on that pair alone.
+
+Enrichment (`--enrich [--peak P] [--min-enrichment T]`, `peak=P` on pileup() / pileup_band() / pileup_trans_records() /
+pileup_trans_batch(); tests/pileup_enrich_reference.py restates the rules).  Every used loop against its own local background,
+HiCCUPS's four neighbourhoods, in all three modes above.  Without the switch (`peak=None`) nothing is launched and nothing changes.
+  * Parameters: w, the window half-width above, and the peak half-width p, 0 <= p < w (default 2).
+  * Cell (a, b), |a|, |b| <= w, is the pixel (x + a, y + b) as above.  The peak box is |a| <= p and |b| <= p.  The
+    neighbourhoods, in the fixed order DONUT, LL, H, V:
+      DONUT  outside the peak box, a != 0 and b != 0;
+      LL     1 <= a <= w and -w <= b <= -1, outside the peak box (the side nearer the diagonal, as the LL corner);
+      H      |a| <= 1 and p < |b| <= w;
+      V      |b| <= 1 and p < |a| <= w.
+  * A cell counts when its obs is not NaN and its expected value e is not 0.  cis: e = E[|(y + b) - (x + a)|], and that distance
+    must be <= D.  trans: e is the pair's scalar E.
+  * Per loop and neighbourhood N, over the counted cells: S_o = sum obs, S_e = sum e, cnt = their number.
+    EXP_N = E_centre * S_o / S_e (E_centre = E[y - x], or the pair's E), NaN when cnt = 0, S_e = 0 or the obs centre is NaN.
+    FE_N = obs centre / EXP_N, NaN when EXP_N is 0 or NaN.  FE_MIN = the smallest of the four, NaN when any of them is NaN.
+  * The aggregate, on the host, per neighbourhood: apa_oe[w, w] / mean of apa_oe over the neighbourhood's non-NaN cells (NaN when
+    there is none or the mean is 0), for every chromosome or pair and for the genome-wide pile-up.
+  * Files: PREFIX.enrich.tsv (each row as read, then STATUS OBS_CENTER E_CENTER EXP_* FE_* FE_MIN; NaN for a row that is not
+    `used`), PREFIX.enrich.stats.tsv (one line per chromosome or pair and `all`: the aggregate's four ratios), and with
+    --min-enrichment T PREFIX.enriched.tsv: the input's header and the unchanged lines of the `used` rows with FE_MIN >= T (NaN
+    fails), a loop list the tools read.  The four files above stay byte for byte what they are without --enrich.
+  * Refused, one `Error:` line before anything is read: --peak or --min-enrichment without --enrich; P >= w (or P < 0).
+  * Not done: a Poisson p-value (the band holds balanced values, not counts); widening w where a neighbourhood is sparse.
+Device work (mustache_amd/csrc/mst_pileup_enrich.hip): mst_pileup_enrich, one wave per loop over the window of obs that is already
+resident, the twelve sums per loop; they come back in the one concatenated copy each mode waits for.  The ratios are NumPy's.
 """
 import argparse
 import math
@@ -90,6 +116,11 @@ METRICS = ("P2LL", "P2UL", "P2UR", "P2LR", "ZscoreLL", "P2M")
 STATS_HEADER = "CHR\tROWS_IN\tLOOPS_USED\t" + "\t".join(METRICS) + "\tOE_P2LL\n"
 LOOP_COLUMNS = ("STATUS", "OBS_CENTER", "OE_CENTER", "P2LL")
 DEFAULT_HEADER = "BIN1_CHR\tBIN1_START\tBIN1_END\tBIN2_CHROMOSOME\tBIN2_START\tBIN2_END\tFDR\tDETECTION_SCALE"
+NEIGHBOURHOODS = ("DONUT", "LL", "H", "V")
+DEFAULT_PEAK = 2
+ENRICH_COLUMNS = ("STATUS", "OBS_CENTER", "E_CENTER") + tuple("EXP_" + n for n in NEIGHBOURHOODS) \
+    + tuple("FE_" + n for n in NEIGHBOURHOODS) + ("FE_MIN",)
+ENRICH_STATS_HEADER = "CHR\tLOOPS_USED\t" + "\t".join("OE_P2" + n for n in NEIGHBOURHOODS) + "\n"
 
 
 class PileupError(ValueError):
@@ -102,6 +133,12 @@ def check_window(w, q):
                           % (w, MAX_W, (2 * MAX_W + 1) ** 2))
     if not 1 <= int(q) <= 2 * int(w) + 1:
         raise PileupError("corner size q = %d is outside 1 .. 2w + 1 = %d" % (q, 2 * int(w) + 1))
+
+
+def check_peak(w, p):
+    if not 0 <= int(p) < int(w):
+        raise PileupError("peak half-width p = %d is outside 0 .. w - 1 = %d: the neighbourhoods lie between the peak box and "
+                          "the window's edge" % (p, int(w) - 1))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -133,6 +170,78 @@ def metrics(M, w, q):
         rest = np.delete(M.reshape(-1), w * (2 * w + 1) + w)
         out["P2M"] = float(c / rest.mean()) if rest.size else math.nan
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# enrichment of every loop over its local background (host; the sums are the device's, mst_pileup_enrich)
+# ----------------------------------------------------------------------------------------------------------------------
+def enrichment_masks(w, p):
+    """bool [4, 2w+1, 2w+1]: the cells of DONUT, LL, H, V (rows = a index, columns = b index)."""
+    w, p = int(w), int(p)
+    check_peak(w, p)
+    off = np.arange(-w, w + 1)
+    a, b = off[:, None], off[None, :]
+    outside = (np.abs(a) > p) | (np.abs(b) > p)
+    return np.stack([outside & (a != 0) & (b != 0), outside & (a >= 1) & (b <= -1),
+                     (np.abs(a) <= 1) & (np.abs(b) > p), (np.abs(b) <= 1) & (np.abs(a) > p)])
+
+
+def enrich_windows(obs, w, p, E=None, xs=None, ys=None, e_loop=None):
+    """sums, a device float64 [L, 4, 3] tensor (S_o, S_e, cnt per neighbourhood), of the windows `obs` (device float64
+    [L, 2w+1, 2w+1]).  cis: E (device float64 [D + 1]) with xs, ys (device int64 [L]); trans: e_loop (device float64 [L]).
+    L = 0 launches nothing."""
+    import torch
+    from . import _lib
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    lib = require_gpu()
+    L = int(obs.shape[0])
+    cis = E is not None
+    with torch.cuda.device(obs.device):
+        sums = torch.empty((L, 4, 3), dtype=torch.float64, device=obs.device)
+        _lib.check(lib.mst_pileup_enrich(_ptr(obs) if L else None, L, int(w), int(p), _ptr(E) if cis else None,
+                                         int(E.numel()) - 1 if cis else 0, _ptr(xs) if cis and L else None,
+                                         _ptr(ys) if cis and L else None, None if cis else (_ptr(e_loop) if L else None),
+                                         _ptr(sums) if L else None, _stream()))
+    return sums
+
+
+def enrichment(sums, centre_obs, centre_e):
+    """(EXP [L, 4], FE [L, 4], FE_MIN [L]) of the sums [L, 4, 3] mst_pileup_enrich wrote, each loop's obs centre and its E_centre."""
+    sums = np.asarray(sums, np.float64).reshape(-1, 4, 3)
+    so, se, cnt = np.ascontiguousarray(sums.transpose(2, 1, 0))          # each [4, L] with unit stride: a third of the time
+    c = np.asarray(centre_obs, np.float64).reshape(1, -1)
+    e = np.asarray(centre_e, np.float64).reshape(1, -1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        exp = e * so / se
+        exp[(cnt == 0) | (se == 0) | np.isnan(c)] = np.nan
+        fe = c / exp                                     # a NaN EXP hands itself on
+        fe[exp == 0] = np.nan
+    fe_min = np.minimum(np.minimum(fe[0], fe[1]), np.minimum(fe[2], fe[3]))          # np.minimum hands a NaN on
+    return exp.T, fe.T, fe_min
+
+
+def aggregate_enrichment(apa_oe, w, p):
+    """float64 [4]: apa_oe[w, w] / mean of apa_oe over each neighbourhood's non-NaN cells; NaN when there is none or the mean is 0."""
+    M = np.asarray(apa_oe, np.float64)
+    out = np.full(4, np.nan)
+    for k, mask in enumerate(enrichment_masks(w, p)):
+        cells = M[mask]
+        cells = cells[~np.isnan(cells)]
+        if cells.size and cells.mean() != 0:
+            out[k] = M[int(w), int(w)] / cells.mean()
+    return out
+
+
+def _peak_kw(peak):
+    """the keyword a driver hands on: a run without a peak makes the call it has always made"""
+    return {} if peak is None else {"peak": peak}
+
+
+def _enrich_result(sums, centre_obs, centre_e, apa_oe, w, p):
+    """the keys a pile-up dict gains under `peak`"""
+    exp, fe, fe_min = enrichment(sums, centre_obs, centre_e)
+    return {"center_e": np.asarray(centre_e, np.float64), "enrich_sums": np.asarray(sums, np.float64).reshape(-1, 4, 3),
+            "enrich_exp": exp, "enrich_fe": fe, "fe_min": fe_min, "enrich_agg": aggregate_enrichment(apa_oe, w, p)}
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -194,30 +303,37 @@ def reduce(obs, oe, order, w, ws):
     return agg
 
 
-def _empty_result(w, q):
+def _empty_result(w, q, peak=None):
     S = 2 * w + 1
     z = np.zeros((S, S))
     M = np.full((S, S), np.nan)
+    if peak is not None:
+        return dict(_empty_result(w, q), **_enrich_result(np.zeros((0, 4, 3)), np.zeros(0), np.zeros(0), M, w, peak))
     return {"valid": None, "expected": None, "obs": None, "oe": None, "sum_obs": z, "count_obs": z.copy(), "sum_oe": z.copy(),
             "count_oe": z.copy(), "apa": M, "apa_oe": M.copy(), "center_obs": np.zeros(0), "center_oe": np.zeros(0),
             "p2ll": np.zeros(0), "metrics": metrics(M, w, q), "metrics_oe": metrics(M, w, q)}
 
 
-def pileup_band(band, n, D, xs, ys, w=10, q=6):
+def pileup_band(band, n, D, xs, ys, w=10, q=6, peak=None):
     """The pile-up of one chromosome's raw band (device float64 [rows >= D + 1, n]) around the loops (xs, ys) (bins, host
     arrays or tensors, y - x + 2w <= D).  Returns a dict: "valid", "expected", "obs", "oe" (device tensors), "sum_obs",
     "count_obs", "sum_oe", "count_oe", "apa" (mean obs), "apa_oe" (host [2w+1, 2w+1]), "center_obs", "center_oe", "p2ll"
-    (host [L], input order), "metrics" and "metrics_oe" (dicts of METRICS).  L = 0 returns empty aggregates without a launch."""
+    (host [L], input order), "metrics" and "metrics_oe" (dicts of METRICS).  L = 0 returns empty aggregates without a launch.
+    peak=p adds the enrichment of every loop (the module docstring has the rules): "center_e" (E[y - x], host [L]),
+    "enrich_sums" [L, 4, 3], "enrich_exp", "enrich_fe" [L, 4], "fe_min" [L] and "enrich_agg" [4], from one more launch inside the
+    same host wait."""
     import torch
     w, q = int(w), int(q)
     check_window(w, q)
+    if peak is not None:
+        check_peak(w, peak)
     xs = np.asarray(xs.cpu() if isinstance(xs, torch.Tensor) else xs, np.int64).reshape(-1)
     ys = np.asarray(ys.cpu() if isinstance(ys, torch.Tensor) else ys, np.int64).reshape(-1)
     if len(xs) != len(ys):
         raise PileupError("xs and ys differ in length (%d, %d)" % (len(xs), len(ys)))
     L, S = len(xs), 2 * w + 1
     if L == 0:
-        return _empty_result(w, q)
+        return _empty_result(w, q, peak)
     from ._lib import require_gpu
     lib = require_gpu()
     dev = band.device
@@ -229,25 +345,34 @@ def pileup_band(band, n, D, xs, ys, w=10, q=6):
         obs, oe, st = windows(band, n, D, E, xd, yd, w, q)
         order = torch.from_numpy(np.lexsort((ys, xs)).astype(np.int32)).to(dev, non_blocking=True)
         agg = reduce(obs, oe, order, w, ws)
-        host = torch.cat([agg.view(-1), st.view(-1)]).cpu().numpy()       # the one wait
-    agg_h, st_h = host[:4 * S * S].reshape(4, S, S), host[4 * S * S:].reshape(L, 3)
+        parts = [agg.view(-1), st.view(-1)]
+        if peak is not None:
+            parts += [enrich_windows(obs, w, peak, E=E, xs=xd, ys=yd).view(-1), E[yd - xd]]
+        host = torch.cat(parts).cpu().numpy()                             # the one wait
+    agg_h, st_h = host[:4 * S * S].reshape(4, S, S), host[4 * S * S:4 * S * S + 3 * L].reshape(L, 3)
     apa, apa_oe = mean_map(agg_h[0], agg_h[1]), mean_map(agg_h[2], agg_h[3])
-    return {"valid": valid, "expected": E, "obs": obs, "oe": oe, "sum_obs": agg_h[0], "count_obs": agg_h[1],
-            "sum_oe": agg_h[2], "count_oe": agg_h[3], "apa": apa, "apa_oe": apa_oe, "center_obs": st_h[:, 0].copy(),
-            "center_oe": st_h[:, 1].copy(), "p2ll": st_h[:, 2].copy(), "metrics": metrics(apa, w, q),
-            "metrics_oe": metrics(apa_oe, w, q)}
+    out = {"valid": valid, "expected": E, "obs": obs, "oe": oe, "sum_obs": agg_h[0], "count_obs": agg_h[1],
+           "sum_oe": agg_h[2], "count_oe": agg_h[3], "apa": apa, "apa_oe": apa_oe, "center_obs": st_h[:, 0].copy(),
+           "center_oe": st_h[:, 1].copy(), "p2ll": st_h[:, 2].copy(), "metrics": metrics(apa, w, q),
+           "metrics_oe": metrics(apa_oe, w, q)}
+    if peak is not None:
+        out.update(_enrich_result(host[-13 * L:-L], out["center_obs"], host[-L:], apa_oe, w, peak))
+    return out
 
 
-def pileup_trans_records(x, y, v, n1, n2, xs, ys, w=10, q=6):
+def pileup_trans_records(x, y, v, n1, n2, xs, ys, w=10, q=6, peak=None):
     """The pile-up of one inter-chromosomal pair's records (x = bins of A, y = bins of B, v > 0; host arrays or device tensors)
     on the n1 x n2 map around the loops (xs, ys) (bins of A, bins of B).  Returns pileup_band's dict with "expected" the
     scalar E (a float) and "valid" the pair (rows uint8 [n1], columns uint8 [n2]) of device tensors.  L = 0 still finds the
-    valid flags and E; N = 0 gives E = 0.  One host wait."""
+    valid flags and E; N = 0 gives E = 0.  One host wait.  peak=p adds pileup_band's enrichment keys, every cell's e and E_centre
+    being the scalar E."""
     import torch
     from . import _lib
     from ._lib import ptr as _ptr, stream as _stream, require_gpu
     w, q, n1, n2 = int(w), int(q), int(n1), int(n2)
     check_window(w, q)
+    if peak is not None:
+        check_peak(w, peak)
     xs = np.asarray(xs.cpu() if isinstance(xs, torch.Tensor) else xs, np.int64).reshape(-1)
     ys = np.asarray(ys.cpu() if isinstance(ys, torch.Tensor) else ys, np.int64).reshape(-1)
     if len(xs) != len(ys):
@@ -279,13 +404,19 @@ def pileup_trans_records(x, y, v, n1, n2, xs, ys, w=10, q=6):
                                                 _ptr(st) if L else None, _ptr(ws), ws.numel(), _stream()))
         order = torch.from_numpy(np.lexsort((ys, xs)).astype(np.int32)).to(dev, non_blocking=True)
         agg = reduce(obs, oe, order, w, ws)
-        host = torch.cat([agg.view(-1), st.view(-1), E]).cpu().numpy()    # the one wait
-    agg_h, st_h = host[:4 * S * S].reshape(4, S, S), host[4 * S * S:-1].reshape(L, 3)
+        parts = [agg.view(-1), st.view(-1), E]
+        if peak is not None:
+            parts.insert(2, enrich_windows(obs, w, peak, e_loop=E.expand(L).contiguous()).view(-1))
+        host = torch.cat(parts).cpu().numpy()                             # the one wait
+    agg_h, st_h = host[:4 * S * S].reshape(4, S, S), host[4 * S * S:4 * S * S + 3 * L].reshape(L, 3)
     apa, apa_oe = mean_map(agg_h[0], agg_h[1]), mean_map(agg_h[2], agg_h[3])
-    return {"valid": (rows, cols), "expected": float(host[-1]), "obs": obs, "oe": oe, "sum_obs": agg_h[0], "count_obs": agg_h[1],
-            "sum_oe": agg_h[2], "count_oe": agg_h[3], "apa": apa, "apa_oe": apa_oe, "center_obs": st_h[:, 0].copy(),
-            "center_oe": st_h[:, 1].copy(), "p2ll": st_h[:, 2].copy(), "metrics": metrics(apa, w, q),
-            "metrics_oe": metrics(apa_oe, w, q)}
+    out = {"valid": (rows, cols), "expected": float(host[-1]), "obs": obs, "oe": oe, "sum_obs": agg_h[0], "count_obs": agg_h[1],
+           "sum_oe": agg_h[2], "count_oe": agg_h[3], "apa": apa, "apa_oe": apa_oe, "center_obs": st_h[:, 0].copy(),
+           "center_oe": st_h[:, 1].copy(), "p2ll": st_h[:, 2].copy(), "metrics": metrics(apa, w, q),
+           "metrics_oe": metrics(apa_oe, w, q)}
+    if peak is not None:
+        out.update(_enrich_result(host[-1 - 12 * L:-1], out["center_obs"], np.full(L, host[-1]), apa_oe, w, peak))
+    return out
 
 
 def _host_ptr(a):
@@ -294,19 +425,22 @@ def _host_ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
-def pileup_trans_batch(x, y, v, seg_off, dims, loops, w=10, q=6):
+def pileup_trans_batch(x, y, v, seg_off, dims, loops, w=10, q=6, peak=None):
     """pileup_trans_records for P inter-chromosomal pairs in shared launches (csrc/mst_pileup_trans_batch.hip).  x, y, v: the
     pairs' records concatenated (device int32 / int32 / float64, or host arrays; None when there is none), pair p owning
     [seg_off[p], seg_off[p + 1]) -- seg_off a HOST table of P + 1 entries; a record whose v is not > 0 is ignored, so the output of
     mst_balance_apply_pairs goes in unfiltered.  dims: [(n1, n2)] per pair; loops: [(xs, ys)] per pair (host arrays, bins of A
     and of B; either may be empty).  Returns one dict per pair with pileup_trans_records' keys -- "obs", "oe" and "valid" are
     views into the batch's device tensors -- and "kept", the records of the pair that counted.  Every value has the bits
-    pileup_trans_records gives on that pair's records with v > 0 alone.  One host wait for the whole batch."""
+    pileup_trans_records gives on that pair's records with v > 0 alone.  One host wait for the whole batch.  peak=p adds the
+    enrichment keys to every pair's dict: one launch over all the windows, each loop's e its own pair's E, gathered on the device."""
     import torch
     from . import _lib
     from ._lib import ptr as _ptr, stream as _stream, require_gpu
     w, q, P = int(w), int(q), len(dims)
     check_window(w, q)
+    if peak is not None:
+        check_peak(w, peak)
     if len(loops) != P:
         raise PileupError("dims and loops differ in length (%d, %d)" % (P, len(loops)))
     seg = np.ascontiguousarray(seg_off, np.int64).reshape(-1)
@@ -356,10 +490,15 @@ def pileup_trans_batch(x, y, v, seg_off, dims, loops, w=10, q=6):
             _stream()))
         _lib.check(lib.mst_pileup_reduce_segmented(_ptr(obs) if L else None, _ptr(oe) if L else None, _ptr(order_d) if L else None,
                                                    L, _host_ptr(loop_off), P, w, _ptr(agg), _ptr(ws), ws.numel(), _stream()))
-        host = torch.cat([agg.view(-1), st.view(-1), E, kept.view(torch.float64)]).cpu().numpy()      # the one wait
+        parts = [agg.view(-1), st.view(-1), E, kept.view(torch.float64)]
+        if peak is not None:                           # e_loop: the E of the pair each loop belongs to
+            pair_of = torch.from_numpy(np.repeat(np.arange(P, dtype=np.int64), np.diff(loop_off))).to(dev, non_blocking=True)
+            parts.insert(2, enrich_windows(obs, w, peak, e_loop=E[pair_of]).view(-1))
+        host = torch.cat(parts).cpu().numpy()                                                         # the one wait
     agg_h = host[:P * 4 * S * S].reshape(P, 4, S, S)
     st_h = host[P * 4 * S * S:P * 4 * S * S + 3 * L].reshape(L, 3)
     E_h, kept_h = host[-2 * P:-P], host[-P:].view(np.int64)
+    en_h = host[P * 4 * S * S + 3 * L:P * 4 * S * S + 15 * L].reshape(L, 4, 3) if peak is not None else None
     row_off = np.concatenate([[0], np.cumsum(n1)])
     col_off = np.concatenate([[0], np.cumsum(n2)])
     out = []
@@ -372,6 +511,8 @@ def pileup_trans_batch(x, y, v, seg_off, dims, loops, w=10, q=6):
                     "count_obs": a[1], "sum_oe": a[2], "count_oe": a[3], "apa": apa, "apa_oe": apa_oe,
                     "center_obs": st_h[l0:l1, 0].copy(), "center_oe": st_h[l0:l1, 1].copy(), "p2ll": st_h[l0:l1, 2].copy(),
                     "metrics": metrics(apa, w, q), "metrics_oe": metrics(apa_oe, w, q)})
+        if peak is not None:
+            out[-1].update(_enrich_result(en_h[l0:l1], out[-1]["center_obs"], np.full(l1 - l0, E_h[p]), apa_oe, w, peak))
     return out
 
 
@@ -509,14 +650,36 @@ def _read_band(f, chromosome, res, D, norm=False, bias=False, balance=None, devi
 
 class PileupResult:
     """What pileup() returns: the table, per row `status`, `obs_center`, `oe_center`, `p2ll`; `chromosomes` = [(name, rows in,
-    loops used, pile-up dict)] in run order; `all` = the genome-wide pile-up dict (sums, counts, means, metrics)."""
+    loops used, pile-up dict)] in run order; `all` = the genome-wide pile-up dict (sums, counts, means, metrics).  Under `peak`
+    also per row `e_center`, `enrich_exp`, `enrich_fe` ([rows, 4]: DONUT, LL, H, V) and `fe_min`, NaN for a row that was not
+    used, and "enrich_agg" in every pile-up dict; without it they are None."""
 
-    def __init__(self, table, status, w, q):
-        self.table, self.status, self.w, self.q = table, status, w, q
+    def __init__(self, table, status, w, q, peak=None):
+        self.table, self.status, self.w, self.q, self.peak = table, status, w, q, peak
         L = len(table)
         self.obs_center, self.oe_center, self.p2ll = np.full(L, np.nan), np.full(L, np.nan), np.full(L, np.nan)
+        self.e_center = self.enrich_exp = self.enrich_fe = self.fe_min = None
+        if peak is not None:
+            self.e_center, self.fe_min = np.full(L, np.nan), np.full(L, np.nan)
+            self.enrich_exp, self.enrich_fe = np.full((L, 4), np.nan), np.full((L, 4), np.nan)
         self.chromosomes = []
         self.all = None
+
+    def take(self, rows, part):
+        """the per-loop values of pile-up dict `part` to the table rows `rows` (one per loop of `part`, in its order)"""
+        rows = np.asarray(rows, np.int64)
+        self.obs_center[rows], self.oe_center[rows], self.p2ll[rows] = part["center_obs"], part["center_oe"], part["p2ll"]
+        if self.peak is not None:
+            self.e_center[rows], self.fe_min[rows] = part["center_e"], part["fe_min"]
+            self.enrich_exp[rows], self.enrich_fe[rows] = part["enrich_exp"], part["enrich_fe"]
+
+    def total(self, tot):
+        """`all` from the four genome-wide sums and counts"""
+        apa, apa_oe = mean_map(tot[0], tot[1]), mean_map(tot[2], tot[3])
+        self.all = {"sum_obs": tot[0], "count_obs": tot[1], "sum_oe": tot[2], "count_oe": tot[3], "apa": apa, "apa_oe": apa_oe,
+                    "metrics": metrics(apa, self.w, self.q), "metrics_oe": metrics(apa_oe, self.w, self.q)}
+        if self.peak is not None:
+            self.all["enrich_agg"] = aggregate_enrichment(apa_oe, self.w, self.peak)
 
 
 def _read_pair(f, norm, A, B, res, device):
@@ -533,7 +696,7 @@ def _read_pair(f, norm, A, B, res, device):
         raise
 
 
-def _pileup_trans(f, table, res, chromosomes, norm, bias, balance, w, q, n_min, x_max, device, verbose):
+def _pileup_trans(f, table, res, chromosomes, norm, bias, balance, w, q, n_min, x_max, device, verbose, peak=None):
     """pileup() in trans mode: one pile-up per chromosome pair."""
     import torch
     from .request import balance_on_trans, trans_input
@@ -543,14 +706,14 @@ def _pileup_trans(f, table, res, chromosomes, norm, bias, balance, w, q, n_min, 
     if why:
         raise PileupError(why)
     status, a, b, pairs = classify(table, res, chromosomes, n_min, x_max, trans=True)
-    out = PileupResult(table, status, w, q)
+    out = PileupResult(table, status, w, q, peak)
     S = 2 * w + 1
     tot = [np.zeros((S, S)) for _ in range(4)]
     for A, B in pairs:
         pair = frozenset((_key(A), _key(B)))
         rows = [k for k in range(len(table)) if status[k] is None
                 and frozenset((_key(table.chr1[k]), _key(table.chr2[k]))) == pair]
-        part, used = _empty_result(w, q), []
+        part, used = _empty_result(w, q, peak), []
         got = _read_pair(f, norm, A, B, res, device)
         if got is None:
             for k in rows:
@@ -562,19 +725,16 @@ def _pileup_trans(f, table, res, chromosomes, norm, bias, balance, w, q, n_min, 
             for k in rows:
                 status[k] = "off_map" if a[k] >= n1 or b[k] >= n2 else "used"
             used = [k for k in rows if status[k] == "used"]
-            part = pileup_trans_records(x, y, v, n1, n2, a[used], b[used], w, q)
+            part = pileup_trans_records(x, y, v, n1, n2, a[used], b[used], w, q, **_peak_kw(peak))
             del x, y, v, got
-            for j, k in enumerate(used):
-                out.obs_center[k], out.oe_center[k], out.p2ll[k] = part["center_obs"][j], part["center_oe"][j], part["p2ll"][j]
+            out.take(used, part)
         part = {k_: v_ for k_, v_ in part.items() if k_ not in ("valid", "expected", "obs", "oe")}   # device arrays freed
         out.chromosomes.append(("%s,%s" % (A, B), len(rows), len(used), part))
         for t, name in zip(tot, ("sum_obs", "count_obs", "sum_oe", "count_oe")):
             t += part[name]                              # genome-wide: in the order the pairs ran
         if verbose:
             print("pile-up of the pair %s,%s: %d of %d rows used, P2M %r" % (A, B, len(used), len(rows), part["metrics"]["P2M"]))
-    apa, apa_oe = mean_map(tot[0], tot[1]), mean_map(tot[2], tot[3])
-    out.all = {"sum_obs": tot[0], "count_obs": tot[1], "sum_oe": tot[2], "count_oe": tot[3], "apa": apa, "apa_oe": apa_oe,
-               "metrics": metrics(apa, w, q), "metrics_oe": metrics(apa_oe, w, q)}
+    out.total(tot)
     return out
 
 
@@ -611,7 +771,7 @@ def _window_batches(loops_of, w, budget, names):
 
 
 def _pileup_trans_genome(f, table, res, chromosomes, norm, bias, balance, method, pixels, pairs_zero_based, w, q, n_min, x_max,
-                         device, verbose):
+                         device, verbose, peak=None):
     """pileup() in trans mode on the genome-balanced map (the module docstring has the rules): the genome read and balanced
     once, every pair's records balanced and piled up in shared launches, one host wait per batch."""
     from . import pairs as pairs_mod
@@ -628,7 +788,7 @@ def _pileup_trans_genome(f, table, res, chromosomes, norm, bias, balance, method
     if why:
         raise PileupError(why)
     status, a, b, pairs = classify(table, res, chromosomes, n_min, x_max, trans=True)
-    out = PileupResult(table, status, w, q)
+    out = PileupResult(table, status, w, q, peak)
     import torch
     try:
         gb = solve_genome(read_genome(f, res, pixels, device, pairs_zero_based, verbose), method)
@@ -656,7 +816,7 @@ def _pileup_trans_genome(f, table, res, chromosomes, norm, bias, balance, method
             status[k] = "off_map" if a[k] >= n1 or b[k] >= n2 else "used"
         used_of[p] = [k for k in rows if status[k] == "used"]
         live.append(p)
-    parts = [_empty_result(w, q) for _ in pairs]
+    parts = [_empty_result(w, q, peak) for _ in pairs]
     drop = ("valid", "expected", "obs", "oe", "kept")
     with torch.cuda.device(gb.device):
         budget = window_budget()
@@ -667,7 +827,8 @@ def _pileup_trans_genome(f, table, res, chromosomes, norm, bias, balance, method
                                                           max_records=APPLY_BATCH_RECORDS):
                 batch = mine[k0:k1]
                 dims = [(gb.bins[gb.index(pairs[p][0])], gb.bins[gb.index(pairs[p][1])]) for p in batch]
-                got = pileup_trans_batch(x, y, v, seg, dims, [(a[used_of[p]], b[used_of[p]]) for p in batch], w, q)
+                got = pileup_trans_batch(x, y, v, seg, dims, [(a[used_of[p]], b[used_of[p]]) for p in batch], w, q,
+                                         **_peak_kw(peak))
                 del x, y, v
                 for p, part in zip(batch, got):
                     if part["kept"] == 0:               # nothing of the pair survives the balancing: its result is discarded
@@ -675,9 +836,7 @@ def _pileup_trans_genome(f, table, res, chromosomes, norm, bias, balance, method
                             status[k] = "no_pair"
                         used_of[p] = []
                         continue
-                    for j, k in enumerate(used_of[p]):
-                        out.obs_center[k], out.oe_center[k], out.p2ll[k] = part["center_obs"][j], part["center_oe"][j], \
-                            part["p2ll"][j]
+                    out.take(used_of[p], part)
                     parts[p] = {k_: v_ for k_, v_ in part.items() if k_ not in drop}
                 del got
     S = 2 * w + 1
@@ -690,39 +849,42 @@ def _pileup_trans_genome(f, table, res, chromosomes, norm, bias, balance, method
         if verbose:
             print("pile-up of the pair %s,%s: %d of %d rows used, P2M %r" % (A, B, len(used_of[p]), len(rows_of[p]),
                                                                             part["metrics"]["P2M"]))
-    apa, apa_oe = mean_map(tot[0], tot[1]), mean_map(tot[2], tot[3])
-    out.all = {"sum_obs": tot[0], "count_obs": tot[1], "sum_oe": tot[2], "count_oe": tot[3], "apa": apa, "apa_oe": apa_oe,
-               "metrics": metrics(apa, w, q), "metrics_oe": metrics(apa_oe, w, q)}
+    out.total(tot)
     return out
 
 
 def pileup(f, loops, res, chromosomes=None, norm=False, bias=False, balance=None, w=10, q=6, n_min=None, x_max=None,
-           device=None, verbose=False, trans=False, balance_genome=None, balance_pixels="all", pairs_zero_based=False):
+           device=None, verbose=False, trans=False, balance_genome=None, balance_pixels="all", pairs_zero_based=False, peak=None):
     """Pile up map `f` around the loops of `loops` (a TSV path or a LoopTable) at resolution `res` (bp).  The reader
     arguments (`norm`, `bias`, `balance`) mean what they mean for the caller; `n_min` is in bins (None: 30), `x_max` in bp.
     trans=True piles up the inter-chromosomal rows instead, pair by pair (the module docstring has the rules); in that mode
     `chromosomes` of the result holds ("A,B", rows in, loops used, pile-up dict).  balance_genome="NEWTON" | "ICE" (with
     trans=True; balance_pixels "all" | "inter"; pairs_zero_based for a pairs file) piles the rows up on the genome-balanced map
-    of a raw `.hic` file or a `.pairs` / `.pairs.gz` file, every pair in shared launches.  Returns a PileupResult."""
+    of a raw `.hic` file or a `.pairs` / `.pairs.gz` file, every pair in shared launches.  peak=p (0 <= p < w) scores every
+    used loop against its local background in any of the three modes ("Enrichment" in the module docstring).  Returns a
+    PileupResult."""
     w, q, res = int(w), int(q), int(res)
     check_window(w, q)
+    if peak is not None:
+        peak = int(peak)
+        check_peak(w, peak)
     table = read_loops(loops) if isinstance(loops, (str, os.PathLike)) else loops
     if balance_genome is not None:
         if not trans:
             raise PileupError("--balance-genome is for inter-chromosomal pile-ups: give --trans (--balance balances one "
                               "chromosome's own map)")
         return _pileup_trans_genome(f, table, res, chromosomes, norm, bias, balance, balance_genome, balance_pixels,
-                                    pairs_zero_based, w, q, n_min, x_max, device, verbose)
+                                    pairs_zero_based, w, q, n_min, x_max, device, verbose, peak)
     if trans:
-        return _pileup_trans(f, table, res, chromosomes, norm, bias, balance, w, q, n_min, x_max, device, verbose)
+        return _pileup_trans(f, table, res, chromosomes, norm, bias, balance, w, q, n_min, x_max, device, verbose, peak)
     status, x, y, selected = classify(table, res, chromosomes, n_min, None if x_max is None else int(x_max) // res)
-    out = PileupResult(table, status, w, q)
+    out = PileupResult(table, status, w, q, peak)
     S = 2 * w + 1
     tot = [np.zeros((S, S)) for _ in range(4)]
     for chrom in selected:
         rows = [k for k in range(len(table)) if _key(table.chr1[k]) == _key(chrom) and status[k] != "trans"]
         cand = [k for k in rows if status[k] is None]
-        part = _empty_result(w, q)
+        part = _empty_result(w, q, peak)
         used = []
         if cand:
             D = int(max(y[k] - x[k] for k in cand)) + 2 * w
@@ -734,10 +896,9 @@ def pileup(f, loops, res, chromosomes=None, norm=False, bias=False, balance=None
                 for k in cand:
                     status[k] = "off_map" if y[k] >= n else "used"
                 used = [k for k in cand if status[k] == "used"]
-                part = pileup_band(band, n, D, x[used], y[used], w, q)
+                part = pileup_band(band, n, D, x[used], y[used], w, q, **_peak_kw(peak))
                 del band
-            for j, k in enumerate(used):
-                out.obs_center[k], out.oe_center[k], out.p2ll[k] = part["center_obs"][j], part["center_oe"][j], part["p2ll"][j]
+            out.take(used, part)
         part = {k_: v for k_, v in part.items() if k_ not in ("valid", "expected", "obs", "oe")}   # device arrays freed
         out.chromosomes.append((chrom, len(rows), len(used), part))
         for t, name in zip(tot, ("sum_obs", "count_obs", "sum_oe", "count_oe")):
@@ -745,9 +906,7 @@ def pileup(f, loops, res, chromosomes=None, norm=False, bias=False, balance=None
         if verbose:
             print("pile-up of chromosome %s: %d of %d rows used, P2LL %r" % (chrom, len(used), len(rows),
                                                                            part["metrics"]["P2LL"]))
-    apa, apa_oe = mean_map(tot[0], tot[1]), mean_map(tot[2], tot[3])
-    out.all = {"sum_obs": tot[0], "count_obs": tot[1], "sum_oe": tot[2], "count_oe": tot[3], "apa": apa, "apa_oe": apa_oe,
-               "metrics": metrics(apa, w, q), "metrics_oe": metrics(apa_oe, w, q)}
+    out.total(tot)
     return out
 
 
@@ -782,6 +941,32 @@ def write_outputs(prefix, res):
                          zip(res.table.lines, res.status, res.obs_center, res.oe_center, res.p2ll)))
 
 
+def write_enrichment(prefix, res, min_enrichment=None):
+    """PREFIX.enrich.tsv and PREFIX.enrich.stats.tsv of a PileupResult made with `peak`; with min_enrichment = T also
+    PREFIX.enriched.tsv, the `used` rows with FE_MIN >= T as a loop list (NaN fails).  Returns how many rows that list holds
+    (None without T)."""
+    if res.peak is None:
+        raise PileupError("this pile-up ran without a peak half-width: there is no enrichment to write")
+    with open(prefix + ".enrich.tsv", "w") as fh:
+        fh.write(res.table.header + "\t" + "\t".join(ENRICH_COLUMNS) + "\n")
+        for k, line in enumerate(res.table.lines):
+            vals = [res.obs_center[k], res.e_center[k]] + list(res.enrich_exp[k]) + list(res.enrich_fe[k]) + [res.fe_min[k]]
+            fh.write("%s\t%s\t%s\n" % (line, res.status[k], "\t".join(_r(v) for v in vals)))
+    with open(prefix + ".enrich.stats.tsv", "w") as fh:
+        fh.write(ENRICH_STATS_HEADER)
+        for name, _rows_in, used, part in res.chromosomes:
+            fh.write("%s\t%d\t%s\n" % (name, used, "\t".join(_r(v) for v in part["enrich_agg"])))
+        fh.write("all\t%d\t%s\n" % (sum(u for _, _, u, _ in res.chromosomes), "\t".join(_r(v) for v in res.all["enrich_agg"])))
+    if min_enrichment is None:
+        return None
+    with np.errstate(invalid="ignore"):
+        keep = [k for k in range(len(res.table)) if res.status[k] == "used" and res.fe_min[k] >= min_enrichment]
+    with open(prefix + ".enriched.tsv", "w") as fh:
+        fh.write(res.table.header + "\n")
+        fh.write("".join(res.table.lines[k] + "\n" for k in keep))
+    return len(keep)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # command line
 # ----------------------------------------------------------------------------------------------------------------------
@@ -808,7 +993,29 @@ def parse_args(args):
     add_arguments(p)                 # --balance-genome, --balance-pixels, --pairs-trans: with --trans, the genome-balanced map
     p.add_argument("--pairs-zero-based", dest="pairs_zero_based", action="store_true",
                    help="OPTIONAL: .pairs / .pairs.gz input only: positions are 0-based (bin = pos // res)")
+    p.add_argument("--enrich", dest="enrich", action="store_true",
+                   help="score every used loop against its donut, lower-left, horizontal and vertical neighbourhoods: "
+                        "PREFIX.enrich.tsv and PREFIX.enrich.stats.tsv")
+    p.add_argument("--peak", dest="peak", type=int, default=None, metavar="P",
+                   help="with --enrich: half-width of the peak box the neighbourhoods leave out (default %d, below -w)" % DEFAULT_PEAK)
+    p.add_argument("--min-enrichment", dest="min_enrichment", type=float, default=None, metavar="T",
+                   help="with --enrich: also write PREFIX.enriched.tsv, the used rows with FE_MIN >= T as a loop list")
     return p.parse_args(args)
+
+
+def enrich_request(args):
+    """What --enrich / --peak / --min-enrichment ask: the peak half-width, None for a run without them; PileupError with the
+    text of the `Error:` line for a combination that cannot be honoured.  Reads nothing and touches no GPU."""
+    if not args.enrich:
+        for flag, given in (("--peak", args.peak), ("--min-enrichment", args.min_enrichment)):
+            if given is not None:
+                raise PileupError("%s without --enrich: it belongs to the enrichment of every loop; give --enrich" % flag)
+        return None
+    peak = DEFAULT_PEAK if args.peak is None else args.peak
+    if not 0 <= peak < args.w:
+        raise PileupError("--peak %d with -w %d: the peak half-width P must be in 0 .. w - 1 (P >= w leaves no neighbourhood)"
+                          % (peak, args.w))
+    return peak
 
 
 def genome_request(args, f, world):
@@ -868,6 +1075,7 @@ def main(argv=None):
         return
     try:
         genome = genome_request(args, f, world)
+        peak = enrich_request(args)
     except PileupError as e:
         print("Error: %s" % e)
         return
@@ -892,7 +1100,7 @@ def main(argv=None):
         res_ = pileup(f, args.loops, res, chromosomes=args.chromosome, norm=args.norm_method, bias=args.biasfile or False,
                       balance=balance, w=args.w, q=args.q, n_min=args.n_min, x_max=x_max, verbose=True, trans=args.trans,
                       balance_genome=genome[0] if genome else None, balance_pixels=genome[1] if genome else "all",
-                      pairs_zero_based=args.pairs_zero_based)
+                      pairs_zero_based=args.pairs_zero_based, peak=peak)
     except (PileupError, TransError) as e:
         print("Error: %s" % e)
         return
@@ -905,6 +1113,11 @@ def main(argv=None):
     a = res_.all["metrics"]
     print("%d of %d loops piled up: P2LL %r, ZscoreLL %r, P2M %r -> %s.{apa,oe,stats,loops}.tsv"
           % (sum(u for _, _, u, _ in res_.chromosomes), len(res_.table), a["P2LL"], a["ZscoreLL"], a["P2M"], args.prefix))
+    if peak is not None:
+        kept = write_enrichment(args.prefix, res_, args.min_enrichment)
+        print("enrichment with peak half-width %d: aggregate over DONUT, LL, H, V %s -> %s.enrich.tsv, %s.enrich.stats.tsv%s"
+              % (peak, ", ".join(_r(v) for v in res_.all["enrich_agg"]), args.prefix, args.prefix,
+                 "" if kept is None else "; %d loops with FE_MIN >= %r -> %s.enriched.tsv" % (kept, args.min_enrichment, args.prefix)))
 
 
 if __name__ == "__main__":

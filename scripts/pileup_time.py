@@ -1,7 +1,8 @@
 """Pile-up (APA) timing on a synthetic chr1 @ 1 kb raw band built on the device (248 957 bins, D = 2 020) with 20 000
-loops, w = 10 (GPU box): device events around the three stages (valid + expected, windows, reduce) and the whole
-pileup_band call, median of --steps after --warmup; bytes moved from shapes and the expected pass's share of 6.3 TB/s.
-Prints one JSON line.  python scripts/pileup_time.py [--steps 20] [--warmup 3]"""
+loops, w = 10 (GPU box): device events around the three stages (valid + expected, windows, reduce), the enrichment of every loop
+(mst_pileup_enrich, peak half-width --peak) and the whole pileup_band call without and with `peak`, median of --steps after
+--warmup; bytes moved from shapes, the expected pass's share of 6.3 TB/s and the enrichment against its byte model (8 L (2w+1)^2
+bytes read).  Prints one JSON line.  python scripts/pileup_time.py [--steps 20] [--warmup 3] [--peak 2]"""
 import argparse
 import json
 import os
@@ -36,8 +37,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--loops", type=int, default=20000)
+    ap.add_argument("--peak", type=int, default=2)
     a = ap.parse_args()
-    n, D, w, q, L = 248957, 2020, 10, 6, a.loops
+    n, D, w, q, L, p = 248957, 2020, 10, 6, a.loops, a.peak
     dev = torch.device("cuda", 0)
     band = torch.empty((D + 2, n), dtype=torch.float64, device=dev)
     for i0 in range(0, n, 16384):
@@ -60,12 +62,16 @@ def main():
     t_exp = timed(lambda: pl.expected(band, n, D, ws), a.steps, a.warmup)
     t_win = timed(lambda: pl.windows(band, n, D, E, xd, yd, w, q), a.steps, a.warmup)
     t_red = timed(lambda: pl.reduce(obs, oe, order, w, ws), a.steps, a.warmup)
+    t_enr = timed(lambda: pl.enrich_windows(obs, w, p, E=E, xs=xd, ys=yd), a.steps, a.warmup)
     t_all = timed(lambda: pl.pileup_band(band, n, D, xs, ys, w, q), a.steps, a.warmup)
-    r = pl.pileup_band(band, n, D, xs, ys, w, q)
+    t_peak = timed(lambda: pl.pileup_band(band, n, D, xs, ys, w, q, peak=p), a.steps, a.warmup)
+    t_all2 = timed(lambda: pl.pileup_band(band, n, D, xs, ys, w, q), a.steps, a.warmup)       # again: the run-to-run spread
+    r = pl.pileup_band(band, n, D, xs, ys, w, q, peak=p)
     band_bytes = (D + 1) * n * 8
     exp_bytes = 2 * band_bytes                                    # the valid pass and the expected pass each read the band once
     win_bytes = L * S * S * 8 * 3                                 # band reads + obs and oe writes
     red_bytes = L * S * S * 8 * 2                                 # obs and oe read once
+    enr_bytes = L * S * S * 8                                     # obs read once (the 96 L bytes written are 0.03 of it)
     ms = lambda t: round(t[0], 4)                                 # noqa: E731
     print(json.dumps({
         "metric": "pileup_chr1_1kb_ms", "n": n, "D": D, "loops": L, "w": w, "steps": a.steps, "warmup": a.warmup,
@@ -76,7 +82,12 @@ def main():
         "expected_model_ms": round(exp_bytes / (HBM_TBS * 1e12) * 1e3, 4),
         "expected_share_of_6p3_TBs": round(exp_bytes / (t_exp[0] * 1e-3) / (HBM_TBS * 1e12), 4),
         "windows_TBs": round(win_bytes / (t_win[0] * 1e-3) / 1e12, 3), "reduce_TBs": round(red_bytes / (t_red[0] * 1e-3) / 1e12, 3),
+        "peak": p, "enrich_ms": ms(t_enr), "enrich_min_max_ms": [round(t_enr[1], 4), round(t_enr[2], 4)], "enrich_bytes": enr_bytes,
+        "enrich_model_ms": round(enr_bytes / (HBM_TBS * 1e12) * 1e3, 4), "enrich_TBs": round(enr_bytes / (t_enr[0] * 1e-3) / 1e12, 3),
+        "pileup_band_peak_ms": ms(t_peak), "pileup_band_peak_min_max_ms": [round(t_peak[1], 4), round(t_peak[2], 4)],
+        "pileup_band_again_ms": ms(t_all2), "pileup_band_again_min_max_ms": [round(t_all2[1], 4), round(t_all2[2], 4)],
         "P2LL": r["metrics"]["P2LL"], "valid_bins": int(valid.sum().item()),
+        "loops_scored": int((~np.isnan(r["fe_min"])).sum()), "enrich_agg": [float(v) for v in r["enrich_agg"]],
     }))
 
 
