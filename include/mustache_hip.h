@@ -673,6 +673,25 @@ MST_STABLE int mst_pileup_reduce_segmented(const double *obs, const double *oe, 
 MST_STABLE int mst_pileup_enrich(const double *obs, int64_t L, int32_t w, int32_t p, const double *expected, int32_t D,
                                  const int64_t *xs, const int64_t *ys, const double *e_loop, double *sums, void *stream);
 
+/* ---- one loop list piled up on two maps (rules: "Two maps" in mustache_amd/pileup.py; tests/pileup_compare_reference.py
+ * restates them).  Added without a change of MST_ABI_REVISION, as mst_pileup_enrich was.  oe1, oe2: dev f64 [L][2w+1][2w+1],
+ * the oe windows two pile-ups of the SAME L loops in the same order left on the device (mst_pileup_windows,
+ * mst_pileup_trans_windows).  A cell of loop l is shared when neither oe1[l] nor oe2[l] is NaN there. */
+/* sums dev f64 [L][4][3]: per loop and neighbourhood (DONUT, LL, H, V of mst_pileup_enrich, peak half-width p) over the shared
+ * cells of the neighbourhood: the sum of oe1, the sum of oe2, their number.  The order of every sum depends only on the cell
+ * index: a loop's twelve numbers have the same bits in every run, at any position and for any L.  No workspace, no atomics.
+ * 0 <= p < w <= 64, anything else is MST_E_ARG; so is a null oe1, oe2 or sums with L > 0; L = 0 launches nothing. */
+MST_STABLE int mst_pileup_compare(const double *oe1, const double *oe2, int64_t L, int32_t w, int32_t p, double *sums,
+                                  void *stream);
+/* agg dev f64 [3][(2w+1)^2] = per cell, over the windows order[0 .. L) (dev int32; the caller sorts the loops by (x, y)) that
+ * share the cell: the sum of oe1, the sum of oe2, their number.  Chunks of 512 and every addition in mst_pileup_reduce's order:
+ * where the NaN masks of oe1 and oe2 coincide, rows 0, 1, 2 have the bits of mst_pileup_reduce's sum of oe (row 2) on oe1, the same
+ * on oe2, and its count of oe (row 3).  An order entry outside 0 .. L-1 is skipped.  workspace: dev, 24 * ceil(L / 512) * (2w+1)^2 bytes -- a workspace that
+ * serves mst_pileup_reduce for (L, w) serves this call.  0 <= w <= 64, L < 2^31; L = 0 zeroes agg.  No float atomics:
+ * bit-identical from run to run and under any permutation of the loops the caller sorts. */
+MST_STABLE int mst_pileup_reduce_pair(const double *oe1, const double *oe2, const int32_t *order, int64_t L, int32_t w,
+                                      double *agg, void *workspace, uint64_t workspace_bytes, void *stream);
+
 /* ---- read pairs -> pixels (rules: mustache_amd/pairs.py; tests/pairs_reference.py restates them).  Added without a change
  * of MST_ABI_REVISION, as mst_balance_apply_pairs was: a library from before the addition is refused by its missing symbols. */
 /* One pass over the rows (pos1, pos2: dev int32 [n_rows]) of one chromosome.  A row is dropped when a position is < 1 or

@@ -102,6 +102,44 @@ HiCCUPS's four neighbourhoods, in all three modes above.  Without the switch (`p
   * Not done: a Poisson p-value (the band holds balanced values, not counts); widening w where a neighbourhood is sparse.
 Device work (mustache_amd/csrc/mst_pileup_enrich.hip): mst_pileup_enrich, one wave per loop over the window of obs that is already
 resident, the twelve sums per loop; they come back in the one concatenated copy each mode waits for.  The ratios are NumPy's.
+
+Two maps (`-f2 FILE [-b2 BIAS] [--peak P] [--min-lfc T]`, `pileup_pair()`, `pileup_band_pair()`, `pileup_trans_records_pair()`;
+tests/pileup_compare_reference.py restates the rules).  One loop list piled up on two maps f (sample 1) and f2 (sample 2) at one
+resolution with the same w, q and a peak half-width p (0 <= p < w, default 2), and what differs between them scored.  --balance,
+-norm, -n, -x, -ch and --trans apply to both maps alike; -b is the bias file of -f, -b2 that of -f2.  Without -f2 nothing
+changes and nothing is launched.
+  * Rows: classify() runs once.  Per chromosome D = max(y - x) + 2w over the kept rows as above, one D for both maps, and both
+    bands are read before either is piled up.  A row is `no_chrom` when either map lacks the chromosome, `off_map` when
+    y >= min(n_1, n_2), `used` otherwise: one status column, and a `used` row is used on both maps.  Trans, pair by pair:
+    `no_pair` when either file lacks the pair or has no record of it, `off_map` when a >= min(n1_1, n1_2) or b >= min(n2_1, n2_2).
+  * Per sample: each sample's pile-up dict is what pileup_band() (trans: pileup_trans_records()) gives on that map with the
+    jointly used loops, to the bit; the four files above are written per sample as PREFIX.1.* and PREFIX.2.*.
+  * Shared cell: a cell of loop l is shared when neither oe1[l] nor oe2[l] is NaN there.
+  * Per loop and neighbourhood N (DONUT, LL, H, V of enrichment_masks(w, p)), over the shared cells of N: S_1 = sum oe1, S_2 =
+    sum oe2, cnt.  R_sN = c_s / (S_s / cnt), c_s the loop's oe centre on sample s; NaN when cnt = 0, when c_s is NaN or when
+    S_s / cnt is 0.  LFC_N = log2(R_1N / R_2N), NaN unless both R are finite and > 0.  LFC: NaN when any LFC_N is NaN; the
+    smallest when all four are > 0, the largest when all four are < 0, 0.0 otherwise -- as FE_MIN, a loop counts as stronger on
+    one map only when every neighbourhood agrees.  Positive means stronger on -f.
+  * Paired aggregate: the used loops sorted by (x, y) (trans: (a, b)); per cell, over the loops where the cell is shared, T_1 =
+    sum oe1, T_2 = sum oe2, C = their number, chunks of 512 loops added in chunk order as mst_pileup_reduce does; genome-wide the
+    chromosome (or pair) partials are added in run order on the host.  M_s = T_s / C (NaN where C = 0); the differential map is
+    log2(M_1 / M_2), NaN unless both are > 0.  Per chromosome (or pair) and `all`: P2LL_s = metrics(M_s, w, q)["P2LL"], LFC_P2LL
+    = log2(P2LL_1 / P2LL_2) and AGG_LFC_N = log2(aggregate_enrichment(M_1, w, p)[N] / aggregate_enrichment(M_2, w, p)[N]), each
+    NaN unless both operands are finite and > 0.
+  * Files beside the eight per-sample ones: PREFIX.compare.tsv (each row as read, then STATUS OE_CENTER_1 OE_CENTER_2 R1_* R2_*
+    LFC_* LFC; NaN for a row that is not `used`), PREFIX.diff.tsv (the differential map, as write_matrix writes),
+    PREFIX.compare.stats.tsv (CHR LOOPS_USED P2LL_1 P2LL_2 LFC_P2LL AGG_LFC_*: one line per chromosome or pair, and `all`); with
+    --min-lfc T (finite, > 0) PREFIX.up1.tsv, the header and the unchanged lines of the used rows with LFC >= T, and
+    PREFIX.up2.tsv, those with LFC <= -T: loop lists the tools read.  NaN fails both.
+  * Refused, one `Error:` line before anything is read (compare_request): -b2 or --min-lfc without -f2; an -f2 or -b2 that does
+    not exist; --min-lfc not finite or <= 0; P outside 0 .. w - 1; -f2 with --enrich or --min-enrichment (per-loop enrichment of
+    each sample alone is what a single-map run is for); -f2 with --balance-genome, --balance-pixels or --pairs-trans (the
+    genome-balanced two-map pile-up is not built).
+  * Not claimed: a significance -- there are no counts; a minimum cnt; depth matching -- O/E and the ratio to the local
+    background remove the scale, not the noise.
+Device work (mustache_amd/csrc/mst_pileup_compare.hip) over the two stacks of oe windows the two pile-ups leave resident:
+mst_pileup_compare, one wave per loop, the twelve sums per loop under the joint mask; mst_pileup_reduce_pair, the reduce above
+with three accumulators.  One host wait per chromosome or pair beyond the two per-sample pile-ups' own: one concatenated copy.
 """
 import argparse
 import math
@@ -121,6 +159,9 @@ DEFAULT_PEAK = 2
 ENRICH_COLUMNS = ("STATUS", "OBS_CENTER", "E_CENTER") + tuple("EXP_" + n for n in NEIGHBOURHOODS) \
     + tuple("FE_" + n for n in NEIGHBOURHOODS) + ("FE_MIN",)
 ENRICH_STATS_HEADER = "CHR\tLOOPS_USED\t" + "\t".join("OE_P2" + n for n in NEIGHBOURHOODS) + "\n"
+COMPARE_COLUMNS = ("STATUS", "OE_CENTER_1", "OE_CENTER_2") + tuple("R1_" + n for n in NEIGHBOURHOODS) \
+    + tuple("R2_" + n for n in NEIGHBOURHOODS) + tuple("LFC_" + n for n in NEIGHBOURHOODS) + ("LFC",)
+COMPARE_STATS_HEADER = "CHR\tLOOPS_USED\tP2LL_1\tP2LL_2\tLFC_P2LL\t" + "\t".join("AGG_LFC_" + n for n in NEIGHBOURHOODS) + "\n"
 
 
 class PileupError(ValueError):
@@ -517,6 +558,187 @@ def pileup_trans_batch(x, y, v, seg_off, dims, loops, w=10, q=6, peak=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# one loop list on two maps ("Two maps" in the module docstring; the sums are the device's, csrc/mst_pileup_compare.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def compare_windows(oe1, oe2, w, p):
+    """sums, a device float64 [L, 4, 3] tensor (S_1, S_2, cnt per neighbourhood over the shared cells), of the two stacks of oe
+    windows (device float64 [L, 2w+1, 2w+1] each, the same loops in the same order).  L = 0 launches nothing."""
+    import torch
+    from . import _lib
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    lib = require_gpu()
+    L = int(oe1.shape[0])
+    if oe2 is not None and tuple(oe2.shape) != tuple(oe1.shape):
+        raise PileupError("the two window stacks differ in shape (%s, %s)" % (tuple(oe1.shape), tuple(oe2.shape)))
+    with torch.cuda.device(oe1.device):
+        sums = torch.empty((L, 4, 3), dtype=torch.float64, device=oe1.device)
+        _lib.check(lib.mst_pileup_compare(_ptr(oe1) if L else None, _ptr(oe2) if L and oe2 is not None else None, L, int(w),
+                                          int(p), _ptr(sums) if L else None, _stream()))
+    return sums
+
+
+def reduce_pair(oe1, oe2, order, w, ws):
+    """agg [3, (2w+1)^2] device tensor: T_1 = sum oe1, T_2 = sum oe2, C = the number, per cell over the windows in `order` (int32
+    device) that share the cell.  `ws`: a workspace that serves reduce() for these loops."""
+    import torch
+    from . import _lib
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    lib = require_gpu()
+    S, L = 2 * int(w) + 1, int(order.numel())
+    with torch.cuda.device(oe1.device):
+        agg = torch.empty((3, S * S), dtype=torch.float64, device=oe1.device)
+        _lib.check(lib.mst_pileup_reduce_pair(_ptr(oe1) if L else None, _ptr(oe2) if L else None, _ptr(order) if L else None, L,
+                                              int(w), _ptr(agg), _ptr(ws), ws.numel(), _stream()))
+    return agg
+
+
+def _log2_ratio(a, b):
+    """log2(a / b), NaN unless both are finite and > 0"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    with np.errstate(divide="ignore", over="ignore", under="ignore", invalid="ignore"):
+        ok = (a > 0) & (b > 0) & (a < np.inf) & (b < np.inf)          # a NaN fails every comparison
+        return np.where(ok, np.log2(a / b), np.nan)
+
+
+def compare_ratios(sums, c1, c2):
+    """(R1 [L, 4], R2 [L, 4], LFC_N [L, 4]) of the sums [L, 4, 3] mst_pileup_compare wrote and each loop's oe centre on the two
+    samples."""
+    sums = np.asarray(sums, np.float64).reshape(-1, 4, 3)
+    s1, s2, cnt = np.ascontiguousarray(sums.transpose(2, 1, 0))         # each [4, L] with unit stride, as in enrichment()
+    out = []
+    for s, c in ((s1, c1), (s2, c2)):
+        c = np.asarray(c, np.float64).reshape(1, -1)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            bg = s / cnt
+            r = c / bg                                   # a NaN centre hands itself on
+        r[(cnt == 0) | (bg == 0)] = np.nan
+        out.append(r)
+    return out[0].T, out[1].T, _log2_ratio(out[0], out[1]).T
+
+
+def lfc_summary(lfc_n):
+    """[L]: NaN when any of the four LFC_N is NaN; the smallest when all four are > 0, the largest when all are < 0, else 0.0."""
+    a = np.ascontiguousarray(np.asarray(lfc_n, np.float64).reshape(-1, 4).T)          # [4, L] with unit stride
+    with np.errstate(invalid="ignore"):
+        lo, hi = np.minimum(np.minimum(a[0], a[1]), np.minimum(a[2], a[3])), np.maximum(np.maximum(a[0], a[1]), np.maximum(a[2], a[3]))
+        out = np.where(lo > 0, lo, np.where(hi < 0, hi, 0.0))            # all four > 0: the smallest; all four < 0: the largest
+    out[np.isnan(lo)] = np.nan                                           # np.minimum hands a NaN on
+    return out
+
+
+def diff_map(T1, T2, C):
+    """log2(M_1 / M_2) with M_s = T_s / C (NaN where C = 0): NaN unless both means are > 0."""
+    return _log2_ratio(mean_map(T1, C), mean_map(T2, C))
+
+
+def compare_aggregate(T1, T2, C, w, q, p):
+    """The paired aggregate's dict: "t1", "t2", "count" (the sums as given), "m1", "m2" (T_s / C), "diff" (diff_map), "p2ll_1",
+    "p2ll_2", "lfc_p2ll" (floats) and "agg_lfc" [4] (DONUT, LL, H, V)."""
+    S = 2 * int(w) + 1
+    T1, T2, C = (np.asarray(t, np.float64).reshape(S, S) for t in (T1, T2, C))
+    m1, m2 = mean_map(T1, C), mean_map(T2, C)
+    p1, p2 = metrics(m1, w, q)["P2LL"], metrics(m2, w, q)["P2LL"]
+    return {"t1": T1, "t2": T2, "count": C, "m1": m1, "m2": m2, "diff": _log2_ratio(m1, m2), "p2ll_1": p1, "p2ll_2": p2,
+            "lfc_p2ll": float(_log2_ratio(p1, p2)),
+            "agg_lfc": _log2_ratio(aggregate_enrichment(m1, w, p), aggregate_enrichment(m2, w, p))}
+
+
+def _compare_result(sums, c1, c2, agg, w, q, p):
+    """the compare dict of one chromosome or pair: the per-loop arrays and the paired aggregate"""
+    S = 2 * w + 1
+    sums = np.asarray(sums, np.float64).reshape(-1, 4, 3)
+    r1, r2, lfc_n = compare_ratios(sums, c1, c2)
+    agg = np.asarray(agg, np.float64).reshape(3, S, S)
+    return dict(compare_aggregate(agg[0], agg[1], agg[2], w, q, p), sums=sums, r1=r1, r2=r2, lfc_n=lfc_n, lfc=lfc_summary(lfc_n))
+
+
+def _empty_compare(w, q, p):
+    """the compare dict of no loop at all: empty arrays, zero sums, NaN ratios"""
+    S = 2 * w + 1
+    return _compare_result(np.zeros((0, 4, 3)), np.zeros(0), np.zeros(0), np.zeros((3, S, S)), w, q, p)
+
+
+def _compare_resident(r1, r2, xs, ys, w, q, p):
+    """the compare dict of two pile-up dicts of the same loops (xs, ys) whose "oe" windows are still on the device: two launches
+    and a finish, one host wait"""
+    import torch
+    L, S = len(xs), 2 * w + 1
+    if L == 0:
+        return _empty_compare(w, q, p)
+    from ._lib import require_gpu
+    lib = require_gpu()
+    oe1, oe2 = r1["oe"], r2["oe"]
+    with torch.cuda.device(oe1.device):
+        ws = _workspace(lib, 1, 0, L, w, oe1.device)
+        order = torch.from_numpy(np.lexsort((ys, xs)).astype(np.int32)).to(oe1.device, non_blocking=True)
+        parts = [reduce_pair(oe1, oe2, order, w, ws).view(-1), compare_windows(oe1, oe2, w, p).view(-1)]
+        host = torch.cat(parts).cpu().numpy()                             # the one wait
+    return _compare_result(host[3 * S * S:], r1["center_oe"], r2["center_oe"], host[:3 * S * S], w, q, p)
+
+
+def _loop_bins(xs, ys):
+    import torch
+    xs = np.asarray(xs.cpu() if isinstance(xs, torch.Tensor) else xs, np.int64).reshape(-1)
+    ys = np.asarray(ys.cpu() if isinstance(ys, torch.Tensor) else ys, np.int64).reshape(-1)
+    if len(xs) != len(ys):
+        raise PileupError("xs and ys differ in length (%d, %d)" % (len(xs), len(ys)))
+    return xs, ys
+
+
+def pileup_band_pair(band1, n1, band2, n2, D, xs, ys, w=10, q=6, peak=DEFAULT_PEAK):
+    """One chromosome on two maps: (dict 1, dict 2, compare dict).  band1, band2: the two raw bands (device float64 [rows >= D + 1,
+    n_s]); the loops (xs, ys) must lie on both maps (y < min(n1, n2), y - x + 2w <= D).  Dict s is pileup_band(band_s, n_s, D, xs,
+    ys, w, q) to the bit, its "obs" dropped (None) as soon as its "oe" is in hand; the compare dict holds "sums" [L, 4, 3], "r1",
+    "r2", "lfc_n" [L, 4], "lfc" [L] (input order) and compare_aggregate()'s keys.  One host wait beyond the two pile-ups' own.
+    L = 0 returns empty arrays without a launch."""
+    w, q, peak = int(w), int(q), int(peak)
+    check_window(w, q)
+    check_peak(w, peak)
+    xs, ys = _loop_bins(xs, ys)
+    r1 = pileup_band(band1, n1, D, xs, ys, w, q)
+    del band1                                            # a caller that holds no reference of its own has it freed here
+    r1["obs"] = None
+    r2 = pileup_band(band2, n2, D, xs, ys, w, q)
+    del band2
+    r2["obs"] = None
+    return r1, r2, _compare_resident(r1, r2, xs, ys, w, q, peak)
+
+
+def pileup_trans_records_pair(rec1, dims1, rec2, dims2, xs, ys, w=10, q=6, peak=DEFAULT_PEAK):
+    """One inter-chromosomal pair on two maps: (dict 1, dict 2, compare dict).  rec_s = (x, y, v), the pair's records on sample s
+    (host arrays or device tensors), dims_s = (n1, n2) of that map; the loops (xs, ys) = (bins of A, bins of B) must lie on both
+    maps.  Dict s is pileup_trans_records(*rec_s, *dims_s, xs, ys, w, q) to the bit with "obs" dropped; the compare dict is
+    pileup_band_pair's.  A sample without a record has E = 0, so every ratio is NaN.  One host wait beyond the two pile-ups'."""
+    w, q, peak = int(w), int(q), int(peak)
+    check_window(w, q)
+    check_peak(w, peak)
+    xs, ys = _loop_bins(xs, ys)
+    r1 = pileup_trans_records(rec1[0], rec1[1], rec1[2], dims1[0], dims1[1], xs, ys, w, q)
+    r1["obs"] = None
+    r2 = pileup_trans_records(rec2[0], rec2[1], rec2[2], dims2[0], dims2[1], xs, ys, w, q)
+    r2["obs"] = None
+    return r1, r2, _compare_resident(r1, r2, xs, ys, w, q, peak)
+
+
+def joint_status(ys, n1, n2):
+    """The status of every eligible cis row of one chromosome on two maps of n1 and n2 bins (None: the map lacks the chromosome):
+    `no_chrom` when either is missing, `off_map` when y >= min(n1, n2), `used` otherwise."""
+    if n1 is None or n2 is None:
+        return ["no_chrom"] * len(ys)
+    n = min(int(n1), int(n2))
+    return ["off_map" if int(y) >= n else "used" for y in ys]
+
+
+def joint_status_trans(a, b, dims1, dims2):
+    """joint_status for the rows of one pair: dims_s = (n1, n2) of sample s, None when the file lacks the pair or has no record
+    of it (`no_pair`); `off_map` when a >= min(n1_1, n1_2) or b >= min(n2_1, n2_2)."""
+    if dims1 is None or dims2 is None:
+        return ["no_pair"] * len(a)
+    na, nb = min(int(dims1[0]), int(dims2[0])), min(int(dims1[1]), int(dims2[1]))
+    return ["off_map" if int(i) >= na or int(j) >= nb else "used" for i, j in zip(a, b)]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # loop lists
 # ----------------------------------------------------------------------------------------------------------------------
 def _key(c):
@@ -910,6 +1132,117 @@ def pileup(f, loops, res, chromosomes=None, norm=False, bias=False, balance=None
     return out
 
 
+class PileupPairResult:
+    """What pileup_pair() returns: `first`, `second` (the PileupResult of each sample; they share `table` and ONE `status`
+    list), per row `r1`, `r2`, `lfc_n` ([rows, 4]: DONUT, LL, H, V) and `lfc`, NaN for a row that was not used; `chromosomes`
+    = [(name, loops used, compare dict)] in run order (trans: "A,B"); `all` = the genome-wide compare dict
+    (compare_aggregate's keys)."""
+
+    def __init__(self, table, status, w, q, peak):
+        self.table, self.status, self.w, self.q, self.peak = table, status, w, q, peak
+        self.first, self.second = PileupResult(table, status, w, q), PileupResult(table, status, w, q)
+        L, S = len(table), 2 * w + 1
+        self.r1, self.r2, self.lfc_n = np.full((L, 4), np.nan), np.full((L, 4), np.nan), np.full((L, 4), np.nan)
+        self.lfc = np.full(L, np.nan)
+        self.chromosomes = []
+        self.all = None
+        self._tot = [[np.zeros((S, S)) for _ in range(4)], [np.zeros((S, S)) for _ in range(4)], [np.zeros((S, S)) for _ in range(3)]]
+
+    def add(self, name, rows_in, used, part1, part2, cmp):
+        """one chromosome's or pair's three dicts (the loops of `used`, table rows, in their order): the per-row values, the
+        per-sample entries and the genome-wide partial sums, in the order of the calls"""
+        rows = np.asarray(used, np.int64)
+        self.r1[rows], self.r2[rows], self.lfc_n[rows], self.lfc[rows] = cmp["r1"], cmp["r2"], cmp["lfc_n"], cmp["lfc"]
+        for res, part, tot in ((self.first, part1, self._tot[0]), (self.second, part2, self._tot[1])):
+            res.take(used, part)
+            part = {k: v for k, v in part.items() if k not in ("valid", "expected", "obs", "oe")}       # device arrays freed
+            res.chromosomes.append((name, rows_in, len(used), part))
+            for t, key in zip(tot, ("sum_obs", "count_obs", "sum_oe", "count_oe")):
+                t += part[key]
+        for t, key in zip(self._tot[2], ("t1", "t2", "count")):
+            t += cmp[key]
+        self.chromosomes.append((name, len(used), {k: v for k, v in cmp.items() if k not in ("sums", "r1", "r2", "lfc_n", "lfc")}))
+
+    def total(self):
+        self.first.total(self._tot[0])
+        self.second.total(self._tot[1])
+        self.all = compare_aggregate(self._tot[2][0], self._tot[2][1], self._tot[2][2], self.w, self.q, self.peak)
+
+
+def _pileup_pair_trans(f1, f2, table, res, chromosomes, norm, bias, bias2, balance, w, q, n_min, x_max, device, verbose, peak):
+    """pileup_pair() in trans mode: one pair of pile-ups per chromosome pair, from the files' stored vectors."""
+    import torch
+    from .request import balance_on_trans, trans_input
+    why = trans_input((f1,)) or trans_input((f2,)) or balance_on_trans(balance or None)
+    if why is None and (bias or bias2):
+        why = "-b / -b2 do not apply to inter-chromosomal pairs"
+    if why:
+        raise PileupError(why)
+    status, a, b, pairs = classify(table, res, chromosomes, n_min, x_max, trans=True)
+    out = PileupPairResult(table, status, w, q, peak)
+    for A, B in pairs:
+        pair = frozenset((_key(A), _key(B)))
+        rows = [k for k in range(len(table)) if status[k] is None
+                and frozenset((_key(table.chr1[k]), _key(table.chr2[k]))) == pair]
+        got = [_read_pair(f, norm, A, B, res, device) for f in (f1, f2)]          # both maps before either is piled up
+        dims = [None if g is None else (int(torch.as_tensor(g[0]).max().item()) + 1, int(torch.as_tensor(g[1]).max().item()) + 1)
+                for g in got]
+        for k, s in zip(rows, joint_status_trans(a[rows], b[rows], dims[0], dims[1])):
+            status[k] = s
+        used = [k for k in rows if status[k] == "used"]
+        if dims[0] is None or dims[1] is None:
+            p1, p2, cmp = _empty_result(w, q), _empty_result(w, q), _empty_compare(w, q, peak)
+        else:
+            p1, p2, cmp = pileup_trans_records_pair(got[0][:3], dims[0], got[1][:3], dims[1], a[used], b[used], w, q, peak)
+        del got
+        out.add("%s,%s" % (A, B), len(rows), used, p1, p2, cmp)
+        if verbose:
+            print("pile-up of the pair %s,%s on both maps: %d of %d rows used, LFC_P2LL %r" % (A, B, len(used), len(rows),
+                                                                                          cmp["lfc_p2ll"]))
+    out.total()
+    return out
+
+
+def pileup_pair(f1, f2, loops, res, chromosomes=None, norm=False, bias=False, balance=None, w=10, q=6, n_min=None, x_max=None,
+                device=None, verbose=False, trans=False, peak=DEFAULT_PEAK, bias2=False):
+    """Pile up the maps `f1` and `f2` around the loops of `loops` and score what differs ("Two maps" in the module docstring).
+    The arguments are pileup()'s and apply to both maps alike; `bias` is the bias file of f1, `bias2` that of f2; `peak` is the
+    peak half-width of the four neighbourhoods.  Returns a PileupPairResult."""
+    w, q, res, peak = int(w), int(q), int(res), int(peak)
+    check_window(w, q)
+    check_peak(w, peak)
+    table = read_loops(loops) if isinstance(loops, (str, os.PathLike)) else loops
+    if trans:
+        return _pileup_pair_trans(f1, f2, table, res, chromosomes, norm, bias, bias2, balance, w, q, n_min, x_max, device, verbose,
+                                  peak)
+    status, x, y, selected = classify(table, res, chromosomes, n_min, None if x_max is None else int(x_max) // res)
+    out = PileupPairResult(table, status, w, q, peak)
+    for chrom in selected:
+        rows = [k for k in range(len(table)) if _key(table.chr1[k]) == _key(chrom) and status[k] != "trans"]
+        cand = [k for k in rows if status[k] is None]
+        p1, p2, cmp, used = _empty_result(w, q), _empty_result(w, q), _empty_compare(w, q, peak), []
+        if cand:
+            D = int(max(y[k] - x[k] for k in cand)) + 2 * w
+            bands, ns = [], []
+            for f, b in ((f1, bias), (f2, bias2)):       # both bands before either is piled up: the smaller n decides off_map
+                band, n = _read_band(f, chrom, res, D, norm, b, balance, device, verbose)
+                bands.append(band)
+                ns.append(None if band is None else n)
+            for k, s in zip(cand, joint_status(y[cand], ns[0], ns[1])):
+                status[k] = s
+            used = [k for k in cand if status[k] == "used"]
+            if ns[0] is not None and ns[1] is not None:
+                # the bands leave the list in the call: each is freed inside it as soon as its sample's oe is in hand
+                p1, p2, cmp = pileup_band_pair(bands.pop(0), ns[0], bands.pop(0), ns[1], D, x[used], y[used], w, q, peak)
+            del bands
+        out.add(chrom, len(rows), used, p1, p2, cmp)
+        if verbose:
+            print("pile-up of chromosome %s on both maps: %d of %d rows used, LFC_P2LL %r" % (chrom, len(used), len(rows),
+                                                                                         cmp["lfc_p2ll"]))
+    out.total()
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # output files
 # ----------------------------------------------------------------------------------------------------------------------
@@ -967,6 +1300,40 @@ def write_enrichment(prefix, res, min_enrichment=None):
     return len(keep)
 
 
+def write_compare(prefix, res, min_lfc=None):
+    """PREFIX.compare.tsv, PREFIX.diff.tsv and PREFIX.compare.stats.tsv of a PileupPairResult; with min_lfc = T also
+    PREFIX.up1.tsv, the `used` rows with LFC >= T, and PREFIX.up2.tsv, those with LFC <= -T, as loop lists (NaN fails both).
+    Returns the two lists' lengths (None without T).  The per-sample files are write_outputs(prefix + ".1", res.first) and
+    write_outputs(prefix + ".2", res.second)."""
+    with open(prefix + ".compare.tsv", "w") as fh:
+        fh.write(res.table.header + "\t" + "\t".join(COMPARE_COLUMNS) + "\n")
+        for k, line in enumerate(res.table.lines):
+            vals = [res.first.oe_center[k], res.second.oe_center[k]] + list(res.r1[k]) + list(res.r2[k]) + list(res.lfc_n[k]) \
+                + [res.lfc[k]]
+            fh.write("%s\t%s\t%s\n" % (line, res.status[k], "\t".join(_r(v) for v in vals)))
+    write_matrix(prefix + ".diff.tsv", res.all["diff"])
+
+    def stats_row(name, used, c):
+        return "%s\t%d\t%s\n" % (name, used, "\t".join(_r(v) for v in [c["p2ll_1"], c["p2ll_2"], c["lfc_p2ll"]] + list(c["agg_lfc"])))
+    with open(prefix + ".compare.stats.tsv", "w") as fh:
+        fh.write(COMPARE_STATS_HEADER)
+        for name, used, c in res.chromosomes:
+            fh.write(stats_row(name, used, c))
+        fh.write(stats_row("all", sum(u for _, u, _ in res.chromosomes), res.all))
+    if min_lfc is None:
+        return None
+    kept = []
+    with np.errstate(invalid="ignore"):
+        # by the LFC as written: repr() round-trips a float64, so this is the value a reader of compare.tsv sees
+        for ext, ok in ((".up1.tsv", res.lfc >= min_lfc), (".up2.tsv", res.lfc <= -min_lfc)):
+            keep = [k for k in range(len(res.table)) if res.status[k] == "used" and ok[k]]
+            with open(prefix + ext, "w") as fh:
+                fh.write(res.table.header + "\n")
+                fh.write("".join(res.table.lines[k] + "\n" for k in keep))
+            kept.append(len(keep))
+    return tuple(kept)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # command line
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1000,7 +1367,44 @@ def parse_args(args):
                    help="with --enrich: half-width of the peak box the neighbourhoods leave out (default %d, below -w)" % DEFAULT_PEAK)
     p.add_argument("--min-enrichment", dest="min_enrichment", type=float, default=None, metavar="T",
                    help="with --enrich: also write PREFIX.enriched.tsv, the used rows with FE_MIN >= T as a loop list")
+    p.add_argument("-f2", "--file2", dest="f2_path", default=None,
+                   help="a second contact map: pile the list up on both maps and score what differs (PREFIX.1.*, PREFIX.2.*, "
+                        "PREFIX.compare.tsv, PREFIX.diff.tsv, PREFIX.compare.stats.tsv; --peak sets the neighbourhoods)")
+    p.add_argument("-b2", "--biases2", dest="biasfile2", default=None, help="with -f2: bias vector of the second text map")
+    p.add_argument("--min-lfc", dest="min_lfc", type=float, default=None, metavar="T",
+                   help="with -f2: also write PREFIX.up1.tsv (used rows with LFC >= T) and PREFIX.up2.tsv (LFC <= -T)")
     return p.parse_args(args)
+
+
+def compare_request(args, world):
+    """What -f2 / -b2 / --min-lfc ask: the peak half-width of a two-map run, None for a run without -f2; PileupError with the
+    text of the `Error:` line for a combination that cannot be honoured.  Reads nothing and touches no GPU."""
+    if args.f2_path is None:
+        for flag, given in (("-b2", args.biasfile2), ("--min-lfc", args.min_lfc)):
+            if given is not None:
+                raise PileupError("%s without -f2: it belongs to the pile-up on two maps; give -f2 FILE" % flag)
+        return None
+    if world > 1:
+        raise PileupError("the pile-up on two maps runs on one GPU only (this run has %d ranks)" % world)
+    if not os.path.exists(args.f2_path):
+        raise PileupError("Couldn't find the second contact file %s" % args.f2_path)
+    if args.biasfile2 is not None and not os.path.exists(args.biasfile2):
+        raise PileupError("Couldn't find the bias file of the second map %s" % args.biasfile2)
+    if args.enrich or args.min_enrichment is not None:
+        raise PileupError("-f2 with %s: the enrichment of every loop on one sample alone is what a run without -f2 gives; "
+                          "the two-map run scores the difference (--peak, --min-lfc)"
+                          % ("--enrich" if args.enrich else "--min-enrichment"))
+    for flag, given in (("--balance-genome", args.balance_genome is not None), ("--balance-pixels", args.balance_pixels_given),
+                        ("--pairs-trans", args.pairs_trans)):
+        if given:
+            raise PileupError("-f2 with %s: the pile-up on two genome-balanced maps is not built; pile each map up alone" % flag)
+    if args.min_lfc is not None and not (math.isfinite(args.min_lfc) and args.min_lfc > 0):
+        raise PileupError("--min-lfc %r: the threshold T must be finite and > 0 (up1 holds LFC >= T, up2 LFC <= -T)" % args.min_lfc)
+    peak = DEFAULT_PEAK if args.peak is None else args.peak
+    if not 0 <= peak < args.w:
+        raise PileupError("--peak %d with -w %d: the peak half-width P must be in 0 .. w - 1 (P >= w leaves no neighbourhood)"
+                          % (peak, args.w))
+    return peak
 
 
 def enrich_request(args):
@@ -1074,8 +1478,9 @@ def main(argv=None):
         print("Error: Couldn't find specified bias file")
         return
     try:
+        two = compare_request(args, world)
         genome = genome_request(args, f, world)
-        peak = enrich_request(args)
+        peak = enrich_request(args) if two is None else None         # with -f2, --peak is the two-map run's own
     except PileupError as e:
         print("Error: %s" % e)
         return
@@ -1084,6 +1489,8 @@ def main(argv=None):
         from .balance import BalanceError, check_request
         try:
             balance = check_request(args.balance, f, args.biasfile, args.norm_method, world)
+            if two is not None:                          # --balance applies to both maps alike
+                check_request(args.balance, args.f2_path, args.biasfile2, args.norm_method, world, bias_flag="-b2")
         except BalanceError as e:
             print("Error: %s" % e)
             return
@@ -1097,6 +1504,20 @@ def main(argv=None):
     from .trans import TransError
     try:
         check_window(args.w, args.q)
+        if two is not None:
+            pair = pileup_pair(f, args.f2_path, args.loops, res, chromosomes=args.chromosome, norm=args.norm_method,
+                               bias=args.biasfile or False, balance=balance, w=args.w, q=args.q, n_min=args.n_min, x_max=x_max,
+                               verbose=True, trans=args.trans, peak=two, bias2=args.biasfile2 or False)
+            write_outputs(args.prefix + ".1", pair.first)
+            write_outputs(args.prefix + ".2", pair.second)
+            kept = write_compare(args.prefix, pair, args.min_lfc)
+            print("%d of %d loops piled up on both maps, peak half-width %d%s: LFC_P2LL %r -> %s.{1,2}.{apa,oe,stats,loops}.tsv, "
+                  "%s.{compare,diff,compare.stats}.tsv%s"
+                  % (sum(u for _, u, _ in pair.chromosomes), len(pair.table), two,
+                     "" if kept is None else "; %d loops with LFC >= %r, %d with LFC <= %r" % (kept[0], args.min_lfc, kept[1],
+                                                                                                -args.min_lfc),
+                     pair.all["lfc_p2ll"], args.prefix, args.prefix, "" if kept is None else ", %s.{up1,up2}.tsv" % args.prefix))
+            return
         res_ = pileup(f, args.loops, res, chromosomes=args.chromosome, norm=args.norm_method, bias=args.biasfile or False,
                       balance=balance, w=args.w, q=args.q, n_min=args.n_min, x_max=x_max, verbose=True, trans=args.trans,
                       balance_genome=genome[0] if genome else None, balance_pixels=genome[1] if genome else "all",

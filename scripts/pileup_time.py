@@ -2,7 +2,9 @@
 loops, w = 10 (GPU box): device events around the three stages (valid + expected, windows, reduce), the enrichment of every loop
 (mst_pileup_enrich, peak half-width --peak) and the whole pileup_band call without and with `peak`, median of --steps after
 --warmup; bytes moved from shapes, the expected pass's share of 6.3 TB/s and the enrichment against its byte model (8 L (2w+1)^2
-bytes read).  Prints one JSON line.  python scripts/pileup_time.py [--steps 20] [--warmup 3] [--peak 2]"""
+bytes read).  The two-map leg (two_map_leg) piles the same list up on a second band: pileup_band_pair as a whole, and
+mst_pileup_compare and mst_pileup_reduce_pair alone against their byte model at the copy bandwidth measured in the same run.
+Prints one JSON line.  python scripts/pileup_time.py [--steps 20] [--warmup 3] [--peak 2]"""
 import argparse
 import json
 import os
@@ -30,6 +32,42 @@ def timed(fn, steps, warmup):
         torch.cuda.synchronize()
         out.append(e0.elapsed_time(e1))
     return float(np.median(out)), float(min(out)), float(max(out))
+
+
+def two_map_leg(a, band, n, D, xs, ys, w, q, p, oe, order, ws, dev):
+    """The same list on two maps: a second band from another seed, pileup_band_pair as a whole, and mst_pileup_compare and
+    mst_pileup_reduce_pair alone on the two resident stacks of oe windows, each against its byte model (16 L (2w+1)^2 bytes read)
+    at the bandwidth a device-to-device copy of 1 GiB reaches on this card in this run."""
+    L, S = len(xs), 2 * w + 1
+    band2 = torch.empty_like(band)
+    for i0 in range(0, n, 16384):
+        i1 = min(n, i0 + 16384)
+        band2[:, i0:i1] = band_counts(n, D, 300.0, 8000, 2, i0=i0, i1=i1, device=dev)
+    xd, yd = torch.from_numpy(xs).to(dev), torch.from_numpy(ys).to(dev)
+    _valid2, E2 = pl.expected(band2, n, D, ws)
+    _obs2, oe2, _st2 = pl.windows(band2, n, D, E2, xd, yd, w, q)
+    del _obs2
+    src = torch.empty(1 << 27, dtype=torch.float64, device=dev).normal_()
+    dst = torch.empty_like(src)
+    torch.cuda.synchronize()
+    t_copy = timed(lambda: dst.copy_(src), a.steps, a.warmup)
+    copy_tbs = 2 * src.numel() * 8 / (t_copy[0] * 1e-3) / 1e12       # read + write
+    del src, dst
+    t_cmp = timed(lambda: pl.compare_windows(oe, oe2, w, p), a.steps, a.warmup)
+    t_red = timed(lambda: pl.reduce_pair(oe, oe2, order, w, ws), a.steps, a.warmup)
+    t_old = timed(lambda: pl.reduce(oe, oe2, order, w, ws), a.steps, a.warmup)     # the four-sum reduce on the same bytes
+    t_pair = timed(lambda: pl.pileup_band_pair(band, n, band2, n, D, xs, ys, w, q, p), a.steps, a.warmup)
+    _r1, _r2, c = pl.pileup_band_pair(band, n, band2, n, D, xs, ys, w, q, p)
+    kernel_bytes = 16 * L * S * S
+    model = kernel_bytes / (copy_tbs * 1e12) * 1e3
+    rnd = lambda t: [round(t[0], 4), round(t[1], 4), round(t[2], 4)]     # noqa: E731
+    return {"copy_1GiB_TBs": round(copy_tbs, 3), "copy_ms_med_min_max": rnd(t_copy), "two_map_kernel_bytes": kernel_bytes,
+            "two_map_model_ms": round(model, 4),
+            "compare_ms_med_min_max": rnd(t_cmp), "compare_over_model": round(t_cmp[0] / model, 2),
+            "reduce_pair_ms_med_min_max": rnd(t_red), "reduce_pair_over_model": round(t_red[0] / model, 2),
+            "reduce_on_the_same_windows_ms_med_min_max": rnd(t_old),
+            "pileup_band_pair_ms_med_min_max": rnd(t_pair), "two_map_lfc_p2ll": c["lfc_p2ll"],
+            "two_map_loops_scored": int((~np.isnan(c["lfc"])).sum())}
 
 
 def main():
@@ -67,6 +105,7 @@ def main():
     t_peak = timed(lambda: pl.pileup_band(band, n, D, xs, ys, w, q, peak=p), a.steps, a.warmup)
     t_all2 = timed(lambda: pl.pileup_band(band, n, D, xs, ys, w, q), a.steps, a.warmup)       # again: the run-to-run spread
     r = pl.pileup_band(band, n, D, xs, ys, w, q, peak=p)
+    two = two_map_leg(a, band, n, D, xs, ys, w, q, p, oe, order, ws, dev)
     band_bytes = (D + 1) * n * 8
     exp_bytes = 2 * band_bytes                                    # the valid pass and the expected pass each read the band once
     win_bytes = L * S * S * 8 * 3                                 # band reads + obs and oe writes
@@ -74,6 +113,7 @@ def main():
     enr_bytes = L * S * S * 8                                     # obs read once (the 96 L bytes written are 0.03 of it)
     ms = lambda t: round(t[0], 4)                                 # noqa: E731
     print(json.dumps({
+        **two,
         "metric": "pileup_chr1_1kb_ms", "n": n, "D": D, "loops": L, "w": w, "steps": a.steps, "warmup": a.warmup,
         "expected_ms": ms(t_exp), "windows_ms": ms(t_win), "reduce_ms": ms(t_red), "pileup_band_ms": ms(t_all),
         "expected_min_max_ms": [round(t_exp[1], 4), round(t_exp[2], 4)],
