@@ -31,6 +31,13 @@
 //   place between the sieve's two comparisons, and the radius switch has no path without a case, so the axis-1 pass
 //   accumulates straight into G (scripts/isa_census.py --state-copies, tests/test_level_state_copies.py).
 // Only the found pixels (~1 % of the block) and 2 x 18 partial statistics per tile are written back.
+// Outside the level loop (scripts/isa_census.py prints it by path; tests/test_outside_loop_census.py bounds it):
+//   statistics: the slots of st start at {inf, 0}; only a wave that owns a tested pixel writes its slots.
+//   epilogue: a workgroup without a tested pixel (61 % of a dense launch) writes the identity statistics and leaves -- no
+//     ballot, no barrier.  A tested one exchanges its waves' record totals ONCE (one barrier; ct is dead by then); every wave
+//     forms its own prefix and the total from them, one lane reserves the slots in both blocks, and the statistics are folded
+//     while that atomic is under way.  Nothing found: no second barrier, no record loop.  A wave without records leaves
+//     behind the second barrier.
 // 77 KB of LDS per workgroup -> two independent workgroups per CU, so one's LDS window loads overlap the other's
 // FP64 work instead of every wave of the CU alternating between the two in barrier lock-step.
 // The kernel is FP64-VALU bound (~1150 non-fusable flops per pixel for the blurs alone), not HBM bound.
@@ -278,6 +285,7 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
     double *part = partial + (size_t)slot * n_tested * 2;
 
     uint32_t in_mask = 0, nz_mask = 0;  // per-k bits: column inside the block / tested pixel owned by this thread
+    int any_nz;                         // some thread of the workgroup owns a tested pixel (workgroup-uniform)
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int gx = x0 + cg * K + k;
@@ -293,7 +301,7 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
             const int gx = x0 + rc;
             if (row_own && gx >= 0 && gx < CH && rc >= 1 && rc <= T::ITC && nb[(size_t)gy * CH + gx]) nz_mask |= 1u << k;
         }
-        const int any_nz = __syncthreads_or(nz_mask != 0);
+        any_nz = __syncthreads_or(nz_mask != 0);
         if (!any_nz && skip_empty) {
             for (int t = tid; t < n_tested; t += T::NT) {
                 part[2 * t] = INFINITY;
@@ -405,19 +413,27 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
         }
         __syncthreads();
         uint32_t mine = 0;
+        // The thread's K flags are K consecutive bytes at a multiple of K: read as words.  A flag byte is 0 or 1, and
+        // w * 0x204081 puts bytes 0 .. 3 of w side by side at bits 21 .. 24 (every partial product lands on a bit of its own,
+        // so nothing carries).  Owned columns are region columns 1 .. ITC: the first group drops its first, the last its last.
+        static_assert(K % 4 == 0 && (RGC & 3) == 0 && T::ITC == RGC - 2, "flag bytes are gathered four at a time");
+        uint32_t flag_bits = 0;
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int rc = cg * K + k;
-            if (row_own && ((in_mask >> k) & 1u) && rc >= 1 && rc <= T::ITC && nzb[rr * RGC + rc]) nz_mask |= 1u << k;
+        for (int w = 0; w < K / 4; ++w) {
+            const uint32_t four = reinterpret_cast<const uint32_t *>(nzb)[(rr * RGC + cg * K) / 4 + w];
+            flag_bits |= (((four * 0x00204081u) >> 21) & 0xFu) << (4 * w);
         }
-        mine = __builtin_popcount(nz_mask);
+        constexpr uint32_t ALLK = (1u << K) - 1u;
+        const uint32_t col_mask = cg == 0 ? ALLK & ~1u : cg == T::NCG - 1 ? ALLK >> 1 : ALLK;
+        nz_mask = row_own ? flag_bits & in_mask & col_mask : 0u;
+        // the wave's count from K ballots, in scalar registers (integer: exact in any order)
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+        for (int k = 0; k < K; ++k) mine += (uint32_t)__builtin_popcountll(__ballot((nz_mask >> k) & 1u));
         if ((tid & 63) == 0 && mine) {                                         // integer: exact in any order
             atomicAdd(src.nz_count + b, mine);
             if (b2 >= 0) atomicAdd(src.nz_count + b2, mine);
         }
-        const int any_nz = __syncthreads_or(nz_mask != 0);                  // also fences nzb reads before vb is reused
+        any_nz = __syncthreads_or(nz_mask != 0);                            // also fences nzb reads before vb is reused
         if (!any_nz && skip_empty) {
             for (int t = tid; t < n_tested; t += T::NT) {
                 part[2 * t] = INFINITY;
@@ -441,6 +457,17 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
     }
     const int wave = tid >> 6, lane = tid & 63;
     const bool wave_has_nz = __any(nz_mask != 0);
+    // the statistics slots start at the identities {inf, 0}: only a wave that owns a tested pixel writes its slots in the level
+    // loop, and a workgroup without any never reads them (the epilogue's short path).  The level loop's barriers lie between
+    // these stores and the first slot a wave writes.
+    // Not in the wide tile: there the store inside the branch costs a scalar spill in the level loop, so every wave writes its
+    // slot at every tested level as before, and nothing has to be initialised.
+    constexpr bool ST_ONCE = T::RMAX <= 14;
+    if (ST_ONCE && any_nz)
+        for (int i = tid; i < n_tested * T::NW; i += T::NT) {
+            st[2 * i] = INFINITY;
+            st[2 * i + 1] = 0.0;
+        }
     const bool wave_all_in = __all(in_mask == (1u << K) - 1u);   // no pixel of this wave lies outside the block
     double *de_mine = de + (cg * 2) * RGR + rr;                                   // [cg][0 = left edge, 1 = right edge][rr]
     const double *de_left = de + ((cg > 0 ? cg - 1 : 0) * 2 + 1) * RGR + rr;      // left neighbour's right edge
@@ -527,8 +554,7 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
             // then the new maxima are written over them, then the comparisons against the new ones.  A wave without a tested
             // pixel touches neither: its Mc keeps the initial zeros, which nobody reads (every reader is under wave_has_nz).
             uint32_t en = 0, gn = 0;   // en: D_new == M_new;  gn: D_new > M_prev (M of the level before it); pixel k at bit K - 1 - k
-            // the level statistics of a tested level (kl >= 4); a wave without a tested pixel keeps the identities {inf, 0}
-            double lmin = INFINITY, lsum = 0.0;
+            [[maybe_unused]] double lmin_all = INFINITY, lsum_all = 0.0;      // (wide tile: every wave writes its slot)
             if (wave_has_nz) {
                 const double dl = de_left[0], dr = de_right[0];      // requested first: the comparisons below cover the LDS latency
                 // the comparisons belong to the sieve, which the reference evaluates on the tested pixels only
@@ -557,6 +583,7 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
                 if (kl >= 4) {
                     // tested level = D_{kl-2}: previous = D_{kl-3} (ep), current (Dc, ec, gp), next = this one (Mc by now, en)
                     const uint32_t code = (uint32_t)tested + 1u;
+                    double lmin = INFINITY, lsum = 0.0;      // the level's statistics over this thread's tested pixels
                     // branch-free form: the five terms fold into ONE floating-point comparison per pixel (D_c > best and
                     // D_c > M_n <=> D_c > max(best, M_n): no NaN reaches here) and one bit of a mask that is combined for all
                     // K pixels at once; updates and statistics are selects, so the K pixels are independent instruction streams
@@ -590,12 +617,24 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
                     });
                     // fixed-order DPP reduction inside the wave (total lands in lane 63), one slot per (level, wave)
                     if (!MST_VARIANT(2)) wave_reduce_min_sum(lmin, lsum);
+                    // a wave without a tested pixel leaves its slot at the identities it was given before the loop
+                    if constexpr (ST_ONCE) {
+                        if (lane == 63) {
+                            st[(tested * T::NW + wave) * 2] = lmin;
+                            st[(tested * T::NW + wave) * 2 + 1] = lsum;
+                        }
+                    } else {
+                        lmin_all = lmin;
+                        lsum_all = lsum;
+                    }
                 }
             }
             if (kl >= 4) {
-                if (lane == 63) {
-                    st[(tested * T::NW + wave) * 2] = lmin;
-                    st[(tested * T::NW + wave) * 2 + 1] = lsum;
+                if constexpr (!ST_ONCE) {
+                    if (lane == 63) {
+                        st[(tested * T::NW + wave) * 2] = lmin_all;
+                        st[(tested * T::NW + wave) * 2 + 1] = lsum_all;
+                    }
                 }
                 ++tested;
             }
@@ -641,37 +680,69 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
         if (qs == -1.0 && us == 0x12345u) part[0] = qs;      // never true: keeps the injected chains alive
     }
 #endif
-    uint32_t my_total = 0;
-    uint32_t before[K];                 // records of this wave that precede mine for the same k
-    uint32_t kbase[K];                  // records of this wave for smaller k
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const unsigned long long bal = __ballot(lvl[k] != 0);
-        before[k] = __builtin_popcountll(bal & ((1ull << lane) - 1ull));
-        kbase[k] = my_total;
-        my_total += (uint32_t)__builtin_popcountll(bal);      // wave-uniform
+    // [census: epilogue empty]  A workgroup without a tested pixel (workgroup-uniform, from __syncthreads_or) found nothing and
+    // its statistics are the identities: what the skip_empty return writes, and the bits the fold below would form from slots
+    // that all hold {inf, 0}.
+    if (T::RMAX <= 14 && !any_nz) {     // (the wide tile does not carry any_nz through its level loop: it goes the long way)
+        for (int t = tid; t < tested; t += T::NT) {
+            part[2 * t] = INFINITY;
+            part[2 * t + 1] = 0.0;
+        }
+        return;
     }
-    uint32_t *cnt_lds = reinterpret_cast<uint32_t *>(de);      // edge strip is dead now
-    __syncthreads();
+    // [census: epilogue reservation]  Wave totals: a wave without a tested pixel holds lvl == 0 everywhere and counts nothing.
+    unsigned long long bal[K];          // lanes of this wave with a record for pixel k
+    uint32_t my_total = 0;              // wave-uniform
+#pragma unroll
+    for (int k = 0; k < K; ++k) bal[k] = 0;
+    if (wave_has_nz) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            bal[k] = __ballot(lvl[k] != 0);
+            my_total += (uint32_t)__builtin_popcountll(bal[k]);
+        }
+    }
+    // The totals are exchanged ONCE; every wave forms its own prefix and the workgroup's total from them.  ct is dead behind
+    // the last level's barriers (the edge strip is not: the last level's maxima read it), so the exchange needs no barrier in
+    // front of it, and the one behind it also makes every wave's statistics slots visible to the fold.
+    uint32_t *cnt_lds = reinterpret_cast<uint32_t *>(ct);
     if (lane == 0) cnt_lds[wave] = my_total;
     __syncthreads();
-    if (tid == 0) {
-        uint32_t tot = 0;
-        for (int w = 0; w < T::NW; ++w) {
-            const uint32_t n = cnt_lds[w];
-            cnt_lds[w] = tot;
-            tot += n;
-        }
-        cnt_lds[T::NW] = tot ? atomicAdd(found_count + e_b, tot) : 0u;
-        cnt_lds[T::NW + 1] = (tot && e_b2 >= 0) ? atomicAdd(found_count + e_b2, tot) : 0u;
+    uint32_t tot = 0, wave_off = 0;
+#pragma unroll
+    for (int w = 0; w < T::NW; ++w) {
+        const uint32_t n = cnt_lds[w];
+        wave_off += w < wave ? n : 0u;
+        tot += n;
     }
+    tot = __builtin_amdgcn_readfirstlane(tot);
+    if (tot && tid == 0) {              // one lane reserves the workgroup's slots in both blocks
+        cnt_lds[T::NW] = atomicAdd(found_count + e_b, tot);
+        cnt_lds[T::NW + 1] = e_b2 >= 0 ? atomicAdd(found_count + e_b2, tot) : 0u;
+    }
+    // [census: epilogue fold]
+    for (int t = tid; t < tested; t += T::NT) {
+        double mn = st[(t * T::NW) * 2], sm = st[(t * T::NW) * 2 + 1];
+        for (int w = 1; w < T::NW; ++w) {
+            const double a = st[(t * T::NW + w) * 2];
+            mn = a < mn ? a : mn;
+            sm = sm + st[(t * T::NW + w) * 2 + 1];
+        }
+        part[2 * t] = mn;
+        part[2 * t + 1] = sm;
+    }
+    if (!tot) return;                   // tested, nothing found (workgroup-uniform): no record loop
     __syncthreads();
-    const uint32_t wave_base = cnt_lds[T::NW] + cnt_lds[wave];
-    const uint32_t wave_base2 = cnt_lds[T::NW + 1] + cnt_lds[wave];
+    // [census: epilogue records]
+    if (!my_total) return;              // (wave-uniform; no barrier follows)
+    const uint32_t wave_base = cnt_lds[T::NW] + wave_off;
+    const uint32_t wave_base2 = cnt_lds[T::NW + 1] + wave_off;
+    uint32_t kbase = 0;                 // records of this wave for smaller k
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         if (lvl[k]) {
-            const uint32_t off = kbase[k] + before[k];
+            // kbase + the records of the lanes below mine
+            const uint32_t off = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[k], kbase));
             mst_found rec;
             rec.pixel = (uint32_t)gy * (uint32_t)e_CH + (uint32_t)(e_x0 + cg * K + k);
             rec.level = lvl[k];
@@ -682,17 +753,7 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
                 found[(size_t)e_b2 * found_cap + wave_base2 + off] = rec;
             }
         }
-    }
-    __syncthreads();
-    for (int t = tid; t < tested; t += T::NT) {
-        double mn = st[(t * T::NW) * 2], sm = st[(t * T::NW) * 2 + 1];
-        for (int w = 1; w < T::NW; ++w) {
-            const double a = st[(t * T::NW + w) * 2];
-            mn = a < mn ? a : mn;
-            sm = sm + st[(t * T::NW + w) * 2 + 1];
-        }
-        part[2 * t] = mn;
-        part[2 * t + 1] = sm;
+        kbase += (uint32_t)__builtin_popcountll(bal[k]);
     }
 }
 

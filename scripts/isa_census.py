@@ -111,7 +111,8 @@ def category(op, text):
     return "other"
 
 
-def kernel_text(defines, src=SRC):
+def kernel_text(defines, src=SRC, keep_files=False):
+    """the assembly lines of the default tile's band-source kernel; keep_files: with the file's .file directives in front"""
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
         subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + list(defines) + ["-I" + os.path.dirname(SRC), "-I" + os.path.join(ROOT, "include"),
@@ -119,7 +120,7 @@ def kernel_text(defines, src=SRC):
         lines = open(out).read().split("\n")
     i0 = next(i for i, l in enumerate(lines) if KERNEL.match(l))
     i1 = next(i for i in range(i0, len(lines)) if lines[i].startswith(".Lfunc_end"))
-    return lines[i0 + 1:i1]
+    return ([l for l in lines if re.match(r"\s*\.file\s", l)] if keep_files else []) + lines[i0 + 1:i1]
 
 
 def blocks(lines):
@@ -315,7 +316,144 @@ def state_copies_report(lib):
         print("  %-55s K = %d   %3d | %d" % (title, K, per_level, behind))
 
 
+# ---- outside the level loop, by path (staging, tested mask, state initialisation, epilogue) -------------------------------------
+# The kernel is compiled with line tables (-gline-tables-only: the instruction stream is the same, .loc directives are added)
+# and every instruction outside the level loop is booked on the path whose source lines it comes from.  A path starts at its
+# anchor line and ends at the next anchor: a "[census: <path>]" tag in a comment where the source has one, else the line that
+# opens the path in the revisions without tags.  Instructions of inlined helpers (other files, or above the kernel) go with
+# the instruction before them.
+EMPTY_PATH = "epilogue: empty workgroup"      # the short path of a workgroup without a tested pixel, where the source has one
+PATHS = [
+    ("prologue: work item, in_mask", [r"^scale_space_kernel\("]),
+    ("staging: dense source", [r"if constexpr \(!BAND\) \{"]),
+    ("staging: band setup, tile kind", [r"// ---- band source"]),
+    ("staging: constant", [r"if \(constant\) \{"]),
+    ("staging: inner diagonal walk", [r"\} else if \(inner\) \{"]),
+    ("staging: border", [r"// border tiles"]),
+    ("tested mask: build, count, any_nz", [r"uint32_t mine = 0;"]),
+    ("state init, pass addresses", [r"// per-pixel rolling state"]),
+    ("level loop: entry and exit", [r"for \(int o = 0; o < n_oct"]),
+    ("epilogue: arguments", [r"// ---- found pixels"]),
+    (EMPTY_PATH, [r"\[census: epilogue empty\]"]),
+    ("epilogue: reservation", [r"\[census: epilogue reservation\]", r"uint32_t my_total = 0;"]),
+    ("epilogue: statistics fold", [r"\[census: epilogue fold\]", r"for \(int t = tid; t < tested; t \+= T::NT\)"]),
+    ("epilogue: record writes", [r"\[census: epilogue records\]", r"const uint32_t wave_base = "]),
+]
+KINDS = ("constant tile", "inner tile, tested", "border tile")
+# Trips of a path's loops per tile kind, for the busiest wave of the default tile (CTR = 60, CTC = 92, CTP = 62, 256 threads, 4
+# waves): constant 92 * 62 / 2 / 256 double2 stores; inner walk 151 diagonals in rounds of 4 waves x 19; border 60 * 92 / 256
+# elements; every other loop outside the level loop runs once in the wave that runs it (the fold, the st slots, thread 0's scan).
+LOOP_TRIPS = {"staging: constant": 92 * 62 / 2 / 256.0, "staging: inner diagonal walk": 2.0, "staging: border": 60 * 92 / 256.0}
+STAGING_OF = {"staging: constant": KINDS[0], "staging: inner diagonal walk": KINDS[1], "staging: border": KINDS[2]}
+
+
+def path_anchors(src):
+    """[(first line, path)] in line order, and the kernel's (first, last) line, from the source text"""
+    text = open(src).read().split("\n")
+    k0 = next(i for i, l in enumerate(text) if l.startswith("scale_space_kernel(")) + 1
+    k1 = next(i for i in range(k0, len(text)) if text[i].startswith("// partial[item][t][2]")) + 1
+    out = []
+    for path, alts in PATHS:
+        for rx in alts:
+            hit = next((i + 1 for i in range(k0 - 1, k1) if re.search(rx, text[i])), None)
+            if hit:
+                out.append((hit, path))
+                break
+    return sorted(out), (k0, k1)
+
+
+def outside_by_path(lines, src, loop_labels, files):
+    """{path: {"straight": Counter, "looped": Counter}} of the instructions outside the level loop; lines: kernel_text(..., line
+    tables); loop_labels: the labels of the level loop's blocks; files: main_files(lines, src)"""
+    anchors, (k0, k1) = path_anchors(src)
+    res = collections.OrderedDict((p, {"straight": collections.Counter(), "looped": collections.Counter()}) for _, p in anchors)
+    path, skip, looped, fresh = anchors[0][1], False, False, False
+    for l in lines:
+        m = re.match(r"^(\.LBB\d+_\d+):\s*(;.*)?$", l) or re.match(r"^; %bb\.(\d+):\s*(;.*)?$", l)
+        if m:
+            skip, looped, fresh = m.group(1) in loop_labels, "Loop" in (m.group(2) or ""), True
+            continue
+        t = l.strip()
+        m = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
+        if m:
+            if int(m.group(1)) in files and k0 <= int(m.group(2)) <= k1:
+                path = [p for a, p in anchors if a <= int(m.group(2))][-1]
+            continue
+        if not t or t.startswith((";", ".")):
+            if t.startswith(";") and "Loop" in t and fresh:
+                looped = True
+            continue
+        fresh = False
+        if not skip:
+            res[path]["looped" if looped else "straight"][category(t.split()[0], t)] += 1
+    return res
+
+
+def main_files(lines, src):
+    """the .file numbers that name the kernel's own source file"""
+    out = set()
+    for l in lines:
+        m = re.match(r'\s*\.file\s+(\d+)\s+(.*)$', l)
+        if m and os.path.basename(src) in m.group(2):
+            out.add(int(m.group(1)))
+    return out
+
+
+def outside_report(res):
+    valu = lambda c: sum(c[x] for x in VALU)
+    has_empty_path = EMPTY_PATH in res      # path_anchors found its tag in the source
+    print()
+    print("outside the level loop by path, static VALU per thread: straight-line | inside a loop | SALU, and weighted by trip")
+    print("count for three tile kinds (busiest wave; record writes with every pixel's branch taken = an upper bound; a path")
+    print("that a kind does not run counts 0; the constant tile owns no tested pixel)")
+    print("  %-36s %8s %7s %6s | %14s %19s %12s" % (("path", "straight", "looped", "SALU") + KINDS))
+    tot = [0.0, 0.0, 0.0]
+    tot_static = 0
+    for path, d in res.items():
+        s, lp = valu(d["straight"]), valu(d["looped"])
+        if not s and not lp and not d["straight"]["SALU"] and not d["looped"]["SALU"]:
+            continue
+        w = []
+        for kind in KINDS:
+            if path in STAGING_OF:
+                run = STAGING_OF[path] == kind
+            elif path == EMPTY_PATH:
+                run = kind == KINDS[0]
+            elif path in ("epilogue: reservation", "epilogue: statistics fold", "epilogue: record writes"):
+                run = not (has_empty_path and kind == KINDS[0])
+            else:
+                run = True
+            w.append((s + lp * LOOP_TRIPS.get(path, 1.0)) if run else 0.0)
+        tot = [a + b for a, b in zip(tot, w)]
+        tot_static += s + lp
+        print("  %-36s %8d %7d %6d | %14.0f %19.0f %12.0f" % (path, s, lp, d["straight"]["SALU"] + d["looped"]["SALU"], w[0], w[1], w[2]))
+    print("  %-36s %8d %7s %6s | %14.0f %19.0f %12.0f" % ("all paths", tot_static, "", "", tot[0], tot[1], tot[2]))
+
+
+def outside_valu(lib=LIB):
+    """{title: static VALU instructions outside the level loop} for every scale_space_kernel of a BUILT library
+    (tests/test_outside_loop_census.py).  The level loop as in state_copies(): the innermost loop around the radius cases."""
+    is_tap = lambda op: op.startswith(("v_mul_f64", "v_fma_f64", "v_fmac_f64"))
+    res = {}
+    for name, ins in disassemble(lib).items():
+        if "scale_space_kernel" not in name:
+            continue
+        taps = [a for a, op, _, _ in ins if is_tap(op)]
+        around = [(a, t) for a, t in branch_edges(ins) if t <= taps[0] and a >= taps[-1]]
+        head = max(t for _, t in around)
+        end = max(a for a, t in around if t == head)
+        res[kernel_title(name)] = sum(1 for a, op, text, _ in ins if not head <= a <= end and category(op, text) in VALU)
+    return res
+
+
 def main():
+    if "--outside-valu" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--outside-valu"]
+        lib = os.path.abspath(rest[0]) if rest else LIB
+        print("static VALU outside the level loop, per thread, from %s" % os.path.relpath(lib, ROOT))
+        for title, n in sorted(outside_valu(lib).items()):
+            print("  %-55s %5d" % (title, n))
+        return
     if "--state-copies" in sys.argv[1:]:
         rest = [a for a in sys.argv[1:] if a != "--state-copies"]
         state_copies_report(os.path.abspath(rest[0]) if rest else LIB)
@@ -439,6 +577,10 @@ def main():
             outside.update(count(ins))
     print("  outside the loop, static VALU (staging loops run several times)  %d per thread = %.1f per pixel if run once"
           % (sum(outside[c] for c in VALU), sum(outside[c] for c in VALU) * f))
+    src = srcs[0] if srcs else SRC
+    located = kernel_text(list(defines) + ["-gline-tables-only"], src, keep_files=True)
+    res = outside_by_path(located, src, {lab for lab, ann, ins in in_loop}, main_files(located, src))
+    outside_report(res)
 
 
 if __name__ == "__main__":
