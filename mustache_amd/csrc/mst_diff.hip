@@ -22,6 +22,7 @@
 #include <vector>
 #include "mst_common.h"
 #include "mst_fir.h"
+#include "mst_stage_walk.h"
 
 namespace {
 
@@ -191,50 +192,17 @@ struct BandSource {
             val = both ? ((fill ? 2.0 : r1) - (fill ? 2.0 : r2)) : 0.0;
         };
         if (inner) {
-            constexpr int ND = T::CTR + T::CTC - 1;
-            constexpr int PER = (T::CTR + 63) / 64;
-            constexpr int U = 10 / PER > 0 ? 10 / PER : 1;   // diagonals in flight per wave (two loads each)
-            for (int q0 = tid >> 6; q0 < ND; q0 += T::NW * U) {
-                double a1[U][PER], a2[U][PER];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int q = q0 + u * T::NW;
-                    const int dd = q - (T::CTR - 1);
-                    const int off = X0 - Y0 + dd;
-                    const int i_lo = dd < 0 ? -dd : 0;
-                    const int i_hi = T::CTC - dd < T::CTR ? T::CTC - dd : T::CTR;
-                    const bool in_band = q < ND && off >= 0 && off <= dpx + 1;
-                    const int64_t at = (int64_t)(in_band ? off : 0) * n + start + Y0;
-#pragma unroll
-                    for (int e = 0; e < PER; ++e) {
-                        const int i = i_lo + (tid & 63) + 64 * e;
-                        const bool ok = in_band && i < i_hi && start + X0 + i + dd < n;
-                        a1[u][e] = ok ? band1[at + i] : 0.0;
-                        a2[u][e] = ok ? band2[at + i] : 0.0;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int q = q0 + u * T::NW;
-                    if (q >= ND) break;
-                    const int dd = q - (T::CTR - 1);
-                    const int off = X0 - Y0 + dd;
-                    const int i_lo = dd < 0 ? -dd : 0;
-                    const int i_hi = T::CTC - dd < T::CTR ? T::CTC - dd : T::CTR;
-#pragma unroll
-                    for (int e = 0; e < PER; ++e) {
-                        const int i = i_lo + (tid & 63) + 64 * e;
-                        if (i >= i_hi) continue;
-                        const int j = i + dd;
-                        double val;
-                        bool both;
-                        pixel(a1[u][e], a2[u][e], off, val, both);
-                        ct[j * T::CTP + i] = val;
-                        const int ri = i - RMAX, rj = j - RMAX;
-                        if (ri >= 0 && ri < RGR && rj >= 0 && rj < RGC) nzb[ri * RGC + rj] = both ? 1 : 0;
-                    }
-                }
-            }
+            // the fused kernel's diagonal walk, two bands per element (mst_stage_walk.h)
+            const double *const bands[2] = {band1, band2};
+            stage_inner_walk<T, 2>(bands, n, start, dpx, Y0, X0, ct, nzb, tid,
+                                   [&](const double (&raw)[2], int off, bool in_tile, double *cp, bool in_region, uint8_t *zp)
+                                       __attribute__((always_inline)) {
+                                           double val;
+                                           bool both;
+                                           pixel(raw[0], raw[1], off, val, both);
+                                           if (in_tile) *cp = val;
+                                           if (in_region) *zp = both ? 1 : 0;
+                                       });
         } else {
             for (int idx = tid; idx < T::CTR * T::CTC; idx += T::NT) {
                 const int i = idx / T::CTC, j = idx - i * T::CTC;

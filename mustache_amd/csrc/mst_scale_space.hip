@@ -32,6 +32,9 @@
 //   accumulates straight into G (scripts/isa_census.py --state-copies, tests/test_level_state_copies.py).
 // Only the found pixels (~1 % of the block) and 2 x 18 partial statistics per tile are written back.
 // Outside the level loop (scripts/isa_census.py prints it by path; tests/test_outside_loop_census.py bounds it):
+//   staging of an inner tile from the band: the diagonal walk of mst_stage_walk.h (shared with mst_diff.hip).  A lane owns a tile
+//     row on every diagonal, so a diagonal costs a lane one add and one compare per load and the stores' addresses are lane
+//     constants plus an immediate; the band row, the fills and the tested rule are wave-uniform and live on the scalar side.
 //   statistics: the slots of st start at {inf, 0}; only a wave that owns a tested pixel writes its slots.
 //   epilogue: a workgroup without a tested pixel (61 % of a dense launch) writes the identity statistics and leaves -- no
 //     ballot, no barrier.  A tested one exchanges its waves' record totals ONCE (one barrier; ct is dead by then); every wave
@@ -63,6 +66,7 @@
 #include "mst_common.h"
 
 #include "mst_fir.h"
+#include "mst_stage_walk.h"
 
 namespace {
 
@@ -347,53 +351,15 @@ scale_space_kernel(const double *__restrict__ c, const uint8_t *__restrict__ nz,
             static_assert((RGR * RGC) % 16 == 0, "nzb is cleared in 16-byte pieces");
             for (int i = tid; i < RGR * RGC / 16; i += T::NT) nz4[i] = make_uint4(0, 0, 0, 0);
         } else if (inner) {
-            // walk the tile by diagonals: pixels (Y0+i, X0+i+dd) of one diagonal are CONTIGUOUS in band row off = X0-Y0+dd,
-            // so a wave reads one 480-byte run per diagonal; the fill decision is wave-uniform.  All loads of a wave's
-            // share (U diagonals per round, two rounds) are issued before the first LDS store: the staging is latency
-            // bound (each diagonal lives in a different band row), so memory-level parallelism is what shortens it.
-            constexpr int ND = T::CTR + T::CTC - 1;
-            constexpr int PER = (T::CTR + 63) / 64;      // elements of one diagonal per lane
-            constexpr int U2 = (ND + 2 * T::NW - 1) / (2 * T::NW);
-            constexpr int U = U2 * PER <= 20 ? U2 : 20 / PER;       // diagonals in flight per wave: loads first, then the stores
-            for (int q0 = tid >> 6; q0 < ND; q0 += T::NW * U) {
-                double rawv[U][PER];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int q = q0 + u * T::NW;
-                    const int dd = q - (T::CTR - 1);
-                    const int off = X0 - Y0 + dd;
-                    const int i_lo = dd < 0 ? -dd : 0;
-                    const int i_hi = T::CTC - dd < T::CTR ? T::CTC - dd : T::CTR;
-                    const bool in_band = q < ND && off >= 0 && off <= dpx + 1;
-                    const double *brow = bandp + (int64_t)(in_band ? off : 0) * n + start + Y0;
-#pragma unroll
-                    for (int e = 0; e < PER; ++e) {
-                        const int i = i_lo + (tid & 63) + 64 * e;
-                        rawv[u][e] = (in_band && i < i_hi && start + X0 + i + dd < n) ? brow[i] : 0.0;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int q = q0 + u * T::NW;
-                    if (q >= ND) break;
-                    const int dd = q - (T::CTR - 1);
-                    const int off = X0 - Y0 + dd;
-                    const int i_lo = dd < 0 ? -dd : 0;
-                    const int i_hi = T::CTC - dd < T::CTR ? T::CTC - dd : T::CTR;
-                    const bool filled = off <= 4 || off >= dpx + 1;
-#pragma unroll
-                    for (int e = 0; e < PER; ++e) {
-                        const int i = i_lo + (tid & 63) + 64 * e;
-                        if (i >= i_hi) continue;
-                        const int j = i + dd;
-                        const double raw = rawv[u][e];
-                        ct[j * T::CTP + i] = filled ? 2.0 : raw;
-                        const int ri = i - RMAX, rj = j - RMAX;
-                        if (ri >= 0 && ri < RGR && rj >= 0 && rj < RGC)
-                            nzb[ri * RGC + rj] = (raw != 0.0 && off >= 4) ? 1 : 0;
-                    }
-                }
-            }
+            // one diagonal walk for every band source (mst_stage_walk.h): a lane owns a tile row, the fills and the tested rule
+            // are wave-uniform per diagonal
+            const double *const bands[1] = {__builtin_amdgcn_readfirstlane(b >= src.split) ? src.band2 : src.band};
+            stage_inner_walk<T, 1>(bands, n, start, dpx, Y0, X0, ct, nzb, tid,
+                                   [&](const double (&raw)[1], int off, bool in_tile, double *cp, bool in_region, uint8_t *zp)
+                                       __attribute__((always_inline)) {
+                                           if (in_tile) *cp = (off <= 4 || off >= dpx + 1) ? 2.0 : raw[0];
+                                           if (in_region) *zp = (raw[0] != 0.0 && off >= 4) ? 1 : 0;
+                                       });
         } else {
             // border tiles: element-wise with reflection (few tiles; loads are served by L2)
             for (int idx = tid; idx < T::CTR * T::CTC; idx += T::NT) {

@@ -3,7 +3,7 @@
 category and by phase, for every blur radius of the default level table -- the audit of the PMC figure "VALU instructions per
 computed pixel" (profiles/r05g_pmc_traffic.json: 2370 on band tiles, of which 1335 are the blur's executed flops).
 
-    python scripts/isa_census.py [-DMST_...=...] [other_revision.hip] > profiles/r06_isa_census.txt
+    python scripts/isa_census.py [-DMST_...=...] [other_revision.hip [other_mst_diff.hip]] > profiles/r06_isa_census.txt
 
 How: hipcc -S (device only, the product flags of mustache_amd/csrc/Makefile) on mst_scale_space.hip; the band-source kernel of
 the default tile (Tile<32,64,14,8,1,false,false>, BAND = true) is cut into basic blocks with LLVM's own loop annotations
@@ -12,6 +12,9 @@ radius switch: [axis-0 main items] -> [axis-0 leftover pieces, executed by the f
 [axis-1 pass]; the radius of a case follows from its multiplies (8 (r + 1) in the main block).  Everything else in the loop is
 common to all radii: tap fetch, dispatch, DoG, edge strip, second barrier, 3 x 3 maximum, sieve, statistics, state moves.
 Blocks of the branchy sieve form that only run when some lane passes a test are counted as executed (an upper bound).
+
+The report ends with the inner tile's diagonal walk (mst_stage_walk.h) in the fused kernel and, beside it, in diff_dog_kernel's
+band source (fused_walk(), diff_walk(); tests/test_stage_walk_census.py).
 
     python scripts/isa_census.py --window-loads [library.so] > profiles/<tag>_window_loads.txt
 
@@ -111,14 +114,14 @@ def category(op, text):
     return "other"
 
 
-def kernel_text(defines, src=SRC, keep_files=False):
+def kernel_text(defines, src=SRC, keep_files=False, kernel=KERNEL, flags=FLAGS):
     """the assembly lines of the default tile's band-source kernel; keep_files: with the file's .file directives in front"""
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
-        subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + list(defines) + ["-I" + os.path.dirname(SRC), "-I" + os.path.join(ROOT, "include"),
+        subprocess.run(["/opt/rocm/bin/hipcc"] + list(flags) + list(defines) + ["-I" + os.path.dirname(SRC), "-I" + os.path.join(ROOT, "include"),
                         src, "-o", out], check=True, capture_output=True)
         lines = open(out).read().split("\n")
-    i0 = next(i for i, l in enumerate(lines) if KERNEL.match(l))
+    i0 = next(i for i, l in enumerate(lines) if kernel.match(l))
     i1 = next(i for i in range(i0, len(lines)) if lines[i].startswith(".Lfunc_end"))
     return ([l for l in lines if re.match(r"\s*\.file\s", l)] if keep_files else []) + lines[i0 + 1:i1]
 
@@ -322,6 +325,8 @@ def state_copies_report(lib):
 # anchor line and ends at the next anchor: a "[census: <path>]" tag in a comment where the source has one, else the line that
 # opens the path in the revisions without tags.  Instructions of inlined helpers (other files, or above the kernel) go with
 # the instruction before them.
+WALK_PATH = "staging: inner diagonal walk"
+WALK_HEADER = "mst_stage_walk.h"      # the walk's body since round 11; the fused kernel calls it behind `} else if (inner) {`
 EMPTY_PATH = "epilogue: empty workgroup"      # the short path of a workgroup without a tested pixel, where the source has one
 PATHS = [
     ("prologue: work item, in_mask", [r"^scale_space_kernel\("]),
@@ -368,6 +373,7 @@ def outside_by_path(lines, src, loop_labels, files):
     anchors, (k0, k1) = path_anchors(src)
     res = collections.OrderedDict((p, {"straight": collections.Counter(), "looped": collections.Counter()}) for _, p in anchors)
     path, skip, looped, fresh = anchors[0][1], False, False, False
+    walk_files = header_files(lines, WALK_HEADER)      # the walk's body lies in a header of its own: booked where it is called
     for l in lines:
         m = re.match(r"^(\.LBB\d+_\d+):\s*(;.*)?$", l) or re.match(r"^; %bb\.(\d+):\s*(;.*)?$", l)
         if m:
@@ -378,6 +384,8 @@ def outside_by_path(lines, src, loop_labels, files):
         if m:
             if int(m.group(1)) in files and k0 <= int(m.group(2)) <= k1:
                 path = [p for a, p in anchors if a <= int(m.group(2))][-1]
+            elif int(m.group(1)) in walk_files and WALK_PATH in res:
+                path = WALK_PATH
             continue
         if not t or t.startswith((";", ".")):
             if t.startswith(";") and "Loop" in t and fresh:
@@ -389,14 +397,99 @@ def outside_by_path(lines, src, loop_labels, files):
     return res
 
 
-def main_files(lines, src):
-    """the .file numbers that name the kernel's own source file"""
+def header_files(lines, name):
+    """the .file numbers that name a source file or header"""
     out = set()
     for l in lines:
         m = re.match(r'\s*\.file\s+(\d+)\s+(.*)$', l)
-        if m and os.path.basename(src) in m.group(2):
+        if m and name in m.group(2):
             out.add(int(m.group(1)))
     return out
+
+
+def main_files(lines, src):
+    """the .file numbers that name the kernel's own source file"""
+    return header_files(lines, os.path.basename(src))
+
+
+# ---- the inner tile's diagonal walk (mst_stage_walk.h), in the fused kernel and in the difference kernel -------------------------
+# Fused kernel: the path "staging: inner diagonal walk" of outside_by_path().  Difference kernel (mst_diff.hip, band source, the
+# tile of the fused kernel's default radius): the instructions of the header and of the lines between `if (inner) {` and the
+# `} else {` that closes it in BandSource::stage.  Weighted = straight + looped x rounds (busiest wave).
+DIFF_SRC = os.path.join(ROOT, "mustache_amd", "csrc", "mst_diff.hip")
+DIFF_FLAGS = [f for f in FLAGS if f not in ("-fno-honor-nans", "-mno-amdgpu-ieee")]
+DIFF_KERNEL = re.compile(r"^_ZN\S*diff_dog_kernelINS_4TileILi32ELi64ELi14ELi8ELi1ELb0ELb0EEENS_10BandSourceEEE\S*:")
+DIFF_ROUNDS = 4.0      # 38 diagonals per wave, 10 in flight (two loads each)
+
+
+def walk_level_loop(bl):
+    """(head label, blocks) of the level loop among blocks(): the depth-2 loop that holds barriers"""
+    heads = collections.Counter()
+    for lab, ann, ins in bl:
+        m = re.search(r"Header=(BB\d+_\d+) Depth=2", ann)
+        if m and any(op == "s_barrier" for op, _ in ins):
+            heads[m.group(1)] += 1
+    head = heads.most_common(1)[0][0]
+    return head, [b for b in bl if re.search(r"(Header=%s Depth=2|Parent Loop %s)" % (head, head), b[1])]
+
+
+def fused_walk(src=SRC, defines=()):
+    """{"straight", "looped", "salu", "weighted"}: VALU per thread of the fused kernel's inner walk (default tile, band source),
+    compiled from the source (tests/test_stage_walk_census.py)"""
+    head, in_loop = walk_level_loop(blocks(kernel_text(defines, src)))
+    located = kernel_text(list(defines) + ["-gline-tables-only"], src, keep_files=True)
+    d = outside_by_path(located, src, {lab for lab, ann, ins in in_loop}, main_files(located, src))[WALK_PATH]
+    valu = lambda c: sum(c[x] for x in VALU)
+    s, lp = valu(d["straight"]), valu(d["looped"])
+    return {"straight": s, "looped": lp, "salu": d["straight"]["SALU"] + d["looped"]["SALU"], "weighted": s + lp * LOOP_TRIPS[WALK_PATH]}
+
+
+def diff_walk(src=DIFF_SRC):
+    """the same figures for diff_dog_kernel's band source"""
+    lines = kernel_text(["-gline-tables-only"], src, keep_files=True, kernel=DIFF_KERNEL, flags=DIFF_FLAGS)
+    text = open(src).read().split("\n")
+    a = next(i for i, l in enumerate(text) if re.search(r"^\s*if \(inner\) \{", l)) + 1
+    b = next(i for i in range(a, len(text)) if re.match(r"^        \} else \{", text[i])) + 1
+    # the element rule both of the source's paths share (the `pixel` lambda above them) goes with the instruction before it
+    p0 = next(i for i, l in enumerate(text) if "auto pixel = " in l) + 1
+    p1 = next(i for i in range(p0, len(text)) if re.match(r"^\s*\};", text[i])) + 1
+    own, walk = main_files(lines, src), header_files(lines, WALK_HEADER)
+    c = {"straight": collections.Counter(), "looped": collections.Counter()}
+    inside, looped, fresh = False, False, False
+    for l in lines:
+        m = re.match(r"^(\.LBB\d+_\d+):\s*(;.*)?$", l) or re.match(r"^; %bb\.(\d+):\s*(;.*)?$", l)
+        if m:
+            looped, fresh = "Loop" in (m.group(2) or ""), True
+            continue
+        t = l.strip()
+        m = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
+        if m:
+            f, ln = int(m.group(1)), int(m.group(2))
+            if f in walk:
+                inside = True
+            elif f in own and not p0 <= ln <= p1:
+                inside = a <= ln < b
+            continue
+        if not t or t.startswith((";", ".")):
+            if t.startswith(";") and "Loop" in t and fresh:
+                looped = True
+            continue
+        fresh = False
+        if inside:
+            c["looped" if looped else "straight"][category(t.split()[0], t)] += 1
+    valu = lambda k: sum(k[x] for x in VALU)
+    s, lp = valu(c["straight"]), valu(c["looped"])
+    return {"straight": s, "looped": lp, "salu": c["straight"]["SALU"] + c["looped"]["SALU"], "weighted": s + lp * DIFF_ROUNDS}
+
+
+def walk_report(src, defines, diff_src):
+    print()
+    print("the inner tile's diagonal walk, VALU per thread: straight-line | inside a loop | SALU | weighted by rounds (busiest wave)")
+    f = fused_walk(src, defines)
+    print("  %-58s %8d %7d %6d | %6.0f" % ("scale_space_kernel Tile<32,64,14,8,1,0,0> band source", f["straight"], f["looped"], f["salu"], f["weighted"]))
+    if diff_src and not defines:
+        d = diff_walk(diff_src)
+        print("  %-58s %8d %7d %6d | %6.0f" % ("diff_dog_kernel Tile<32,64,14,8,1,0,0> band source", d["straight"], d["looped"], d["salu"], d["weighted"]))
 
 
 def outside_report(res):
@@ -581,6 +674,8 @@ def main():
     located = kernel_text(list(defines) + ["-gline-tables-only"], src, keep_files=True)
     res = outside_by_path(located, src, {lab for lab, ann, ins in in_loop}, main_files(located, src))
     outside_report(res)
+    # a second file names the revision of mst_diff.hip that goes with another revision of the fused kernel
+    walk_report(src, defines, srcs[1] if len(srcs) > 1 else None if srcs else DIFF_SRC)
 
 
 if __name__ == "__main__":
