@@ -692,6 +692,34 @@ MST_STABLE int mst_pileup_compare(const double *oe1, const double *oe2, int64_t 
 MST_STABLE int mst_pileup_reduce_pair(const double *oe1, const double *oe2, const int32_t *order, int64_t L, int32_t w,
                                       double *agg, void *workspace, uint64_t workspace_bytes, void *stream);
 
+/* ---- the significance of every loop of a pile-up from raw counts (rules: "Significance" in mustache_amd/pileup.py;
+ * tests/pileup_poisson_reference.py restates them).  Added without a change of MST_ABI_REVISION, as mst_pileup_enrich was. */
+/* One pass over a chromosome's raw records (x, dist: dev int32 [R]; count: dev float32 [R] when count_kind = 0, dev int64 [R]
+ * when count_kind = 1): counts[k] (dev int64 [K], zeroed by the call) = the sum of the counts of the records whose pixel
+ * (x << 32 | dist) is keys[k].  keys: dev int64 [K], strictly ascending (an unsorted list loses hits, never memory safety).  A
+ * record whose dist lies outside [min_sep, max_sep] (0 <= min_sep <= max_sep; the range of the keys' distances) is left at
+ * once.  A float32 count inside that range that is no integer value in [0, 2^63) sets *flag (dev int64, ACCUMULATED: the caller
+ * zeroes it) to 1 and is not added: the caller refuses the map, nothing is rounded.  Integer atomic adds: the result has the same
+ * bits under any order of the records, and a pixel that occurs in several records gets their sum.  K = 0 does nothing; R = 0
+ * zeroes counts and launches nothing. */
+MST_STABLE int mst_pileup_centre_counts(const int32_t *x, const int32_t *dist, const void *count, int32_t count_kind, int64_t R,
+                                        const int64_t *keys, int64_t K, int32_t min_sep, int32_t max_sep, int64_t *counts,
+                                        int64_t *flag, void *stream);
+/* One lane per (loop, neighbourhood).  sums: dev f64 [L][4][3] as mst_pileup_enrich wrote them; centre_obs, centre_e: dev f64
+ * [L], each loop's obs centre and its E_centre; counts: dev int64 [L], each loop's raw centre count; bias: dev f64 [n]; xs, ys:
+ * dev int64 [L] (an index outside 0 .. n-1 reads no bias and counts as NaN).  Outputs, each dev f64 [L][4]:
+ *   EXP    = centre_e * S_o / S_e in that order, NaN when cnt = 0, S_e = 0 or centre_obs is NaN;  FE = centre_obs / EXP, NaN when
+ *            EXP is 0 or NaN -- the bits of pileup.enrichment() wherever the value is a number;
+ *   LAMBDA = (EXP * bias[xs]) * bias[ys], NaN when EXP is NaN or either bias is NaN or < 0.2;
+ *   P      = P(Poisson(LAMBDA) >= count): NaN when LAMBDA is NaN (or < 0); else 1 when count = 0; else 0 when LAMBDA = 0; else
+ *            the regularised lower incomplete gamma function P(count, LAMBDA) in float64 (power series for LAMBDA <= 1 or
+ *            LAMBDA <= count, 1 - Q by the continued fraction otherwise, both to a relative term of 2^-53).
+ * A tail that has not converged within the kernel's iteration cap is NaN and adds 1 to *unconverged (dev int64, ACCUMULATED: the
+ * caller zeroes it).  L = 0 launches nothing. */
+MST_STABLE int mst_pileup_poisson(const double *sums, const double *centre_obs, const double *centre_e, const int64_t *counts,
+                                  const double *bias, int64_t n, const int64_t *xs, const int64_t *ys, int64_t L, double *exp_out,
+                                  double *fe_out, double *lambda_out, double *p_out, int64_t *unconverged, void *stream);
+
 /* ---- read pairs -> pixels (rules: mustache_amd/pairs.py; tests/pairs_reference.py restates them).  Added without a change
  * of MST_ABI_REVISION, as mst_balance_apply_pairs was: a library from before the addition is refused by its missing symbols. */
 /* One pass over the rows (pos1, pos2: dev int32 [n_rows]) of one chromosome.  A row is dropped when a position is < 1 or

@@ -134,6 +134,8 @@ _SIGNATURES = {
     "mst_pileup_reduce_segmented_workspace_bytes": (_u64, [_p, _i32, _i32]),
     "mst_pileup_reduce_segmented": (ctypes.c_int, [_p, _p, _p, _i64, _p, _i32, _i32, _p, _p, _u64, _p]),
     "mst_pileup_enrich": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),
+    "mst_pileup_centre_counts": (ctypes.c_int, [_p, _p, _p, _i32, _i64, _p, _i64, _i32, _i32, _p, _p, _p]),
+    "mst_pileup_poisson": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p, _p]),
     "mst_pileup_compare": (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _p, _p]),
     "mst_pileup_reduce_pair": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _u64, _p]),
     "mst_pairs_bin": (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i64, _i64, _i32, _p, _p, _p, _i64, _p, _p]),

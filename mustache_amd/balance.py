@@ -435,6 +435,12 @@ def balance_records_device(xd, dd, vd, distance_in_bp, chromosome, res, dev, met
     stores them or float64) -> n = max bin + 1, `method` on the device, the bias applied on the device as
     v' = (v / b[x]) / b[y] (NaN or < 0.2 count as +inf), then v' > 0 and the reader's distance rule -> (x, y, v) host arrays,
     None when nothing is left."""
+    return balance_records_with_bias(xd, dd, vd, distance_in_bp, chromosome, res, dev, method=method, **kw)[0]
+
+
+def balance_records_with_bias(xd, dd, vd, distance_in_bp, chromosome, res, dev, method="ICE", **kw):
+    """balance_records_device for a caller that goes on with the bias (pileup.py, "Significance"): -> (that function's result,
+    the bias vector solve() returned as a device float64 [n] tensor)."""
     import torch
     from ._lib import ptr as _ptr, stream as _stream, require_gpu
     from . import _lib
@@ -459,5 +465,5 @@ def balance_records_device(xd, dd, vd, distance_in_bp, chromosome, res, dev, met
         x, y, v = xd[keep].to(torch.int64).cpu().numpy(), yd[keep].cpu().numpy(), out[keep].cpu().numpy()
     if len(v) == 0:
         print(f'There is no contact in chrmosome {chromosome} to work on.')
-        return None
-    return x, y, v
+        return None, bd
+    return (x, y, v), bd

@@ -99,9 +99,53 @@ HiCCUPS's four neighbourhoods, in all three modes above.  Without the switch (`p
     --min-enrichment T PREFIX.enriched.tsv: the input's header and the unchanged lines of the `used` rows with FE_MIN >= T (NaN
     fails), a loop list the tools read.  The four files above stay byte for byte what they are without --enrich.
   * Refused, one `Error:` line before anything is read: --peak or --min-enrichment without --enrich; P >= w (or P < 0).
-  * Not done: a Poisson p-value (the band holds balanced values, not counts); widening w where a neighbourhood is sparse.
+  * Not done: widening w where a neighbourhood is sparse.  A Poisson p-value needs the raw counts beside the balanced band:
+    "Significance" below, in the one mode that has them.
 Device work (mustache_amd/csrc/mst_pileup_enrich.hip): mst_pileup_enrich, one wave per loop over the window of obs that is already
 resident, the twelve sums per loop; they come back in the one concatenated copy each mode waits for.  The ratios are NumPy's.
+
+Significance (`--enrich --poisson [--max-fdr T]` under `--balance ICE|NEWTON` on a `.hic` or pairs file, `poisson=True` on pileup(),
+`poisson=PoissonInput(...)` on pileup_band(); tests/pileup_poisson_reference.py restates the rules cell by cell).  A fold
+enrichment cannot tell a centre count of 3 from one of 300; under --balance the chromosome's raw integer pixel set and the bias
+are on the device anyway, so every used loop gets a Poisson p-value against each of its four backgrounds and the list a BH FDR.
+Without the switch nothing is launched, no result gains a key and no file changes.
+  * For a used loop at bins (x, y), with the window half-width w and the peak half-width p of the enrichment:
+      c        the raw count of pixel (x, y) in the chromosome's raw pixel set (balance.read_hic_raw / pairs.read_pairs_raw): an
+               integer, 0 when the set has no such pixel; a pixel that occurs in several records counts their sum;
+      b1, b2   bias[x], bias[y] of the vector balance.solve returned;
+      EXP_N    for N in DONUT, LL, H, V exactly the enrichment's: the same sums, the same NaN rules, the same bits;
+      LAMBDA_N = (EXP_N * b1) * b2 -- HiCCUPS's step, the expected value of the balanced map taken back to count space by the
+               centre pixel's two bias values; NaN when EXP_N is NaN, or when either bias is NaN or < 0.2 (the bins
+               balance_records_device treats as +inf);
+      P_N      = P(Poisson(LAMBDA_N) >= c): NaN when LAMBDA_N is NaN (whatever c is; so is a negative LAMBDA_N, which no count
+               data gives); else 1.0 when c = 0; else 0.0 when LAMBDA_N = 0; else the regularised lower incomplete gamma function
+               P(c, LAMBDA_N) (1.0 at LAMBDA_N = +inf);
+      P_MAX    the largest of the four, NaN when one of them is: a loop must beat all four backgrounds, as in HiCCUPS.
+  * The tail, in float64: for x <= 1 or x <= a the power series sum_k x^k / ((a + 1) .. (a + k)) with the prefactor
+    exp(a log x - x - lgamma(a)) / a, otherwise 1 - Q by the continued fraction (the classical cephes / Numerical Recipes
+    split); both stop at a relative term of 2^-53.  At most 131 072 iterations (c = lambda = 2^24, the largest integer a `.hic`
+    float32 count holds exactly, takes 30 767); a tail that has not converged by then is NaN and is counted
+    ("poisson_unconverged"), never a wrong number.  The error grows like c * 2^-53 through the prefactor: 1e-9 relative to SciPy
+    holds for c < 5 000 with a margin of 50.
+  * Q_N: Benjamini-Hochberg over the used loops OF THE WHOLE RUN, all chromosomes together, once per neighbourhood, over the
+    loops whose P_N is not NaN: ascending sort, p * m / rank, suffix minimum, clip at 1 -- mst_bh_fdr, the rule the callers' own
+    q-values follow.  Q_MAX is the largest of the four, NaN when one is.  This is BH over the list, NOT HiCCUPS's lambda-chunked
+    FDR over every pixel of the map.
+  * Files: PREFIX.poisson.tsv (each row as read, then STATUS RAW_CENTER BIAS1 BIAS2 LAMBDA_* P_* P_MAX Q_* Q_MAX; NaN for a row
+    that is not `used`) and, with --max-fdr T, PREFIX.significant.tsv: the input's header and the unchanged lines of the `used`
+    rows with Q_MAX <= T (NaN fails), a loop list the tools read.  The six files above stay byte for byte what the same run
+    writes without --poisson.  One line reports the used loops, those with a defined P_MAX and those that pass --max-fdr.
+  * Refused, one `Error:` line before anything is read (poisson_request): --poisson without --enrich; without --balance
+    ICE|NEWTON (stored vectors and -b leave no raw counts in hand); with --trans, --balance-genome or -f2; on text or `.cool`
+    input (text counts may be fractional and may repeat a pixel); in a multi-rank run; --max-fdr without --poisson or outside
+    (0, 1].  A `.hic` file whose counts are fractional ends the run with one `Error:` line that names the chromosome: a flag
+    word written by the kernel, nothing is rounded.
+  * Not claimed: agreement with Juicer's own output.
+Device work (mustache_amd/csrc/mst_pileup_poisson.hip): mst_pileup_centre_counts, the one new pass over the map -- every raw record
+against the sorted centre pixels of the list, a 64-bit integer atomic add per hit, so the counts have the same bits under any
+record order; mst_pileup_poisson, one lane per (loop, neighbourhood): EXP and FE in enrichment()'s operation order (the host
+ratios are not run in this mode), LAMBDA and the tail.  Everything rides in the one concatenated copy the chromosome already waits
+for; the genome-wide BH adds one wait at the end of the run.
 
 Two maps (`-f2 FILE [-b2 BIAS] [--peak P] [--min-lfc T]`, `pileup_pair()`, `pileup_band_pair()`, `pileup_trans_records_pair()`;
 tests/pileup_compare_reference.py restates the rules).  One loop list piled up on two maps f (sample 1) and f2 (sample 2) at one
@@ -159,6 +203,8 @@ DEFAULT_PEAK = 2
 ENRICH_COLUMNS = ("STATUS", "OBS_CENTER", "E_CENTER") + tuple("EXP_" + n for n in NEIGHBOURHOODS) \
     + tuple("FE_" + n for n in NEIGHBOURHOODS) + ("FE_MIN",)
 ENRICH_STATS_HEADER = "CHR\tLOOPS_USED\t" + "\t".join("OE_P2" + n for n in NEIGHBOURHOODS) + "\n"
+POISSON_COLUMNS = ("STATUS", "RAW_CENTER", "BIAS1", "BIAS2") + tuple("LAMBDA_" + n for n in NEIGHBOURHOODS) \
+    + tuple("P_" + n for n in NEIGHBOURHOODS) + ("P_MAX",) + tuple("Q_" + n for n in NEIGHBOURHOODS) + ("Q_MAX",)
 COMPARE_COLUMNS = ("STATUS", "OE_CENTER_1", "OE_CENTER_2") + tuple("R1_" + n for n in NEIGHBOURHOODS) \
     + tuple("R2_" + n for n in NEIGHBOURHOODS) + tuple("LFC_" + n for n in NEIGHBOURHOODS) + ("LFC",)
 COMPARE_STATS_HEADER = "CHR\tLOOPS_USED\tP2LL_1\tP2LL_2\tLFC_P2LL\t" + "\t".join("AGG_LFC_" + n for n in NEIGHBOURHOODS) + "\n"
@@ -278,11 +324,122 @@ def _peak_kw(peak):
     return {} if peak is None else {"peak": peak}
 
 
-def _enrich_result(sums, centre_obs, centre_e, apa_oe, w, p):
-    """the keys a pile-up dict gains under `peak`"""
-    exp, fe, fe_min = enrichment(sums, centre_obs, centre_e)
+def _enrich_result(sums, centre_obs, centre_e, apa_oe, w, p, ratios=None):
+    """the keys a pile-up dict gains under `peak`; ratios = (EXP, FE) [L, 4] when the device has made them (poisson_windows)"""
+    if ratios is None:
+        exp, fe, fe_min = enrichment(sums, centre_obs, centre_e)
+    else:
+        exp, fe = ratios
+        fe_min = _nan_extreme(np.minimum, fe)
     return {"center_e": np.asarray(centre_e, np.float64), "enrich_sums": np.asarray(sums, np.float64).reshape(-1, 4, 3),
             "enrich_exp": exp, "enrich_fe": fe, "fe_min": fe_min, "enrich_agg": aggregate_enrichment(apa_oe, w, p)}
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# significance of every loop from raw counts ("Significance" in the module docstring; csrc/mst_pileup_poisson.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+class PoissonInput:
+    """What `poisson=` takes: one chromosome's raw pixel set on the device as balance.read_hic_raw / pairs.read_pairs_raw leave
+    it -- x, dist: int32 [R]; count: float32 (a `.hic` file's) or int64 (read pairs) [R] -- and the bias vector balance.solve
+    returned for it (float64 [n], host array or device tensor; NaN on masked bins)."""
+
+    def __init__(self, x, dist, count, bias):
+        self.x, self.dist, self.count, self.bias = x, dist, count, bias
+
+
+def _nan_extreme(op, a):
+    """op (np.minimum / np.maximum, which hand a NaN on) over the four columns of a [L, 4] array -> [L]"""
+    a = np.asarray(a, np.float64).reshape(-1, 4)
+    return op(op(a[:, 0], a[:, 1]), op(a[:, 2], a[:, 3]))
+
+
+def centre_counts(x, dist, count, keys, min_sep, max_sep, flag=None):
+    """(counts, flag): counts, a device int64 [K] tensor, = per key the sum of the raw counts of the records (device x, dist
+    int32 [R]; count float32 or int64 [R]) whose pixel x << 32 | dist is that key.  keys: device int64 [K], strictly ascending;
+    [min_sep, max_sep]: the range of the keys' distances.  flag: a zeroed device int64 [1] tensor (made here when None) that
+    holds 1 afterwards when a float32 count inside the range is no integer value.  K = 0 or R = 0 launches nothing."""
+    import torch
+    from . import _lib
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    lib = require_gpu()
+    R, K = int(count.numel()), int(keys.numel())
+    if count.dtype not in (torch.float32, torch.int64):
+        raise PileupError("raw counts are float32 (a .hic file's) or int64 (read pairs), not %s" % count.dtype)
+    if x.dtype != torch.int32 or dist.dtype != torch.int32 or keys.dtype != torch.int64 or not (x.numel() == dist.numel() == R):
+        raise PileupError("raw records are x int32, dist int32 and count of one length, keys are int64 (got %s, %s, %d, %d, %d, %s)"
+                          % (x.dtype, dist.dtype, x.numel(), dist.numel(), R, keys.dtype))
+    with torch.cuda.device(keys.device):
+        x, dist, count, keys = x.contiguous(), dist.contiguous(), count.contiguous(), keys.contiguous()
+        counts = torch.empty(K, dtype=torch.int64, device=keys.device)
+        if flag is None:
+            flag = torch.zeros(1, dtype=torch.int64, device=keys.device)
+        _lib.check(lib.mst_pileup_centre_counts(_ptr(x) if R else None, _ptr(dist) if R else None, _ptr(count) if R else None,
+                                                0 if count.dtype == torch.float32 else 1, R, _ptr(keys) if K else None, K,
+                                                int(min_sep), int(max_sep), _ptr(counts) if K else None, _ptr(flag), _stream()))
+    return counts, flag
+
+
+def poisson_windows(sums, centre_obs, centre_e, counts, bias, xs, ys, unconverged=None):
+    """(out, unconverged): out, a device float64 [4, L, 4] tensor = EXP, FE, LAMBDA, P of every loop and neighbourhood, from the
+    sums [L, 4, 3] enrich_windows() wrote, each loop's obs centre, E_centre (device float64 [L]) and raw centre count (device int64
+    [L]), the bias (device float64 [n]) and xs, ys (device int64 [L]).  unconverged: a zeroed device int64 [1] tensor (made here
+    when None) to which every tail that did not converge adds 1 (its P is NaN).  L = 0 launches nothing."""
+    import torch
+    from . import _lib
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    lib = require_gpu()
+    L = int(xs.numel())
+    with torch.cuda.device(sums.device):
+        out = torch.empty((4, L, 4), dtype=torch.float64, device=sums.device)
+        if unconverged is None:
+            unconverged = torch.zeros(1, dtype=torch.int64, device=sums.device)
+        if L:
+            centre_obs, centre_e, counts, bias = centre_obs.contiguous(), centre_e.contiguous(), counts.contiguous(), bias.contiguous()
+            _lib.check(lib.mst_pileup_poisson(_ptr(sums), _ptr(centre_obs), _ptr(centre_e), _ptr(counts), _ptr(bias),
+                                              int(bias.numel()), _ptr(xs), _ptr(ys), L, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                              _ptr(out[3]), _ptr(unconverged), _stream()))
+    return out, unconverged
+
+
+def bh_rows(p):
+    """Q [rows, 4]: Benjamini-Hochberg per column of P [rows, 4] (host) over its non-NaN entries, NaN where P is NaN -- the
+    device's mst_bh_fdr with B = 4 and cap = rows, the rule the callers' own q-values follow.  One host wait; rows = 0 or no
+    number at all launches nothing."""
+    import torch
+    from . import _lib
+    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    p = np.asarray(p, np.float64).reshape(-1, 4)
+    m = len(p)
+    q = np.full((m, 4), np.nan)
+    have = [np.flatnonzero(~np.isnan(p[:, k])) for k in range(4)]
+    if m == 0 or not any(len(h) for h in have):
+        return q
+    lib = require_gpu()
+    packed = np.zeros((4, m))
+    for k, h in enumerate(have):
+        packed[k, :len(h)] = p[h, k]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        pv = torch.from_numpy(packed).to(dev)
+        count = torch.tensor([len(h) for h in have], dtype=torch.int32, device=dev)
+        qd = torch.empty_like(pv)
+        ws_bytes = int(lib.mst_bh_workspace_bytes(4, m))
+        if ws_bytes == 0:
+            raise PileupError("%d loops are too many for one BH launch (4 * loops must fit in int32)" % m)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.mst_bh_fdr(_ptr(pv), _ptr(count), 4, m, _ptr(qd), _ptr(ws), ws_bytes, _stream()))
+        qh = qd.cpu().numpy()                                             # the one wait
+    for k, h in enumerate(have):
+        q[h, k] = qh[k, :len(h)]
+    return q
+
+
+def _poisson_result(out, counts, bias1, bias2):
+    """the keys a pile-up dict gains under `poisson`"""
+    out = np.asarray(out, np.float64).reshape(4, -1, 4)
+    return {"raw_center": np.asarray(counts, np.int64).reshape(-1), "bias1": np.asarray(bias1, np.float64),
+            "bias2": np.asarray(bias2, np.float64), "poisson_lambda": out[2], "poisson_p": out[3],
+            "p_max": _nan_extreme(np.maximum, out[3])}
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -344,10 +501,13 @@ def reduce(obs, oe, order, w, ws):
     return agg
 
 
-def _empty_result(w, q, peak=None):
+def _empty_result(w, q, peak=None, poisson=False):
     S = 2 * w + 1
     z = np.zeros((S, S))
     M = np.full((S, S), np.nan)
+    if poisson:
+        return dict(_empty_result(w, q, peak), poisson_unconverged=0,
+                    **_poisson_result(np.zeros((4, 0, 4)), np.zeros(0, np.int64), np.zeros(0), np.zeros(0)))
     if peak is not None:
         return dict(_empty_result(w, q), **_enrich_result(np.zeros((0, 4, 3)), np.zeros(0), np.zeros(0), M, w, peak))
     return {"valid": None, "expected": None, "obs": None, "oe": None, "sum_obs": z, "count_obs": z.copy(), "sum_oe": z.copy(),
@@ -355,26 +515,31 @@ def _empty_result(w, q, peak=None):
             "p2ll": np.zeros(0), "metrics": metrics(M, w, q), "metrics_oe": metrics(M, w, q)}
 
 
-def pileup_band(band, n, D, xs, ys, w=10, q=6, peak=None):
+def pileup_band(band, n, D, xs, ys, w=10, q=6, peak=None, poisson=None):
     """The pile-up of one chromosome's raw band (device float64 [rows >= D + 1, n]) around the loops (xs, ys) (bins, host
     arrays or tensors, y - x + 2w <= D).  Returns a dict: "valid", "expected", "obs", "oe" (device tensors), "sum_obs",
     "count_obs", "sum_oe", "count_oe", "apa" (mean obs), "apa_oe" (host [2w+1, 2w+1]), "center_obs", "center_oe", "p2ll"
     (host [L], input order), "metrics" and "metrics_oe" (dicts of METRICS).  L = 0 returns empty aggregates without a launch.
     peak=p adds the enrichment of every loop (the module docstring has the rules): "center_e" (E[y - x], host [L]),
     "enrich_sums" [L, 4, 3], "enrich_exp", "enrich_fe" [L, 4], "fe_min" [L] and "enrich_agg" [4], from one more launch inside the
-    same host wait."""
+    same host wait.
+    poisson=PoissonInput(...) (with `peak`; "Significance" in the module docstring) adds "raw_center" (int64 [L]), "bias1", "bias2"
+    [L], "poisson_lambda", "poisson_p" [L, 4] and "p_max" [L] from two more launches inside the same wait; EXP and FE are then the
+    device's, with the bits enrichment() gives.  A float32 count that is no integer value is a PileupError."""
     import torch
     w, q = int(w), int(q)
     check_window(w, q)
     if peak is not None:
         check_peak(w, peak)
+    elif poisson is not None:
+        raise PileupError("poisson= without peak=: the significance is taken against the four neighbourhoods of the enrichment")
     xs = np.asarray(xs.cpu() if isinstance(xs, torch.Tensor) else xs, np.int64).reshape(-1)
     ys = np.asarray(ys.cpu() if isinstance(ys, torch.Tensor) else ys, np.int64).reshape(-1)
     if len(xs) != len(ys):
         raise PileupError("xs and ys differ in length (%d, %d)" % (len(xs), len(ys)))
     L, S = len(xs), 2 * w + 1
     if L == 0:
-        return _empty_result(w, q, peak)
+        return _empty_result(w, q, peak, poisson is not None)
     from ._lib import require_gpu
     lib = require_gpu()
     dev = band.device
@@ -388,7 +553,22 @@ def pileup_band(band, n, D, xs, ys, w=10, q=6, peak=None):
         agg = reduce(obs, oe, order, w, ws)
         parts = [agg.view(-1), st.view(-1)]
         if peak is not None:
-            parts += [enrich_windows(obs, w, peak, E=E, xs=xd, ys=yd).view(-1), E[yd - xd]]
+            sums, e_centre = enrich_windows(obs, w, peak, E=E, xs=xd, ys=yd), E[yd - xd]
+            parts += [sums.view(-1), e_centre]
+        if poisson is not None:
+            if bool(((xs < 0) | (ys < xs)).any()):
+                raise PileupError("poisson=: a loop's bins must satisfy 0 <= x <= y")
+            sep = ys - xs
+            keys, inverse = np.unique((xs << 32) | sep, return_inverse=True)          # the centre pixels, each once
+            words = torch.zeros(2, dtype=torch.int64, device=dev)                     # fractional-count flag, tails not converged
+            per_key, _ = centre_counts(poisson.x, poisson.dist, poisson.count, torch.from_numpy(keys).to(dev, non_blocking=True),
+                                       int(sep.min()), int(sep.max()), flag=words[:1])
+            counts = per_key[torch.from_numpy(inverse.reshape(-1).astype(np.int64)).to(dev, non_blocking=True)]
+            bias = torch.as_tensor(poisson.bias).to(dev, dtype=torch.float64)
+            if int(bias.numel()) <= int(ys.max()):
+                raise PileupError("poisson=: the bias vector has %d bins, the loops reach bin %d" % (bias.numel(), int(ys.max())))
+            out4, _ = poisson_windows(sums, st[:, 0], e_centre, counts, bias, xd, yd, unconverged=words[1:])
+            parts += [out4.view(-1), counts.view(torch.float64), bias[xd], bias[yd], words.view(torch.float64)]
         host = torch.cat(parts).cpu().numpy()                             # the one wait
     agg_h, st_h = host[:4 * S * S].reshape(4, S, S), host[4 * S * S:4 * S * S + 3 * L].reshape(L, 3)
     apa, apa_oe = mean_map(agg_h[0], agg_h[1]), mean_map(agg_h[2], agg_h[3])
@@ -396,8 +576,19 @@ def pileup_band(band, n, D, xs, ys, w=10, q=6, peak=None):
            "sum_oe": agg_h[2], "count_oe": agg_h[3], "apa": apa, "apa_oe": apa_oe, "center_obs": st_h[:, 0].copy(),
            "center_oe": st_h[:, 1].copy(), "p2ll": st_h[:, 2].copy(), "metrics": metrics(apa, w, q),
            "metrics_oe": metrics(apa_oe, w, q)}
-    if peak is not None:
-        out.update(_enrich_result(host[-13 * L:-L], out["center_obs"], host[-L:], apa_oe, w, peak))
+    at = 4 * S * S + 3 * L
+    if poisson is not None:
+        tail = host[at + 13 * L:]
+        bad, unconverged = (int(v) for v in tail[19 * L:].view(np.int64))
+        if bad:
+            raise PileupError("a raw count is not an integer value: the significance needs raw integer counts")
+        out4 = tail[:16 * L].reshape(4, L, 4)
+        out.update(_enrich_result(host[at:at + 12 * L], out["center_obs"], host[at + 12 * L:at + 13 * L], apa_oe, w, peak,
+                                  ratios=(out4[0], out4[1])))
+        out.update(_poisson_result(out4, tail[16 * L:17 * L].view(np.int64), tail[17 * L:18 * L], tail[18 * L:19 * L]))
+        out["poisson_unconverged"] = unconverged
+    elif peak is not None:
+        out.update(_enrich_result(host[at:at + 12 * L], out["center_obs"], host[at + 12 * L:], apa_oe, w, peak))
     return out
 
 
@@ -870,20 +1061,59 @@ def _read_band(f, chromosome, res, D, norm=False, bias=False, balance=None, devi
     return band_from_host_coo(x, y, np.ascontiguousarray(v, dtype=np.float64), n, D, dev), n
 
 
+def _read_band_raw(f, chromosome, res, D, balance, device=None, verbose=False):
+    """_read_band under `poisson`: (band, n, PoissonInput), or (None, 0, None).  The chromosome's raw pixel set is read as
+    read_contacts reads it under `balance` (balance.read_hic_raw / pairs.read_pairs_raw), balanced by the same call
+    (balance.balance_records_with_bias) and scattered by the same band_from_host_coo, so the band has the values _read_band
+    gives; the raw records and the bias stay on the device."""
+    import torch
+    from .balance import balance_records_with_bias, check_request, method_of
+    from .mustache import read_raw_sample
+    from .normalize import band_from_host_coo
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    check_request(balance, f, False, False)
+    if verbose:
+        print("Reading contact map...")
+    try:
+        raw = read_raw_sample(f, False, res, D * res, chromosome, device=dev, balance=balance, verbose=verbose)
+    except NameError:                                  # a file without this chromosome
+        return None, 0, None
+    if raw is None:
+        return None, 0, None
+    xd, dd, counts, dev, _depth = raw
+    vd = counts if counts.dtype == torch.float32 else counts.to(torch.float64)
+    r, bias = balance_records_with_bias(xd, dd, vd, D * res, chromosome, res, dev, method=method_of(balance))
+    if r is None:
+        return None, 0, None
+    x = np.ascontiguousarray(r[0], dtype=np.int64)
+    y = np.ascontiguousarray(r[1], dtype=np.int64)
+    n = int(max(x.max(), y.max())) + 1
+    return band_from_host_coo(x, y, np.ascontiguousarray(r[2], dtype=np.float64), n, D, dev), n, PoissonInput(xd, dd, counts, bias)
+
+
 class PileupResult:
     """What pileup() returns: the table, per row `status`, `obs_center`, `oe_center`, `p2ll`; `chromosomes` = [(name, rows in,
     loops used, pile-up dict)] in run order; `all` = the genome-wide pile-up dict (sums, counts, means, metrics).  Under `peak`
     also per row `e_center`, `enrich_exp`, `enrich_fe` ([rows, 4]: DONUT, LL, H, V) and `fe_min`, NaN for a row that was not
-    used, and "enrich_agg" in every pile-up dict; without it they are None."""
+    used, and "enrich_agg" in every pile-up dict; without it they are None.  Under `poisson` also per row `raw_center`, `bias1`,
+    `bias2`, `p_max`, `poisson_lambda`, `poisson_p` ([rows, 4]) and, once total() has run the genome-wide BH over the used rows,
+    `poisson_q` ([rows, 4]) and `q_max`; NaN for a row that was not used, None without `poisson`."""
 
-    def __init__(self, table, status, w, q, peak=None):
-        self.table, self.status, self.w, self.q, self.peak = table, status, w, q, peak
+    def __init__(self, table, status, w, q, peak=None, poisson=False):
+        self.table, self.status, self.w, self.q, self.peak, self.poisson = table, status, w, q, peak, bool(poisson)
         L = len(table)
         self.obs_center, self.oe_center, self.p2ll = np.full(L, np.nan), np.full(L, np.nan), np.full(L, np.nan)
         self.e_center = self.enrich_exp = self.enrich_fe = self.fe_min = None
         if peak is not None:
             self.e_center, self.fe_min = np.full(L, np.nan), np.full(L, np.nan)
             self.enrich_exp, self.enrich_fe = np.full((L, 4), np.nan), np.full((L, 4), np.nan)
+        self.raw_center = self.bias1 = self.bias2 = self.p_max = self.poisson_lambda = self.poisson_p = None
+        self.poisson_q = self.q_max = None
+        self.poisson_unconverged = 0
+        if self.poisson:
+            self.raw_center, self.bias1, self.bias2, self.p_max = (np.full(L, np.nan) for _ in range(4))
+            self.poisson_lambda, self.poisson_p = np.full((L, 4), np.nan), np.full((L, 4), np.nan)
+            self._scored = []                            # the used rows, in the order they were taken
         self.chromosomes = []
         self.all = None
 
@@ -894,6 +1124,11 @@ class PileupResult:
         if self.peak is not None:
             self.e_center[rows], self.fe_min[rows] = part["center_e"], part["fe_min"]
             self.enrich_exp[rows], self.enrich_fe[rows] = part["enrich_exp"], part["enrich_fe"]
+        if self.poisson:
+            self.raw_center[rows], self.bias1[rows], self.bias2[rows] = part["raw_center"], part["bias1"], part["bias2"]
+            self.poisson_lambda[rows], self.poisson_p[rows], self.p_max[rows] = part["poisson_lambda"], part["poisson_p"], part["p_max"]
+            self.poisson_unconverged += part["poisson_unconverged"]
+            self._scored.append(rows)
 
     def total(self, tot):
         """`all` from the four genome-wide sums and counts"""
@@ -902,6 +1137,11 @@ class PileupResult:
                     "metrics": metrics(apa, self.w, self.q), "metrics_oe": metrics(apa_oe, self.w, self.q)}
         if self.peak is not None:
             self.all["enrich_agg"] = aggregate_enrichment(apa_oe, self.w, self.peak)
+        if self.poisson:                                 # BH over the used loops of the whole run, all chromosomes together
+            rows = np.concatenate(self._scored) if self._scored else np.zeros(0, np.int64)
+            self.poisson_q, self.q_max = np.full((len(self.table), 4), np.nan), np.full(len(self.table), np.nan)
+            self.poisson_q[rows] = bh_rows(self.poisson_p[rows])
+            self.q_max[rows] = _nan_extreme(np.maximum, self.poisson_q[rows])
 
 
 def _read_pair(f, norm, A, B, res, device):
@@ -1076,20 +1316,26 @@ def _pileup_trans_genome(f, table, res, chromosomes, norm, bias, balance, method
 
 
 def pileup(f, loops, res, chromosomes=None, norm=False, bias=False, balance=None, w=10, q=6, n_min=None, x_max=None,
-           device=None, verbose=False, trans=False, balance_genome=None, balance_pixels="all", pairs_zero_based=False, peak=None):
+           device=None, verbose=False, trans=False, balance_genome=None, balance_pixels="all", pairs_zero_based=False, peak=None,
+           poisson=False):
     """Pile up map `f` around the loops of `loops` (a TSV path or a LoopTable) at resolution `res` (bp).  The reader
     arguments (`norm`, `bias`, `balance`) mean what they mean for the caller; `n_min` is in bins (None: 30), `x_max` in bp.
     trans=True piles up the inter-chromosomal rows instead, pair by pair (the module docstring has the rules); in that mode
     `chromosomes` of the result holds ("A,B", rows in, loops used, pile-up dict).  balance_genome="NEWTON" | "ICE" (with
     trans=True; balance_pixels "all" | "inter"; pairs_zero_based for a pairs file) piles the rows up on the genome-balanced map
     of a raw `.hic` file or a `.pairs` / `.pairs.gz` file, every pair in shared launches.  peak=p (0 <= p < w) scores every
-    used loop against its local background in any of the three modes ("Enrichment" in the module docstring).  Returns a
-    PileupResult."""
+    used loop against its local background in any of the three modes ("Enrichment" in the module docstring).  poisson=True (with `peak` and balance="ICE" |
+    "NEWTON" on a `.hic` or pairs file, intra-chromosomal only) adds each used loop's Poisson p-values from the raw counts and
+    the run's BH q-values ("Significance").  Returns a PileupResult."""
     w, q, res = int(w), int(q), int(res)
     check_window(w, q)
     if peak is not None:
         peak = int(peak)
         check_peak(w, peak)
+    if poisson:
+        why = poisson_conflict(f, peak is not None, balance, bias, trans, balance_genome is not None)
+        if why:
+            raise PileupError(why)
     table = read_loops(loops) if isinstance(loops, (str, os.PathLike)) else loops
     if balance_genome is not None:
         if not trans:
@@ -1100,17 +1346,21 @@ def pileup(f, loops, res, chromosomes=None, norm=False, bias=False, balance=None
     if trans:
         return _pileup_trans(f, table, res, chromosomes, norm, bias, balance, w, q, n_min, x_max, device, verbose, peak)
     status, x, y, selected = classify(table, res, chromosomes, n_min, None if x_max is None else int(x_max) // res)
-    out = PileupResult(table, status, w, q, peak)
+    out = PileupResult(table, status, w, q, peak, poisson)
     S = 2 * w + 1
     tot = [np.zeros((S, S)) for _ in range(4)]
     for chrom in selected:
         rows = [k for k in range(len(table)) if _key(table.chr1[k]) == _key(chrom) and status[k] != "trans"]
         cand = [k for k in rows if status[k] is None]
-        part = _empty_result(w, q, peak)
+        part = _empty_result(w, q, peak, poisson)
         used = []
         if cand:
             D = int(max(y[k] - x[k] for k in cand)) + 2 * w
-            band, n = _read_band(f, chrom, res, D, norm, bias, balance, device, verbose)
+            raw = None
+            if poisson:
+                band, n, raw = _read_band_raw(f, chrom, res, D, balance, device, verbose)
+            else:
+                band, n = _read_band(f, chrom, res, D, norm, bias, balance, device, verbose)
             if band is None:
                 for k in cand:
                     status[k] = "no_chrom"
@@ -1118,8 +1368,14 @@ def pileup(f, loops, res, chromosomes=None, norm=False, bias=False, balance=None
                 for k in cand:
                     status[k] = "off_map" if y[k] >= n else "used"
                 used = [k for k in cand if status[k] == "used"]
-                part = pileup_band(band, n, D, x[used], y[used], w, q, **_peak_kw(peak))
-                del band
+                try:
+                    part = pileup_band(band, n, D, x[used], y[used], w, q, **_peak_kw(peak), **({"poisson": raw} if poisson else {}))
+                except PileupError as e:
+                    if "not an integer value" not in str(e):
+                        raise
+                    raise PileupError("chromosome %s holds a count that is not an integer value: --poisson needs raw integer "
+                                      "counts" % chrom)
+                del band, raw
             out.take(used, part)
         part = {k_: v for k_, v in part.items() if k_ not in ("valid", "expected", "obs", "oe")}   # device arrays freed
         out.chromosomes.append((chrom, len(rows), len(used), part))
@@ -1300,6 +1556,30 @@ def write_enrichment(prefix, res, min_enrichment=None):
     return len(keep)
 
 
+def write_poisson(prefix, res, max_fdr=None):
+    """PREFIX.poisson.tsv of a PileupResult made with `poisson` (each row as read, then POISSON_COLUMNS; NaN for a row that is not
+    `used`); with max_fdr = T also PREFIX.significant.tsv, the `used` rows with Q_MAX <= T as a loop list (NaN fails).  Returns
+    (used loops, those with a defined P_MAX, the rows of that list or None without T)."""
+    if not res.poisson or res.poisson_q is None:
+        raise PileupError("this pile-up ran without `poisson`: there is no significance to write")
+    with open(prefix + ".poisson.tsv", "w") as fh:
+        fh.write(res.table.header + "\t" + "\t".join(POISSON_COLUMNS) + "\n")
+        for k, line in enumerate(res.table.lines):
+            vals = [res.raw_center[k], res.bias1[k], res.bias2[k]] + list(res.poisson_lambda[k]) + list(res.poisson_p[k]) \
+                + [res.p_max[k]] + list(res.poisson_q[k]) + [res.q_max[k]]
+            fh.write("%s\t%s\t%s\n" % (line, res.status[k], "\t".join(_r(v) for v in vals)))
+    used = [k for k in range(len(res.table)) if res.status[k] == "used"]
+    defined = sum(1 for k in used if not np.isnan(res.p_max[k]))
+    if max_fdr is None:
+        return len(used), defined, None
+    with np.errstate(invalid="ignore"):
+        keep = [k for k in used if res.q_max[k] <= max_fdr]
+    with open(prefix + ".significant.tsv", "w") as fh:
+        fh.write(res.table.header + "\n")
+        fh.write("".join(res.table.lines[k] + "\n" for k in keep))
+    return len(used), defined, len(keep)
+
+
 def write_compare(prefix, res, min_lfc=None):
     """PREFIX.compare.tsv, PREFIX.diff.tsv and PREFIX.compare.stats.tsv of a PileupPairResult; with min_lfc = T also
     PREFIX.up1.tsv, the `used` rows with LFC >= T, and PREFIX.up2.tsv, those with LFC <= -T, as loop lists (NaN fails both).
@@ -1367,6 +1647,11 @@ def parse_args(args):
                    help="with --enrich: half-width of the peak box the neighbourhoods leave out (default %d, below -w)" % DEFAULT_PEAK)
     p.add_argument("--min-enrichment", dest="min_enrichment", type=float, default=None, metavar="T",
                    help="with --enrich: also write PREFIX.enriched.tsv, the used rows with FE_MIN >= T as a loop list")
+    p.add_argument("--poisson", dest="poisson", action="store_true",
+                   help="with --enrich and --balance ICE|NEWTON on a .hic or pairs file: a Poisson p-value of every used loop's raw "
+                        "centre count against each neighbourhood and BH q-values over the whole list: PREFIX.poisson.tsv")
+    p.add_argument("--max-fdr", dest="max_fdr", type=float, default=None, metavar="T",
+                   help="with --poisson: also write PREFIX.significant.tsv, the used rows with Q_MAX <= T as a loop list")
     p.add_argument("-f2", "--file2", dest="f2_path", default=None,
                    help="a second contact map: pile the list up on both maps and score what differs (PREFIX.1.*, PREFIX.2.*, "
                         "PREFIX.compare.tsv, PREFIX.diff.tsv, PREFIX.compare.stats.tsv; --peak sets the neighbourhoods)")
@@ -1405,6 +1690,47 @@ def compare_request(args, world):
         raise PileupError("--peak %d with -w %d: the peak half-width P must be in 0 .. w - 1 (P >= w leaves no neighbourhood)"
                           % (peak, args.w))
     return peak
+
+
+POISSON_INPUT = "--poisson on %s: the significance needs raw integer counts, one record per pixel -- a .hic file or a .pairs / " \
+                ".pairs.gz file (text counts may be fractional and may repeat a pixel; a .cool file is not read raw)"
+
+
+def poisson_conflict(f, enrich, balance, bias=None, trans=False, genome=False, f2=None, world=1):
+    """Why a run cannot take --poisson (the text of the `Error:` line), None when it can.  Reads nothing."""
+    from .pairs import is_pairs
+    if not enrich:
+        return "--poisson without --enrich: the p-values are taken against the four neighbourhoods of the enrichment; give --enrich"
+    if f2 is not None:
+        return "--poisson with -f2: the significance of a loop on two maps is not built; pile each map up alone"
+    if genome:
+        return "--poisson with --balance-genome: the genome-balanced pile-up keeps no raw counts beside the map"
+    if trans:
+        return "--poisson with --trans: inter-chromosomal pile-ups keep no raw counts beside the map; it is for intra-chromosomal loops"
+    if not balance or str(balance).upper() not in ("ICE", "NEWTON"):
+        return "--poisson without --balance ICE|NEWTON: stored vectors and -b leave no raw counts in hand; give --balance" \
+            + (" (and drop -b)" if bias else "")
+    if not (is_pairs(f) or str(f).endswith(".hic")):
+        return POISSON_INPUT % f
+    if world > 1:
+        return "--poisson in a multi-rank run (world size %d): the q-values are taken over the whole list on one GPU" % world
+    return None
+
+
+def poisson_request(args, f, world):
+    """What --poisson / --max-fdr ask: (True, the threshold or None), (False, None) for a run without them; PileupError with
+    the text of the `Error:` line for a combination that cannot be honoured.  Reads nothing and touches no GPU."""
+    if not args.poisson:
+        if args.max_fdr is not None:
+            raise PileupError("--max-fdr without --poisson: it selects by the q-values of the significance test; give --poisson")
+        return False, None
+    why = poisson_conflict(f, args.enrich, args.balance, args.biasfile, args.trans,
+                           args.balance_genome is not None or args.balance_pixels_given or args.pairs_trans, args.f2_path, world)
+    if why:
+        raise PileupError(why)
+    if args.max_fdr is not None and not 0.0 < args.max_fdr <= 1.0:              # a NaN fails both comparisons
+        raise PileupError("--max-fdr %r: the threshold T must lie in (0, 1] (significant.tsv holds Q_MAX <= T)" % args.max_fdr)
+    return True, args.max_fdr
 
 
 def enrich_request(args):
@@ -1481,6 +1807,7 @@ def main(argv=None):
         two = compare_request(args, world)
         genome = genome_request(args, f, world)
         peak = enrich_request(args) if two is None else None         # with -f2, --peak is the two-map run's own
+        poisson, max_fdr = poisson_request(args, f, world)
     except PileupError as e:
         print("Error: %s" % e)
         return
@@ -1521,7 +1848,7 @@ def main(argv=None):
         res_ = pileup(f, args.loops, res, chromosomes=args.chromosome, norm=args.norm_method, bias=args.biasfile or False,
                       balance=balance, w=args.w, q=args.q, n_min=args.n_min, x_max=x_max, verbose=True, trans=args.trans,
                       balance_genome=genome[0] if genome else None, balance_pixels=genome[1] if genome else "all",
-                      pairs_zero_based=args.pairs_zero_based, peak=peak)
+                      pairs_zero_based=args.pairs_zero_based, peak=peak, **({"poisson": True} if poisson else {}))
     except (PileupError, TransError) as e:
         print("Error: %s" % e)
         return
@@ -1539,6 +1866,12 @@ def main(argv=None):
         print("enrichment with peak half-width %d: aggregate over DONUT, LL, H, V %s -> %s.enrich.tsv, %s.enrich.stats.tsv%s"
               % (peak, ", ".join(_r(v) for v in res_.all["enrich_agg"]), args.prefix, args.prefix,
                  "" if kept is None else "; %d loops with FE_MIN >= %r -> %s.enriched.tsv" % (kept, args.min_enrichment, args.prefix)))
+    if poisson:
+        used, defined, kept = write_poisson(args.prefix, res_, max_fdr)
+        print("significance of %d used loops: %d with a defined P_MAX%s%s -> %s.poisson.tsv%s"
+              % (used, defined, "" if kept is None else ", %d with Q_MAX <= %r" % (kept, max_fdr),
+                 "" if not res_.poisson_unconverged else " (%d tails did not converge: NaN)" % res_.poisson_unconverged,
+                 args.prefix, "" if kept is None else ", %s.significant.tsv" % args.prefix))
 
 
 if __name__ == "__main__":

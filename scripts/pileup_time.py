@@ -4,6 +4,9 @@ loops, w = 10 (GPU box): device events around the three stages (valid + expected
 --warmup; bytes moved from shapes, the expected pass's share of 6.3 TB/s and the enrichment against its byte model (8 L (2w+1)^2
 bytes read).  The two-map leg (two_map_leg) piles the same list up on a second band: pileup_band_pair as a whole, and
 mst_pileup_compare and mst_pileup_reduce_pair alone against their byte model at the copy bandwidth measured in the same run.
+The significance leg (poisson_leg) takes the band's non-zero pixels, rounded, as the chromosome's raw record set (float32 counts, a
+bias of ones): mst_pileup_centre_counts alone against its byte model (12 bytes per record at 6.3 TB/s), mst_pileup_poisson alone,
+and the whole pileup_band call with `peak` and with `peak` and `poisson`, the two alternating.
 Prints one JSON line.  python scripts/pileup_time.py [--steps 20] [--warmup 3] [--peak 2]"""
 import argparse
 import json
@@ -70,6 +73,58 @@ def two_map_leg(a, band, n, D, xs, ys, w, q, p, oe, order, ws, dev):
             "two_map_loops_scored": int((~np.isnan(c["lfc"])).sum())}
 
 
+def poisson_leg(a, band, n, D, xs, ys, w, q, p, obs, E, dev):
+    """The raw record set: every band pixel whose rounded value is >= 1, as (x, dist, float32 count), slab by slab; the bias is 1
+    everywhere, so the balanced band is the raw map and raw_center must equal rint(center_obs)."""
+    xr, dr, cr = [], [], []
+    for i0 in range(0, n, 16384):
+        i1 = min(n, i0 + 16384)
+        c = torch.round(band[:D + 1, i0:i1])
+        d, x = torch.nonzero(c >= 1.0, as_tuple=True)
+        xr.append((x + i0).to(torch.int32))
+        dr.append(d.to(torch.int32))
+        cr.append(c[d, x].to(torch.float32))
+    raw = pl.PoissonInput(torch.cat(xr), torch.cat(dr), torch.cat(cr), torch.ones(n, dtype=torch.float64, device=dev))
+    del xr, dr, cr
+    R, L = int(raw.count.numel()), len(xs)
+    sep = ys - xs
+    keys, inverse = np.unique((xs << 32) | sep, return_inverse=True)
+    kd = torch.from_numpy(keys).to(dev)
+    xd, yd = torch.from_numpy(xs).to(dev), torch.from_numpy(ys).to(dev)
+    lo, hi = int(sep.min()), int(sep.max())
+    in_range = int(((raw.dist >= lo) & (raw.dist <= hi)).sum().item())
+    sums = pl.enrich_windows(obs, w, p, E=E, xs=xd, ys=yd)
+    per_key, flag = pl.centre_counts(raw.x, raw.dist, raw.count, kd, lo, hi)
+    counts = per_key[torch.from_numpy(inverse.reshape(-1).astype(np.int64)).to(dev)]
+    centre, e_centre = obs[:, w, w].contiguous(), E[yd - xd]
+    torch.cuda.synchronize()
+    t_cnt = timed(lambda: pl.centre_counts(raw.x, raw.dist, raw.count, kd, lo, hi), a.steps, a.warmup)
+    t_tail = timed(lambda: pl.poisson_windows(sums, centre, e_centre, counts, raw.bias, xd, yd), a.steps, a.warmup)
+    t_peak, t_both = [], []
+    for _ in range(a.warmup):
+        pl.pileup_band(band, n, D, xs, ys, w, q, peak=p)
+        pl.pileup_band(band, n, D, xs, ys, w, q, peak=p, poisson=raw)
+    for _ in range(a.steps):                                      # alternating: both see the same machine
+        t_peak.append(timed(lambda: pl.pileup_band(band, n, D, xs, ys, w, q, peak=p), 1, 0)[0])
+        t_both.append(timed(lambda: pl.pileup_band(band, n, D, xs, ys, w, q, peak=p, poisson=raw), 1, 0)[0])
+    r = pl.pileup_band(band, n, D, xs, ys, w, q, peak=p, poisson=raw)
+    plain = pl.pileup_band(band, n, D, xs, ys, w, q, peak=p)
+    same = all(np.array_equal(r[k], plain[k], equal_nan=True) for k in ("enrich_exp", "enrich_fe", "fe_min", "enrich_sums"))
+    rec_bytes = 8 * R + 4 * in_range                              # x and dist of every record, the count of those inside the range
+    model = 12 * R / (HBM_TBS * 1e12) * 1e3
+    rnd = lambda t: [round(float(np.median(t)), 4), round(float(min(t)), 4), round(float(max(t)), 4)]     # noqa: E731
+    return {"poisson_records": R, "poisson_records_in_range": in_range, "poisson_keys": int(len(keys)),
+            "centre_counts_ms_med_min_max": [round(v, 4) for v in t_cnt], "centre_counts_model_ms": round(model, 4),
+            "centre_counts_over_model": round(t_cnt[0] / model, 2), "centre_counts_bytes_read": rec_bytes,
+            "centre_counts_TBs": round(rec_bytes / (t_cnt[0] * 1e-3) / 1e12, 3),
+            "poisson_kernel_ms_med_min_max": [round(v, 4) for v in t_tail],
+            "pileup_band_peak_alternating_ms_med_min_max": rnd(t_peak), "pileup_band_poisson_ms_med_min_max": rnd(t_both),
+            "poisson_fractional_flag": int(flag.item()), "poisson_unconverged": int(r["poisson_unconverged"]),
+            "poisson_raw_equals_rint_obs": bool((r["raw_center"] == np.rint(r["center_obs"])).all()),
+            "poisson_ratios_equal_host": bool(same), "poisson_p_max_defined": int((~np.isnan(r["p_max"])).sum()),
+            "poisson_p_max_below_0p05": int((r["p_max"] < 0.05).sum())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -106,6 +161,7 @@ def main():
     t_all2 = timed(lambda: pl.pileup_band(band, n, D, xs, ys, w, q), a.steps, a.warmup)       # again: the run-to-run spread
     r = pl.pileup_band(band, n, D, xs, ys, w, q, peak=p)
     two = two_map_leg(a, band, n, D, xs, ys, w, q, p, oe, order, ws, dev)
+    two.update(poisson_leg(a, band, n, D, xs, ys, w, q, p, obs, E, dev))
     band_bytes = (D + 1) * n * 8
     exp_bytes = 2 * band_bytes                                    # the valid pass and the expected pass each read the band once
     win_bytes = L * S * S * 8 * 3                                 # band reads + obs and oe writes
