@@ -613,9 +613,13 @@ MST_STABLE int mst_pileup_reduce(const double *obs, const double *oe, const int3
 
 /* ---- the pile-up of an inter-chromosomal (trans) pair, from its records (rules: the trans part of mustache_amd/pileup.py;
  * tests/pileup_trans_reference.py restates them).  x, y: dev int32 [N] (bin of A, bin of B), v: dev f64 [N], v > 0 and finite,
- * N < 2^31; a record outside [0, n1) x [0, n2) is ignored.  No float atomics: every output is bit-identical from run to run and
- * under any permutation of the records and of the loops. */
-/* workspace bytes of one call (and of the mst_pileup_reduce that follows it); 0 for a bad argument or w > 64. */
+ * N < 2^31; a record outside [0, n1) x [0, n2) is ignored.  Outside that domain: a record with !(v > 0) -- 0.0, negative, NaN
+ * -- is ignored altogether (no valid flag, no share of the sum, no window), as mst_pileup_trans_batch ignores it; +inf counts
+ * and makes expected NaN.  The call is mst_pileup_trans_batch with P = 1.  No float atomics: every output is bit-identical
+ * from run to run and under any permutation of the records and of the loops. */
+/* workspace bytes of one call (and of the mst_pileup_reduce that follows it), whatever N is: about 8 MiB for the chunk table
+ * of 2^31 records, beside the loops' and the row bits' share; 0 for a bad argument or w > 64.  mst_pileup_trans_windows refuses
+ * a workspace smaller than this. */
 MST_STABLE uint64_t mst_pileup_trans_workspace_bytes(int64_t n1, int64_t n2, int64_t L, int32_t w);
 /* valid_rows[i] (dev uint8 [n1], overwritten) = 1 when a record has x = i, valid_cols[j] (dev uint8 [n2]) alike for y;
  * expected[0] (dev f64 [1]) = the exact sum of v over all records (one rounding; NaN when a v is not finite) / (#valid rows *
@@ -638,9 +642,9 @@ MST_STABLE int mst_pileup_trans_windows(const int32_t *x, const int32_t *y, cons
  * A record with !(v > 0) -- 0.0, negative, NaN -- is ignored altogether (no flag, no share of the sum, no window), and so is a
  * record outside [0, n1[p]) x [0, n2[p]); +inf counts and makes that pair's expected NaN, and only that pair's.
  * expected dev f64 [P]; kept dev int64 [P]: the records of the pair that counted; obs, oe dev f64 [L][2w+1][2w+1]; loop_stats
- * dev f64 [L][3].  For every pair every output has the bits mst_pileup_trans_windows gives on that pair's records with v > 0
- * alone; no float atomics; bit-identical under any permutation of the records within a segment and of the loops within a
- * segment.  0 <= w <= 64, 1 <= q <= 2w + 1, 1 <= P <= 65535, N < 2^31; L = 0 and N = 0 are served. */
+ * dev f64 [L][3].  For every pair every output has the bits mst_pileup_trans_windows gives on that pair's records alone (the
+ * same kernels with P = 1); no float atomics; bit-identical under any permutation of the records within a segment and of the
+ * loops within a segment.  0 <= w <= 64, 1 <= q <= 2w + 1, 1 <= P <= 65535, N < 2^31; L = 0 and N = 0 are served. */
 /* workspace bytes of one call; 0 for a bad argument (P outside 1 .. 65535, w > 64, tables that do not rise from 0). */
 MST_STABLE uint64_t mst_pileup_trans_batch_workspace_bytes(const int64_t *seg_off, const int64_t *n1, const int64_t *loop_off,
                                                            int32_t P, int32_t w);

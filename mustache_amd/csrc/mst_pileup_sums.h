@@ -1,4 +1,4 @@
-// Fixed-order block sums and the window limits shared by the pile-up kernels (mst_pileup.hip, mst_pileup_trans.hip).
+// Fixed-order block sums and the window limits shared by the pile-up kernels (mst_pileup.hip, mst_pileup_trans_batch.hip).
 #pragma once
 #include "mst_common.h"
 

@@ -1,8 +1,12 @@
-// The inter-chromosomal pile-up of mst_pileup_trans.hip for P chromosome pairs at once (mustache_amd/pileup.py states the rules,
-// genome mode; tests/pileup_trans_reference.py restates them per pair).  The records of the pairs are concatenated (x, y, v with
-// seg_off, as mst_balance_apply_pairs writes them), and so are the loops (lx, ly with loop_off).
+// Aggregate peak analysis (APA) of a loop list on inter-chromosomal (trans) pairs, P chromosome pairs at once (mustache_amd/pileup.py
+// states the rules; tests/pileup_trans_reference.py restates them per pair).  A trans pair has no band and no distance decay: the
+// map is the pair's COO records (x = bin of A, y = bin of B, v > 0), the expected value one scalar per pair.  The records of the
+// pairs are concatenated (x, y, v with seg_off, as mst_balance_apply_pairs writes them), and so are the loops (lx, ly with loop_off).
 //
-//   mst_pileup_trans_batch        per pair what mst_pileup_trans_windows gives on that pair's records with v > 0 alone, to the bit
+//   mst_pileup_trans_batch        per pair: one pass over the records for the valid rows / columns, the exact total and the window
+//                                 cells; then E, oe, each loop's centres and its own P2LL.  A pair's values do not depend on the
+//                                 pairs beside it.
+//   mst_pileup_trans_windows      a single pair: the same body with P = 1 (host tables seg_off = {0, N}, loop_off = {0, L})
 //   mst_pileup_reduce_segmented   per pair what mst_pileup_reduce gives on that pair's windows with that pair's order, to the bit
 //
 // A record with !(v > 0) -- zero, negative, NaN -- is ignored altogether: no valid flag, nothing in the sum, no window.  So the
@@ -15,23 +19,30 @@
 //   rank table    (first loop, pair): kThreads loops of ONE pair
 //
 // Launches behind mst_pileup_trans_batch, in stream order (five and a few memsets, whatever P is):
-//   rank_kernel      one workgroup per rank-table entry: its loops sorted by row INSIDE their segment (sx, sy, sid at the
-//                    segment's own positions) -- sum of L_p^2 comparisons, not (sum L_p)^2.
-//   init_kernel      one workgroup per loop: window cells 0.0 / NaN with ITS pair's n1, n2; the row bits of (pair, row).
-//   records_kernel   workgroups stride over the chunk table.  The exact sum's LDS limbs, the kept and the non-finite counts and
-//                    the LDS copy of the row bits belong to the pair of the current chunk; when the next chunk is another
-//                    pair's, the limbs are flushed (64-bit integer atomics into that pair's words) and the next pair's row bits
-//                    are loaded: once per workgroup and pair.  A pair whose bitmap exceeds kLdsFlagWords reads it from global
-//                    memory -- decided per pair, the same values either way.  Window cells: integer max on the bit pattern; the
-//                    binary search runs inside [loop0, loop1) of the pair.
-//   expected_kernel  one workgroup per pair: E and kept.
-//   finish_kernel    one workgroup per loop, reading its pair's E.
+//   rank_kernel      one workgroup per rank-table entry: its loops sorted by row (lx, ties by input position) INSIDE their segment
+//                    (sx, sy, sid at the segment's own positions) -- sum of L_p^2 comparisons, not (sum L_p)^2; L_p is a loop
+//                    list (thousands), not a map.
+//   init_kernel      one workgroup per loop: window cells 0.0 / NaN with ITS pair's n1, n2; the bit "some window covers this row"
+//                    of (pair, row) for its rows lx - w .. lx + w (integer atomicOr).
+//   records_kernel   workgroups stride over the chunk table, 16 B read per record (x, y int32, v f64).  Every record that counts
+//                    marks its pair's valid_rows[x] and valid_cols[y] (plain racing stores of 1) and adds v to the exact sum
+//                    (mst_exact_sum.h).  The exact sum's LDS limbs, the kept and the non-finite counts and the LDS copy of the row
+//                    bits belong to the pair of the current chunk; when the next chunk is another pair's, the limbs are flushed
+//                    (64-bit integer atomics into that pair's words) and the next pair's row bits are loaded: once per workgroup
+//                    and pair.  A pair whose bitmap exceeds kLdsFlagWords reads it from global memory -- decided per pair, the
+//                    same values either way.  A record whose row bit is set binary-searches sx inside [loop0, loop1) of the pair
+//                    for the first loop with lx >= x - w, walks the run up to lx <= x + w and writes the cell of every loop with
+//                    |y - ly| <= w: a 64-bit integer max on the bit pattern of the positive double, so a repeated pixel keeps
+//                    its largest value whatever the order.
+//   expected_kernel  one workgroup per pair: E = exact total / (#valid rows * #valid columns) (integer counts, one division), kept.
+//   finish_kernel    one workgroup per loop, reading its pair's E: oe = obs / E, the two centres and P2LL in a fixed tree.
 // mst_pileup_reduce_segmented is two launches: the partial sums of every (cell block, 512-loop chunk of one pair), then per
-// (pair, cell) the chunks of that pair in chunk order.
+// (pair, cell) the chunks of that pair in chunk order, with the arithmetic of mst_pileup.hip's reduce.
 //
-// The arithmetic of every kernel is that of its single-pair counterpart in mst_pileup_trans.hip / mst_pileup.hip, expression for
-// expression; the sums are integer sums (mst_exact_sum.h) or fixed-order trees.  No float atomics: every output is bit-identical
-// from run to run and under any permutation of the records within a segment and of the loops within a segment.
+// The exact sum keeps kSumCopies copies of its LDS limbs, chosen by lane: the values of a trans map share a few exponents, so the
+// lanes of a wave hit the same limbs, and LDS atomics on one address are served one after another.  The sums are integer sums
+// (mst_exact_sum.h) or fixed-order trees.  No float atomics: every output is bit-identical from run to run and under any
+// permutation of the records within a segment and of the loops within a segment.
 #include <cmath>
 #include <vector>
 #include "mst_common.h"
@@ -51,7 +62,7 @@ using mst_pileup::grid_ok;
 using mst_pileup::kThreads;
 using mst_pileup::kWaves;
 
-constexpr int kLdsFlagWords = 4096;        // as mst_pileup_trans.hip: 16 KiB of row bits in LDS = 131 072 rows of one pair
+constexpr int kLdsFlagWords = 4096;        // 16 KiB of row bits in LDS = 131 072 rows of one pair; beyond, read from global
 constexpr int kSumCopies = 16;             // copies of the exact sum's LDS limbs, one per lane & 15
 constexpr int kSumStride = kLimbs + 1;
 constexpr int kRecordBlocks = 2048;        // grid cap of the record pass
@@ -59,6 +70,8 @@ constexpr int kChunk = 4096;               // records of a chunk: 16 per thread,
 constexpr int kLoopChunk = 512;            // loops per chunk of the reduce, as mst_pileup.hip
 constexpr int kLoopsPerWave = kLoopChunk / kWaves;
 constexpr int kMaxPairs = 65535;
+constexpr int64_t kMaxRecords = ((int64_t)1 << 31) - 1;      // of one call
+constexpr uint64_t kKeptSlot = 256;        // mst_pileup_trans_windows: the batch's `kept` word, at the start of the workspace
 
 struct PairRow {                           // one pair of the batch
     int64_t seg0, seg1;                    // its records
@@ -402,46 +415,32 @@ int check_pairs(const char *who, int32_t P) {
     return MST_OK;
 }
 
-}  // namespace
-
-extern "C" uint64_t mst_pileup_trans_batch_workspace_bytes(const int64_t *seg_off, const int64_t *n1, const int64_t *loop_off,
-                                                           int32_t P, int32_t w) {
-    if (P < 1 || P > kMaxPairs || w < 0 || w > mst_pileup::kMaxW || !seg_off || !n1 || !loop_off) return 0;
-    if (!offsets_ok(seg_off, P, seg_off[P]) || !offsets_ok(loop_off, P, loop_off[P])) return 0;
-    for (int32_t p = 0; p < P; ++p)
-        if (n1[p] < 1 || n1[p] > INT32_MAX) return 0;
-    return layout(seg_off, n1, loop_off, P, loop_off[P]).end + 256;
-}
-
-extern "C" int mst_pileup_trans_batch(const int32_t *x, const int32_t *y, const double *v, int64_t N, const int64_t *seg_off,
-                                      const int64_t *n1, const int64_t *n2, const int64_t *lx, const int64_t *ly, int64_t L,
-                                      const int64_t *loop_off, int32_t P, int32_t w, int32_t q, uint8_t *valid_rows,
-                                      uint8_t *valid_cols, double *expected, int64_t *kept, double *obs, double *oe,
-                                      double *loop_stats, void *workspace, uint64_t workspace_bytes, void *stream) {
-    MST_RANGE("pileup: mst_pileup_trans_batch");
-    int rc = check_w("mst_pileup_trans_batch", w, q);
+// ---- the body behind both entry points (`who` names the caller in a refusal): every check, the tables, the launches ------------
+int run_batch(const char *who, const int32_t *x, const int32_t *y, const double *v, int64_t N, const int64_t *seg_off,
+              const int64_t *n1, const int64_t *n2, const int64_t *lx, const int64_t *ly, int64_t L, const int64_t *loop_off,
+              int32_t P, int32_t w, int32_t q, uint8_t *valid_rows, uint8_t *valid_cols, double *expected, int64_t *kept,
+              double *obs, double *oe, double *loop_stats, void *workspace, uint64_t workspace_bytes, void *stream) {
+    int rc = check_w(who, w, q);
     if (rc != MST_OK) return rc;
-    if ((rc = check_pairs("mst_pileup_trans_batch", P)) != MST_OK) return rc;
-    if (N < 0 || N >= ((int64_t)1 << 31) || L < 0 || L > INT32_MAX || !n1 || !n2 || !valid_rows || !valid_cols || !expected ||
+    if ((rc = check_pairs(who, P)) != MST_OK) return rc;
+    if (N < 0 || N > kMaxRecords || L < 0 || L > INT32_MAX || !n1 || !n2 || !valid_rows || !valid_cols || !expected ||
         !kept || (N > 0 && (!x || !y || !v)) || (L > 0 && (!lx || !ly || !obs || !oe || !loop_stats)))
-        return mst::fail(MST_E_ARG, "mst_pileup_trans_batch: bad argument (N %lld < 2^31 records, L %lld)", (long long)N,
-                         (long long)L);
+        return mst::fail(MST_E_ARG, "%s: bad argument (N %lld < 2^31 records, L %lld)", who, (long long)N, (long long)L);
     if (!offsets_ok(seg_off, P, N) || !offsets_ok(loop_off, P, L))
-        return mst::fail(MST_E_ARG, "mst_pileup_trans_batch: seg_off / loop_off (host, P + 1 entries) must rise from 0 to N = %lld "
-                         "/ L = %lld", (long long)N, (long long)L);
+        return mst::fail(MST_E_ARG, "%s: seg_off / loop_off (host, P + 1 entries) must rise from 0 to N = %lld / L = %lld", who,
+                         (long long)N, (long long)L);
     int64_t rows = 0, cols = 0;
     for (int32_t p = 0; p < P; ++p) {
         if (n1[p] < 1 || n2[p] < 1 || n1[p] > INT32_MAX || n2[p] > INT32_MAX)
-            return mst::fail(MST_E_ARG, "mst_pileup_trans_batch: pair %d is %lld x %lld bins", (int)p, (long long)n1[p],
-                             (long long)n2[p]);
+            return mst::fail(MST_E_ARG, "%s: pair %d is %lld x %lld bins", who, (int)p, (long long)n1[p], (long long)n2[p]);
         rows += n1[p];
         cols += n2[p];
     }
     const Layout o = layout(seg_off, n1, loop_off, P, L);
     if (!workspace || workspace_bytes < o.end)
-        return mst::fail(MST_E_ARG, "mst_pileup_trans_batch: workspace of %llu bytes, %llu needed",
-                         (unsigned long long)workspace_bytes, (unsigned long long)o.end);
-    if (L > 0 && (rc = grid_ok("mst_pileup_trans_batch", L)) != MST_OK) return rc;
+        return mst::fail(MST_E_ARG, "%s: workspace of %llu bytes, %llu needed", who, (unsigned long long)workspace_bytes,
+                         (unsigned long long)o.end);
+    if (L > 0 && (rc = grid_ok(who, L)) != MST_OK) return rc;
 
     // the tables: one blob, one copy
     static thread_local std::vector<char> blob;
@@ -507,6 +506,53 @@ extern "C" int mst_pileup_trans_batch(const int32_t *x, const int32_t *y, const 
         MST_LAUNCH_CHECK();
     }
     return MST_OK;
+}
+
+}  // namespace
+
+extern "C" uint64_t mst_pileup_trans_batch_workspace_bytes(const int64_t *seg_off, const int64_t *n1, const int64_t *loop_off,
+                                                           int32_t P, int32_t w) {
+    if (P < 1 || P > kMaxPairs || w < 0 || w > mst_pileup::kMaxW || !seg_off || !n1 || !loop_off) return 0;
+    if (!offsets_ok(seg_off, P, seg_off[P]) || !offsets_ok(loop_off, P, loop_off[P])) return 0;
+    for (int32_t p = 0; p < P; ++p)
+        if (n1[p] < 1 || n1[p] > INT32_MAX) return 0;
+    return layout(seg_off, n1, loop_off, P, loop_off[P]).end + 256;
+}
+
+extern "C" int mst_pileup_trans_batch(const int32_t *x, const int32_t *y, const double *v, int64_t N, const int64_t *seg_off,
+                                      const int64_t *n1, const int64_t *n2, const int64_t *lx, const int64_t *ly, int64_t L,
+                                      const int64_t *loop_off, int32_t P, int32_t w, int32_t q, uint8_t *valid_rows,
+                                      uint8_t *valid_cols, double *expected, int64_t *kept, double *obs, double *oe,
+                                      double *loop_stats, void *workspace, uint64_t workspace_bytes, void *stream) {
+    MST_RANGE("pileup: mst_pileup_trans_batch");
+    return run_batch("mst_pileup_trans_batch", x, y, v, N, seg_off, n1, n2, lx, ly, L, loop_off, P, w, q, valid_rows, valid_cols,
+                     expected, kept, obs, oe, loop_stats, workspace, workspace_bytes, stream);
+}
+
+// ---- a single pair: a batch of one.  The caller's workspace starts with the slot of the batch's `kept` word, which this call does
+// not hand out.  N is no argument of the size query, so it reports the chunk table of the most records a call takes (8 MiB).
+extern "C" uint64_t mst_pileup_trans_workspace_bytes(int64_t n1, int64_t n2, int64_t L, int32_t w) {
+    if (n1 <= 0 || n2 <= 0 || n1 > INT32_MAX || n2 > INT32_MAX || L < 0 || L > INT32_MAX || w < 0 || w > mst_pileup::kMaxW) return 0;
+    const int64_t seg_off[2] = {0, kMaxRecords}, loop_off[2] = {0, L};
+    const uint64_t own = kKeptSlot + layout(seg_off, &n1, loop_off, 1, L).end;
+    const uint64_t red = mst_pileup_workspace_bytes(1, 0, L, w);                              // mst_pileup_reduce comes after
+    return (own > red ? own : red) + 256;
+}
+
+extern "C" int mst_pileup_trans_windows(const int32_t *x, const int32_t *y, const double *v, int64_t N, int64_t n1, int64_t n2,
+                                        const int64_t *lx, const int64_t *ly, int64_t L, int32_t w, int32_t q, uint8_t *valid_rows,
+                                        uint8_t *valid_cols, double *expected, double *obs, double *oe, double *loop_stats,
+                                        void *workspace, uint64_t workspace_bytes, void *stream) {
+    MST_RANGE("pileup: mst_pileup_trans_windows");
+    const uint64_t need = mst_pileup_trans_workspace_bytes(n1, n2, L, w);      // 0: a bad n1, n2, L or w, which run_batch names
+    if (need && (!workspace || workspace_bytes < need))
+        return mst::fail(MST_E_ARG, "mst_pileup_trans_windows: workspace of %llu bytes, %llu needed",
+                         (unsigned long long)workspace_bytes, (unsigned long long)need);
+    const int64_t seg_off[2] = {0, N}, loop_off[2] = {0, L};
+    char *base = static_cast<char *>(workspace);
+    return run_batch("mst_pileup_trans_windows", x, y, v, N, seg_off, &n1, &n2, lx, ly, L, loop_off, 1, w, q, valid_rows,
+                     valid_cols, expected, reinterpret_cast<int64_t *>(base), obs, oe, loop_stats, base ? base + kKeptSlot : nullptr,
+                     need ? need - kKeptSlot : 0, stream);
 }
 
 extern "C" uint64_t mst_pileup_reduce_segmented_workspace_bytes(const int64_t *loop_off, int32_t P, int32_t w) {

@@ -48,8 +48,12 @@ restates the rules).  Without the switch nothing changes: rows with two chromoso
     diagonal than another: the four corners are equivalent by symmetry, and "LL" names an index range only.
   * Aggregate: the loops sorted by (a, b), the same reduce with the same chunks of 512; genome-wide = the pair partials added
     in run order; the same metrics().  Bit-identical under any permutation of the records and of the rows.
-Device work (mustache_amd/csrc/mst_pileup_trans.hip): one pass over the pair's records finds the valid rows and columns, the
-exact total and the window cells together; one host wait per pair.
+  * Records outside the rule: pileup_trans_records() ignores a record whose v is not > 0 (zero, negative, NaN) altogether -- no
+    valid flag, no share of E, no window -- as it ignores one off the map; +inf counts and makes E NaN.  read_trans_contacts
+    hands over v > 0 and finite only, so no run meets either.
+Device work (mustache_amd/csrc/mst_pileup_trans_batch.hip): one pass over the pair's records finds the valid rows and columns,
+the exact total and the window cells together; one host wait per pair.  A pair alone is a batch of one pair of the genome
+mode's kernels below.
 
 Genome mode (`--trans --balance-genome ICE|NEWTON [--balance-pixels all|inter] [--pairs-trans]`, `pileup(..., trans=True,
 balance_genome=...)`, `pileup_trans_batch()`): the lists the callers write from a raw `.hic` file or a pairs file, piled up on
@@ -72,10 +76,10 @@ the map they were called from.  The rows, the windows, E, the aggregate and the 
   * Refused: --balance-genome without --trans, with --balance, -b or -norm other than NONE, on `.cool` / `.mcool` / text input;
     --balance-pixels without --balance-genome; a pairs file without --pairs-trans; --pairs-trans without --balance-genome or
     on another input; --pairs-zero-based without --pairs-trans (no other pile-up bins a pairs file with it).  Each is one `Error:` line before anything is read.
-Device work (mustache_amd/csrc/mst_pileup_trans_batch.hip): mst_pileup_trans_batch is mst_pileup_trans_windows for P pairs in
-five launches -- a record whose v' is not > 0 is skipped in the pass, so the balanced records go in without a compaction --
-and mst_pileup_reduce_segmented the reduce for P pairs in two; every pair's values have the bits the single-pair entry points
-give on that pair alone.
+Device work (mustache_amd/csrc/mst_pileup_trans_batch.hip): mst_pileup_trans_batch serves P pairs in five launches -- a record
+whose v' is not > 0 is skipped in the pass, so the balanced records go in without a compaction -- and
+mst_pileup_reduce_segmented is the reduce for P pairs in two; every pair's values have the bits a batch of that pair alone
+gives.
 
 Enrichment (`--enrich [--peak P] [--min-enrichment T]`, `peak=P` on pileup() / pileup_band() / pileup_trans_records() /
 pileup_trans_batch(); tests/pileup_enrich_reference.py restates the rules).  Every used loop against its own local background,
@@ -501,18 +505,46 @@ def reduce(obs, oe, order, w, ws):
     return agg
 
 
+def _loop_bins(xs, ys):
+    import torch
+    xs = np.asarray(xs.cpu() if isinstance(xs, torch.Tensor) else xs, np.int64).reshape(-1)
+    ys = np.asarray(ys.cpu() if isinstance(ys, torch.Tensor) else ys, np.int64).reshape(-1)
+    if len(xs) != len(ys):
+        raise PileupError("xs and ys differ in length (%d, %d)" % (len(xs), len(ys)))
+    return xs, ys
+
+
+def _one_copy(parts):
+    """The one concatenated copy, and the one host wait, of a chromosome, pair or batch.  parts: [(name, device tensor)] in the
+    order they travel, float64 or int64 (carried as float64 bits).  Returns {name: flat host array}, an int64 part viewed back."""
+    import torch
+    host = torch.cat([(t.view(torch.float64) if t.dtype == torch.int64 else t).view(-1) for _, t in parts]).cpu().numpy()
+    out, at = {}, 0
+    for name, t in parts:
+        piece = host[at:at + t.numel()]
+        out[name] = piece.view(np.int64) if t.dtype == torch.int64 else piece
+        at += t.numel()
+    return out
+
+
+def _result(agg, st, w, q, valid, expected, obs, oe):
+    """The 15 keys every pile-up dict has, from the host aggregate [4, S, S], the host loop statistics [L, 3] and the device
+    handles (or whatever stands for them)."""
+    apa, apa_oe = mean_map(agg[0], agg[1]), mean_map(agg[2], agg[3])
+    return {"valid": valid, "expected": expected, "obs": obs, "oe": oe, "sum_obs": agg[0], "count_obs": agg[1], "sum_oe": agg[2],
+            "count_oe": agg[3], "apa": apa, "apa_oe": apa_oe, "center_obs": st[:, 0].copy(), "center_oe": st[:, 1].copy(),
+            "p2ll": st[:, 2].copy(), "metrics": metrics(apa, w, q), "metrics_oe": metrics(apa_oe, w, q)}
+
+
 def _empty_result(w, q, peak=None, poisson=False):
     S = 2 * w + 1
-    z = np.zeros((S, S))
-    M = np.full((S, S), np.nan)
     if poisson:
         return dict(_empty_result(w, q, peak), poisson_unconverged=0,
                     **_poisson_result(np.zeros((4, 0, 4)), np.zeros(0, np.int64), np.zeros(0), np.zeros(0)))
     if peak is not None:
-        return dict(_empty_result(w, q), **_enrich_result(np.zeros((0, 4, 3)), np.zeros(0), np.zeros(0), M, w, peak))
-    return {"valid": None, "expected": None, "obs": None, "oe": None, "sum_obs": z, "count_obs": z.copy(), "sum_oe": z.copy(),
-            "count_oe": z.copy(), "apa": M, "apa_oe": M.copy(), "center_obs": np.zeros(0), "center_oe": np.zeros(0),
-            "p2ll": np.zeros(0), "metrics": metrics(M, w, q), "metrics_oe": metrics(M, w, q)}
+        return dict(_empty_result(w, q), **_enrich_result(np.zeros((0, 4, 3)), np.zeros(0), np.zeros(0), np.full((S, S), np.nan),
+                                                          w, peak))
+    return _result(np.zeros((4, S, S)), np.zeros((0, 3)), w, q, None, None, None, None)
 
 
 def pileup_band(band, n, D, xs, ys, w=10, q=6, peak=None, poisson=None):
@@ -533,10 +565,7 @@ def pileup_band(band, n, D, xs, ys, w=10, q=6, peak=None, poisson=None):
         check_peak(w, peak)
     elif poisson is not None:
         raise PileupError("poisson= without peak=: the significance is taken against the four neighbourhoods of the enrichment")
-    xs = np.asarray(xs.cpu() if isinstance(xs, torch.Tensor) else xs, np.int64).reshape(-1)
-    ys = np.asarray(ys.cpu() if isinstance(ys, torch.Tensor) else ys, np.int64).reshape(-1)
-    if len(xs) != len(ys):
-        raise PileupError("xs and ys differ in length (%d, %d)" % (len(xs), len(ys)))
+    xs, ys = _loop_bins(xs, ys)
     L, S = len(xs), 2 * w + 1
     if L == 0:
         return _empty_result(w, q, peak, poisson is not None)
@@ -551,10 +580,10 @@ def pileup_band(band, n, D, xs, ys, w=10, q=6, peak=None, poisson=None):
         obs, oe, st = windows(band, n, D, E, xd, yd, w, q)
         order = torch.from_numpy(np.lexsort((ys, xs)).astype(np.int32)).to(dev, non_blocking=True)
         agg = reduce(obs, oe, order, w, ws)
-        parts = [agg.view(-1), st.view(-1)]
+        parts = [("agg", agg), ("st", st)]
         if peak is not None:
             sums, e_centre = enrich_windows(obs, w, peak, E=E, xs=xd, ys=yd), E[yd - xd]
-            parts += [sums.view(-1), e_centre]
+            parts += [("sums", sums), ("e_centre", e_centre)]
         if poisson is not None:
             if bool(((xs < 0) | (ys < xs)).any()):
                 raise PileupError("poisson=: a loop's bins must satisfy 0 <= x <= y")
@@ -568,87 +597,39 @@ def pileup_band(band, n, D, xs, ys, w=10, q=6, peak=None, poisson=None):
             if int(bias.numel()) <= int(ys.max()):
                 raise PileupError("poisson=: the bias vector has %d bins, the loops reach bin %d" % (bias.numel(), int(ys.max())))
             out4, _ = poisson_windows(sums, st[:, 0], e_centre, counts, bias, xd, yd, unconverged=words[1:])
-            parts += [out4.view(-1), counts.view(torch.float64), bias[xd], bias[yd], words.view(torch.float64)]
-        host = torch.cat(parts).cpu().numpy()                             # the one wait
-    agg_h, st_h = host[:4 * S * S].reshape(4, S, S), host[4 * S * S:4 * S * S + 3 * L].reshape(L, 3)
-    apa, apa_oe = mean_map(agg_h[0], agg_h[1]), mean_map(agg_h[2], agg_h[3])
-    out = {"valid": valid, "expected": E, "obs": obs, "oe": oe, "sum_obs": agg_h[0], "count_obs": agg_h[1],
-           "sum_oe": agg_h[2], "count_oe": agg_h[3], "apa": apa, "apa_oe": apa_oe, "center_obs": st_h[:, 0].copy(),
-           "center_oe": st_h[:, 1].copy(), "p2ll": st_h[:, 2].copy(), "metrics": metrics(apa, w, q),
-           "metrics_oe": metrics(apa_oe, w, q)}
-    at = 4 * S * S + 3 * L
+            parts += [("out4", out4), ("counts", counts), ("bias1", bias[xd]), ("bias2", bias[yd]), ("words", words)]
+        host = _one_copy(parts)
+    out = _result(host["agg"].reshape(4, S, S), host["st"].reshape(L, 3), w, q, valid, E, obs, oe)
     if poisson is not None:
-        tail = host[at + 13 * L:]
-        bad, unconverged = (int(v) for v in tail[19 * L:].view(np.int64))
+        bad, unconverged = (int(v) for v in host["words"])
         if bad:
             raise PileupError("a raw count is not an integer value: the significance needs raw integer counts")
-        out4 = tail[:16 * L].reshape(4, L, 4)
-        out.update(_enrich_result(host[at:at + 12 * L], out["center_obs"], host[at + 12 * L:at + 13 * L], apa_oe, w, peak,
+        out4 = host["out4"].reshape(4, L, 4)
+        out.update(_enrich_result(host["sums"], out["center_obs"], host["e_centre"], out["apa_oe"], w, peak,
                                   ratios=(out4[0], out4[1])))
-        out.update(_poisson_result(out4, tail[16 * L:17 * L].view(np.int64), tail[17 * L:18 * L], tail[18 * L:19 * L]))
+        out.update(_poisson_result(out4, host["counts"], host["bias1"], host["bias2"]))
         out["poisson_unconverged"] = unconverged
     elif peak is not None:
-        out.update(_enrich_result(host[at:at + 12 * L], out["center_obs"], host[at + 12 * L:], apa_oe, w, peak))
+        out.update(_enrich_result(host["sums"], out["center_obs"], host["e_centre"], out["apa_oe"], w, peak))
     return out
 
 
 def pileup_trans_records(x, y, v, n1, n2, xs, ys, w=10, q=6, peak=None):
     """The pile-up of one inter-chromosomal pair's records (x = bins of A, y = bins of B, v > 0; host arrays or device tensors)
-    on the n1 x n2 map around the loops (xs, ys) (bins of A, bins of B).  Returns pileup_band's dict with "expected" the
-    scalar E (a float) and "valid" the pair (rows uint8 [n1], columns uint8 [n2]) of device tensors.  L = 0 still finds the
-    valid flags and E; N = 0 gives E = 0.  One host wait.  peak=p adds pileup_band's enrichment keys, every cell's e and E_centre
-    being the scalar E."""
-    import torch
-    from . import _lib
-    from ._lib import ptr as _ptr, stream as _stream, require_gpu
+    on the n1 x n2 map around the loops (xs, ys) (bins of A, bins of B): pileup_trans_batch's dict of a batch of this one pair.
+    That is pileup_band's dict with "expected" the scalar E (a float), "valid" the pair (rows uint8 [n1], columns uint8 [n2]) of
+    device tensors and "kept", the records that counted (those with v > 0 on the map).  L = 0 still finds the valid flags and E;
+    N = 0 gives E = 0.  One host wait.  peak=p adds pileup_band's enrichment keys, every cell's e and E_centre being the scalar E."""
     w, q, n1, n2 = int(w), int(q), int(n1), int(n2)
     check_window(w, q)
     if peak is not None:
         check_peak(w, peak)
-    xs = np.asarray(xs.cpu() if isinstance(xs, torch.Tensor) else xs, np.int64).reshape(-1)
-    ys = np.asarray(ys.cpu() if isinstance(ys, torch.Tensor) else ys, np.int64).reshape(-1)
-    if len(xs) != len(ys):
-        raise PileupError("xs and ys differ in length (%d, %d)" % (len(xs), len(ys)))
+    xs, ys = _loop_bins(xs, ys)
     if not (len(x) == len(y) == len(v)):
         raise PileupError("x, y and v differ in length (%d, %d, %d)" % (len(x), len(y), len(v)))
     if n1 < 1 or n2 < 1:
         raise PileupError("a trans map needs n1 >= 1 and n2 >= 1 (got %d x %d)" % (n1, n2))
-    lib = require_gpu()
-    dev = v.device if isinstance(v, torch.Tensor) and v.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    L, S = len(xs), 2 * w + 1
-    with torch.cuda.device(dev):
-        x = torch.as_tensor(x).to(dev, dtype=torch.int32).contiguous()
-        y = torch.as_tensor(y).to(dev, dtype=torch.int32).contiguous()
-        v = torch.as_tensor(v).to(dev, dtype=torch.float64).contiguous()
-        ws = torch.empty(max(int(lib.mst_pileup_trans_workspace_bytes(n1, n2, L, w)), 256), dtype=torch.uint8, device=dev)
-        rows = torch.empty(n1, dtype=torch.uint8, device=dev)
-        cols = torch.empty(n2, dtype=torch.uint8, device=dev)
-        E = torch.empty(1, dtype=torch.float64, device=dev)
-        obs = torch.empty((L, S, S), dtype=torch.float64, device=dev)
-        oe = torch.empty_like(obs)
-        st = torch.empty((L, 3), dtype=torch.float64, device=dev)
-        xd = torch.from_numpy(xs).to(dev, non_blocking=True)
-        yd = torch.from_numpy(ys).to(dev, non_blocking=True)
-        N = int(v.numel())
-        _lib.check(lib.mst_pileup_trans_windows(_ptr(x) if N else None, _ptr(y) if N else None, _ptr(v) if N else None, N, n1, n2,
-                                                _ptr(xd) if L else None, _ptr(yd) if L else None, L, w, q, _ptr(rows), _ptr(cols),
-                                                _ptr(E), _ptr(obs) if L else None, _ptr(oe) if L else None,
-                                                _ptr(st) if L else None, _ptr(ws), ws.numel(), _stream()))
-        order = torch.from_numpy(np.lexsort((ys, xs)).astype(np.int32)).to(dev, non_blocking=True)
-        agg = reduce(obs, oe, order, w, ws)
-        parts = [agg.view(-1), st.view(-1), E]
-        if peak is not None:
-            parts.insert(2, enrich_windows(obs, w, peak, e_loop=E.expand(L).contiguous()).view(-1))
-        host = torch.cat(parts).cpu().numpy()                             # the one wait
-    agg_h, st_h = host[:4 * S * S].reshape(4, S, S), host[4 * S * S:4 * S * S + 3 * L].reshape(L, 3)
-    apa, apa_oe = mean_map(agg_h[0], agg_h[1]), mean_map(agg_h[2], agg_h[3])
-    out = {"valid": (rows, cols), "expected": float(host[-1]), "obs": obs, "oe": oe, "sum_obs": agg_h[0], "count_obs": agg_h[1],
-           "sum_oe": agg_h[2], "count_oe": agg_h[3], "apa": apa, "apa_oe": apa_oe, "center_obs": st_h[:, 0].copy(),
-           "center_oe": st_h[:, 1].copy(), "p2ll": st_h[:, 2].copy(), "metrics": metrics(apa, w, q),
-           "metrics_oe": metrics(apa_oe, w, q)}
-    if peak is not None:
-        out.update(_enrich_result(host[-1 - 12 * L:-1], out["center_obs"], np.full(L, host[-1]), apa_oe, w, peak))
-    return out
+    return pileup_trans_batch(x, y, v, [0, len(v)], [(n1, n2)], [(xs, ys)], w, q, peak)[0]
 
 
 def _host_ptr(a):
@@ -658,13 +639,14 @@ def _host_ptr(a):
 
 
 def pileup_trans_batch(x, y, v, seg_off, dims, loops, w=10, q=6, peak=None):
-    """pileup_trans_records for P inter-chromosomal pairs in shared launches (csrc/mst_pileup_trans_batch.hip).  x, y, v: the
-    pairs' records concatenated (device int32 / int32 / float64, or host arrays; None when there is none), pair p owning
-    [seg_off[p], seg_off[p + 1]) -- seg_off a HOST table of P + 1 entries; a record whose v is not > 0 is ignored, so the output of
+    """The pile-up of P inter-chromosomal pairs in shared launches (csrc/mst_pileup_trans_batch.hip).  x, y, v: the pairs' records
+    concatenated (device int32 / int32 / float64, or host arrays; None when there is none), pair p owning [seg_off[p],
+    seg_off[p + 1]) -- seg_off a HOST table of P + 1 entries; a record whose v is not > 0 is ignored, so the output of
     mst_balance_apply_pairs goes in unfiltered.  dims: [(n1, n2)] per pair; loops: [(xs, ys)] per pair (host arrays, bins of A
-    and of B; either may be empty).  Returns one dict per pair with pileup_trans_records' keys -- "obs", "oe" and "valid" are
-    views into the batch's device tensors -- and "kept", the records of the pair that counted.  Every value has the bits
-    pileup_trans_records gives on that pair's records with v > 0 alone.  One host wait for the whole batch.  peak=p adds the
+    and of B; either may be empty).  Returns one dict per pair: pileup_band's keys with "expected" the pair's scalar E (a float)
+    and "valid" the pair (rows uint8 [n1], columns uint8 [n2]) -- "obs", "oe" and "valid" are views into the batch's device
+    tensors -- and "kept", the records of the pair that counted.  A pair's values do not depend on the pairs beside it: they have
+    the bits of a batch of that pair alone (pileup_trans_records).  One host wait for the whole batch.  peak=p adds the
     enrichment keys to every pair's dict: one launch over all the windows, each loop's e its own pair's E, gathered on the device."""
     import torch
     from . import _lib
@@ -722,29 +704,23 @@ def pileup_trans_batch(x, y, v, seg_off, dims, loops, w=10, q=6, peak=None):
             _stream()))
         _lib.check(lib.mst_pileup_reduce_segmented(_ptr(obs) if L else None, _ptr(oe) if L else None, _ptr(order_d) if L else None,
                                                    L, _host_ptr(loop_off), P, w, _ptr(agg), _ptr(ws), ws.numel(), _stream()))
-        parts = [agg.view(-1), st.view(-1), E, kept.view(torch.float64)]
+        parts = [("agg", agg), ("st", st), ("E", E), ("kept", kept)]
         if peak is not None:                           # e_loop: the E of the pair each loop belongs to
             pair_of = torch.from_numpy(np.repeat(np.arange(P, dtype=np.int64), np.diff(loop_off))).to(dev, non_blocking=True)
-            parts.insert(2, enrich_windows(obs, w, peak, e_loop=E[pair_of]).view(-1))
-        host = torch.cat(parts).cpu().numpy()                                                         # the one wait
-    agg_h = host[:P * 4 * S * S].reshape(P, 4, S, S)
-    st_h = host[P * 4 * S * S:P * 4 * S * S + 3 * L].reshape(L, 3)
-    E_h, kept_h = host[-2 * P:-P], host[-P:].view(np.int64)
-    en_h = host[P * 4 * S * S + 3 * L:P * 4 * S * S + 15 * L].reshape(L, 4, 3) if peak is not None else None
+            parts.insert(2, ("sums", enrich_windows(obs, w, peak, e_loop=E[pair_of])))
+        host = _one_copy(parts)
+    agg_h, st_h = host["agg"].reshape(P, 4, S, S), host["st"].reshape(L, 3)
     row_off = np.concatenate([[0], np.cumsum(n1)])
     col_off = np.concatenate([[0], np.cumsum(n2)])
     out = []
     for p in range(P):
         l0, l1 = int(loop_off[p]), int(loop_off[p + 1])
-        a = agg_h[p]
-        apa, apa_oe = mean_map(a[0], a[1]), mean_map(a[2], a[3])
-        out.append({"valid": (rows[int(row_off[p]):int(row_off[p + 1])], cols[int(col_off[p]):int(col_off[p + 1])]),
-                    "expected": float(E_h[p]), "kept": int(kept_h[p]), "obs": obs[l0:l1], "oe": oe[l0:l1], "sum_obs": a[0],
-                    "count_obs": a[1], "sum_oe": a[2], "count_oe": a[3], "apa": apa, "apa_oe": apa_oe,
-                    "center_obs": st_h[l0:l1, 0].copy(), "center_oe": st_h[l0:l1, 1].copy(), "p2ll": st_h[l0:l1, 2].copy(),
-                    "metrics": metrics(apa, w, q), "metrics_oe": metrics(apa_oe, w, q)})
+        valid = (rows[int(row_off[p]):int(row_off[p + 1])], cols[int(col_off[p]):int(col_off[p + 1])])
+        out.append(_result(agg_h[p], st_h[l0:l1], w, q, valid, float(host["E"][p]), obs[l0:l1], oe[l0:l1]))
+        out[-1]["kept"] = int(host["kept"][p])
         if peak is not None:
-            out[-1].update(_enrich_result(en_h[l0:l1], out[-1]["center_obs"], np.full(l1 - l0, E_h[p]), apa_oe, w, peak))
+            out[-1].update(_enrich_result(host["sums"].reshape(L, 4, 3)[l0:l1], out[-1]["center_obs"],
+                                          np.full(l1 - l0, host["E"][p]), out[-1]["apa_oe"], w, peak))
     return out
 
 
@@ -853,7 +829,7 @@ def _compare_resident(r1, r2, xs, ys, w, q, p):
     """the compare dict of two pile-up dicts of the same loops (xs, ys) whose "oe" windows are still on the device: two launches
     and a finish, one host wait"""
     import torch
-    L, S = len(xs), 2 * w + 1
+    L = len(xs)
     if L == 0:
         return _empty_compare(w, q, p)
     from ._lib import require_gpu
@@ -862,18 +838,8 @@ def _compare_resident(r1, r2, xs, ys, w, q, p):
     with torch.cuda.device(oe1.device):
         ws = _workspace(lib, 1, 0, L, w, oe1.device)
         order = torch.from_numpy(np.lexsort((ys, xs)).astype(np.int32)).to(oe1.device, non_blocking=True)
-        parts = [reduce_pair(oe1, oe2, order, w, ws).view(-1), compare_windows(oe1, oe2, w, p).view(-1)]
-        host = torch.cat(parts).cpu().numpy()                             # the one wait
-    return _compare_result(host[3 * S * S:], r1["center_oe"], r2["center_oe"], host[:3 * S * S], w, q, p)
-
-
-def _loop_bins(xs, ys):
-    import torch
-    xs = np.asarray(xs.cpu() if isinstance(xs, torch.Tensor) else xs, np.int64).reshape(-1)
-    ys = np.asarray(ys.cpu() if isinstance(ys, torch.Tensor) else ys, np.int64).reshape(-1)
-    if len(xs) != len(ys):
-        raise PileupError("xs and ys differ in length (%d, %d)" % (len(xs), len(ys)))
-    return xs, ys
+        host = _one_copy([("agg", reduce_pair(oe1, oe2, order, w, ws)), ("sums", compare_windows(oe1, oe2, w, p))])
+    return _compare_result(host["sums"], r1["center_oe"], r2["center_oe"], host["agg"], w, q, p)
 
 
 def pileup_band_pair(band1, n1, band2, n2, D, xs, ys, w=10, q=6, peak=DEFAULT_PEAK):

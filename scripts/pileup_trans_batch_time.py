@@ -1,12 +1,15 @@
 """Segmented inter-chromosomal pile-up timing on one MI355X: the batched call (pileup.pileup_trans_batch: mst_pileup_trans_batch +
 mst_pileup_reduce_segmented, one host wait) beside the loop of per-pair pileup.pileup_trans_records calls on the same records and
-loops -- the per-pair path, one host wait per pair.  Device events around each, the host wait included; median of --steps after
---warmup.  The per-pair loop gets the records already filtered by v > 0 and cut per pair (the batch takes them concatenated and
-unfiltered), so its own boolean indexing is not charged to it.
+loops -- the per-pair path: a loop of batches of one pair each through the same kernels, one host wait per pair.  Device events
+around each, the host wait included; median of --steps after --warmup.  The per-pair loop gets the records already filtered by
+v > 0 and cut per pair (the batch takes them concatenated and unfiltered), so its own boolean indexing is not charged to it.
   case "genome"  276 pairs (24 chromosomes of 80 .. 1 250 bins, as a human genome at 200 kb), 20 records per 1 000 cells, 40 loops
                  per pair, w = 10: many small pairs.
-  case "pair"    the single pair of scripts/pileup_trans_time.py (24 900 x 24 300 bins, 5e7 records, 2 000 loops) as a batch of
-                 one, beside the single-pair call; the per-pair path is timed twice, for its run-to-run spread.
+  case "pair"    the single pair of scripts/pileup_trans_time.py (24 900 x 24 300 bins, --records records, default 5e7, 2 000
+                 loops) as a batch of one, beside pileup_trans_records on the filtered records; the per-pair path is timed twice,
+                 for its run-to-run spread.
+profiles/pileup_trans_batch_time_parent.json holds three runs (two plain, one with --records 1000000) from the commit that still
+had single-pair kernels behind pileup_trans_records; profiles/pileup_trans_batch_time.json the same three runs of this code.
 Prints one JSON line.
 python scripts/pileup_trans_batch_time.py [--steps 20] [--warmup 3] > profiles/pileup_trans_batch_time.json"""
 import argparse

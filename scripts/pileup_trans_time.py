@@ -1,7 +1,8 @@
 """Inter-chromosomal pile-up timing on one synthetic pair built on the device (24 900 x 24 300 bins, 5e7 records, 2 000 loops,
-w = 10; GPU box): device events around the record pass with everything behind it (mst_pileup_trans_windows: loop ordering,
-window initialisation, records, E, finish), the reduce, and the whole pileup_trans_records call, median of --steps after
---warmup; the record pass's traffic model (16 B per record) and its share of 6.3 TB/s.  Prints one JSON line.
+w = 10; GPU box): device events around the record pass with everything behind it (mst_pileup_trans_windows, the kernels of
+mst_pileup_trans_batch with P = 1: the table upload, loop ordering, window initialisation, records, E, finish), the reduce, and
+the whole pileup_trans_records call (a batch of one pair, with the segmented reduce), median of --steps after --warmup; the
+record pass's traffic model (16 B per record) and its share of 6.3 TB/s.  Prints one JSON line.
 python scripts/pileup_trans_time.py [--steps 20] [--warmup 3] > profiles/pileup_trans_time.json"""
 import argparse
 import json

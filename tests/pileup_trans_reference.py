@@ -1,5 +1,6 @@
 """NumPy restatement of the inter-chromosomal (trans) pile-up of mustache_amd/pileup.py -- the definition the device kernels
-(mustache_amd/csrc/mst_pileup_trans.hip) and the `--trans` run are tested against.  Host arrays only, no GPU.
+(mustache_amd/csrc/mst_pileup_trans_batch.hip, a pair alone being a batch of one) and the `--trans` run are tested against.
+Host arrays only, no GPU.
 
 records: x = bins of A, y = bins of B, v > 0, on the n1 x n2 map.  The map is never made dense: windows are looked up among
 the sorted unique pixels, so a map with a million rows and a handful of records costs nothing.

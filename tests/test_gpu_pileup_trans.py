@@ -1,4 +1,4 @@
-"""The inter-chromosomal pile-up on the MI355X (mustache_amd/pileup.py, csrc/mst_pileup_trans.hip) against the NumPy
+"""The inter-chromosomal pile-up on the MI355X (mustache_amd/pileup.py, csrc/mst_pileup_trans_batch.hip) against the NumPy
 restatement (tests/pileup_trans_reference.py): windows, E, valid flags, aggregates and metrics; bit-identity under permutation
 of the records and of the loops; repeated pixels; the edges (no record, no loop, the reduce's chunk edge, row flags beyond
 LDS, the window limit); a `--trans` run on a `.hic` file; planted loops."""

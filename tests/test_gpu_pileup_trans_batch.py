@@ -1,8 +1,10 @@
 """The segmented inter-chromosomal pile-up on the MI355X (csrc/mst_pileup_trans_batch.hip, pileup.pileup_trans_batch): for every
-pair of a batch the bytes of mst_pileup_trans_windows + mst_pileup_reduce on that pair's records filtered by v > 0 (through
-pileup.pileup_trans_records, which calls exactly those two), and the NumPy restatement (tests/pileup_trans_reference.py) with the
-comparisons test_gpu_pileup_trans.py makes.  Segment isolation, the chunk cuts of the record pass and of the reduce, ignored
-record values, +inf, a repeated pixel, the row bits on both sides of the LDS switch, determinism, argument errors."""
+pair of a batch the bytes of a batch of that pair alone, on its records filtered by v > 0 (pileup.pileup_trans_records), and the
+NumPy restatement (tests/pileup_trans_reference.py) with the comparisons test_gpu_pileup_trans.py makes.  Segment isolation, the
+chunk cuts of the record pass and of the reduce, ignored record values, +inf, a repeated pixel, the row bits on both sides of
+the LDS switch, determinism, argument errors; the single-pair C entry point (mst_pileup_trans_windows, then mst_pileup_reduce),
+which Python no longer goes through.  test_gpu_pileup_trans_digests.py holds the batch of one to the bits of the single-pair
+kernels that were there before it."""
 import itertools
 
 import numpy as np
@@ -84,7 +86,7 @@ def _concat(recs):
 
 
 def _oracle(recs, dims, loops, w, q):
-    """per pair: the single-pair entry points on the records filtered by v > 0"""
+    """per pair: a batch of that pair alone (pileup_trans_records) on the records filtered by v > 0"""
     from mustache_amd.pileup import pileup_trans_records
     out = []
     for (x, y, v), (n1, n2), (xs, ys) in zip(recs, dims, loops):
@@ -394,6 +396,68 @@ def test_bit_identical_under_permutation_and_from_run_to_run():
         assert a[p]["expected"] == c[p]["expected"] and a[p]["kept"] == c[p]["kept"]
         for i in (0, 1):
             assert np.array_equal(a[p]["valid"][i].cpu().numpy(), c[p]["valid"][i].cpu().numpy())
+
+
+# ---- the single-pair C entry point ---------------------------------------------------------------------------------------------------
+def _c_single(x, y, v, n1, n2, xs, ys, w, q, short=0):
+    """lib.mst_pileup_trans_windows, then lib.mst_pileup_reduce on the same workspace (`short` bytes less than the size query
+    reports) -> (return code of the first, {name: bytes of an output}); the outputs start out as 0xA5 bytes"""
+    import torch
+    from mustache_amd import _lib
+    lib = _lib.require_gpu()
+    N, L, S = len(v), len(xs), 2 * w + 1
+    d = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t)).cuda() if len(a) else None
+    xd, yd, vd, lx, ly = d(x, np.int32), d(y, np.int32), d(v, np.float64), d(xs, np.int64), d(ys, np.int64)
+    order = d(np.lexsort((ys, xs)), np.int32)
+    fill = lambda *shape: torch.full(shape, 0xA5, dtype=torch.uint8, device="cuda")
+    out = {"rows": fill(n1), "cols": fill(n2), "expected": fill(8), "agg": fill(4 * S * S * 8)}
+    if L:
+        out.update(obs=fill(L * S * S * 8), oe=fill(L * S * S * 8), stats=fill(L * 3 * 8))
+    need = int(lib.mst_pileup_trans_workspace_bytes(n1, n2, L, w))
+    assert need > 0
+    ws = torch.empty(need - short, dtype=torch.uint8, device="cuda")
+    rc = lib.mst_pileup_trans_windows(_lib.ptr(xd), _lib.ptr(yd), _lib.ptr(vd), N, n1, n2, _lib.ptr(lx), _lib.ptr(ly), L, w, q,
+                                      _lib.ptr(out["rows"]), _lib.ptr(out["cols"]), _lib.ptr(out["expected"]), _lib.ptr(out.get("obs")),
+                                      _lib.ptr(out.get("oe")), _lib.ptr(out.get("stats")), _lib.ptr(ws), ws.numel(), None)
+    if rc == _lib.MST_OK:
+        _lib.check(lib.mst_pileup_reduce(_lib.ptr(out.get("obs")), _lib.ptr(out.get("oe")), _lib.ptr(order), L, w, _lib.ptr(out["agg"]),
+                                         _lib.ptr(ws), ws.numel(), None))
+    torch.cuda.synchronize()
+    return rc, {k: t.cpu().numpy().tobytes() for k, t in out.items()}
+
+
+def _batch_bytes(r):
+    """the outputs of _c_single from a dict of pileup_trans_batch"""
+    out = {"rows": r["valid"][0].cpu().numpy().tobytes(), "cols": r["valid"][1].cpu().numpy().tobytes(),
+           "expected": np.float64(r["expected"]).tobytes(),
+           "agg": np.stack([r[k] for k in ("sum_obs", "count_obs", "sum_oe", "count_oe")]).tobytes()}
+    if len(r["p2ll"]):
+        out.update(obs=r["obs"].cpu().numpy().tobytes(), oe=r["oe"].cpu().numpy().tobytes(),
+                   stats=np.stack([r["center_obs"], r["center_oe"], r["p2ll"]], axis=1).tobytes())
+    return out
+
+
+def test_the_single_pair_c_entry_point_is_a_batch_of_one():
+    from mustache_amd import _lib
+    rng = np.random.default_rng(13)
+    n1, n2, w, q = 60, 45, 3, 2
+    x, y, v = _records(n1, n2, 900, rng)                      # a tenth of the values are 0.0, -1.5, NaN, -0.0
+    xs, ys = _edge_loops(n1, n2, w, 20, rng)
+    keep = v > 0
+    assert 40 < int((~keep).sum()) < 200 and np.isnan(v).any() and (v < 0).any()
+    clean = (x[keep], y[keep], v[keep])
+    none, no_loop = (x[:0], y[:0], v[:0]), (xs[:0], ys[:0])
+    for recs, loops in ((clean, (xs, ys)), (none, (xs, ys)), (clean, no_loop)):          # the pair, N = 0, L = 0
+        rc, got = _c_single(*recs, n1, n2, *loops, w, q)
+        want = _batch_bytes(_batch([recs], [(n1, n2)], [loops], w, q)[0])
+        assert rc == _lib.MST_OK and sorted(got) == sorted(want)
+        for k in want:
+            assert got[k] == want[k], k
+    rc, dirty = _c_single(x, y, v, n1, n2, xs, ys, w, q)     # ignored values: the result on the records filtered by v > 0
+    assert rc == _lib.MST_OK and dirty == _c_single(*clean, n1, n2, xs, ys, w, q)[1]
+    rc, untouched = _c_single(*clean, n1, n2, xs, ys, w, q, short=1)                     # a workspace one byte short
+    assert rc == _lib.MST_E_ARG and "workspace" in _lib.require_gpu().mst_last_error().decode()
+    assert all(set(b) == {0xA5} for b in untouched.values())                            # nothing was launched
 
 
 # ---- argument errors -------------------------------------------------------------------------------------------------------------
