@@ -606,8 +606,10 @@ MST_STABLE int mst_pileup_windows(const double *band, int64_t n, int32_t band_ro
                                   const int64_t *x, const int64_t *y, int64_t L, int32_t w, int32_t q, double *obs, double *oe,
                                   double *loop_stats, void *stream);
 /* agg dev f64 [4][(2w+1)^2] = per cell: sum of the non-NaN obs, their count, sum of the non-NaN oe, their count, over the
- * windows order[0 .. L) (dev int32, a permutation of 0 .. L-1; the caller sorts the loops by (x, y)).  The order is cut into
- * chunks of 512; each chunk's partial sums are added in chunk order.  L = 0 zeroes agg. */
+ * windows order[0 .. L) (dev int32, a permutation of 0 .. L-1; the caller sorts the loops by (x, y)); an entry outside 0 .. L-1
+ * is skipped.  The order is cut into chunks of 512; each chunk's partial sums are added in chunk order.  L = 0 zeroes agg.
+ * This call, mst_pileup_reduce_segmented and mst_pileup_reduce_pair are one pair of kernels (csrc/mst_pileup_reduce.hip; its
+ * additions one by one: ordered_aggregate in tests/pileup_reference.py). */
 MST_STABLE int mst_pileup_reduce(const double *obs, const double *oe, const int32_t *order, int64_t L, int32_t w, double *agg,
                                  void *workspace, uint64_t workspace_bytes, void *stream);
 
@@ -653,10 +655,11 @@ MST_STABLE int mst_pileup_trans_batch(const int32_t *x, const int32_t *y, const 
                                       const int64_t *loop_off, int32_t P, int32_t w, int32_t q, uint8_t *valid_rows,
                                       uint8_t *valid_cols, double *expected, int64_t *kept, double *obs, double *oe,
                                       double *loop_stats, void *workspace, uint64_t workspace_bytes, void *stream);
-/* agg dev f64 [P][4][(2w+1)^2]: for pair p what mst_pileup_reduce gives on that pair's windows with that pair's order, to the
- * bit.  order dev int32 [L]: positions [loop_off[p], loop_off[p + 1]) hold pair p's loops (indices into obs / oe, so inside
+/* agg dev f64 [P][4][(2w+1)^2]: mst_pileup_reduce per pair, by the same kernels: a pair's sums do not depend on the pairs
+ * beside it.  order dev int32 [L]: positions [loop_off[p], loop_off[p + 1]) hold pair p's loops (indices into obs / oe, so inside
  * that range themselves; any other index is skipped) in the order they are added: chunks of 512 that never cross a segment,
- * added in chunk order.  A pair without a loop gets zeros.  loop_off: host, as above.  Two launches whatever P is. */
+ * added in chunk order.  A pair without a loop gets zeros; L = 0 zeroes agg.  loop_off: host, as above.  Two launches whatever
+ * P is. */
 MST_STABLE uint64_t mst_pileup_reduce_segmented_workspace_bytes(const int64_t *loop_off, int32_t P, int32_t w);
 MST_STABLE int mst_pileup_reduce_segmented(const double *obs, const double *oe, const int32_t *order, int64_t L,
                                            const int64_t *loop_off, int32_t P, int32_t w, double *agg, void *workspace,
@@ -688,9 +691,8 @@ MST_STABLE int mst_pileup_enrich(const double *obs, int64_t L, int32_t w, int32_
 MST_STABLE int mst_pileup_compare(const double *oe1, const double *oe2, int64_t L, int32_t w, int32_t p, double *sums,
                                   void *stream);
 /* agg dev f64 [3][(2w+1)^2] = per cell, over the windows order[0 .. L) (dev int32; the caller sorts the loops by (x, y)) that
- * share the cell: the sum of oe1, the sum of oe2, their number.  Chunks of 512 and every addition in mst_pileup_reduce's order:
- * where the NaN masks of oe1 and oe2 coincide, rows 0, 1, 2 have the bits of mst_pileup_reduce's sum of oe (row 2) on oe1, the same
- * on oe2, and its count of oe (row 3).  An order entry outside 0 .. L-1 is skipped.  workspace: dev, 24 * ceil(L / 512) * (2w+1)^2 bytes -- a workspace that
+ * share the cell: the sum of oe1, the sum of oe2, their number.  mst_pileup_reduce's kernels under the joint mask: the same
+ * chunks of 512 and the same order of additions.  An order entry outside 0 .. L-1 is skipped.  workspace: dev, 24 * ceil(L / 512) * (2w+1)^2 bytes -- a workspace that
  * serves mst_pileup_reduce for (L, w) serves this call.  0 <= w <= 64, L < 2^31; L = 0 zeroes agg.  No float atomics:
  * bit-identical from run to run and under any permutation of the loops the caller sorts. */
 MST_STABLE int mst_pileup_reduce_pair(const double *oe1, const double *oe2, const int32_t *order, int64_t L, int32_t w,

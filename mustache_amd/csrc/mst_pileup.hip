@@ -3,14 +3,12 @@
 //
 //   mst_pileup_expected  valid bins and the expected count per diagonal, E[d], d = 0 .. D
 //   mst_pileup_windows   one (2w+1) x (2w+1) window of obs and oe per loop, its centre and its own P2LL
-//   mst_pileup_reduce    per cell: sum and non-NaN count of obs and oe over the loops, in a given (sorted) loop order
+// The reduce over the windows is mst_pileup_reduce (mst_pileup_reduce.hip).
 //
 // The band is diagonal-major (band[d * n + i] = pixel (i, i + d), csrc/mst_band.hip), raw counts, at least D + 1 rows.
 // Every sum runs in a fixed order that depends only on absolute positions: E[d] adds fixed kColChunk-column chunks of an
-// absolute column grid (each a fixed per-thread order plus a fixed tree), then the chunks in chunk order; the reduce adds
-// kLoopChunk-loop chunks of the sorted order (four waves of 128 loops each, in order, then the waves in index order), then the
-// chunks in chunk order.  No float atomics: the results are bit-identical from run to run and under any permutation of the
-// loops the caller sorts.  The valid flags are plain racing stores of the value 1.
+// absolute column grid (each a fixed per-thread order plus a fixed tree), then the chunks in chunk order.  No float atomics: the
+// results are bit-identical from run to run.  The valid flags are plain racing stores of the value 1.
 #include <cmath>
 #include "mst_common.h"
 #include "mst_pileup_sums.h"
@@ -25,18 +23,13 @@ using mst_pileup::kThreads;
 using mst_pileup::kWaves;
 constexpr int kValidRows = 32;             // band rows per workgroup of the valid pass
 constexpr int kColChunk = 4096;            // columns per chunk of the expected pass (absolute grid)
-constexpr int kLoopChunk = 512;            // loops per chunk of the reduce
-constexpr int kLoopsPerWave = kLoopChunk / kWaves;
 constexpr int kMaxW = mst_pileup::kMaxW;
 
 inline int64_t col_chunks(int64_t n) { return (n + kColChunk - 1) / kColChunk; }
-inline int64_t loop_chunks(int64_t L) { return (L + kLoopChunk - 1) / kLoopChunk; }
-inline int64_t cells_of(int w) { return (int64_t)(2 * w + 1) * (2 * w + 1); }
 
 // workspace, used in turn from its start: mst_pileup_expected's partial sums [(D+1) x chunks] f64 and counts (same) int64, then
-// mst_pileup_reduce's partials [chunks][4][cells] f64
+// mst_pileup_reduce's partials (mst_pileup_sums.h)
 inline uint64_t ws_expected(int64_t n, int32_t D) { return 2 * align256((uint64_t)(D + 1) * col_chunks(n) * 8); }
-inline uint64_t ws_reduce(int64_t L, int32_t w) { return align256((uint64_t)loop_chunks(L) * 4 * cells_of(w) * 8); }
 
 // ---- valid bins: bin i is valid when a non-zero pixel (i, j), |i - j| <= D, touches it -----------------------------------
 // Workgroup (column block cb, row block rb): thread t reads band[d][i] for i = cb * 256 + t and kValidRows rows d.  A hit
@@ -161,61 +154,6 @@ windows_kernel(const double *__restrict__ band, int64_t n, int32_t D, const doub
     }
 }
 
-// ---- reduce: workgroup (cell block cb of 64 cells, loop chunk k).  Wave v adds the chunk's loops v * 128 .. v * 128 + 127 in
-// sorted order for its 64 cells; the four wave partials are added in wave order.  part[k][0..3][cell].
-__global__ void __launch_bounds__(kThreads)
-reduce_partial_kernel(const double *__restrict__ obs, const double *__restrict__ oe, const int32_t *__restrict__ order,
-                      int64_t L, int64_t cells, int64_t cell_blocks, double *__restrict__ part) {
-    __shared__ double red[kWaves][4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t cb = blockIdx.x % cell_blocks, k = blockIdx.x / cell_blocks;
-    const int64_t cell = cb * 64 + lane;
-    const int64_t p0 = k * kLoopChunk + (int64_t)wave * kLoopsPerWave;
-    const int64_t p1 = (p0 + kLoopsPerWave < L) ? p0 + kLoopsPerWave : L;
-    double so = 0.0, co = 0.0, se = 0.0, ce = 0.0;
-    if (cell < cells) {
-        for (int64_t p = p0; p < p1; ++p) {
-            const int64_t l = order[p];
-            if (l < 0 || l >= L) continue;
-            const double vo = obs[l * cells + cell], ve = oe[l * cells + cell];
-            if (vo == vo) {
-                so = so + vo;
-                co = co + 1.0;
-            }
-            if (ve == ve) {
-                se = se + ve;
-                ce = ce + 1.0;
-            }
-        }
-    }
-    red[wave][0][lane] = so;
-    red[wave][1][lane] = co;
-    red[wave][2][lane] = se;
-    red[wave][3][lane] = ce;
-    __syncthreads();
-    if (wave == 0 && cell < cells) {
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            double t = red[0][m][lane];
-#pragma unroll
-            for (int v = 1; v < kWaves; ++v) t = t + red[v][m][lane];
-            part[(k * 4 + m) * cells + cell] = t;
-        }
-    }
-}
-
-__global__ void __launch_bounds__(kThreads)
-reduce_finish_kernel(int64_t cells, int64_t nchunks, const double *__restrict__ part, double *__restrict__ agg) {
-    const int64_t cell = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (cell >= cells) return;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        double t = 0.0;
-        for (int64_t k = 0; k < nchunks; ++k) t = t + part[(k * 4 + m) * cells + cell];
-        agg[m * cells + cell] = t;
-    }
-}
-
 int check_band(const char *who, const double *band, int64_t n, int32_t band_rows, int32_t D) {
     if (!band || n <= 0 || D < 0 || band_rows < D + 1)
         return mst::fail(MST_E_ARG, "%s: bad band (n %lld, rows %d, D %d: the band needs at least D + 1 rows)", who, (long long)n,
@@ -227,7 +165,7 @@ int check_band(const char *who, const double *band, int64_t n, int32_t band_rows
 
 extern "C" uint64_t mst_pileup_workspace_bytes(int64_t n, int32_t D, int64_t L, int32_t w) {
     if (n <= 0 || D < 0 || L < 0 || w < 0 || w > kMaxW) return 0;
-    const uint64_t a = ws_expected(n, D), b = ws_reduce(L, w);      // the two passes use the workspace in turn
+    const uint64_t a = ws_expected(n, D), b = align256(mst_pileup::partials_bytes(mst_pileup::loop_chunks(L), 4, w));      // used in turn
     return (a > b ? a : b) + 256;
 }
 
@@ -270,32 +208,6 @@ extern "C" int mst_pileup_windows(const double *band, int64_t n, int32_t band_ro
     if (L == 0) return MST_OK;
     if ((rc = grid_ok("mst_pileup_windows", L)) != MST_OK) return rc;
     windows_kernel<<<(unsigned)L, kThreads, 0, mst::as_stream(stream)>>>(band, n, D, expected, x, y, w, q, obs, oe, loop_stats);
-    MST_LAUNCH_CHECK();
-    return MST_OK;
-}
-
-extern "C" int mst_pileup_reduce(const double *obs, const double *oe, const int32_t *order, int64_t L, int32_t w, double *agg,
-                                 void *workspace, uint64_t workspace_bytes, void *stream) {
-    MST_RANGE("pileup: mst_pileup_reduce");
-    int rc = check_w("mst_pileup_reduce", w, 1);
-    if (rc != MST_OK) return rc;
-    if (L < 0 || L > INT32_MAX || !agg || (L > 0 && (!obs || !oe || !order)))
-        return mst::fail(MST_E_ARG, "mst_pileup_reduce: bad argument (L %lld)", (long long)L);
-    const int64_t cells = cells_of(w);
-    hipStream_t s = mst::as_stream(stream);
-    if (L == 0) {
-        MST_HIP(hipMemsetAsync(agg, 0, (size_t)(4 * cells * 8), s));
-        return MST_OK;
-    }
-    if (!workspace || workspace_bytes < ws_reduce(L, w))
-        return mst::fail(MST_E_ARG, "mst_pileup_reduce: workspace of %llu bytes, %llu needed",
-                         (unsigned long long)workspace_bytes, (unsigned long long)ws_reduce(L, w));
-    const int64_t cell_blocks = (cells + 63) / 64, nchunks = loop_chunks(L);
-    if ((rc = grid_ok("mst_pileup_reduce", cell_blocks * nchunks)) != MST_OK) return rc;
-    double *part = static_cast<double *>(workspace);
-    reduce_partial_kernel<<<(unsigned)(cell_blocks * nchunks), kThreads, 0, s>>>(obs, oe, order, L, cells, cell_blocks, part);
-    MST_LAUNCH_CHECK();
-    reduce_finish_kernel<<<(unsigned)((cells + kThreads - 1) / kThreads), kThreads, 0, s>>>(cells, nchunks, part, agg);
     MST_LAUNCH_CHECK();
     return MST_OK;
 }

@@ -7,7 +7,7 @@
 //                                 cells; then E, oe, each loop's centres and its own P2LL.  A pair's values do not depend on the
 //                                 pairs beside it.
 //   mst_pileup_trans_windows      a single pair: the same body with P = 1 (host tables seg_off = {0, N}, loop_off = {0, L})
-//   mst_pileup_reduce_segmented   per pair what mst_pileup_reduce gives on that pair's windows with that pair's order, to the bit
+// The reduce over the pairs' windows is mst_pileup_reduce_segmented (mst_pileup_reduce.hip).
 //
 // A record with !(v > 0) -- zero, negative, NaN -- is ignored altogether: no valid flag, nothing in the sum, no window.  So the
 // output of mst_balance_apply_pairs goes in as it is, without a compaction per pair.
@@ -36,8 +36,6 @@
 //                    its largest value whatever the order.
 //   expected_kernel  one workgroup per pair: E = exact total / (#valid rows * #valid columns) (integer counts, one division), kept.
 //   finish_kernel    one workgroup per loop, reading its pair's E: oe = obs / E, the two centres and P2LL in a fixed tree.
-// mst_pileup_reduce_segmented is two launches: the partial sums of every (cell block, 512-loop chunk of one pair), then per
-// (pair, cell) the chunks of that pair in chunk order, with the arithmetic of mst_pileup.hip's reduce.
 //
 // The exact sum keeps kSumCopies copies of its LDS limbs, chosen by lane: the values of a trans map share a few exponents, so the
 // lanes of a wave hit the same limbs, and LDS atomics on one address are served one after another.  The sums are integer sums
@@ -57,19 +55,19 @@ using mst_exact::kLimbs;
 using mst_exact::kSumWords;
 using mst_pileup::align256;
 using mst_pileup::block_sum2;
+using mst_pileup::check_pairs;
 using mst_pileup::check_w;
 using mst_pileup::grid_ok;
+using mst_pileup::kMaxPairs;
 using mst_pileup::kThreads;
 using mst_pileup::kWaves;
+using mst_pileup::offsets_ok;
 
 constexpr int kLdsFlagWords = 4096;        // 16 KiB of row bits in LDS = 131 072 rows of one pair; beyond, read from global
 constexpr int kSumCopies = 16;             // copies of the exact sum's LDS limbs, one per lane & 15
 constexpr int kSumStride = kLimbs + 1;
 constexpr int kRecordBlocks = 2048;        // grid cap of the record pass
 constexpr int kChunk = 4096;               // records of a chunk: 16 per thread, 64 KiB read
-constexpr int kLoopChunk = 512;            // loops per chunk of the reduce, as mst_pileup.hip
-constexpr int kLoopsPerWave = kLoopChunk / kWaves;
-constexpr int kMaxPairs = 65535;
 constexpr int64_t kMaxRecords = ((int64_t)1 << 31) - 1;      // of one call
 constexpr uint64_t kKeptSlot = 256;        // mst_pileup_trans_windows: the batch's `kept` word, at the start of the workspace
 
@@ -121,14 +119,6 @@ Layout layout(const int64_t *seg_off, const int64_t *n1, const int64_t *loop_off
     o.tables = o.bits + align256((uint64_t)o.nwords * 4);
     o.end = o.tables + o.t_bytes;
     return o;
-}
-
-// non-decreasing from 0 to `total`
-bool offsets_ok(const int64_t *off, int32_t P, int64_t total) {
-    if (!off || off[0] != 0 || off[P] != total) return false;
-    for (int32_t p = 0; p < P; ++p)
-        if (off[p + 1] < off[p]) return false;
-    return true;
 }
 
 // ---- the loops by row, inside their segment --------------------------------------------------------------------------------
@@ -329,92 +319,6 @@ finish_kernel(const double *__restrict__ obs, const double *__restrict__ expecte
     }
 }
 
-// ---- the segmented reduce: workgroup (cell block cb, chunk kg of the batch).  chunk_off[p] = the chunks before pair p; chunk
-// kg is chunk kg - chunk_off[p] of its pair p and covers the positions loop_off[p] + 512 (kg - chunk_off[p]) ... of `order`,
-// never past loop_off[p + 1].  Wave v adds its 128 loops in order for its 64 cells; the four wave partials in wave order.
-__global__ void __launch_bounds__(kThreads)
-reduce_partial_kernel(const double *__restrict__ obs, const double *__restrict__ oe, const int32_t *__restrict__ order,
-                      const int64_t *__restrict__ loop_off, const int64_t *__restrict__ chunk_off, int32_t P, int64_t cells,
-                      int64_t cell_blocks, double *__restrict__ part) {
-    __shared__ double red[kWaves][4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t cb = blockIdx.x % cell_blocks, kg = blockIdx.x / cell_blocks;
-    const int32_t pair = mst::segment_of(chunk_off, 0, P, kg);
-    const int64_t l0 = loop_off[pair], l1 = loop_off[pair + 1];
-    const int64_t cell = cb * 64 + lane;
-    const int64_t p0 = l0 + (kg - chunk_off[pair]) * kLoopChunk + (int64_t)wave * kLoopsPerWave;
-    const int64_t p1 = (p0 + kLoopsPerWave < l1) ? p0 + kLoopsPerWave : l1;
-    double so = 0.0, co = 0.0, se = 0.0, ce = 0.0;
-    if (cell < cells) {
-        for (int64_t p = p0; p < p1; ++p) {
-            const int64_t l = order[p];
-            if (l < l0 || l >= l1) continue;                          // not a loop of this pair
-            const double vo = obs[l * cells + cell], ve = oe[l * cells + cell];
-            if (vo == vo) {
-                so = so + vo;
-                co = co + 1.0;
-            }
-            if (ve == ve) {
-                se = se + ve;
-                ce = ce + 1.0;
-            }
-        }
-    }
-    red[wave][0][lane] = so;
-    red[wave][1][lane] = co;
-    red[wave][2][lane] = se;
-    red[wave][3][lane] = ce;
-    __syncthreads();
-    if (wave == 0 && cell < cells) {
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            double t = red[0][m][lane];
-#pragma unroll
-            for (int u = 1; u < kWaves; ++u) t = t + red[u][m][lane];
-            part[(kg * 4 + m) * cells + cell] = t;
-        }
-    }
-}
-
-// workgroup (pair, block of 256 cells): the pair's chunks in chunk order; zeros for a pair without a loop
-__global__ void __launch_bounds__(kThreads)
-reduce_finish_kernel(int64_t cells, int64_t cell_blocks, const int64_t *__restrict__ chunk_off, const double *__restrict__ part,
-                     double *__restrict__ agg) {
-    const int64_t pair = blockIdx.x / cell_blocks;
-    const int64_t cell = (blockIdx.x % cell_blocks) * kThreads + threadIdx.x;
-    if (cell >= cells) return;
-    const int64_t k0 = chunk_off[pair], k1 = chunk_off[pair + 1];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        double t = 0.0;
-        for (int64_t k = k0; k < k1; ++k) t = t + part[(k * 4 + m) * cells + cell];
-        agg[(pair * 4 + m) * cells + cell] = t;
-    }
-}
-
-inline int64_t loop_chunks(int64_t L) { return (L + kLoopChunk - 1) / kLoopChunk; }
-
-struct ReduceLayout {
-    uint64_t tables, part, end;
-    int64_t nchunks;
-};
-
-ReduceLayout reduce_layout(const int64_t *loop_off, int32_t P, int32_t w) {
-    ReduceLayout o;
-    o.nchunks = 0;
-    for (int32_t p = 0; p < P; ++p) o.nchunks += loop_chunks(loop_off[p + 1] - loop_off[p]);
-    const uint64_t cells = (uint64_t)(2 * w + 1) * (2 * w + 1);
-    o.tables = 0;
-    o.part = o.tables + align256((uint64_t)2 * (P + 1) * 8);
-    o.end = o.part + align256((uint64_t)o.nchunks * 4 * cells * 8);
-    return o;
-}
-
-int check_pairs(const char *who, int32_t P) {
-    if (P < 1 || P > kMaxPairs) return mst::fail(MST_E_ARG, "%s: P = %d pairs is outside 1 .. %d", who, (int)P, kMaxPairs);
-    return MST_OK;
-}
-
 // ---- the body behind both entry points (`who` names the caller in a refusal): every check, the tables, the launches ------------
 int run_batch(const char *who, const int32_t *x, const int32_t *y, const double *v, int64_t N, const int64_t *seg_off,
               const int64_t *n1, const int64_t *n2, const int64_t *lx, const int64_t *ly, int64_t L, const int64_t *loop_off,
@@ -553,50 +457,4 @@ extern "C" int mst_pileup_trans_windows(const int32_t *x, const int32_t *y, cons
     return run_batch("mst_pileup_trans_windows", x, y, v, N, seg_off, &n1, &n2, lx, ly, L, loop_off, 1, w, q, valid_rows,
                      valid_cols, expected, reinterpret_cast<int64_t *>(base), obs, oe, loop_stats, base ? base + kKeptSlot : nullptr,
                      need ? need - kKeptSlot : 0, stream);
-}
-
-extern "C" uint64_t mst_pileup_reduce_segmented_workspace_bytes(const int64_t *loop_off, int32_t P, int32_t w) {
-    if (P < 1 || P > kMaxPairs || w < 0 || w > mst_pileup::kMaxW || !loop_off || !offsets_ok(loop_off, P, loop_off[P])) return 0;
-    return reduce_layout(loop_off, P, w).end + 256;
-}
-
-extern "C" int mst_pileup_reduce_segmented(const double *obs, const double *oe, const int32_t *order, int64_t L,
-                                           const int64_t *loop_off, int32_t P, int32_t w, double *agg, void *workspace,
-                                           uint64_t workspace_bytes, void *stream) {
-    MST_RANGE("pileup: mst_pileup_reduce_segmented");
-    int rc = check_w("mst_pileup_reduce_segmented", w, 1);
-    if (rc != MST_OK) return rc;
-    if ((rc = check_pairs("mst_pileup_reduce_segmented", P)) != MST_OK) return rc;
-    if (L < 0 || L > INT32_MAX || !agg || (L > 0 && (!obs || !oe || !order)) || !offsets_ok(loop_off, P, L))
-        return mst::fail(MST_E_ARG, "mst_pileup_reduce_segmented: bad argument (L %lld; loop_off: host, P + 1 entries rising from 0 "
-                         "to L)", (long long)L);
-    const ReduceLayout o = reduce_layout(loop_off, P, w);
-    if (!workspace || workspace_bytes < o.end)
-        return mst::fail(MST_E_ARG, "mst_pileup_reduce_segmented: workspace of %llu bytes, %llu needed",
-                         (unsigned long long)workspace_bytes, (unsigned long long)o.end);
-    const int64_t cells = (int64_t)(2 * w + 1) * (2 * w + 1);
-    const int64_t cell_blocks = (cells + 63) / 64, finish_blocks = (cells + kThreads - 1) / kThreads;
-    if (o.nchunks > 0 && (rc = grid_ok("mst_pileup_reduce_segmented", cell_blocks * o.nchunks)) != MST_OK) return rc;
-    if ((rc = grid_ok("mst_pileup_reduce_segmented", finish_blocks * P)) != MST_OK) return rc;
-    static thread_local std::vector<int64_t> table;
-    table.assign((size_t)2 * (P + 1), 0);
-    int64_t *h_loop_off = table.data(), *h_chunk_off = table.data() + (P + 1);
-    for (int32_t p = 0; p < P; ++p) {
-        h_loop_off[p] = loop_off[p];
-        h_chunk_off[p + 1] = h_chunk_off[p] + loop_chunks(loop_off[p + 1] - loop_off[p]);
-    }
-    h_loop_off[P] = loop_off[P];
-    hipStream_t s = mst::as_stream(stream);
-    char *base = static_cast<char *>(workspace);
-    auto *d_loop_off = reinterpret_cast<int64_t *>(base + o.tables), *d_chunk_off = d_loop_off + (P + 1);
-    double *part = reinterpret_cast<double *>(base + o.part);
-    MST_HIP(mst::upload_small(d_loop_off, table.data(), table.size() * 8, s));
-    if (o.nchunks > 0) {
-        reduce_partial_kernel<<<(unsigned)(cell_blocks * o.nchunks), kThreads, 0, s>>>(obs, oe, order, d_loop_off, d_chunk_off, P,
-                                                                                       cells, cell_blocks, part);
-        MST_LAUNCH_CHECK();
-    }
-    reduce_finish_kernel<<<(unsigned)(finish_blocks * P), kThreads, 0, s>>>(cells, finish_blocks, d_chunk_off, part, agg);
-    MST_LAUNCH_CHECK();
-    return MST_OK;
 }

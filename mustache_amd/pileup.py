@@ -25,7 +25,8 @@ Rules:
 Not claimed: agreement with Juicer's own output.
 
 Device work (mustache_amd/csrc/mst_pileup.hip): valid flags and E (two reads of the band), the windows with each loop's
-centre and P2LL, and the reduce; one host wait per chromosome, when the aggregates come back.
+centre and P2LL; the reduce of every mode is csrc/mst_pileup_reduce.hip (tests/pileup_reference.py, ordered_aggregate, restates
+its additions one by one).  One host wait per chromosome, when the aggregates come back.
 
 Inter-chromosomal lists (`--trans`, `pileup(..., trans=True)`, `pileup_trans_records()`; tests/pileup_trans_reference.py
 restates the rules).  Without the switch nothing changes: rows with two chromosomes keep the status `trans`.
@@ -78,8 +79,8 @@ the map they were called from.  The rows, the windows, E, the aggregate and the 
     on another input; --pairs-zero-based without --pairs-trans (no other pile-up bins a pairs file with it).  Each is one `Error:` line before anything is read.
 Device work (mustache_amd/csrc/mst_pileup_trans_batch.hip): mst_pileup_trans_batch serves P pairs in five launches -- a record
 whose v' is not > 0 is skipped in the pass, so the balanced records go in without a compaction -- and
-mst_pileup_reduce_segmented is the reduce for P pairs in two; every pair's values have the bits a batch of that pair alone
-gives.
+mst_pileup_reduce_segmented (csrc/mst_pileup_reduce.hip) is the reduce for P pairs in two; every pair's values have the bits a
+batch of that pair alone gives.
 
 Enrichment (`--enrich [--peak P] [--min-enrichment T]`, `peak=P` on pileup() / pileup_band() / pileup_trans_records() /
 pileup_trans_batch(); tests/pileup_enrich_reference.py restates the rules).  Every used loop against its own local background,
@@ -106,7 +107,8 @@ HiCCUPS's four neighbourhoods, in all three modes above.  Without the switch (`p
   * Not done: widening w where a neighbourhood is sparse.  A Poisson p-value needs the raw counts beside the balanced band:
     "Significance" below, in the one mode that has them.
 Device work (mustache_amd/csrc/mst_pileup_enrich.hip): mst_pileup_enrich, one wave per loop over the window of obs that is already
-resident, the twelve sums per loop; they come back in the one concatenated copy each mode waits for.  The ratios are NumPy's.
+resident, the twelve sums per loop by the walk of csrc/mst_pileup_sums.h (neighbourhood_sums; ordered_neighbourhood_sums in
+tests/pileup_enrich_reference.py restates its additions one by one); they come back in the one concatenated copy each mode waits for.  The ratios are NumPy's.
 
 Significance (`--enrich --poisson [--max-fdr T]` under `--balance ICE|NEWTON` on a `.hic` or pairs file, `poisson=True` on pileup(),
 `poisson=PoissonInput(...)` on pileup_band(); tests/pileup_poisson_reference.py restates the rules cell by cell).  A fold
@@ -169,7 +171,7 @@ changes and nothing is launched.
     smallest when all four are > 0, the largest when all four are < 0, 0.0 otherwise -- as FE_MIN, a loop counts as stronger on
     one map only when every neighbourhood agrees.  Positive means stronger on -f.
   * Paired aggregate: the used loops sorted by (x, y) (trans: (a, b)); per cell, over the loops where the cell is shared, T_1 =
-    sum oe1, T_2 = sum oe2, C = their number, chunks of 512 loops added in chunk order as mst_pileup_reduce does; genome-wide the
+    sum oe1, T_2 = sum oe2, C = their number, chunks of 512 loops added in chunk order; genome-wide the
     chromosome (or pair) partials are added in run order on the host.  M_s = T_s / C (NaN where C = 0); the differential map is
     log2(M_1 / M_2), NaN unless both are > 0.  Per chromosome (or pair) and `all`: P2LL_s = metrics(M_s, w, q)["P2LL"], LFC_P2LL
     = log2(P2LL_1 / P2LL_2) and AGG_LFC_N = log2(aggregate_enrichment(M_1, w, p)[N] / aggregate_enrichment(M_2, w, p)[N]), each
@@ -186,8 +188,8 @@ changes and nothing is launched.
   * Not claimed: a significance -- there are no counts; a minimum cnt; depth matching -- O/E and the ratio to the local
     background remove the scale, not the noise.
 Device work (mustache_amd/csrc/mst_pileup_compare.hip) over the two stacks of oe windows the two pile-ups leave resident:
-mst_pileup_compare, one wave per loop, the twelve sums per loop under the joint mask; mst_pileup_reduce_pair, the reduce above
-with three accumulators.  One host wait per chromosome or pair beyond the two per-sample pile-ups' own: one concatenated copy.
+mst_pileup_compare, one wave per loop, the twelve sums per loop under the joint mask (the same walk, neighbourhood_sums);
+mst_pileup_reduce_pair (csrc/mst_pileup_reduce.hip), the one reduce under the joint mask.  One host wait per chromosome or pair beyond the two per-sample pile-ups' own: one concatenated copy.
 """
 import argparse
 import math
@@ -491,18 +493,33 @@ def windows(band, n, D, E, xd, yd, w, q):
     return obs, oe, st
 
 
-def reduce(obs, oe, order, w, ws):
-    """agg [4, (2w+1)^2] device tensor: sum obs, count obs, sum oe, count oe over the windows in `order` (int32 device)."""
+def _reduce(a, b, order, w, ws, joint=False, loop_off=None):
+    """The one launcher of csrc/mst_pileup_reduce.hip: the sums over the two stacks of windows a, b in `order` (int32 device) into a
+    new device tensor -- [4, (2w+1)^2] from mst_pileup_reduce, [3, (2w+1)^2] from mst_pileup_reduce_pair (joint), [P, 4, (2w+1)^2]
+    from mst_pileup_reduce_segmented (loop_off: the host table of P + 1 offsets).  With no loop the C calls get null pointers and
+    zero the sums."""
     import torch
     from . import _lib
     from ._lib import ptr as _ptr, stream as _stream, require_gpu
     lib = require_gpu()
-    S = 2 * int(w) + 1
-    with torch.cuda.device(obs.device):
-        agg = torch.empty((4, S * S), dtype=torch.float64, device=obs.device)
-        _lib.check(lib.mst_pileup_reduce(_ptr(obs), _ptr(oe), _ptr(order), int(order.numel()), int(w), _ptr(agg), _ptr(ws),
-                                         ws.numel(), _stream()))
+    S, L = 2 * int(w) + 1, int(order.numel())
+    stacks = [_ptr(t) if L else None for t in (a, b, order)]
+    with torch.cuda.device(ws.device):
+        if loop_off is not None:
+            P = len(loop_off) - 1
+            agg = torch.empty((max(P, 1), 4, S * S), dtype=torch.float64, device=ws.device)
+            rc = lib.mst_pileup_reduce_segmented(*stacks, L, _host_ptr(loop_off), P, int(w), _ptr(agg), _ptr(ws), ws.numel(), _stream())
+        else:
+            agg = torch.empty((3 if joint else 4, S * S), dtype=torch.float64, device=ws.device)
+            entry = lib.mst_pileup_reduce_pair if joint else lib.mst_pileup_reduce
+            rc = entry(*stacks, L, int(w), _ptr(agg), _ptr(ws), ws.numel(), _stream())
+        _lib.check(rc)
     return agg
+
+
+def reduce(obs, oe, order, w, ws):
+    """agg [4, (2w+1)^2] device tensor: sum obs, count obs, sum oe, count oe over the windows in `order` (int32 device)."""
+    return _reduce(obs, oe, order, w, ws)
 
 
 def _loop_bins(xs, ys):
@@ -696,14 +713,12 @@ def pileup_trans_batch(x, y, v, seg_off, dims, loops, w=10, q=6, peak=None):
         obs = torch.empty((L, S, S), dtype=torch.float64, device=dev)
         oe = torch.empty_like(obs)
         st = torch.empty((L, 3), dtype=torch.float64, device=dev)
-        agg = torch.empty((max(P, 1), 4, S * S), dtype=torch.float64, device=dev)
         _lib.check(lib.mst_pileup_trans_batch(
             _ptr(x) if N else None, _ptr(y) if N else None, _ptr(v) if N else None, N, _host_ptr(seg), _host_ptr(n1), _host_ptr(n2),
             _ptr(lxy_d) if L else None, _lib.off(lxy_d, L) if L else None, L, _host_ptr(loop_off), P, w, q, _ptr(rows), _ptr(cols),
             _ptr(E), _ptr(kept), _ptr(obs) if L else None, _ptr(oe) if L else None, _ptr(st) if L else None, _ptr(ws), ws.numel(),
             _stream()))
-        _lib.check(lib.mst_pileup_reduce_segmented(_ptr(obs) if L else None, _ptr(oe) if L else None, _ptr(order_d) if L else None,
-                                                   L, _host_ptr(loop_off), P, w, _ptr(agg), _ptr(ws), ws.numel(), _stream()))
+        agg = _reduce(obs, oe, order_d, w, ws, loop_off=loop_off)
         parts = [("agg", agg), ("st", st), ("E", E), ("kept", kept)]
         if peak is not None:                           # e_loop: the E of the pair each loop belongs to
             pair_of = torch.from_numpy(np.repeat(np.arange(P, dtype=np.int64), np.diff(loop_off))).to(dev, non_blocking=True)
@@ -747,16 +762,7 @@ def compare_windows(oe1, oe2, w, p):
 def reduce_pair(oe1, oe2, order, w, ws):
     """agg [3, (2w+1)^2] device tensor: T_1 = sum oe1, T_2 = sum oe2, C = the number, per cell over the windows in `order` (int32
     device) that share the cell.  `ws`: a workspace that serves reduce() for these loops."""
-    import torch
-    from . import _lib
-    from ._lib import ptr as _ptr, stream as _stream, require_gpu
-    lib = require_gpu()
-    S, L = 2 * int(w) + 1, int(order.numel())
-    with torch.cuda.device(oe1.device):
-        agg = torch.empty((3, S * S), dtype=torch.float64, device=oe1.device)
-        _lib.check(lib.mst_pileup_reduce_pair(_ptr(oe1) if L else None, _ptr(oe2) if L else None, _ptr(order) if L else None, L,
-                                              int(w), _ptr(agg), _ptr(ws), ws.numel(), _stream()))
-    return agg
+    return _reduce(oe1, oe2, order, w, ws, joint=True)
 
 
 def _log2_ratio(a, b):

@@ -1,5 +1,5 @@
 """NumPy restatement of one loop list piled up on two maps ("Two maps" in mustache_amd/pileup.py) -- the definition
-mst_pileup_compare and mst_pileup_reduce_pair (mustache_amd/csrc/mst_pileup_compare.hip) and the host ratios are tested
+mst_pileup_compare (mustache_amd/csrc/mst_pileup_compare.hip), mst_pileup_reduce_pair (mst_pileup_reduce.hip) and the host ratios are tested
 against.  Plain loops over the cells of a window and over the loops; host arrays only, no GPU, and nothing of
 mustache_amd.pileup.
 

@@ -52,6 +52,78 @@ def _sums(obs, w, p, e_of):
     return out
 
 
+def ordered_neighbourhood_sums(counted, first, second, w, p):
+    """The device walk (neighbourhood_sums, mustache_amd/csrc/mst_pileup_sums.h), addition by addition in float64.  counted
+    (bool), first, second (float64): [L, 2w+1, 2w+1].  Lane t of 64 adds its cells t, t + 64, ... (row-major) in order into the
+    four neighbourhoods' accumulators, where the cell is counted and belongs to the neighbourhood; then the butterfly a = a +
+    a[lane ^ o] for o = 32, 16, 8, 4, 2, 1, and lane 0 is the result.  The counts are integers.  -> [L, 4, 3] = sum first, sum
+    second, count.  It serves the enrichment (obs and e under "obs not NaN and e not 0") and the comparison of two maps (oe1 and
+    oe2 under the joint mask)."""
+    L, cells = len(counted), (2 * w + 1) ** 2
+    counted = np.asarray(counted, bool).reshape(L, cells)
+    first, second = (np.asarray(v, np.float64).reshape(L, cells) for v in (first, second))
+    inside = masks(w, p).reshape(4, cells)
+    acc = np.zeros((2, L, 4, 64))
+    cnt = np.zeros((L, 4), np.int64)
+    for c0 in range(0, cells, 64):
+        n = min(64, cells - c0)
+        take = counted[:, None, c0:c0 + n] & inside[None, :, c0:c0 + n]                # [L, 4, n]
+        for s, v in enumerate((first, second)):
+            acc[s, :, :, :n] = np.where(take, acc[s, :, :, :n] + v[:, None, c0:c0 + n], acc[s, :, :, :n])
+        cnt += take.sum(2)
+    lanes = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[..., lanes ^ o]
+    return np.stack([acc[0, :, :, 0], acc[1, :, :, 0], cnt.astype(np.float64)], axis=2)
+
+
+# the cases the order-exact tests run: at most 64 cells, 64 .. 128, more than 128, 2w + 1 = 63 and 65 around the walk's carry
+# rule, the largest window
+NEIGHBOURHOOD_SEED = 0
+NEIGHBOURHOOD_CASES = ((1, 0), (3, 1), (4, 1), (5, 2), (10, 2), (31, 5), (32, 5), (64, 2))
+NEIGHBOURHOOD_L = (1, 3, 4, 5)
+
+
+def cis_e(w, E, D, xs, ys):
+    """[L, 2w+1, 2w+1]: the expected value of every cell of every window, E[|(y + b) - (x + a)|], 0 beyond D"""
+    off = np.arange(-w, w + 1)
+    d = np.abs((np.asarray(ys, np.int64)[:, None, None] + off[None, None, :]) - (np.asarray(xs, np.int64)[:, None, None] + off[None, :, None]))
+    return np.where(d <= D, np.asarray(E, np.float64)[np.minimum(d, D)], 0.0)
+
+
+def neighbourhood_case(w, p):
+    """five loops on pileup_reference.order_sensitive values: {"a", "b": two stacks [5, 2w+1, 2w+1] with independent NaNs; "xs",
+    "ys": loops with y - x in 0 .. 40, the first at 40 (some of its cells lie beyond D) and the second at 0; "E" [D + 1] with a
+    zero diagonal, D = 37 + 2w; "e_loop" [5]}"""
+    import pileup_reference as pr
+    rng = np.random.default_rng([NEIGHBOURHOOD_SEED, w, p])
+    L, S, D = 5, 2 * w + 1, 37 + 2 * w
+    sep = rng.integers(0, 41, L)
+    sep[:2] = 40, 0
+    xs = rng.integers(w, 1000, L).astype(np.int64)
+    E = np.abs(pr.order_sensitive(rng, D + 1, nan=0.0))
+    E[7] = 0.0
+    return {"a": pr.order_sensitive(rng, (L, S, S)), "b": pr.order_sensitive(rng, (L, S, S)), "xs": xs, "ys": xs + sep, "E": E,
+            "D": D, "e_loop": np.abs(pr.order_sensitive(rng, L, nan=0.0))}
+
+
+def neighbourhood_inputs(case, w, kind):
+    """(counted, first, second) of ordered_neighbourhood_sums for the three device calls on a neighbourhood_case: "cis" and
+    "trans" (mst_pileup_enrich on stack a) and "compare" (mst_pileup_compare on the two stacks)"""
+    a, b = case["a"], case["b"]
+    if kind == "compare":
+        return ~np.isnan(a) & ~np.isnan(b), a, b
+    e = cis_e(w, case["E"], case["D"], case["xs"], case["ys"]) if kind == "cis" \
+        else np.broadcast_to(case["e_loop"][:, None, None], a.shape)
+    return ~np.isnan(a) & (e != 0), a, e
+
+
+def plain_neighbourhood_sums(counted, first, second, w, p):
+    """[L, 4, 2]: the two sums of ordered_neighbourhood_sums as a plain masked NumPy sum over the window adds them"""
+    take = np.asarray(counted, bool)[:, None] & masks(w, p)[None]
+    return np.stack([np.where(take, np.asarray(v, np.float64)[:, None], 0.0).sum((2, 3)) for v in (first, second)], axis=2)
+
+
 def cis_sums(obs, w, p, E, D, xs, ys):
     """cis: e = E[|(y + b) - (x + a)|]; a cell farther than D from the diagonal does not count."""
     E = np.asarray(E, np.float64)

@@ -244,3 +244,42 @@ def test_planted_loops_are_enriched():
     assert planted["metrics_oe"]["P2LL"] > max(1.5, shifted["metrics_oe"]["P2LL"])
     assert math.isfinite(shifted["metrics"]["P2LL"])
     torch.cuda.synchronize()
+
+
+# ---- the reduce, addition by addition ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("w,L", pr.REDUCE_SINGLE)
+def test_reduce_and_reduce_pair_have_the_bytes_of_the_ordered_restatement(w, L):
+    """mst_pileup_reduce and mst_pileup_reduce_pair on one segment against pr.ordered_aggregate, byte for byte: values on which
+    another order of additions shows (tests/test_pileup_reference.py), independent NaN masks, entries outside 0 .. L-1."""
+    from mustache_amd._lib import require_gpu
+    from mustache_amd.pileup import _workspace, reduce, reduce_pair
+    a, b, order, _off = pr.reduce_case(w, (L,))
+    ad, bd, od = _dev(a), _dev(b), _dev(order)
+    ws = _workspace(require_gpu(), 1, 0, L, w, ad.device)
+    four = reduce(ad, bd, od, w, ws).cpu().numpy()
+    three = reduce_pair(ad, bd, od, w, ws).cpu().numpy()
+    assert four.tobytes() == pr.ordered_aggregate((a, b), order).tobytes()
+    assert three.tobytes() == pr.ordered_aggregate((a, b), order, joint=True).tobytes()
+
+
+# what the size queries returned before the reduce had one home: (arguments, bytes)
+WORKSPACE_CIS = [((1, 0, 0, 0), 768), ((1, 0, 1, 0), 768), ((1, 0, 512, 1), 768), ((1, 0, 513, 10), 28672),
+                 ((1, 0, 1025, 64), 1597952), ((300, 40, 512, 1), 1280), ((4097, 3, 20000, 10), 564736),
+                 ((248957, 2020, 20000, 10), 1972992), ((0, 0, 1, 1), 0), ((1, 0, 1, 65), 0), ((1, -1, 1, 1), 0), ((1, 0, -1, 1), 0)]
+WORKSPACE_TRANS = [((5, 7, 0, 0), 8390656), ((5, 7, 3, 1), 8391680), ((24900, 24300, 2000, 10), 8434432),
+                   ((140000, 50, 5, 64), 8409088), ((700, 600, 100000, 64), 104372992), ((0, 1, 1, 1), 0), ((5, 7, 1, 65), 0)]
+WORKSPACE_SEGMENTED = [((0, 0), 0, 512), ((0, 3, 3, 603), 1, 1536), ((0, 511, 512, 1024, 1537, 1538), 10, 85248),
+                       ((0, 1025), 64, 1598208), ((0, 40, 80, 120), 10, 43008), ((0, 5, 3), 1, 0)]
+
+
+def test_the_workspace_queries_return_what_they_did():
+    from mustache_amd import _lib
+    from mustache_amd.pileup import _host_ptr
+    lib = _lib.load()
+    for args, want in WORKSPACE_CIS:
+        assert lib.mst_pileup_workspace_bytes(*args) == want, args
+    for args, want in WORKSPACE_TRANS:
+        assert lib.mst_pileup_trans_workspace_bytes(*args) == want, args
+    for off, w, want in WORKSPACE_SEGMENTED:
+        loop_off = np.array(off, np.int64)
+        assert lib.mst_pileup_reduce_segmented_workspace_bytes(_host_ptr(loop_off), len(off) - 1, w) == want, (off, w)

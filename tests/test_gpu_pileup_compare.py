@@ -1,4 +1,5 @@
-"""One loop list piled up on two maps on the MI355X (mst_pileup_compare and mst_pileup_reduce_pair, csrc/mst_pileup_compare.hip,
+"""One loop list piled up on two maps on the MI355X (mst_pileup_compare, csrc/mst_pileup_compare.hip; mst_pileup_reduce_pair,
+csrc/mst_pileup_reduce.hip;
 and pileup_band_pair / pileup_trans_records_pair / `-f2` of mustache_amd/pileup.py) against the cell-by-cell restatement
 (tests/pileup_compare_reference.py): cis at every window size the lanes walk differently and every L at which the loops fill
 workgroups and chunks differently, the exact identities, trans pairs, and the command line end to end.
@@ -22,6 +23,7 @@ import numpy as np
 import pytest
 
 import pileup_compare_reference as cr
+import pileup_enrich_reference as er
 import pileup_reference as pr
 import pileup_trans_reference as ptr
 
@@ -246,6 +248,21 @@ def test_argument_errors_come_with_a_message_and_launch_nothing():
         pileup_band_pair(B.cuda(), N, B.cuda(), N, D, [10], [50], 10, 6, 10)
     torch.cuda.synchronize()
     assert not sums.cpu().numpy().any()
+
+
+# ---- the neighbourhood sums, addition by addition ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("L", er.NEIGHBOURHOOD_L)
+@pytest.mark.parametrize("w,p", er.NEIGHBOURHOOD_CASES)
+def test_mst_pileup_compare_has_the_bytes_of_the_ordered_restatement(w, p, L):
+    """mst_pileup_compare under the joint mask of two independent NaN masks against er.ordered_neighbourhood_sums, byte for byte, on values on which another order of
+    additions shows (tests/test_pileup_reference.py)"""
+    import torch
+    from mustache_amd.pileup import compare_windows
+    case = er.neighbourhood_case(w, p)
+    d = lambda v: torch.from_numpy(np.ascontiguousarray(v[:L])).cuda()
+    got = compare_windows(d(case["a"]), d(case["b"]), w, p).cpu().numpy()
+    counted, first, second = (v[:L] for v in er.neighbourhood_inputs(case, w, "compare"))
+    assert got.tobytes() == er.ordered_neighbourhood_sums(counted, first, second, w, p).tobytes()
 
 
 # ---- trans -----------------------------------------------------------------------------------------------------------------------

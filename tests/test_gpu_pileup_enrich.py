@@ -170,6 +170,23 @@ def test_argument_errors_come_with_a_message_and_launch_nothing():
     torch.cuda.synchronize()
 
 
+# ---- the neighbourhood sums, addition by addition ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("L", er.NEIGHBOURHOOD_L)
+@pytest.mark.parametrize("w,p", er.NEIGHBOURHOOD_CASES)
+def test_mst_pileup_enrich_has_the_bytes_of_the_ordered_restatement(w, p, L):
+    """mst_pileup_enrich, cis (a zero diagonal in E, cells beyond D) and trans, against er.ordered_neighbourhood_sums, byte for byte, on values on which another order of
+    additions shows (tests/test_pileup_reference.py)"""
+    import torch
+    from mustache_amd.pileup import enrich_windows
+    case = er.neighbourhood_case(w, p)
+    d = lambda v: torch.from_numpy(np.ascontiguousarray(v[:L])).cuda()
+    got = {"cis": enrich_windows(d(case["a"]), w, p, E=torch.from_numpy(case["E"]).cuda(), xs=d(case["xs"]), ys=d(case["ys"])),
+           "trans": enrich_windows(d(case["a"]), w, p, e_loop=d(case["e_loop"]))}
+    for kind in ("cis", "trans"):
+        counted, first, second = (v[:L] for v in er.neighbourhood_inputs(case, w, kind))
+        assert got[kind].cpu().numpy().tobytes() == er.ordered_neighbourhood_sums(counted, first, second, w, p).tobytes(), kind
+
+
 # ---- trans -------------------------------------------------------------------------------------------------------------------
 def _pair_records(n1, n2, count, seed):
     rng = np.random.default_rng(seed)

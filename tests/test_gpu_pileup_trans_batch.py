@@ -10,6 +10,7 @@ import itertools
 import numpy as np
 import pytest
 
+import pileup_reference as pr
 import pileup_trans_reference as ptr
 
 pytestmark = pytest.mark.gpu
@@ -311,6 +312,25 @@ def test_reduce_segmented_alone_skips_foreign_indices_and_zeroes_empty_pairs():
         one = reduce(obs_d[s:e].contiguous(), oe_d[s:e].contiguous(), local, w, ws1).cpu().numpy()
         assert agg[p].tobytes() == one.tobytes(), p
     assert agg[0][1].max() <= 2.0                            # at most two of pair 0's three loops were added
+
+
+@pytest.mark.parametrize("w,counts", pr.REDUCE_SEGMENTED)
+def test_reduce_segmented_has_the_bytes_of_the_ordered_restatement(w, counts):
+    """mst_pileup_reduce_segmented against pr.ordered_aggregate, byte for byte: values on which another order of
+    additions shows, independent NaN masks, a foreign index in pair 0's range, a pair without a loop."""
+    import torch
+    from mustache_amd import _lib
+    from mustache_amd.pileup import _host_ptr
+    lib = _lib.require_gpu()
+    a, b, order, loop_off = pr.reduce_case(w, counts)
+    L, P, S = len(order), len(counts), 2 * w + 1
+    d = lambda v: torch.from_numpy(np.ascontiguousarray(v)).cuda()
+    ad, bd, od = d(a), d(b), d(order)
+    ws = torch.empty(int(lib.mst_pileup_reduce_segmented_workspace_bytes(_host_ptr(loop_off), P, w)), dtype=torch.uint8, device="cuda")
+    agg = torch.full((P, 4, S * S), -7.0, dtype=torch.float64, device="cuda")
+    _lib.check(lib.mst_pileup_reduce_segmented(_lib.ptr(ad), _lib.ptr(bd), _lib.ptr(od), L, _host_ptr(loop_off), P, w,
+                                               _lib.ptr(agg), _lib.ptr(ws), ws.numel(), None))
+    assert agg.cpu().numpy().tobytes() == pr.ordered_aggregate((a, b), order, loop_off).tobytes()
 
 
 # ---- record values ---------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import pileup_enrich_reference as er
 import pileup_reference as pr
 
 
@@ -226,3 +227,39 @@ def test_cli_output_files(inputs, monkeypatch):
     for j, k in enumerate(used):
         assert float(body[k][9]) == want["center_obs"][j] and float(body[k][11]) == want["p2ll"][j]
     assert all(math.isnan(float(body[k][9])) for k in (3, 4, 5))
+
+
+# ---- the order-exact restatements: their inputs tell one order of additions from another --------------------------------------
+def _bits_differ(a, b):
+    return bool((np.ascontiguousarray(a, np.float64).view(np.int64) != np.ascontiguousarray(b, np.float64).view(np.int64)).any())
+
+
+@pytest.mark.parametrize("w,counts", [(w, (L,)) for w, L in pr.REDUCE_SINGLE if L > 256] + pr.REDUCE_SEGMENTED)
+def test_the_reduce_cases_tell_the_device_order_from_nansum(w, counts):
+    """Up to 129 loops the four runs of 128 are one sequential sum, which np.nansum over the sorted loops is too; in every
+    segment of more than 256 loops each sum row of ordered_aggregate must differ from it in some cell, and the counts never."""
+    a, b, order, loop_off = pr.reduce_case(w, counts)
+    for joint in (False, True):
+        got = pr.ordered_aggregate((a, b), order, loop_off, joint)
+        for seg, c in enumerate(counts):
+            l0, l1 = int(loop_off[seg]), int(loop_off[seg + 1])
+            sa, sb = pr.plain_aggregate(a, b, order, l0, l1, joint)
+            ra, rb = (got[seg][0], got[seg][1]) if joint else (got[seg][0], got[seg][2])
+            assert np.allclose(ra, sa, rtol=0, atol=1e-4) and np.allclose(rb, sb, rtol=0, atol=1e-4)
+            if c > 256:
+                assert _bits_differ(ra, sa) and _bits_differ(rb, sb), (seg, joint)
+            elif c <= 129:
+                assert not _bits_differ(ra, sa) and not _bits_differ(rb, sb), (seg, joint)
+
+
+@pytest.mark.parametrize("w,p", er.NEIGHBOURHOOD_CASES)
+def test_the_neighbourhood_cases_tell_the_lane_order_from_a_plain_sum(w, p):
+    case = er.neighbourhood_case(w, p)
+    for kind in ("cis", "trans", "compare"):
+        counted, first, second = er.neighbourhood_inputs(case, w, kind)
+        got = er.ordered_neighbourhood_sums(counted, first, second, w, p)
+        plain = er.plain_neighbourhood_sums(counted, first, second, w, p)
+        assert np.allclose(got[:, :, :2], plain, rtol=0, atol=1e-4)
+        assert np.array_equal(got[:, :, 2], (np.asarray(counted)[:, None] & er.masks(w, p)[None]).sum((2, 3)))
+        assert _bits_differ(got[:, :, 0], plain[:, :, 0]) and _bits_differ(got[:, :, 1], plain[:, :, 1]), kind
+        assert (got[:, :, 2] > 0).all() or w == 1
